@@ -1,18 +1,28 @@
 #!/usr/bin/env python3
 """bench.py — sequences/sec of one ELBO training step of the KVAE on synthetic 32x32xT bouncing-ball video.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c4-lstm|c5|c5-lstm]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c4-lstm|c5|c5-lstm] [--full] [--dump-outputs DIR]
 
 Workloads (per GPU; weak scaling):
   c2 (default)  BASELINE.json configs[1] / configs[2]: dynamics 'lstm', K=3 modes, z=4, a=2, B=256 sequences of T=50
-  c4 / c4-lstm  BASELINE.json configs[3]: K=7, T=100, B=32 (the reference's batch), switching / lstm dynamics; also times the
-                eval-mode imputation (`KVAE.impute` with the block mask) the config names
+  c4 / c4-lstm  BASELINE.json configs[3]: K=7, T=100, B=32 (the reference's batch), switching / lstm dynamics; with --full
+                also times the eval-mode imputation (`KVAE.impute` with the block mask) the config names
   c5 / c5-lstm  BASELINE.json configs[4] shard: z = u = 16, T = 200, B = 512 per GPU (4096 over 8 GPUs); c5 is the switching
                 model (per-step Q: the 21 804 B/step SURVEY 8(d) quotes), c5-lstm the shared-Q variant
 Any of --batch / --seq-len / --z-dim / --dynamics / --modes overrides the preset; `config.workload` always names what ran.
-The default invocation (no workload flag) times c2 as the headline and then appends short runs of c4, c4-lstm and c5 as
-`"also": {...}` (ms/step, sequences/s, roofline of their dominant LGSSM kernel; c4 with impute and its CPU baseline), so
-that one driver-timed line witnesses every BASELINE config that fits one GPU (`--also none` skips them).
+
+A plain run sets up, warms up (--warmup steps), times exactly --steps steps, writes the outputs of the last timed step when
+--dump-outputs DIR is given, and prints the line: `value` (sequences/s) and `ms_per_step` come from that timed region alone.
+--full adds everything else, after the timed region: the steady-state windows, the roofline leg (eager event-timed pass of
+the LGSSM chain), the CPU baseline, the imputation timing of the c4 presets and - for the default workload - short runs of
+c4, c4-lstm and c5 appended as `"also": {...}` (ms/step, sequences/s, roofline of their dominant LGSSM kernel; c4 with
+impute and its CPU baseline), so that one driver-timed line witnesses every BASELINE config that fits one GPU (`--also none`
+skips them).  The --no-* flags switch single legs of --full off.
+
+--dump-outputs DIR: after the timed steps, what the timed step hands its caller - the tensors Trainer.step returns and the
+parameters its Adam update wrote - as DIR/<name>.npy (float32; float64 for integer tensors), at most 64 MB in all: an array of
+more than 2^22 elements is written as a sample at fixed positions (numpy seed 0).  Model, frames and noise are seeded, so the
+same arguments give the same inputs in every run, and two builds can be compared file by file.
 
 A step = zero_grad + forward (incl. sigmoid(x_logits)) + loss (incl. the active-unit statistics of the reference's
 compute_loss, kept on the device) + backward + [one flat RCCL all-reduce] + clip_grad_norm_(10) + Adam (reference
@@ -51,7 +61,7 @@ PRESETS = {
     "c5": dict(batch=512, seq_len=200, z_dim=16, dynamics="switching", modes=3),
     "c5-lstm": dict(batch=512, seq_len=200, z_dim=16, dynamics="lstm", modes=3),
 }
-ALSO_DEFAULT = ("c4", "c4-lstm", "c5")          # appended to the default run (python bench.py), each a few seconds
+ALSO_DEFAULT = ("c4", "c4-lstm", "c5")          # appended to the default run (python bench.py --full), each a few seconds
 ALSO_STEPS = {"c4": 100, "c4-lstm": 100, "c5": 20}
 BASELINE_NAMES = {
     (256, 50, 4, "lstm", 3): "BASELINE configs[1] (configs[2] per-GPU shard)",
@@ -88,14 +98,21 @@ def parse_args(argv=None):
                     help="launcher/rendezvous rehearsal on the CPU (gloo): no model, no GPU, marks the line dry_run")
     ap.add_argument("--also", default=None,
                     help="comma-separated presets measured briefly after the headline and appended as `also` "
-                         "('none' to skip; default: c4,c4-lstm,c5 on one GPU when no other workload flag is given)")
-    ap.add_argument("--impute", action="store_true", help="also time eval-mode KVAE.impute (default for the c4 presets)")
+                         "('none' to skip; default: c4,c4-lstm,c5 with --full on one GPU when no other workload flag is given)")
+    ap.add_argument("--impute", action="store_true", help="also time eval-mode KVAE.impute (default for the c4 presets under --full)")
     ap.add_argument("--graph-allreduce", action="store_true", help="N > 1: capture the RCCL all-reduce into the step graph")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the steady-state windows, the roofline leg, the CPU baseline, the "
+                         "c4 presets' imputation timing and (default workload) the `also` presets")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
     args = ap.parse_args(argv)
-    plain = args.config == "c2" and all(getattr(args, k) is None for k in ("batch", "seq_len", "dynamics", "modes", "z_dim")) \
-        and not (args.no_graph or args.no_roofline or args.no_steady or args.no_overlap) and args.gpus == 1
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    default_full = args.config == "c2" and all(getattr(args, k) is None for k in ("batch", "seq_len", "dynamics", "modes", "z_dim")) \
+        and not (args.no_graph or args.no_roofline or args.no_steady or args.no_overlap) and args.gpus == 1 and args.full
     if args.also is None:
-        args.also = list(ALSO_DEFAULT) if plain else []
+        args.also = list(ALSO_DEFAULT) if default_full else []
     else:
         args.also = [] if args.also.lower() in ("", "none") else [a for a in args.also.split(",") if a]
     for a in args.also:
@@ -109,7 +126,7 @@ def parse_args(argv=None):
 def apply_preset(args):
     for k, v in PRESETS[args.config].items():
         if k == "impute":
-            args.impute = bool(args.impute or v)
+            args.impute = bool(args.impute or (v and args.full))
         elif getattr(args, k) is None:
             setattr(args, k, v)
 
@@ -292,6 +309,37 @@ def timed_window(trainer, x, steps, world, dev):
     return elapsed, out
 
 
+DUMP_SAMPLE = 1 << 22          # elements written of a larger output (16 MB in f32): a fixed, seeded sample of its positions
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out, model, path):
+    """--dump-outputs: the tensors the last timed Trainer.step returned (loss terms, x_recon, active-unit statistics, grad norm)
+    and the model's parameters / buffers after its Adam update ("param.<state_dict key>"), as <name>.npy.  Floating tensors
+    are written as float32 (float64 stays float64), integer and boolean ones as float64.  A tensor of more than DUMP_SAMPLE
+    elements is written as DUMP_SAMPLE elements of its flattened form at sorted positions drawn with numpy seed 0, so that
+    the same arguments give files of the same meaning.  Returns (files, bytes)."""
+    import numpy as np
+    import torch
+    path = Path(path)
+    path.mkdir(parents=True, exist_ok=True)
+    arrays = {k: v for k, v in out.items() if isinstance(v, torch.Tensor)}
+    arrays.update({"param." + k: v for k, v in model.state_dict().items()})
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_SAMPLE, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        dtype = torch.float64 if t.dtype == torch.float64 or not t.is_floating_point() else torch.float32
+        a = t.to(dtype).cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB of outputs at {name}")
+        np.save(path / f"{name}.npy", a)
+    return len(arrays), total
+
+
 def dry_run_cpu(args):
     """Rehearsal of the launcher + rendezvous path without a GPU (CPU test tier): gloo ranks, one all-reduce."""
     import torch
@@ -439,10 +487,10 @@ def impute_leg(args, cfg, model, x, steps):
     return out
 
 
-def run_workload(args, dev, rank, world, full):
+def run_workload(args, dev, rank, world, headline):
     """One workload end to end: build, capture, time `args.steps` steps (barrier + device sync on both sides, max over ranks),
-    then - rank 0 - the extra legs.  full: steady-state windows and the CPU baseline at full budget (the headline);
-    otherwise a short version of each (the `also` entries of the default run)."""
+    [dump the outputs of the last timed step], then - with --full, rank 0 - the extra legs.  headline: steady-state windows
+    and the CPU baseline at full budget; otherwise a short version of each (the `also` entries of the default --full run)."""
     import gc
     import torch
     from kvae.train.synthetic import bouncing_ball
@@ -486,12 +534,15 @@ def run_workload(args, dev, rank, world, full):
     log(f"[{args.config}] timed region: {ms_per_step:.3f} ms/step, {value:.1f} seq/s, loss {loss:.5f}")
     if not (loss == loss and abs(loss) != float("inf")):
         log(f"[{args.config}] WARNING: the loss is not finite - the timing above measured error paths, not the workload")
+    if headline and rank == 0 and args.dump_outputs:
+        n_files, n_bytes = dump_outputs(out, model, args.dump_outputs)
+        log(f"[{args.config}] outputs of the last timed step: {n_files} arrays, {n_bytes / 2**20:.1f} MB in {args.dump_outputs}")
 
     # ---- steady state: further windows (>= 5 and >= 2 s or >= 200 steps in all for the headline); median and spread ----
     steady = None
-    if not args.no_steady:
+    if args.full and not args.no_steady:
         per = max(4, min(200, int(0.4 / max(ms_per_step * 1e-3, 1e-6)) + 1))   # ~0.4 s per window
-        min_wins, min_s, min_steps = (5, 2.0, 200) if full else (3, 0.6, 60)
+        min_wins, min_s, min_steps = (5, 2.0, 200) if headline else (3, 0.6, 60)
         wins, total_steps, total_s = [], 0, 0.0
         while len(wins) < min_wins or (total_s < min_s and total_steps < min_steps):
             el, _ = timed_window(trainer, x, per, world, dev)
@@ -509,14 +560,14 @@ def run_workload(args, dev, rank, world, full):
             f"(min {sw[0]:.3f}, max {sw[-1]:.3f})")
 
     roofline, chain, impute = None, {}, None
-    if rank == 0 and not args.no_roofline:
-        roofline, chain = roofline_leg(args, cfg, model, x, n_prof_small=10 if full else 5)
+    if rank == 0 and args.full and not args.no_roofline:
+        roofline, chain = roofline_leg(args, cfg, model, x, n_prof_small=10 if headline else 5)
     if rank == 0 and args.impute:
         impute = impute_leg(args, cfg, model, x, steps=max(10, min(50, args.steps)))
         log(f"[{args.config}] impute: {impute}")
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and (full or args.cpu_in_also):
-        cpu = cpu_baseline(args, sd_cpu, frames, budget_s=25.0 if full else 6.0)
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and (headline or args.cpu_in_also):
+        cpu = cpu_baseline(args, sd_cpu, frames, budget_s=25.0 if headline else 6.0)
     res = {"value": round(value, 2), "ms_per_step": round(ms_per_step, 4), "steps": args.steps, "warmup": args.warmup,
            "config": {"workload": workload_name(args, (cfg.z_dim, cfg.u_dim, cfg.a_dim)), "preset": args.config,
                       "global_batch": world * B, "seq_len": T, "parallelism": f"dp{world}", "capture": capture,
@@ -553,9 +604,9 @@ def main():
     backend = dist.get_backend() if world > 1 else "none"
     log(f"rank {rank}/{world} on {torch.cuda.get_device_name(dev)} (device {dev.index}), backend {backend} "
         f"[nccl == RCCL on ROCm]")
-    res = run_workload(args, dev, rank, world, full=True)
+    res = run_workload(args, dev, rank, world, headline=True)
 
-    # ---- the other BASELINE configs under the same clock: short runs appended as `also` (default invocation only) ----------
+    # ---- the other BASELINE configs under the same clock: short runs appended as `also` (default --full invocation) --------
     also = {}
     if args.also:
         for name in args.also:
@@ -565,10 +616,10 @@ def main():
             a.config = name
             apply_preset(a)
             a.steps, a.warmup = ALSO_STEPS.get(name, 30), 5
-            a.impute = PRESETS[name].get("impute", False)
+            a.impute = PRESETS[name].get("impute", False) and a.full
             a.cpu_in_also = name.startswith("c4")   # seconds at B = 32; the stress shard's CPU leg is minutes: `--config c5` has it
             t0 = time.perf_counter()
-            r = run_workload(a, dev, rank, world, full=False)
+            r = run_workload(a, dev, rank, world, headline=False)
             r["wall_s"] = round(time.perf_counter() - t0, 1)
             also[name] = r
 
@@ -577,7 +628,7 @@ def main():
             "metric": "sequences/sec (ELBO training step, 32x32xT bouncing-ball)", "value": res["value"],
             "unit": "sequences/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": res["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
+            "dtype": "f32", "data": "synthetic", "full": args.full,
             "config": dict(res["config"], dist_backend=backend),
             "steady_state": res["steady_state"],
             "roofline": res["roofline"], "lgssm_chain": res["lgssm_chain"], "cpu_baseline": res["cpu_baseline"],

@@ -57,3 +57,51 @@ def test_workload_label_follows_the_arguments():
     b = bench.parse_args(["--batch", "64"])
     assert "configs[1]" not in bench.workload_name(b, (4, 4, 2)) and "batch=64" in bench.workload_name(b, (4, 4, 2))
     assert "configs[1]" in bench.workload_name(bench.parse_args([]), (4, 4, 2))
+
+
+def test_extra_legs_only_with_full():
+    """A plain run times the steps and prints the line; the `also` presets and the c4 presets' imputation need --full."""
+    sys.path.insert(0, str(ROOT))
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.also, a.impute, a.steps, a.warmup, a.dump_outputs) == (False, [], False, 7, 2, None)
+    assert not bench.parse_args(["--config", "c4"]).impute
+    f = bench.parse_args(["--full"])
+    assert f.full and f.also == list(bench.ALSO_DEFAULT)
+    assert bench.parse_args(["--full", "--config", "c4"]).impute
+    assert bench.parse_args(["--full", "--also", "none"]).also == []
+    assert bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+
+
+def test_steps_must_be_positive():
+    r = _run(["--steps", "0"], timeout=60)
+    assert r.returncode != 0 and not _json_lines(r.stdout)
+    assert "--steps" in r.stderr
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path, monkeypatch):
+    """dump_outputs on host tensors: float32 / float64 files, integer tensors as float64, large tensors as the same seeded
+    sample in every call."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, str(ROOT))
+    import bench
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 100)
+    g = torch.Generator().manual_seed(0)
+    out = {"loss": torch.tensor(1.5), "x_recon": torch.rand(4, 10, 1, 8, 8, generator=g),
+           "active_units": torch.tensor(3), "d64": torch.ones(3, dtype=torch.float64), "note": 1.0}
+    model = torch.nn.Linear(5, 3)
+    n_files, n_bytes = bench.dump_outputs(out, model, tmp_path / "a")
+    bench.dump_outputs(out, model, tmp_path / "b")
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["active_units.npy", "d64.npy", "loss.npy", "param.bias.npy", "param.weight.npy", "x_recon.npy"]
+    assert n_files == 6 and n_bytes == sum((tmp_path / "a" / n).stat().st_size - 128 for n in names)
+    ld = lambda d, n: np.load(tmp_path / d / n)
+    assert ld("a", "loss.npy").dtype == np.float32 and float(ld("a", "loss.npy")) == 1.5
+    assert ld("a", "active_units.npy").dtype == np.float64 and float(ld("a", "active_units.npy")) == 3.0
+    assert ld("a", "d64.npy").dtype == np.float64
+    np.testing.assert_array_equal(ld("a", "param.weight.npy"), model.weight.detach().numpy())
+    xs = ld("a", "x_recon.npy")
+    assert xs.shape == (100,) and xs.dtype == np.float32
+    np.testing.assert_array_equal(xs, ld("b", "x_recon.npy"))
+    assert np.isin(xs, out["x_recon"].numpy().reshape(-1)).all()
