@@ -69,7 +69,12 @@ KV_DEV int probe_level(float *Lo, float *sym, const float *X, int n) {
 }
 
 #if defined(KVAE_HOSTSIM)
-KV_DEV void atomic_max_i32(int32_t *p, int32_t v) { if (v > *p) *p = v; }
+// (a real atomic: on emulated wavefronts (tests/hostsim/wave_emu.h) the lanes that record a level are concurrent host threads)
+KV_DEV void atomic_max_i32(int32_t *p, int32_t v) {
+  int32_t cur = __atomic_load_n(p, __ATOMIC_RELAXED);
+  while (v > cur && !__atomic_compare_exchange_n(p, &cur, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {
+  }
+}
 #else
 // (a plain read first: when the whole batch needs a raised level, a hundred thousand wavefronts would otherwise queue on one
 // address - 2.3 ms of atomics at the configs[4] shard - while all but the first few find their level already recorded)

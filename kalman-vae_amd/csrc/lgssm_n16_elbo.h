@@ -22,7 +22,7 @@
 #include "lgssm_elbo.h"
 #include "lgssm_n16.h"
 
-#if !defined(KVAE_HOSTSIM) && !defined(KV_TPP)
+#if (!defined(KVAE_HOSTSIM) || defined(KVAE_WAVE_EMU)) && !defined(KV_TPP)   // KVAE_WAVE_EMU: tests/hostsim/wave_emu.h
 namespace kvae {
 namespace n16 {
 
@@ -34,10 +34,18 @@ struct alignas(16) ELds {
 // acc += (lane C of src's row) * f  - the DPP source is a different register than the accumulator
 template <int C>
 __device__ __forceinline__ void fmac_bcast_src(float &acc, float src, float f) {
+#if defined(KVAE_WAVE_EMU)
+  acc = fmaf(bcast<C>(src), f, acc);
+#else
   asm volatile("v_fmac_f32_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(src), "v"(f), "n"(C));
+#endif
 }
 // two wait states between the VALU write of v and its next DPP read (the compiler cannot see into the asm above)
+#if defined(KVAE_WAVE_EMU)
+__device__ __forceinline__ void dpp_guard(float &) {}
+#else
 __device__ __forceinline__ void dpp_guard(float &v) { asm volatile("s_nop 1" : "+v"(v)); }
+#endif
 
 // Cholesky factor with its rows on the lanes
 struct Chol {
@@ -100,8 +108,10 @@ template <int K>
 __device__ __forceinline__ void inv_step(const Chol &c, float (&y)[N]) {
   // y[C] of the previous step (or the identity just selected into it) -> DPP read: the wait states must sit AFTER those writes,
   // so the guard names the registers (an operand-less s_nop let hipcc sink the initialisation of y[0] below it)
+#if !defined(KVAE_WAVE_EMU)
   asm volatile("s_nop 1" : "+v"(y[0]), "+v"(y[1]), "+v"(y[2]), "+v"(y[3]), "+v"(y[4]), "+v"(y[5]), "+v"(y[6]), "+v"(y[7]), "+v"(y[8]),
                "+v"(y[9]), "+v"(y[10]), "+v"(y[11]), "+v"(y[12]), "+v"(y[13]), "+v"(y[14]), "+v"(y[15]));
+#endif
   inv_cols<K, 0>(c, y);
   if constexpr (K + 2 < N) inv_step<K + 1>(c, y);
 }

@@ -124,6 +124,8 @@ void kvae_wemu_bwd_n4(const kvae_lgssm_problem *, const kvae_lgssm_states *, con
 void kvae_wemu_fwd_n16(const kvae_lgssm_problem *, const kvae_lgssm_states *, int, int);
 void kvae_wemu_bwd_n16(const kvae_lgssm_problem *, const kvae_lgssm_states *, const kvae_lgssm_states *,
                        const kvae_lgssm_input_grads *, float *, int);
+void kvae_wemu_elbo_n16(const kvae_lgssm_problem *, const float *, const float *, const float *, float *, int32_t *, float *,
+                        float *, float *, const kvae_lgssm_input_grads *, int);
 }
 static int g_wave_emu = 0;
 static bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -141,6 +143,16 @@ static bool wave_bwd_ok(const kvae_lgssm_problem *p, const kvae_lgssm_states *sa
                         const kvae_lgssm_input_grads *out, const float *ws, int n) {
   return wave_fwd_ok(p, saved, n) && saved->aux && al16(ws) && al16(up->Sigmas_smooth) && al16(up->Sigmas_filt) &&
          al16(up->Sigmas_pred) && gstack16(out->gA) && gstack16(out->gB) && gstack16(out->gQ) && al16(out->g_Sigma0) && out->gU;
+}
+// the gate of the (16,16,2) ELBO kernels in kvae_lgssm_elbo (kvae_lgssm.hip): n16_ok and the alignment / stride tests next to it
+static bool wave_elbo_ok(const kvae_lgssm_problem *p, const float *mus, const float *Sigs, const float *eps, const float *ws_lz,
+                         const float *g_Sigs, const kvae_lgssm_input_grads *g, bool want_g) {
+  if (!g_wave_emu || p->n != 16 || p->m != 16 || p->p != 2) return false;
+  const bool n16 = stack16(p->A) && stack16(p->Bm) && stack16(p->C) && stack16(p->Q) && al16(p->mu0) && p->mu0_sb % 4 == 0 &&
+                   al16(p->Sigma0) && p->Sigma0_sb % 4 == 0 && al16(p->U);
+  return n16 && ws_lz && al16(mus) && al16(Sigs) && al16(eps) && al16(ws_lz) &&
+         (!want_g || (al16(g_Sigs) && al16(g->gA.ptr) && g->gA.sb % 4 == 0 && g->gA.st % 4 == 0 && al16(g->gB.ptr) &&
+                      g->gB.sb % 4 == 0 && g->gB.st % 4 == 0));
 }
 
 extern "C" {
@@ -205,6 +217,15 @@ int kvae_lgssm_elbo(const kvae_lgssm_problem *prob, const float *mus_smooth, con
   if (rc) return rc;
   if (!mus_smooth || !Sigmas_smooth || !eps || !terms || !chol_levels) return KVAE_ERR_NULL;
   if (g_mus && (!g_Sigmas || !g || !g->gA.ptr || !g->gB.ptr || !g->gC.ptr || !g->gY)) return KVAE_ERR_NULL;
+  const bool want_g = g_mus != nullptr;
+  if (wave_elbo_ok(prob, mus_smooth, Sigmas_smooth, eps, ws_lz, g_Sigmas, g, want_g)) {
+    kvae_lgssm_input_grads gz;
+    memset(&gz, 0, sizeof(gz));
+    chol_levels[0] = chol_levels[1] = chol_levels[2] = 0;   // (the memset before the launches); the main launch writes its family
+    kvae_wemu_elbo_n16(prob, mus_smooth, Sigmas_smooth, eps, terms, chol_levels, ws_lz, g_mus, g_Sigmas, want_g ? g : &gz,
+                       want_g ? 1 : 0);
+    return KVAE_OK;
+  }
   chol_levels[2] = 0;   // kernel family: the generic bodies
   KVAE_DISPATCH(*prob, (run_elbo<D>(*prob, mus_smooth, Sigmas_smooth, eps, terms, chol_levels, ws_lz, g_mus, g_Sigmas, g)));
   return KVAE_OK;

@@ -1,40 +1,80 @@
-// wave_emu.h — TEST-ONLY: run the wavefront-level kernel bodies (csrc/lgssm_q4.h, lgssm_m4.h, lgssm_n16.h: code written per lane
-// around cross-lane instructions - DPP moves, permlane swaps, ds_bpermute, ballots, the f32 MFMA tiles) on the HOST, so that
-// the CPU tier can put their indexing under AddressSanitizer (GPU sanitizers are not available on the pool).
+// wave_emu.h — TEST-ONLY: run the wavefront-level kernel bodies (csrc/lgssm_q4.h, lgssm_m4.h, lgssm_n16.h, lgssm_n16_elbo.h:
+// code written per lane around cross-lane instructions - DPP moves, permlane swaps, ds_bpermute, ballots, the f32 MFMA tiles) on
+// the HOST, so that the CPU tier can put their indexing under AddressSanitizer (GPU sanitizers are not available on the pool).
 //
 // One emulated wavefront = 64 host threads, one per lane, running the very same body; every cross-lane intrinsic is a
 // rendezvous: each lane deposits its operand, a barrier, each lane picks what the instruction would have handed it.  (Two
-// operand buffers used alternately make one barrier per instruction enough: a lane can be at most one instruction ahead.)  The
-// bodies emulated here only use such instructions under wave-uniform control flow.  (The n = 16 ELBO kernels do not: their four
-// row-groups take turns on the matrix cores with DPP traffic inside group-dependent branches - legal on the hardware, where a
-// DPP move only needs its own row active, a deadlock for this rendezvous; they are not emulated.)
+// operand buffers used alternately make one barrier per instruction enough: a lane can be at most one instruction ahead.)
+// Scope of the rendezvous: a DPP move (every control the harness knows - quad_perm, row_mirror, row_half_mirror, row_newbcast -
+// reads inside one 16-lane row) meets the 16 lanes of its ROW only, on that row's own barrier, buffers and parity counter;
+// everything else (MFMA tiles, ds_bpermute, ballot / any, permlane swaps, __syncthreads) meets all 64 lanes.  The "one
+// instruction ahead" argument then holds per scope, and the n = 16 ELBO kernels - four row-groups taking turns on the matrix
+// cores, with DPP traffic inside group-dependent branches, legal on the hardware where a DPP move only needs its own row - run
+// here too.  A wave-scope instruction that only some lanes reach (or a row-scope one only some lanes of a row reach) would wait
+// forever: every barrier has a deadline, past which the harness names the scope, the lane and the block and aborts.
 // Arithmetic of the MFMA shims: k-ascending fmaf chains in fp32, which is what the kernels' parity argument assumes.
-// This is a sanitizer / debug harness, slow by design (a barrier of 64 threads per instruction): tiny problems only.
+// This is a sanitizer / debug harness, slow by design (a barrier per instruction): tiny problems only.
 #pragma once
 #include <math.h>
-#include <pthread.h>
 #include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
+#include <chrono>
+#include <condition_variable>
 #include <functional>
+#include <mutex>
 #include <thread>
 #include <vector>
 
 namespace wemu {
 
-struct Wave {
-  pthread_barrier_t bar;
-  uint32_t a[2][64], b[2][64];
-  Wave() { pthread_barrier_init(&bar, nullptr, 64); }
-  ~Wave() { pthread_barrier_destroy(&bar); }
-};
 struct Dim3 { unsigned x, y, z; };
-inline thread_local Wave *t_wave = nullptr;
-inline thread_local int t_par = 0;
 inline thread_local Dim3 t_tid = {0, 0, 0}, t_bid = {0, 0, 0}, t_gdim = {1, 1, 1};
-
-inline void sync() { pthread_barrier_wait(&t_wave->bar); }
 inline int lane_id() { return (int)(t_tid.x & 63); }
+
+// a barrier of `n` threads with a deadline: a rendezvous that not every member reaches is a harness or kernel-structure error,
+// reported (scope, lane, block) instead of hanging the test tier
+constexpr int kDeadlineSeconds = 10;
+class Barrier {
+ public:
+  Barrier(unsigned n, const char *scope) : n_(n), scope_(scope) {}
+  void wait() {
+    std::unique_lock<std::mutex> lk(m_);
+    const unsigned gen = gen_;
+    if (++count_ == n_) {
+      count_ = 0, ++gen_;
+      cv_.notify_all();
+      return;
+    }
+    if (!cv_.wait_for(lk, std::chrono::seconds(kDeadlineSeconds), [&] { return gen_ != gen; })) {
+      fprintf(stderr, "wave_emu: %s-scope rendezvous not reached by all %u lanes within %d s (lane %d, block %u waiting)\n",
+              scope_, n_, kDeadlineSeconds, lane_id(), t_bid.x);
+      fflush(stderr);
+      abort();
+    }
+  }
+
+ private:
+  std::mutex m_;
+  std::condition_variable cv_;
+  const unsigned n_;
+  const char *scope_;
+  unsigned count_ = 0, gen_ = 0;
+};
+
+struct Wave {
+  Barrier bar{64, "wave"};
+  Barrier row_bar[4]{{16, "row"}, {16, "row"}, {16, "row"}, {16, "row"}};
+  uint32_t a[2][64], b[2][64];   // wave-scope operands
+  uint32_t r[2][64];             // row-scope operands (row k uses lanes 16k..16k+15 of each)
+};
+inline thread_local Wave *t_wave = nullptr;
+inline thread_local int t_par = 0;    // parity of this lane's wave-scope exchanges
+inline thread_local int t_rpar = 0;   // parity of this lane's row-scope exchanges
+
+inline void sync() { t_wave->bar.wait(); }
 // every lane deposits v; returns the buffer to read the other lanes' values from (valid until this lane's next exchange)
 inline const uint32_t *exchange(uint32_t v) {
   const int p = t_par;
@@ -42,6 +82,15 @@ inline const uint32_t *exchange(uint32_t v) {
   t_wave->a[p][lane_id()] = v;
   sync();
   return t_wave->a[p];
+}
+// the same within this lane's 16-lane row only: the returned buffer is valid for the lanes of that row
+inline const uint32_t *row_exchange(uint32_t v) {
+  const int p = t_rpar;
+  t_rpar ^= 1;
+  const int l = lane_id();
+  t_wave->r[p][l] = v;
+  t_wave->row_bar[l >> 4].wait();
+  return t_wave->r[p];
 }
 inline uint32_t fbits(float x) { uint32_t u; memcpy(&u, &x, 4); return u; }
 inline float bitsf(uint32_t u) { float x; memcpy(&x, &u, 4); return x; }
@@ -54,8 +103,8 @@ inline int dpp_source(int lane, int ctrl) {
   if (ctrl >= 0x150 && ctrl <= 0x15F) return (lane & ~15) | (ctrl - 0x150);                // row_newbcast:K
   __builtin_trap();   // a control this harness does not know: extend it rather than guess
 }
-inline int mov_dpp(int v, int ctrl, int, int, bool) {
-  const uint32_t *all = exchange((uint32_t)v);
+inline int mov_dpp(int v, int ctrl, int, int, bool) {   // every control above reads inside the caller's row: a row rendezvous
+  const uint32_t *all = row_exchange((uint32_t)v);
   return (int)all[dpp_source(lane_id(), ctrl)];
 }
 inline float shfl(float v, int src, int) { return bitsf(exchange(fbits(v))[src & 63]); }
@@ -117,7 +166,7 @@ inline void launch(unsigned blocks, const std::function<void()> &body) {
     th.reserve(64);
     for (unsigned l = 0; l < 64; ++l)
       th.emplace_back([&, l] {
-        t_wave = &w, t_par = 0, t_tid = {l, 0, 0}, t_bid = {blk, 0, 0}, t_gdim = {blocks, 1, 1};
+        t_wave = &w, t_par = 0, t_rpar = 0, t_tid = {l, 0, 0}, t_bid = {blk, 0, 0}, t_gdim = {blocks, 1, 1};
         body();
       });
     for (auto &t : th) t.join();

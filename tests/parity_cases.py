@@ -403,7 +403,156 @@ def safe_cholesky_levels_shared_q(DEV, n=16, B=5, T=10):
                 assert rel_err(got.grad.cpu(), r.grad) < 3e-3, (want, k, "four-step")
 
 
-def jitter_golden(DEV, name, levels):
+N16_ELBO_TOL = 1e-4   # per-(b,t) bar of n16_elbo_per_step (measured on gfx950: largest ratio 2.1e-6 over the GPU-tier cases)
+
+
+def _per_step_ratio(got, ref):
+    """Largest per-(b,t) error ratio max|got - ref| / max(max|ref| on the slice, 1e-2 max|ref| on the tensor) of a [B,T,...]
+    gradient stack (float64 reference), and the (b,t) where it occurs."""
+    B, T = ref.shape[:2]
+    err = (got.double() - ref).abs().reshape(B, T, -1).amax(-1)
+    scale = ref.abs().reshape(B, T, -1).amax(-1).clamp_min(1e-2 * float(ref.abs().max())).clamp_min(1e-30)
+    ratio = err / scale
+    k = int(ratio.argmax())
+    return float(ratio.max()), divmod(k, T)
+
+
+def n16_elbo_per_step(DEV, B, T, family, levels=(0, 0), grads=True, q_shared=False):
+    """The (16,16,2) ELBO kernels (csrc/lgssm_n16_elbo.h) step by step against a FLOAT64 run of the torch oracle.
+    family 2: per-step A, B, C and Q, one wavefront per (b,t) (k_elbo_n16<GRADS, HAS_GQ>) - with q_shared, ONE Q for the batch
+    whose gradient is wanted, which keeps the call on one step per wavefront; family 3: a Q shared by the batch and no gradient
+    of Q, four steps per wavefront (k_elbo4_n16<GRADS>).  `levels` = (level of Sigma_s, level of Q) of _safe_cholesky, forced by poisoning one
+    matrix.  The mask is zero at t = 0, at t = T-1, at the first step of the last four-step group and, when B > 1, for a whole
+    sequence.  Checks: the resolved levels and the family that ran (the launch reports it, so no tier passes on the generic
+    kernels); the total within 1e-4 of float64; and every gradient stack per (b,t) - max|got - ref| on the slice within
+    N16_ELBO_TOL of max(max|ref| on the slice, 1e-2 max|ref| on the tensor) - so a wrong tail group, step 0 (the only step whose
+    row-group 3 factorises Sigma0) or a masked step cannot hide behind the tensor's largest entry.  g mus / g Sigma_s must be
+    finite everywhere; a broadcast Q is compared as a whole tensor at the same bar.  Returns {name: (largest per-slice ratio, (b, t))}."""
+    from kvae.kalman.lgssm_ops import LgssmElbo, Slots
+    from oracle import c_oracle
+    from oracle import torch_oracle as O
+    assert family in (2, 3)
+    n, m, p = 16, 16, 2
+    assert not (q_shared and family == 3)
+    shared = family == 3 or q_shared
+    g = torch.Generator().manual_seed(1000 + 37 * B + T)
+    rn = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
+    eye = torch.eye(n, dtype=torch.float64)
+    mus = 0.5 * rn(B, T, n)
+    W = 0.1 * rn(B, T, n, n)
+    Sig = W @ W.mT + 0.3 * eye                                 # dense SPD
+    eps, Y, U = rn(B, T, n), rn(B, T, p), 0.3 * rn(B, T, m)
+    A = 0.9 * eye + 0.08 * rn(B, T, n, n)
+    Bm, Cm = 0.1 * rn(B, T, n, m), 0.3 * rn(B, T, p, n)
+    Wq = rn(*(() if shared else (B, T)), n, n)
+    Q = 0.02 * eye + 0.0005 * (Wq @ Wq.mT)                      # dense SPD: a factor and its transpose differ
+    R = torch.tensor([[0.03, 0.01], [0.01, 0.05]], dtype=torch.float64)
+    mu0 = 0.1 * rn(n)
+    W0 = 0.2 * rn(n, n)
+    S0 = W0 @ W0.T + 0.5 * eye                                  # dense: row-group 3 factorises a real matrix at t = 0
+    mask = torch.ones(B, T, dtype=torch.float64)
+    mask[:, 0] = 0.0
+    mask[:, T - 1] = 0.0
+    mask[:, 4 * ((T - 1) // 4)] = 0.0
+    if B > 1:
+        mask[1] = 0.0
+    lvS, lvQ = levels
+    sig_bad = {0: None, 2: -5e-5, 3: -4e-4, 5: -1.0}[lvS]
+    q_bad = {0: None, 1: -3e-6, 5: -1.0}[lvQ]
+    if sig_bad is not None:
+        Sig[B - 1, max(T - 3, 0)] = torch.diag(torch.tensor([sig_bad] + [0.2] * (n - 1), dtype=torch.float64))
+    if q_bad is not None:
+        assert T >= 2, "Q_t is factorised for t >= 1 only"
+        bad = torch.diag(torch.tensor([0.02] * 2 + [q_bad] + [0.02] * (n - 3), dtype=torch.float64))
+        if not shared:
+            Q[0, T - 1] = bad
+        else:
+            Q = bad
+    # the float32 operands are the problem; the float64 reference runs on exactly their values
+    f32 = [t.float() for t in (mus, Sig, eps, Y, U, mask, A, Bm, Cm, Q, R, mu0, S0)]
+    mus, Sig, eps, Y, U, mask, A, Bm, Cm, Q, R, mu0, S0 = [t.double() for t in f32]
+    d = [t.to(DEV) for t in f32]
+    names = ["mus", "Sigmas", "Y", "U", "A", "B", "C"] + (["Q"] if family == 2 else [])
+    idx = {"mus": 0, "Sigmas": 1, "Y": 3, "U": 4, "A": 6, "B": 7, "C": 8, "Q": 9}
+    leaves = [d[idx[k]].clone().requires_grad_(grads) for k in names]
+    lv = dict(zip(names, leaves))
+    args = [lv.get(k, d[i]) for i, k in enumerate(("mus", "Sigmas", "eps", "Y", "U", "mask", "A", "B", "C", "Q"))]
+    with torch.set_grad_enabled(grads):
+        total, terms, levels_dev = LgssmElbo.apply(*args[:6], None, *args[6:], d[10], d[11], d[12], Slots())
+    c = lambda t: t.detach().cpu()
+    Qx = Q.expand(B, T, n, n)
+    _, rlevels = c_oracle.elbo_terms(*(t.float() for t in (mus, Sig, eps, Y, U, mask, A, Bm, Cm, Qx, R, mu0, S0)))
+    assert list(rlevels[:2]) == list(levels), (list(rlevels), levels)
+    got_lv = c(levels_dev).tolist()
+    assert got_lv[:2] == list(levels), (got_lv, levels)
+    assert got_lv[2] == family, ("kernel family", got_lv[2], family)
+    # float64 reference
+    ref = {k: v.clone().requires_grad_(grads) for k, v in (("mus", mus), ("Sigmas", Sig), ("Y", Y), ("U", U), ("A", A), ("B", Bm),
+                                                            ("C", Cm), ("Q", Q))}
+    with torch.set_grad_enabled(grads):
+        rterms = O.lgssm_elbo_terms(ref["mus"], ref["Sigmas"], ref["Y"], ref["U"], ref["A"], ref["B"], ref["C"], ref["Q"], R, mu0,
+                                    S0, mask, eps)
+        rtotal = sum(rterms)
+    total_f, rtotal_f = float(total.detach()), float(rtotal.detach())
+    assert abs(total_f - rtotal_f) <= 1e-4 * abs(rtotal_f), (total_f, rtotal_f)
+    for i in range(4):
+        assert abs(float(terms[i]) - float(rterms[i].detach())) <= 1e-4 * abs(float(rterms[i].detach())) + 1e-3, (i, float(terms[i]), float(rterms[i].detach()))
+    if not grads:
+        return {}
+    total.backward()
+    rtotal.backward()
+    out = {}
+    for k in names:
+        got = c(lv[k].grad)
+        assert got is not None and bool(torch.isfinite(got).all()), (k, "non-finite gradient")
+        want = ref[k].grad
+        if want.dim() == 2:   # a broadcast Q: the whole tensor
+            out[k] = (float((got.double() - want).abs().max() / want.abs().max().clamp_min(1e-30)), None)
+        else:
+            out[k] = _per_step_ratio(got, want)
+        assert out[k][0] <= N16_ELBO_TOL, (k, out[k], levels, family)
+    return out
+
+
+def n16_elbo_unaligned(DEV, B=2, T=5):
+    """The (16,16,2) ELBO with a Sigma_s stack that starts 4 bytes off a 16-byte boundary: the gate of kvae_lgssm_elbo
+    (16-byte row loads / stores) sends it to the generic kernels (family 0), the aligned call to the matrix-core ones (family 2):
+    same total, same gradients (per (b,t), see n16_elbo_per_step)."""
+    from kvae.kalman.lgssm_ops import LgssmElbo, Slots
+    n, m, p = 16, 16, 2
+    g = torch.Generator().manual_seed(31)
+    rn = lambda *s: torch.randn(*s, generator=g)
+    mus, eps, Y, U = 0.5 * rn(B, T, n), rn(B, T, n), rn(B, T, p), 0.3 * rn(B, T, m)
+    W = 0.1 * rn(B, T, n, n)
+    Sig = W @ W.mT + 0.3 * torch.eye(n)
+    A, Bm, Cm = torch.eye(n) + 0.08 * rn(B, T, n, n), 0.1 * rn(B, T, n, m), 0.3 * rn(B, T, p, n)
+    Wq = rn(B, T, n, n)
+    Q = 0.02 * torch.eye(n) + 0.0005 * (Wq @ Wq.mT)
+    R, mu0, S0 = 0.03 * torch.eye(p), 0.1 * rn(n), 2.0 * torch.eye(n)
+    mask = (torch.rand(B, T, generator=g) > 0.3).float()
+    d = lambda t: t.to(DEV)
+    res = []
+    for odd in (False, True):
+        leaves = [d(t).clone().requires_grad_(True) for t in (mus, Y, U, A, Bm, Cm, Q)]
+        base = torch.zeros(B * T * n * n + (1 if odd else 0), device=DEV)
+        base[(1 if odd else 0):].copy_(d(Sig).reshape(-1))
+        base.requires_grad_(True)
+        Sig_in = base[(1 if odd else 0):].view(B, T, n, n)        # (a .clone() would re-align it)
+        assert (Sig_in.data_ptr() % 16 != 0) == odd
+        total, _, levels = LgssmElbo.apply(leaves[0], Sig_in, d(eps), leaves[1], leaves[2], d(mask), None, leaves[3], leaves[4],
+                                           leaves[5], leaves[6], d(R), d(mu0), d(S0), Slots())
+        total.backward()
+        gS = base.grad[(1 if odd else 0):].view(B, T, n, n)
+        res.append((float(total.detach()), int(levels[2]), [gS.cpu()] + [t.grad.cpu() for t in leaves]))
+    (t_fast, fam_fast, g_fast), (t_slow, fam_slow, g_slow) = res
+    assert (fam_fast, fam_slow) == (2, 0), (fam_fast, fam_slow)
+    assert abs(t_fast - t_slow) <= 2e-5 * abs(t_slow), (t_fast, t_slow)
+    for k, a, b in zip(("Sigmas", "mus", "Y", "U", "A", "B", "C", "Q"), g_fast, g_slow):
+        r = _per_step_ratio(a, b.double())
+        assert r[0] <= 1e-3, (k, r)
+
+
+def jitter_golden(DEV, name, levels, family=None):
     """The product's ELBO (probe + atomicMax level + terms + gradients, csrc/lgssm_elbo.h) against fixtures that drive the
     REFERENCE's own elbo past level 0 of _safe_cholesky (tests/golden/make_goldens_r2.py): resolved levels, value
     (1e-4 rel, north_star) and every gradient the reference's autograd produced (3e-3 rel)."""
@@ -416,6 +565,8 @@ def jitter_golden(DEV, name, levels):
                                leaves["A_list"], leaves["B_list"], leaves["C_list"], leaves["Q_list"], d["R"], d["mu0"],
                                d["Sigma0"], Slots())
     assert levels_dev.cpu().tolist()[:2] == levels
+    if family is not None:   # (the CPU tier on emulated wavefronts: tests/test_wave_emu_elbo.py)
+        assert int(levels_dev[2]) == family, int(levels_dev[2])
     if str(DEV).startswith("cuda") and d["Sig_s"].shape[-1] == 16:
         # the (16,16,2) matrix-core kernels computed this call at a RAISED level themselves (no generic backup launch):
         # family 2 = one step per wavefront (a per-step Q_list)

@@ -187,6 +187,35 @@ def test_safe_cholesky_levels_shared_q(n, B, T):
     parity_cases.safe_cholesky_levels_shared_q(DEV, n, B, T)
 
 
+@pytest.mark.parametrize("family", [2, 3])
+@pytest.mark.parametrize("grads", [True, False])
+@pytest.mark.parametrize("B,T", [(1, 1), (1, 2), (1, 3), (1, 4), (1, 5), (3, 1), (3, 2), (3, 3), (3, 4), (3, 5), (7, 9), (33, 13)])
+def test_elbo_n16_per_step_gpu(family, grads, B, T):
+    """The (16,16,2) ELBO kernels per (b,t) against float64 (parity_cases.n16_elbo_per_step): every T % 4, and grids that are
+    not multiples of the 8 XCDs and span more than one round of the XCD remap ((7,9), (33,13))."""
+    parity_cases.n16_elbo_per_step(DEV, B, T, family, (0, 0), grads)
+
+
+@pytest.mark.parametrize("family", [2, 3])
+@pytest.mark.parametrize("levels", [(0, 0), (0, 1), (3, 0), (5, 0), (2, 5)])
+def test_elbo_n16_levels_per_step_gpu(family, levels):
+    parity_cases.n16_elbo_per_step(DEV, 2, 7, family, levels, True)
+
+
+@pytest.mark.parametrize("levels", [(0, 0), (0, 1)])
+def test_elbo_n16_shared_q_with_its_gradient_gpu(levels):
+    parity_cases.n16_elbo_per_step(DEV, 3, 5, 2, levels, True, q_shared=True)
+
+
+def test_elbo_n16_configs4_slice_per_step_gpu():
+    """A configs[4]-shaped slice (T = 200, shared Q, gradients): four steps per wavefront, per (b,t)."""
+    parity_cases.n16_elbo_per_step(DEV, 8, 200, 3, (0, 0), True)
+
+
+def test_elbo_n16_unaligned_takes_the_generic_kernels_gpu():
+    parity_cases.n16_elbo_unaligned(DEV)
+
+
 @pytest.mark.parametrize("name,levels", JITTER_CASES)
 def test_jitter_golden_gpu(name, levels):
     """_safe_cholesky past level 0, pinned to the REFERENCE (fixtures driven through its own elbo)."""

@@ -30,6 +30,7 @@ parity_cases.dec_up_vs_torch("cpu", 2, 4)
 parity_cases.vae_heads_vs_torch("cpu", 5)
 # the product's wavefront-level kernels (lgssm_m4.h / lgssm_q4.h, lgssm_n16.h) on emulated wavefronts (hostsim/wave_emu.h):
 # ragged last wavefront (19 sequences, 16 per wavefront), the tails of the unrolled loops (T = 3, T = 1), 16-byte accesses
+# (UBSan's alignment check covers every one of them)
 lib = _native.lib_for(torch.zeros(1))
 lib.dll.kvae_hostsim_wave_emu(1)
 for dims in ((19, 3, 4, 4, 2, 3), (1, 1, 4, 4, 2, 2), (2, 3, 16, 16, 2, 2)):
@@ -38,6 +39,12 @@ lib.dll.kvae_wemu_m4_split_max_b(0)      # (4,4,2) again in its single-launch fo
 parity_cases.vs_oracle_random("cpu", 19, 4, 4, 4, 2, 3)
 lib.dll.kvae_wemu_m4_split_max_b(-1)
 assert min(lib.dll.kvae_wemu_launches(i) for i in range(4)) > 0
+# the (16,16,2) ELBO kernels (lgssm_n16_elbo.h): per-step Q with its gradient (k_elbo_n16<true, true>), the four-steps-per-
+# wavefront layout with a ragged last group (T = 5), the diagonal fallback of Sigma_s (elbo_zfix redoes the samples)
+parity_cases.n16_elbo_per_step("cpu", 2, 3, 2, (0, 0), True)
+parity_cases.n16_elbo_per_step("cpu", 2, 5, 3, (0, 0), True)
+parity_cases.n16_elbo_per_step("cpu", 3, 5, 2, (5, 0), True)
+assert min(lib.dll.kvae_wemu_launches(i) for i in (4, 5)) >= 3
 lib.dll.kvae_hostsim_wave_emu(0)
 print("ASAN-OK")
 """
