@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 #define KVAE_MAX_DIM 16
-#define KVAE_ABI_VERSION 10
+#define KVAE_ABI_VERSION 11
 
 typedef enum {
   KVAE_OK = 0,
@@ -389,6 +389,51 @@ int kvae_loss_head_fwd(const float *lpx, const float *regf, const float *mask, c
                        float *coef3, int64_t n, void *stream);
 int kvae_loss_head_bwd(const float *g_loss, const float *coef3, const float *mask, float *g_lpx, float *g_regf,
                        float *g_elbo_kf, int64_t n, void *stream);
+
+/* ---- generation: sampled futures from the learned dynamics (kvae/model/model.py KVAE.generate) ------------------------
+ * R = B*S rollouts (rollout r = b*S + s continues sequence b), H steps each, all in ONE launch.  Step h = 0..H-1:
+ *   lstm (kind 0):      (hc) = LSTM(y_{h-1}, hc), alpha_h = softmax(head(h)) (alpha = 1 for K == 1),
+ *                       A_h, B_h, C_h = sum_k alpha_hk (A_k, B_k, C_k)
+ *   switching (kind 1): pi_h = s_{h-1} P;  s_h = one_hot(argmax(log pi_h + gumbel_h)), or s_h = pi_h without gumbel;
+ *                       A_h, B_h, LQ_h = sum_k s_hk (A_k, B_k, LQ_k), C_h = C_0
+ *   both:               z_h = A_h z_{h-1} + B_h u_h + LQ_h eps_z_h,  a_h = C_h z_h + LR eps_a_h,  y_h = a_h
+ * z_{-1} = mu_b + L0_b eps0_r.  A NULL noise pointer drops that term (all four NULL = the noise-free rollout).  Noise is
+ * never drawn here: the caller draws it.  Limits: n, m, p, K in [1, KVAE_MAX_DIM] (else KVAE_ERR_DIMS); lstm with K > 1
+ * needs hidden == 50 and p == 2 (KVAE_ERR_DIMS); switching with eps_z needs gumbel (one-hot regimes: LQ_h is then the
+ * Cholesky factor of Q_h), else KVAE_ERR_ARG, as is a kind other than 0 / 1. */
+typedef struct {
+  int32_t B, S, H;          /* sequences, samples per sequence, horizon (all >= 1)                                 */
+  int32_t n, m, p, K;       /* dims of z, u, a; modes / regimes                                                     */
+  int32_t kind;             /* 0 = lstm alpha-network, 1 = switching (sticky Markov regimes)                      */
+  int32_t hidden;           /* lstm, K > 1: units of the alpha-network LSTM (must be 50)                          */
+  const float *A;           /* [K,n,n]   required                                                                 */
+  const float *Bm;          /* [K,n,m]   required                                                                 */
+  const float *C;           /* [K,p,n]   required (switching reads C[0] only)                                    */
+  const float *LQ;          /* lstm [n,n] / switching [K,n,n]: Cholesky factors of Q; may be NULL iff eps_z is NULL */
+  const float *LR;          /* [p,p] Cholesky factor of R; may be NULL iff eps_a is NULL                         */
+  const float *mu;          /* [B,n]     mu_{T0-1|T0-1} of the conditioning filter, required                     */
+  const float *L0;          /* [B,n,n]   Cholesky factor of Sigma_{T0-1|T0-1}; may be NULL iff eps0 is NULL       */
+  const float *U;           /* [B,H,m]   controls u_{T0..T0+H-1}; NULL = zeros                                    */
+  const float *w_ih;        /* lstm, K > 1 (else may be NULL): [4*hidden,p] LSTM, torch gate order i|f|g|o         */
+  const float *w_hh;        /* [4*hidden,hidden]                                                                      */
+  const float *b_ih;        /* [4*hidden]                                                                             */
+  const float *b_hh;        /* [4*hidden]                                                                             */
+  const float *head_w;      /* [K,hidden]                                                                             */
+  const float *head_b;      /* [K]                                                                                    */
+  const float *h0;          /* [B,hidden] LSTM state after conditioning step T0-1                                    */
+  const float *c0;          /* [B,hidden]                                                                             */
+  const float *y0;          /* [B,p]      the alpha-network input y_{T0-1} (frame, or C mu_{t|t-1} where hidden)      */
+  const float *P;           /* switching (else may be NULL): [K,K] prior transition matrix, rows sum to 1            */
+  const float *s0;          /* [B,K]      regime of conditioning step T0-1                                           */
+  const float *eps0;        /* [R,n]   or NULL                                                                        */
+  const float *eps_z;       /* [R,H,n] or NULL                                                                        */
+  const float *eps_a;       /* [R,H,p] or NULL                                                                        */
+  const float *gumbel;      /* [R,H,K] or NULL (switching only)                                                      */
+  float *a_out;             /* [R,H,p]  required                                                                      */
+  float *z_out;             /* [R,H,n]  required                                                                      */
+  float *w_out;             /* [R,H,K]  alpha_h or s_h, required                                                      */
+} kvae_gen_problem;
+int kvae_lgssm_generate(const kvae_gen_problem *prob, void *stream);
 
 /* ---- misc --------------------------------------------------------------------------------- */
 int kvae_abi_version(void);

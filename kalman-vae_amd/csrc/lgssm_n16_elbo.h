@@ -661,3 +661,9 @@ __device__ __forceinline__ void elbo_zfix_wave(const kvae_lgssm_problem &P, cons
 }  // namespace n16
 }  // namespace kvae
 #endif
+
+// The host simulation's entry point of the generation rollout (csrc/lgssm_gen.h, its KVAE_WAVE_EMU section): the wavefront
+// emulation unit of the host simulation includes this header, and through it that one.
+#if defined(KVAE_WAVE_EMU)
+#include "lgssm_gen.h"
+#endif

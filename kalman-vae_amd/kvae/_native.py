@@ -17,7 +17,7 @@ LIB_PATH = _HERE / "lib" / "libkvae_lgssm.so"
 KVAE_MAX_DIM = 16
 KVAE_MAX_K = 16
 LSTM_MAX_H, LSTM_MAX_I = 52, 16
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _STATUS = {1: "KVAE_ERR_DIMS (n, m, p must be in [1,16]; B, T >= 1)", 2: "KVAE_ERR_NULL", 3: "KVAE_ERR_LAUNCH",
            4: "KVAE_ERR_ARG"}
@@ -46,6 +46,13 @@ class WgradProblem(C.Structure):  # kvae_wgrad_problem
                 ("R", C.c_int32), ("H", C.c_int32), ("I", C.c_int32), ("bias", C.c_int32), ("T", C.c_int32), ("shift", C.c_int32)]
 
 
+class GenProblem(C.Structure):  # kvae_gen_problem
+    _fields_ = ([(k, C.c_int32) for k in ("B", "S", "H", "n", "m", "p", "K", "kind", "hidden")]
+                + [(k, C.c_void_p) for k in ("A", "Bm", "C", "LQ", "LR", "mu", "L0", "U", "w_ih", "w_hh", "b_ih", "b_hh",
+                                             "head_w", "head_b", "h0", "c0", "y0", "P", "s0", "eps0", "eps_z", "eps_a",
+                                             "gumbel", "a_out", "z_out", "w_out")])
+
+
 class InputGrads(C.Structure):  # kvae_lgssm_input_grads
     _fields_ = [("gA", Stack), ("gB", Stack), ("gC", Stack), ("gQ", Stack),
                 ("gY", C.c_void_p), ("gU", C.c_void_p), ("g_mu0", C.c_void_p), ("g_Sigma0", C.c_void_p)]
@@ -59,7 +66,7 @@ SYMBOLS = ("kvae_lgssm_filter_alpha_lstm", "kvae_lgssm_alpha_lstm_bwd", "kvae_lg
            "kvae_dec_up_fwd", "kvae_dec_up_bwd", "kvae_dec_up_partial_rows", "kvae_dec_up_set_workgroups",
            "kvae_enc_head_fwd", "kvae_enc_head_bwd", "kvae_dec_fc_fwd", "kvae_dec_fc_bwd", "kvae_head_partial_rows",
            "kvae_latent_reg_fwd", "kvae_latent_reg_bwd", "kvae_loss_head_fwd", "kvae_loss_head_bwd",
-           "kvae_lgssm_emission_means", "kvae_rnn_wgrad", "kvae_rnn_wgrad_ws_floats", "kvae_linear_fwd", "kvae_linear_bwd_input",
+           "kvae_lgssm_emission_means", "kvae_lgssm_generate", "kvae_rnn_wgrad", "kvae_rnn_wgrad_ws_floats", "kvae_linear_fwd", "kvae_linear_bwd_input",
            "kvae_abi_version",
            "kvae_last_error", "kvae_build_info")
 
@@ -82,6 +89,8 @@ class LgssmLib:
         d.kvae_lgssm_filter_alpha_lstm.restype = C.c_int
         d.kvae_lgssm_alpha_lstm_bwd.argtypes = [P, S, S, G, vp, C.c_int] + [vp] * 6 + [C.c_int32, C.c_int32] + [vp] * 9
         d.kvae_lgssm_alpha_lstm_bwd.restype = C.c_int
+        d.kvae_lgssm_generate.argtypes = [C.POINTER(GenProblem), vp]
+        d.kvae_lgssm_generate.restype = C.c_int
         d.kvae_lgssm_smooth_bwd.argtypes = [P, S, S, G, vp, C.c_int, vp]
         d.kvae_lgssm_smooth_bwd.restype = C.c_int
         d.kvae_lgssm_elbo.argtypes = [P, vp, vp, vp, vp, vp, vp, vp, vp, G, vp]

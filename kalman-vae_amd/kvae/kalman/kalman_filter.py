@@ -177,6 +177,47 @@ class KalmanFilter(nn.Module):
         ms, Ss, mf, Sf, mp, Sp = self._run(Y, U, mask, with_rts=True)
         return (ms, Ss, mf, Sf, mp, Sp) + tuple(self._last["views"])
 
+    @torch.no_grad()
+    def condition(self, Y, U, mask=None):
+        """Hand-over of the filter over the conditioning frames Y [B,T0,p] to KVAE.generate: mu_{T0-1|T0-1} [B,n],
+        Sigma_{T0-1|T0-1} [B,n,n] and what the dynamics carry across the boundary - lstm (K > 1): the cell state (h, c)
+        [B,H] after step T0-1 and the next alpha-network input y [B,p] (the frame if observed, else C_t mu_{t|t-1}:
+        reference kalman_filter.py:183-185); switching: the regime s [B,K] of step T0-1."""
+        dyn = self.dyn_params
+        Bsz, T0, _ = Y.shape
+        mask = self._mask(mask, Y)
+        dyn.reset_state()
+        out = {}
+        if (not dyn.is_switching_dynamics and dyn.K > 1 and lgssm_ops.alpha_lstm_supported(Y, dyn.lstm, dyn.K)):
+            m = mask if mask is not None else torch.ones(Bsz, T0, device=Y.device, dtype=Y.dtype)
+            mf, Sf, mp, Sp, rec, alpha, h_seq, c_seq = lgssm_ops.AlphaLstmSmooth.apply(
+                Y, U, m, dyn.lstm.weight_ih_l0, dyn.lstm.weight_hh_l0, dyn.lstm.bias_ih_l0, dyn.lstm.bias_hh_l0,
+                dyn.head_w.weight, dyn.head_w.bias, dyn.A, dyn.B, dyn.C, self.Q, self.R, self.mu0, self.Sigma0, False, True)
+            n, mm = self.n, self.m
+            C_last = rec[:, -1, n * n + n * mm:].unflatten(-1, (self.p, n))
+            dyn.state_seq = alpha
+            out.update(h=h_seq[:, -1], c=c_seq[:, -1])
+            mf, mp = mf.unsqueeze(-1), mp.unsqueeze(-1)
+        else:
+            mf, Sf, mp, Sp, _, _, C_list = self.filter(Y, U, mask)
+            C_last = C_list[:, -1]
+            if not dyn.is_switching_dynamics and dyn.K > 1:   # the cell state: the LSTM over the inputs the filter fed it
+                y_dyn = Y if mask is None else (mask.unsqueeze(-1) * Y
+                                                + (1.0 - mask.unsqueeze(-1)) * (C_list @ mp).squeeze(-1))
+                x = torch.cat([Y.new_zeros(Bsz, 1, self.p), y_dyn[:, :-1]], 1)
+                _, (h, c) = dyn.lstm(x)
+                out.update(h=h[0], c=c[0])
+        if dyn.is_switching_dynamics:
+            out["s"] = dyn.state_seq[:, -1]
+        elif dyn.K > 1:
+            y = Y[:, -1]
+            if mask is not None:
+                mt = mask[:, -1:]
+                y = mt * y + (1.0 - mt) * (C_last @ mp[:, -1]).squeeze(-1)
+            out["y"] = y
+        out.update(mu=mf[:, -1].squeeze(-1), Sigma=Sf[:, -1])
+        return out
+
     def emission_means(self, mus_smooth, mus_filt, C_list):
         """(C_t mu_t|T, C_t mu_t|t): the two latent read-outs KVAE.impute decodes (reference model.py:279-288), one launch."""
         last = self._last

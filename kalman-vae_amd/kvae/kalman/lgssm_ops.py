@@ -524,7 +524,9 @@ class AlphaLstmSmooth(torch.autograd.Function):
     and T single-step filter launches each way.  Returns (ms, Ss,) mf, Sf, mp, Sp, record [B,T,A|B|C], alpha [B,T,K]."""
 
     @staticmethod
-    def forward(ctx, Y, U, mask, w_ih, w_hh, b_ih, b_hh, head_w, head_b, A, Bm, Cm, Q, R, mu0, Sigma0, with_rts):
+    def forward(ctx, Y, U, mask, w_ih, w_hh, b_ih, b_hh, head_w, head_b, A, Bm, Cm, Q, R, mu0, Sigma0, with_rts, keep_cell=False):
+        """keep_cell (addition): also return the cell's h_seq, c_seq [B,T,H] - the hand-over KVAE.generate needs - even
+        when nothing is differentiated."""
         Y, U, mask = _f32c(Y), _f32c(U), _f32c(mask)
         ws_ = [_f32c(t.detach()) for t in (w_ih, w_hh, b_ih, b_hh, head_w, head_b, A, Bm, Cm)]
         Bsz, T, p = Y.shape
@@ -537,6 +539,8 @@ class AlphaLstmSmooth(torch.autograd.Function):
         record, alpha = mk(Bsz, T, E), mk(Bsz, T, K)
         need = any(ctx.needs_input_grad)
         gates, c_seq, h_seq, x_seq = (mk(Bsz, T, 4 * H), mk(Bsz, T, H), mk(Bsz, T, H), mk(Bsz, T, p)) if need else (None,) * 4
+        if keep_cell and not need:
+            c_seq, h_seq = mk(Bsz, T, H), mk(Bsz, T, H)
         slots = Slots(A=0, B=n * n, C=n * n + n * m)
         call = _Call(Y, U, mask, record, None, None, None, Q, R, mu0, Sigma0, slots)
         ms, Ss = (mk(Bsz, T, n), mk(Bsz, T, n, n)) if with_rts else (None, None)
@@ -546,16 +550,18 @@ class AlphaLstmSmooth(torch.autograd.Function):
             N.ptr(c_seq), N.ptr(h_seq), N.ptr(x_seq), call.stream)), "kvae_lgssm_filter_alpha_lstm")
         if with_rts:
             call.lib.check(call.lib.dll.kvae_lgssm_rts_fwd(C.byref(call.prob), C.byref(st), call.stream), "kvae_lgssm_rts_fwd")
-        ctx.with_rts, ctx.slots = with_rts, slots
+        ctx.with_rts, ctx.slots, ctx.keep_cell = with_rts, slots, keep_cell
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(Y, U, mask, *ws_, Q, R, mu0, Sigma0, mf, Sf, mp, Sp, ms, Ss, record, alpha, gates, c_seq, h_seq, x_seq)
-        return ((ms, Ss) if with_rts else ()) + (mf, Sf, mp, Sp, record, alpha)
+        return ((ms, Ss) if with_rts else ()) + (mf, Sf, mp, Sp, record, alpha) + ((h_seq, c_seq) if keep_cell else ())
 
     @staticmethod
     def backward(ctx, *gouts):
         (Y, U, mask, w_ih, w_hh, b_ih, b_hh, head_w, head_b, A, Bm, Cm, Q, R, mu0, Sigma0, mf, Sf, mp, Sp, ms, Ss, record, alpha,
          gates, c_seq, h_seq, x_seq) = ctx.saved_tensors
         with_rts, slots = ctx.with_rts, ctx.slots
+        if ctx.keep_cell:   # h_seq / c_seq are read-outs: no gradient flows back through them
+            gouts = gouts[:-2]
         if with_rts:
             g_ms, g_Ss, g_mf, g_Sf, g_mp, g_Sp, g_rec, g_alpha = (_f32c(g) for g in gouts)
         else:
@@ -604,7 +610,7 @@ class AlphaLstmSmooth(torch.autograd.Function):
         if S0 is not None and Sigma0.dim() == 2:
             S0 = N.colsum(S0)
         return (sink.gY if need[0] else None, sink.gU if need[1] else None, None, g_wih, g_whh, g_b, g_b, g_hw, g_hb,
-                gA, gB, gC, None, None, g0, S0, None)
+                gA, gB, gC, None, None, g0, S0, None, None)
 
 
 @torch.no_grad()
@@ -632,3 +638,119 @@ def rts_only(Y, U, mask, packed, A, Bm, Cm, Q, R, mu0, Sigma0, slots, mf, Sf, mp
     st = _states(mf, Sf, mp, Sp, ms, Ss)
     call.lib.check(call.lib.dll.kvae_lgssm_rts_fwd(C.byref(call.prob), C.byref(st), call.stream), "kvae_lgssm_rts_fwd")
     return ms, Ss
+
+
+# ------------------------------------------------------------------------------------------------
+# generation: the closed-loop rollout of KVAE.generate (kvae_lgssm_generate, csrc/lgssm_gen.h)
+# ------------------------------------------------------------------------------------------------
+def safe_cholesky(Sigma, max_tries=5, jitter_init=1e-6):
+    """The reference's _safe_cholesky ladder (kalman_filter.py:282-303 there) over a batch [..., n, n]: symmetrise, add
+    jitter 1e-6 * 10^level until the WHOLE batch factorises (levels 0..4), else the clamped-diagonal fallback."""
+    Sigma = 0.5 * (Sigma + Sigma.mT)
+    eye = torch.eye(Sigma.shape[-1], device=Sigma.device, dtype=Sigma.dtype)
+    jitter = jitter_init
+    for _ in range(max_tries):
+        L, info = torch.linalg.cholesky_ex(Sigma + jitter * eye)
+        if not bool((info != 0).any()):
+            return L
+        jitter *= 10.0
+    return torch.diag_embed(torch.sqrt(torch.diagonal(Sigma, dim1=-2, dim2=-1).clamp(min=1e-6)))
+
+
+GEN_LSTM = dict(hidden=50, p=2)   # the alpha-network shape csrc/lgssm_gen.h holds in LDS
+
+
+def rollout_supported(kind, K, n, m, p, hidden=None, ref=None):
+    """Shapes kvae_lgssm_generate is built for (include/kvae_lgssm.h); every other one takes rollout_torch."""
+    if ref is not None and not (N.fused_ok(ref) and ref.dtype == torch.float32):
+        return False
+    if not all(1 <= d <= N.KVAE_MAX_DIM for d in (n, m, p)) or not 1 <= K <= N.KVAE_MAX_K:
+        return False
+    return kind == "switching" or K == 1 or (hidden == GEN_LSTM["hidden"] and p == GEN_LSTM["p"])
+
+
+def rollout(kind, A, Bm, Cm, mu, L0, U, LQ, LR, S, H, lstm=None, h0=None, c0=None, y0=None, P=None, s0=None,
+            eps0=None, eps_z=None, eps_a=None, gumbel=None, impl=None):
+    """Closed-loop rollout of the learned dynamics for R = B*S rollouts and H steps (semantics: include/kvae_lgssm.h,
+    kvae_lgssm_generate; DESIGN.md section 9).  kind "lstm" | "switching"; A [K,n,n], Bm [K,n,m], Cm [K,p,n]; mu [B,n];
+    L0 [B,n,n]; U [B,H,m] or None; LQ [n,n] (lstm) / [K,n,n] (switching); LR [p,p]; lstm = (w_ih, w_hh, b_ih, b_hh, head_w,
+    head_b) with h0, c0 [B,hidden], y0 [B,p] (K > 1); P [K,K], s0 [B,K] (switching).  Noise tensors [B,S,(H,)d] or None.
+    impl: None = the HIP kernel where the shape is built, else the torch recursion; "kernel" / "torch" force one.
+    Returns a [B,S,H,p], z [B,S,H,n], weights [B,S,H,K]."""
+    K, n, m, p = A.shape[0], A.shape[1], Bm.shape[2], Cm.shape[1]
+    hidden = lstm[1].shape[1] if lstm is not None else None
+    use_kernel = impl == "kernel" or (impl is None and rollout_supported(kind, K, n, m, p, hidden, mu))
+    if not use_kernel:
+        return rollout_torch(kind, A, Bm, Cm, mu, L0, U, LQ, LR, S, H, lstm, h0, c0, y0, P, s0, eps0, eps_z, eps_a, gumbel)
+    Bsz = mu.shape[0]
+    dev = mu.device
+    mk = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
+    a, z, w = mk(Bsz, S, H, p), mk(Bsz, S, H, n), mk(Bsz, S, H, K)
+    keep = {}
+    pr = N.GenProblem()
+    pr.B, pr.S, pr.H, pr.n, pr.m, pr.p, pr.K = Bsz, S, H, n, m, p, K
+    pr.kind = 1 if kind == "switching" else 0
+    pr.hidden = hidden or 0
+    named = dict(A=A, Bm=Bm, C=Cm, LQ=LQ, LR=LR, mu=mu, L0=L0, U=U, P=P, s0=s0, h0=h0, c0=c0, y0=y0,
+                 eps0=eps0, eps_z=eps_z, eps_a=eps_a, gumbel=gumbel)
+    if lstm is not None:
+        named.update(zip(("w_ih", "w_hh", "b_ih", "b_hh", "head_w", "head_b"), lstm))
+    for k, t in named.items():
+        if t is not None:
+            keep[k] = _f32c(t.detach().to(dev))
+            setattr(pr, k, keep[k].data_ptr())
+    pr.a_out, pr.z_out, pr.w_out = a.data_ptr(), z.data_ptr(), w.data_ptr()
+    lib = N.lib_for(mu)
+    lib.check(N.timed("generate", mu, lambda: lib.dll.kvae_lgssm_generate(C.byref(pr), N.stream_for(mu))), "kvae_lgssm_generate")
+    return a, z, w
+
+
+def rollout_torch(kind, A, Bm, Cm, mu, L0, U, LQ, LR, S, H, lstm=None, h0=None, c0=None, y0=None, P=None, s0=None,
+                  eps0=None, eps_z=None, eps_a=None, gumbel=None):
+    """The same recursion as csrc/lgssm_gen.h in torch ops, in the dtype of mu (fp32 on the product path): the shapes the
+    kernel is not built for (alpha-network hidden != 50 or a_dim != 2) - about fifteen launches per step."""
+    K = A.shape[0]
+    Bsz = mu.shape[0]
+    rep = lambda t: t.repeat_interleave(S, 0)
+    flat = lambda t: None if t is None else t.reshape(Bsz * S, *t.shape[2:]).to(mu.dtype)
+    eps0, eps_z, eps_a, gumbel = flat(eps0), flat(eps_z), flat(eps_a), flat(gumbel)
+    z = rep(mu)
+    if eps0 is not None:
+        z = z + (rep(L0) @ eps0.unsqueeze(-1)).squeeze(-1)
+    R = z.shape[0]
+    if kind == "switching":
+        s = rep(s0)
+    elif K == 1:
+        w = z.new_ones(R, 1)
+    else:
+        w_ih, w_hh, b_ih, b_hh, head_w, head_b = lstm
+        h, c, y = rep(h0), rep(c0), rep(y0)
+    a_out, z_out, w_out = [], [], []
+    for t in range(H):
+        if kind == "switching":
+            pi = s @ P
+            if gumbel is not None:
+                s = torch.nn.functional.one_hot((pi.log() + gumbel[:, t]).argmax(-1), K).to(pi.dtype)
+            else:
+                s = pi
+            w = s
+        elif K > 1:
+            gi, gf, gg, go = (y @ w_ih.T + h @ w_hh.T + b_ih + b_hh).chunk(4, -1)
+            c = torch.sigmoid(gf) * c + torch.sigmoid(gi) * torch.tanh(gg)
+            h = torch.sigmoid(go) * torch.tanh(c)
+            w = torch.softmax(h @ head_w.T + head_b, -1)
+        zn = torch.einsum("rk,kij,rj->ri", w, A, z)
+        if U is not None:
+            zn = zn + torch.einsum("rk,kij,rj->ri", w, Bm, rep(U[:, t]))
+        if eps_z is not None:
+            LQt = torch.einsum("rk,kij->rij", w, LQ) if kind == "switching" else LQ
+            zn = zn + (LQt @ eps_z[:, t].unsqueeze(-1)).squeeze(-1)
+        z = zn
+        a = Cm[0] @ z.unsqueeze(-1) if kind == "switching" else torch.einsum("rk,kij,rj->ri", w, Cm, z).unsqueeze(-1)
+        a = a.squeeze(-1)
+        if eps_a is not None:
+            a = a + (LR @ eps_a[:, t].unsqueeze(-1)).squeeze(-1)
+        y = a
+        a_out.append(a), z_out.append(z), w_out.append(w)
+    un = lambda lst: torch.stack(lst, 1).reshape(Bsz, S, H, -1)
+    return un(a_out), un(z_out), un(w_out)

@@ -13,8 +13,9 @@ from torch import nn
 
 from kvae import _native, noise
 from kvae.kalman import dyn_param as base_dyn_param
-from kvae.kalman import switch_dyn_param
+from kvae.kalman import lgssm_ops, switch_dyn_param
 from kvae.kalman.kalman_filter import KalmanFilter
+from kvae.noise import take as _take_noise
 from kvae.vae.losses import LinearScheduler, count_active_units, vae_loss
 from kvae.vae.vae import Decoder, Encoder
 
@@ -285,3 +286,77 @@ class KVAE(nn.Module):
         return {"x_recon": out["x_recon"], "x_imputed": x_imputed, "x_filtered": x_filtered,
                 "a_vae": out["a_samples"], "a_imputed": a_imputed, "a_filtered": a_filtered,
                 "state_probs": out["state_probs"]}
+
+    @torch.no_grad()
+    def generate(self, x, horizon, num_samples=1, u=None, mask=None, noise=True, decode=True):
+        """Continue each sequence: `num_samples` sampled futures of `horizon` frames from the learned dynamics (no counterpart in
+        the reference).  B sequences, T0 = x.shape[1] conditioning frames, S = num_samples, H = horizon.
+
+        1. Conditioning: encode x (as forward does) and run the eval-mode filter over it (optional `mask` [B,T0], controls
+           u[:, :T0]); hand over mu, Sigma of step T0-1 and, for lstm dynamics, the alpha-network's cell state and next input
+           (the frame, or C mu_{t|t-1} where it is hidden), for switching dynamics the regime of step T0-1.
+        2. Start: z = mu + L_Sigma eps0 (L_Sigma: the reference's _safe_cholesky ladder); z = mu without noise.
+        3. Steps t = T0 .. T0+H-1.  lstm: alpha_t = softmax(head(LSTM(y_{t-1}))) (alpha = 1 for K = 1), A_t|B_t|C_t mixed by
+           alpha_t, Q = kalman_filter.Q.  switching: pi_t = s_{t-1} P (sticky prior); with noise s_t = one_hot(argmax(log pi_t +
+           Gumbel)), without noise s_t = pi_t - a mean-field read-out, not a sample; A_t|B_t|Q_t mixed by s_t, C_t = C_0.
+           Both: z_t = A_t z_{t-1} + B_t u_t + L_{Q_t} eps_t, a_t = C_t z_t + L_R eta_t, and y_t = a_t feeds the next step.
+           Without noise the lstm rollout is the filter with the tail hidden: a_t = C_t mu_{t|t-1}.
+        4. x = decoder(a) through the frame VAE.
+
+        Every draw is made here with torch before the one rollout launch (kvae.noise.inject: gen_z0, gen_z, gen_a, gen_gumbel).
+        u: [B, T0+H, m] or None (zeros).  Returns a [B,S,H,p], z [B,S,H,n], weights [B,S,H,K] (alpha or regimes),
+        x [B,S,H,C,h,w] (None with decode=False) and a_vae [B,T0,p].  Training mode and parameters are left as they were."""
+        horizon, num_samples = int(horizon), int(num_samples)
+        if horizon < 1:
+            raise ValueError(f"generate: horizon must be >= 1, got {horizon}")
+        if num_samples < 1:
+            raise ValueError(f"generate: num_samples must be >= 1, got {num_samples}")
+        Bsz, T0 = x.shape[:2]
+        H, S = horizon, num_samples
+        if u is not None and (u.dim() != 3 or u.shape[0] != Bsz or u.shape[1] != T0 + H or u.shape[2] != self.u_dim):
+            raise ValueError(f"generate: u must be [B, T0+H, m] = [{Bsz}, {T0 + H}, {self.u_dim}], got {list(u.shape)}")
+        was_training = self.training
+        self.eval()
+        try:
+            kf, dyn = self.kalman_filter, self.kalman_filter.dyn_params
+            a_vae, _, _ = self.encode_sequence(x)
+            dev, dt = a_vae.device, a_vae.dtype
+            if u is None:
+                u_cond, u_fut = torch.zeros(Bsz, T0, self.u_dim, device=dev, dtype=dt), None
+            else:
+                u = u.to(device=dev, dtype=dt)
+                u_cond, u_fut = u[:, :T0], u[:, T0:]
+            hand = kf.condition(a_vae, u_cond, mask)
+            n, p, K = self.z_dim, self.a_dim, self.K
+            switching = dyn.is_switching_dynamics
+            draws = dict(eps0=None, eps_z=None, eps_a=None, gumbel=None)
+            L0 = LQ = LR = None
+            if noise:
+                def draw(slot, *shape):
+                    v = _take_noise(slot)
+                    return torch.randn(*shape, device=dev, dtype=dt) if v is None else v.to(device=dev, dtype=dt).reshape(shape)
+                draws.update(eps0=draw("gen_z0", Bsz, S, n), eps_z=draw("gen_z", Bsz, S, H, n), eps_a=draw("gen_a", Bsz, S, H, p))
+                if switching:
+                    g = _take_noise("gen_gumbel")
+                    draws["gumbel"] = (-torch.empty(Bsz, S, H, K, device=dev, dtype=dt).exponential_().log() if g is None
+                                       else g.to(device=dev, dtype=dt).reshape(Bsz, S, H, K))
+                L0 = lgssm_ops.safe_cholesky(hand["Sigma"])
+                LQ = lgssm_ops.safe_cholesky(dyn.Q.detach() if switching else kf.Q)
+                LR = lgssm_ops.safe_cholesky(kf.R)
+            if switching:
+                kind, extra = "switching", dict(P=dyn._prior_matrix(dev, dt), s0=hand["s"])
+            elif K > 1:
+                lstm = dyn.lstm
+                kind, extra = "lstm", dict(lstm=tuple(t.detach() for t in (lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0,
+                                                                         lstm.bias_hh_l0, dyn.head_w.weight, dyn.head_w.bias)),
+                                           h0=hand["h"], c0=hand["c"], y0=hand["y"])
+            else:
+                kind, extra = "lstm", {}
+            a, z, w = lgssm_ops.rollout(kind, dyn.A.detach(), dyn.B.detach(), dyn.C.detach(), hand["mu"], L0, u_fut, LQ, LR, S, H,
+                                        **extra, **draws)
+            x_gen = None
+            if decode:
+                x_gen = self._to_pixels(self.decode_sequence(a.reshape(Bsz, S * H, p).to(dt))).unflatten(1, (S, H))
+            return {"a": a, "z": z, "weights": w, "x": x_gen, "a_vae": a_vae}
+        finally:
+            self.train(was_training)

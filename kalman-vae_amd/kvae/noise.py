@@ -7,10 +7,16 @@ The reference draws its randomness from torch's global generator in three places
 Results on a GPU can only be compared with the CPU oracle if both consume the same draws, so the
 drop-in classes look here first: inside `with inject(eps_a=..., eps_z=..., gumbel=...)` the given
 tensors are used instead of fresh device-side draws.
+
+KVAE.generate (no counterpart in the reference) draws four more, all before its one rollout launch:
+  * gen_z0      ~ N(0,1)  [B,S,n]     start state z_{T0-1} = mu + L_Sigma gen_z0
+  * gen_z       ~ N(0,1)  [B,S,H,n]   process noise of each step
+  * gen_a       ~ N(0,1)  [B,S,H,p]   emission noise of each step
+  * gen_gumbel  ~ Gumbel  [B,S,H,K]   regime draws of the switching dynamics
 """
 import contextlib
 
-_slots = {"eps_a": None, "eps_z": None, "gumbel": None}
+_slots = {"eps_a": None, "eps_z": None, "gumbel": None, "gen_z0": None, "gen_z": None, "gen_a": None, "gen_gumbel": None}
 
 
 def take(name):
@@ -20,9 +26,9 @@ def take(name):
 
 
 @contextlib.contextmanager
-def inject(eps_a=None, eps_z=None, gumbel=None):
+def inject(eps_a=None, eps_z=None, gumbel=None, gen_z0=None, gen_z=None, gen_a=None, gen_gumbel=None):
     old = dict(_slots)
-    _slots.update(eps_a=eps_a, eps_z=eps_z, gumbel=gumbel)
+    _slots.update(eps_a=eps_a, eps_z=eps_z, gumbel=gumbel, gen_z0=gen_z0, gen_z=gen_z, gen_a=gen_a, gen_gumbel=gen_gumbel)
     try:
         yield
     finally:
