@@ -22,8 +22,11 @@ __global__ __launch_bounds__(256) void k_gru_fwd_fast(const float *__restrict__ 
   constexpr int G = 3 * H;
   constexpr int HP = (H + 3) / 4 * 4;
   static_assert(G <= 256, "one thread per gate row");
-  __shared__ __attribute__((aligned(16))) float sh_h[HP];
-  __shared__ float sh_r[H], sh_z[H], sh_xn[H], sh_hn[H];
+  KV_LDS16(float, sh_h, [HP]);
+  KV_LDS(float, sh_r, [H]);
+  KV_LDS(float, sh_z, [H]);
+  KV_LDS(float, sh_xn, [H]);
+  KV_LDS(float, sh_hn, [H]);
   const int b = blockIdx.x, dir = blockIdx.y, j = threadIdx.x;
   const GruWeights w = dir ? wb : wf;
   float wr[HP], wi[I], bi = 0.f, bh = 0.f, hprev = 0.f;
@@ -86,9 +89,9 @@ __global__ __launch_bounds__(192) void k_gru_bwd_fast(const float *__restrict__ 
   constexpr int G = 3 * H;
   constexpr int HP = (H + 3) / 4 * 4;
   static_assert(H + I <= 64, "hidden units + inputs must fit one 64-lane column group");
-  __shared__ __attribute__((aligned(16))) float sh_dh[3][HP];   // d_pre_h of the current step, per gate block
-  __shared__ __attribute__((aligned(16))) float sh_di[3][HP];   // d_pre_i of the current step
-  __shared__ float sh_part[3][64];
+  KV_LDS16(float, sh_dh, [3][HP]);   // d_pre_h of the current step, per gate block
+  KV_LDS16(float, sh_di, [3][HP]);   // d_pre_i of the current step
+  KV_LDS(float, sh_part, [3][64]);
   const int b = blockIdx.x, dir = blockIdx.y, g = threadIdx.x >> 6, k = threadIdx.x & 63;
   const GruWeights w = dir ? wb : wf;
   float wc[HP];

@@ -56,27 +56,7 @@ extern "C" void kvae_tpp_launch_elbo(const kvae_lgssm_problem *p, const float *m
 // of a step is a few dozen flops, so a wavefront per sequence spends its time in LDS round trips and wave syncs
 // (119 us forward / 167 us backward at B = 256, T = 50, K = 3); a single lane walks the T steps in registers.
 // ---------------------------------------------------------------------------------------------------------------
-template <int KC>
-__global__ __launch_bounds__(64) void k_regime_fwd_tpp(const float *logits, const float *init_logits, const float *gumbel,
-                                                       const float *P, float *y_seq, float *log_q, float *log_p, int B, int T,
-                                                       float tau, const float *tau_dev, int hard) {
-  const int b = blockIdx.x * 64 + threadIdx.x;
-  if (b >= B) return;
-  if (tau_dev) tau = *tau_dev;
-  RegimeLds L;
-  regime_fwd_body(logits, init_logits, gumbel, P, y_seq, log_q, log_p, b, T, KC, tau, hard, L);
-}
-template <int KC>
-__global__ __launch_bounds__(64) void k_regime_bwd_tpp(const float *logits, const float *init_logits, const float *gumbel,
-                                                       const float *P, const float *y_seq, const float *g_y, const float *g_lq,
-                                                       const float *g_lp, float *g_logits, float *g_init, int B, int T, float tau,
-                                                       const float *tau_dev) {
-  const int b = blockIdx.x * 64 + threadIdx.x;
-  if (b >= B) return;
-  if (tau_dev) tau = *tau_dev;
-  RegimeLds L;
-  regime_bwd_body(logits, init_logits, gumbel, P, y_seq, g_y, g_lq, g_lp, g_logits, g_init, b, T, KC, tau, L);
-}
+#include "regime_tpp.h"
 
 #define KVAE_REGIME_TPP_CASES(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
 // return 1 if a thread-per-sequence instance exists for K (and was launched), 0 otherwise
@@ -128,7 +108,7 @@ __global__ __launch_bounds__(64) void k_regime_bwd_grid(const float *logits, con
 extern "C" int kvae_grid_launch_regime_fwd(const float *logits, const float *init_logits, const float *gumbel, const float *P,
                                            float *y_seq, float *log_q, float *log_p, int B, int T, int K, float tau,
                                            const float *tau_dev, int hard, hipStream_t s) {
-  if (K > 8 || B > 4096) return 0;
+  if (K > 8 || B > KVAE_REGIME_GRID_MAX_B) return 0;
   k_regime_fwd_grid<<<dim3(B), dim3(64), 0, s>>>(logits, init_logits, gumbel, P, y_seq, log_q, log_p, T, K, tau, tau_dev, hard);
   return 1;
 }
@@ -136,7 +116,7 @@ extern "C" int kvae_grid_launch_regime_bwd(const float *logits, const float *ini
                                            const float *y_seq, const float *g_y, const float *g_lq, const float *g_lp,
                                            float *g_logits, float *g_init, int B, int T, int K, float tau, const float *tau_dev,
                                            hipStream_t s) {
-  if (K > 8 || B > 4096) return 0;
+  if (K > 8 || B > KVAE_REGIME_GRID_MAX_B) return 0;
   k_regime_bwd_grid<<<dim3(B), dim3(64), 0, s>>>(logits, init_logits, gumbel, P, y_seq, g_y, g_lq, g_lp, g_logits, g_init, T, K, tau,
                                                  tau_dev);
   return 1;

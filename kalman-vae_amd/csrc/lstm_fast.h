@@ -10,6 +10,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "lds_decl.h"
+
 namespace kvae {
 
 __device__ __forceinline__ float fast_sigmoid(float v) { return 1.0f / (1.0f + __expf(-v)); }
@@ -27,8 +29,8 @@ __global__ __launch_bounds__(256) void k_lstm_fwd_fast(const float *__restrict__
   constexpr int G = 4 * H;
   constexpr int HP = (H + 3) / 4 * 4;
   static_assert(G <= 256, "one thread per gate row");
-  __shared__ __attribute__((aligned(16))) float sh_h[HP];
-  __shared__ float sh_g[G];
+  KV_LDS16(float, sh_h, [HP]);
+  KV_LDS(float, sh_g, [G]);
   const int b = blockIdx.x, j = threadIdx.x;
   float w[HP], wi[I], bias = 0.f, c = 0.f;
 #pragma unroll
@@ -78,8 +80,8 @@ __global__ __launch_bounds__(256) void k_lstm_bwd_fast(const float *__restrict__
   constexpr int G = 4 * H;
   constexpr int HP = (H + 3) / 4 * 4;
   static_assert(H + I <= 64, "hidden units + inputs must fit one 64-lane column group");
-  __shared__ __attribute__((aligned(16))) float sh_d[4][HP];  // d_pre of the current step, per gate block
-  __shared__ float sh_part[4][64];                            // per-gate-block partial sums (dh | dx)
+  KV_LDS16(float, sh_d, [4][HP]);   // d_pre of the current step, per gate block
+  KV_LDS(float, sh_part, [4][64]);  // per-gate-block partial sums (dh | dx)
   const int b = blockIdx.x, g = threadIdx.x >> 6, k = threadIdx.x & 63;
   float wc[HP];
 #pragma unroll

@@ -16,10 +16,15 @@
 //             natural assignment lane (g, k) <-> element [i = g][j = k] (y_{t-1}[g] straight from memory, gl[k] on the lane),
 //             and the adjoint of y_{t-1}, sum_j logits[i][j] gl[j] + P[i][j] gtp[j], is an 8-lane reduction in that same
 //             assignment (G-layout) plus one permute.
-//   The next step's operands are fetched one step ahead; loads are unconditional from clamped addresses (see mask_addr()).
+//   The next step's operands are fetched one step ahead; loads are unconditional from clamped addresses
+//   (the `qn` / `qp` / `qnp` step indices below: the step itself where there is no next one).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+// largest batch the lane-grid kernels take (kvae_lgssm_tpp.hip: above it the chip's wave slots are full and the thread-per-
+// sequence kernels have the better throughput)
+#define KVAE_REGIME_GRID_MAX_B 4096
 
 namespace kvae {
 namespace rgrid {

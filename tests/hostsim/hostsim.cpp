@@ -126,6 +126,18 @@ void kvae_wemu_bwd_n16(const kvae_lgssm_problem *, const kvae_lgssm_states *, co
                        const kvae_lgssm_input_grads *, float *, int);
 void kvae_wemu_elbo_n16(const kvae_lgssm_problem *, const float *, const float *, const float *, float *, int32_t *, float *,
                         float *, float *, const kvae_lgssm_input_grads *, int);
+// wave_emu_rnn.cpp: the recurrent kernels (csrc/lstm_fast.h, gru_fast.h, regime_grid.h, regime_tpp.h) on emulated workgroups
+void kvae_wemu_rnn_note(int);
+void kvae_wemu_lstm_fwd(const float *, const float *, const float *, const float *, const float *, float *, float *, float *, int, int);
+void kvae_wemu_lstm_bwd(const float *, const float *, const float *, const float *, const float *, float *, float *, int, int);
+void kvae_wemu_bigru_fwd(const float *, const float *const *, const float *const *, const float *const *, const float *const *,
+                         float *, float *, int, int);
+void kvae_wemu_bigru_bwd(const float *, const float *, const float *, const float *const *, const float *const *, float *, float *,
+                         float *, int, int);
+int kvae_wemu_regime_fwd(const float *, const float *, const float *, const float *, float *, float *, float *, int, int, int, float,
+                         const float *, int);
+int kvae_wemu_regime_bwd(const float *, const float *, const float *, const float *, const float *, const float *, const float *,
+                         const float *, float *, float *, int, int, int, float, const float *);
 }
 static int g_wave_emu = 0;
 static bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -260,6 +272,10 @@ int kvae_lstm_fwd(const float *x, const float *w_ih, const float *w_hh, const fl
                   float *gates, float *c_seq, int32_t B, int32_t T, int32_t I, int32_t H, void *) {
   if (!x || !w_ih || !w_hh || !b_ih || !b_hh || !h_seq || !gates || !c_seq) return KVAE_ERR_NULL;
   if (B < 1 || T < 1 || I < 1 || I > KVAE_LSTM_MAX_I || H < 1 || H > KVAE_LSTM_MAX_H) return KVAE_ERR_DIMS;
+  if (g_wave_emu && H == 50 && I == 2) {   // the gate of kvae_lgssm.hip: k_lstm_fwd_fast<50, 2>
+    kvae_wemu_lstm_fwd(x, w_ih, w_hh, b_ih, b_hh, h_seq, gates, c_seq, B, T);
+    return KVAE_OK;
+  }
   auto L = std::make_unique<LstmLds>();
   for (int b = 0; b < B; ++b) {
     memset(L.get(), 0xFF, sizeof(*L));
@@ -271,6 +287,10 @@ int kvae_lstm_bwd(const float *g_h, const float *gates, const float *c_seq, cons
                   float *d_pre, float *dx, int32_t B, int32_t T, int32_t I, int32_t H, void *) {
   if (!g_h || !gates || !c_seq || !w_ih || !w_hh || !d_pre || !dx) return KVAE_ERR_NULL;
   if (B < 1 || T < 1 || I < 1 || I > KVAE_LSTM_MAX_I || H < 1 || H > KVAE_LSTM_MAX_H) return KVAE_ERR_DIMS;
+  if (g_wave_emu && H == 50 && I == 2) {   // k_lstm_bwd_fast<50, 2>
+    kvae_wemu_lstm_bwd(g_h, gates, c_seq, w_ih, w_hh, d_pre, dx, B, T);
+    return KVAE_OK;
+  }
   auto L = std::make_unique<LstmLds>();
   for (int b = 0; b < B; ++b) {
     memset(L.get(), 0xFF, sizeof(*L));
@@ -359,6 +379,10 @@ int kvae_regime_fwd(const float *logits, const float *init_logits, const float *
   if (!logits || !init_logits || !gumbel || !P || !y_seq || !log_q || !log_p) return KVAE_ERR_NULL;
   if (tau_dev) tau = *tau_dev;
   if (B < 1 || T < 1 || K < 1 || K > KVAE_REGIME_MAX_K || !(tau > 0.f)) return KVAE_ERR_ARG;
+  if (g_wave_emu) {   // lane grid / thread per sequence as kvae_lgssm.hip chooses; neither: the LDS bodies below
+    if (kvae_wemu_regime_fwd(logits, init_logits, gumbel, P, y_seq, log_q, log_p, B, T, K, tau, tau_dev, hard)) return KVAE_OK;
+    kvae_wemu_rnn_note(8);
+  }
   auto L = std::make_unique<RegimeLds>();
   for (int b = 0; b < B; ++b) {
     memset(L.get(), 0xFF, sizeof(*L));
@@ -373,6 +397,11 @@ int kvae_regime_bwd(const float *logits, const float *init_logits, const float *
     return KVAE_ERR_NULL;
   if (tau_dev) tau = *tau_dev;
   if (B < 1 || T < 1 || K < 1 || K > KVAE_REGIME_MAX_K || !(tau > 0.f)) return KVAE_ERR_ARG;
+  if (g_wave_emu) {
+    if (kvae_wemu_regime_bwd(logits, init_logits, gumbel, P, y_seq, g_y, g_log_q, g_log_p, g_logits, g_init, B, T, K, tau, tau_dev))
+      return KVAE_OK;
+    kvae_wemu_rnn_note(9);
+  }
   auto L = std::make_unique<RegimeLds>();
   for (int b = 0; b < B; ++b) {
     memset(L.get(), 0xFF, sizeof(*L));
@@ -382,13 +411,30 @@ int kvae_regime_bwd(const float *logits, const float *init_logits, const float *
 }
 }
 
-// The bidirectional GRU has only the register-resident gfx950 kernels (gru_fast.h); the host simulation reports the
-// shape as unsupported so that the Python side keeps nn.GRU on host tensors.
+// The bidirectional GRU has only the register-resident gfx950 kernels (gru_fast.h).  With the emulated workgroups on they run
+// here, behind the argument checks of kvae_lgssm.hip; otherwise the host simulation reports the shape as unsupported so that the
+// Python side keeps nn.GRU on host tensors.
 extern "C" {
-int kvae_bigru_fwd(const float *, const float *const *, const float *const *, const float *const *, const float *const *,
-                   float *, float *, int32_t, int32_t, int32_t, int32_t, void *) { return KVAE_ERR_DIMS; }
-int kvae_bigru_bwd(const float *, const float *, const float *, const float *const *, const float *const *, float *, float *,
-                   float *, int32_t, int32_t, int32_t, int32_t, void *) { return KVAE_ERR_DIMS; }
+int kvae_bigru_fwd(const float *x, const float *const w_ih[2], const float *const w_hh[2], const float *const b_ih[2],
+                   const float *const b_hh[2], float *h_seq, float *gates, int32_t B, int32_t T, int32_t I, int32_t H, void *) {
+  if (!g_wave_emu) return KVAE_ERR_DIMS;
+  if (!x || !w_ih || !w_hh || !b_ih || !b_hh || !h_seq || !gates) return KVAE_ERR_NULL;
+  for (int d = 0; d < 2; ++d)
+    if (!w_ih[d] || !w_hh[d] || !b_ih[d] || !b_hh[d]) return KVAE_ERR_NULL;
+  if (B < 1 || T < 1 || H != 50 || I != 2) return KVAE_ERR_DIMS;
+  kvae_wemu_bigru_fwd(x, w_ih, w_hh, b_ih, b_hh, h_seq, gates, B, T);
+  return KVAE_OK;
+}
+int kvae_bigru_bwd(const float *g_h, const float *gates, const float *h_seq, const float *const w_ih[2], const float *const w_hh[2],
+                   float *d_pre_i, float *d_pre_h, float *dx, int32_t B, int32_t T, int32_t I, int32_t H, void *) {
+  if (!g_wave_emu) return KVAE_ERR_DIMS;
+  if (!g_h || !gates || !h_seq || !w_ih || !w_hh || !d_pre_i || !d_pre_h || !dx) return KVAE_ERR_NULL;
+  for (int d = 0; d < 2; ++d)
+    if (!w_ih[d] || !w_hh[d]) return KVAE_ERR_NULL;
+  if (B < 1 || T < 1 || H != 50 || I != 2) return KVAE_ERR_DIMS;
+  kvae_wemu_bigru_bwd(g_h, gates, h_seq, w_ih, w_hh, d_pre_i, d_pre_h, dx, B, T);
+  return KVAE_OK;
+}
 }
 
 #include "../../kalman-vae_amd/csrc/vae_loss.h"

@@ -1,0 +1,5 @@
+// TEST-ONLY stand-in for <hip/hip_runtime.h> when the kernel headers are compiled for the host (tests/hostsim): everything they
+// use of HIP - threadIdx / blockIdx, __syncthreads, __shared__ storage, the cross-lane intrinsics, float4 - comes from wave_emu.h,
+// which the including unit pulls in first.
+#pragma once
+#include "../../wave_emu.h"

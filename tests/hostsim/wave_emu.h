@@ -12,6 +12,12 @@
 // cores, with DPP traffic inside group-dependent branches, legal on the hardware where a DPP move only needs its own row - run
 // here too.  A wave-scope instruction that only some lanes reach (or a row-scope one only some lanes of a row reach) would wait
 // forever: every barrier has a deadline, past which the harness names the scope, the lane and the block and aborts.
+// Workgroups of more than one wavefront (launch_wg: 64, 128, 192 or 256 threads, the recurrent kernels of csrc/lstm_fast.h and
+// gru_fast.h): one host thread per lane of every wavefront of the block; __syncthreads() meets every lane of the BLOCK, all the
+// cross-lane instructions keep the scope above (their wavefront, or their row).  A __shared__ array of a kernel (KV_LDS /
+// KV_LDS16 of csrc/lds_decl.h) and the launch's dynamic LDS (KV_LDS_DYN) are heap allocations of exactly their size, made by the
+// first lane that reaches the declaration, filled with NaNs, freed when the block has ended: AddressSanitizer sees their bounds
+// (a static array of a template kernel is a COMDAT object, which it does not pad), and a read of an element no lane wrote is a NaN.
 // Arithmetic of the MFMA shims: k-ascending fmaf chains in fp32, which is what the kernels' parity argument assumes.
 // This is a sanitizer / debug harness, slow by design (a barrier per instruction): tiny problems only.
 #pragma once
@@ -24,6 +30,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <functional>
+#include <map>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -70,11 +77,41 @@ struct Wave {
   uint32_t a[2][64], b[2][64];   // wave-scope operands
   uint32_t r[2][64];             // row-scope operands (row k uses lanes 16k..16k+15 of each)
 };
+// the workgroup in flight: its barrier (every lane of every wavefront) and its LDS objects, keyed by their declaration
+struct Block {
+  explicit Block(unsigned threads, size_t dyn_bytes) : bar(threads, "block"), dyn_bytes_(dyn_bytes) {}
+  Block(const Block &) = delete;
+  ~Block() {
+    for (auto &kv : lds_) free(kv.second);
+  }
+  void *shared(int key, size_t bytes) {   // key: the declaration (KV_LDS: __COUNTER__), -1: the launch's dynamic LDS
+    std::lock_guard<std::mutex> lk(m_);
+    auto it = lds_.find(key);
+    if (it != lds_.end()) return it->second;
+    void *ptr = nullptr;
+    if (posix_memalign(&ptr, 16, bytes ? bytes : 1) != 0) abort();   // exactly `bytes`: the next byte is a redzone
+    memset(ptr, 0xFF, bytes);                                         // NaNs
+    lds_.emplace(key, ptr);
+    return ptr;
+  }
+  void *dyn_shared() { return shared(-1, dyn_bytes_); }
+  Barrier bar;
+
+ private:
+  std::mutex m_;
+  std::map<int, void *> lds_;
+  const size_t dyn_bytes_;
+};
+inline thread_local Block *t_block = nullptr;
+inline thread_local Dim3 t_bdim = {64, 1, 1};
+inline void *block_shared(int key, size_t bytes) { return t_block->shared(key, bytes); }
+inline void *block_dyn_shared() { return t_block->dyn_shared(); }
 inline thread_local Wave *t_wave = nullptr;
 inline thread_local int t_par = 0;    // parity of this lane's wave-scope exchanges
 inline thread_local int t_rpar = 0;   // parity of this lane's row-scope exchanges
 
-inline void sync() { t_wave->bar.wait(); }
+inline void sync() { t_wave->bar.wait(); }                                       // wave-scope rendezvous of the shims below
+inline void sync_block() { (t_block ? t_block->bar : t_wave->bar).wait(); }      // __syncthreads(): every lane of the workgroup
 // every lane deposits v; returns the buffer to read the other lanes' values from (valid until this lane's next exchange)
 inline const uint32_t *exchange(uint32_t v) {
   const int p = t_par;
@@ -108,6 +145,7 @@ inline int mov_dpp(int v, int ctrl, int, int, bool) {   // every control above r
   return (int)all[dpp_source(lane_id(), ctrl)];
 }
 inline float shfl(float v, int src, int) { return bitsf(exchange(fbits(v))[src & 63]); }
+inline float shfl_xor(float v, int mask, int) { return bitsf(exchange(fbits(v))[(lane_id() ^ mask) & 63]); }
 inline unsigned long long ballot(bool pred) {
   const uint32_t *all = exchange(pred ? 1u : 0u);
   unsigned long long m = 0;
@@ -173,7 +211,37 @@ inline void launch(unsigned blocks, const std::function<void()> &body) {
   }
 }
 
+// launch_wg: a grid of workgroups of `threads` lanes (a multiple of 64, at most 256) with `dyn_bytes` of dynamic LDS, one
+// after the other (x fastest), every lane of a workgroup a host thread
+inline void launch_wg(Dim3 grid, unsigned threads, size_t dyn_bytes, const std::function<void()> &body) {
+  if (threads == 0 || threads % 64 != 0 || threads > 256) {
+    fprintf(stderr, "wave_emu: a workgroup of %u threads is not 1..4 whole wavefronts\n", threads);
+    abort();
+  }
+  const unsigned waves = threads / 64;
+  for (unsigned bz = 0; bz < grid.z; ++bz)
+    for (unsigned by = 0; by < grid.y; ++by)
+      for (unsigned bx = 0; bx < grid.x; ++bx) {
+        Block blk(threads, dyn_bytes);
+        std::vector<Wave> w(waves);
+        std::vector<std::thread> th;
+        th.reserve(threads);
+        for (unsigned l = 0; l < threads; ++l)
+          th.emplace_back([&, l] {
+            t_block = &blk, t_wave = &w[l / 64], t_par = 0, t_rpar = 0;
+            t_tid = {l, 0, 0}, t_bid = {bx, by, bz}, t_gdim = grid, t_bdim = {threads, 1, 1};
+            body();
+            t_block = nullptr;
+          });
+        for (auto &t : th) t.join();
+      }
+}
+
 }  // namespace wemu
+
+struct alignas(16) float4 {
+  float x, y, z, w;
+};
 
 // ---- what the kernel headers see ----------------------------------------------------------------------------------------------
 #define __device__
@@ -184,8 +252,10 @@ inline void launch(unsigned blocks, const std::function<void()> &body) {
 #define threadIdx (wemu::t_tid)
 #define blockIdx (wemu::t_bid)
 #define gridDim (wemu::t_gdim)
-#define __syncthreads() wemu::sync()
+#define blockDim (wemu::t_bdim)
+#define __syncthreads() wemu::sync_block()
 #define __shfl(v, src, w) wemu::shfl((v), (src), (w))
+#define __shfl_xor(v, mask, w) wemu::shfl_xor((v), (mask), (w))
 #define __ballot(p) wemu::ballot((p))
 #define __any(p) wemu::any((p))
 #define __builtin_amdgcn_mov_dpp(v, ctrl, rm, bm, bc) wemu::mov_dpp((v), (ctrl), (rm), (bm), (bc))

@@ -417,6 +417,230 @@ def _per_step_ratio(got, ref):
     return float(ratio.max()), divmod(k, T)
 
 
+# ---- recurrent chain kernels (lstm_fast.h, gru_fast.h, regime_grid.h / regime_tpp.h / regime.h), one (b,t) slice at a time ----
+# Bars = 4 x YARDSTICK (the factor values_vs_fp64_oracle uses for "as good as float32 can be"), where the yardstick of a quantity
+# is the largest per-slice ratio of the FLOAT32 TORCH restatement of the operation (nn.LSTM, nn.GRU, regime_chain run in float32)
+# against its float64 run, over the case lists of both tiers (tests/test_wave_emu_rnn.py, tests/test_hostsim_ops.py,
+# tests/test_gpu_parity.py; rerun: the case functions with yardstick=True).  Largest ratios the kernels reach against the same
+# float64 run, emulated workgroups (expf, a division) | gfx950 (__expf, v_rcp):
+#   lstm.h 4.3e-7 | 7.8e-7   lstm.gates 3.5e-7 | 5.8e-7   lstm.c_seq 4.1e-7 | 7.3e-7   lstm.dx 1.7e-6 | 6.1e-6   lstm.param 3.3e-7 | 3.5e-7
+#   gru.h 2.6e-7 | 3.2e-7    gru.dx 1.2e-6 | 7.6e-6       gru.param 3.5e-7 | 3.0e-7
+#   regime.y 4.2e-7 | 5.2e-7  log_q 2.4e-6 | 2.2e-6  log_p 6.5e-7 | 6.4e-7  g_logits 2.7e-5 | 3.3e-5  g_init 2.3e-5 | 1.5e-5
+#   wgrad.wh / wx / b  - | 3.2e-7 / 4.0e-6 / 1.4e-5    mix.out / g_alpha / g_base  - | 2.4e-7 / 1.5e-6 / 1.9e-7
+#   linear.y / dx / dw / db  - | 1.2e-6 / 2.2e-5 / 2.2e-6 / 7.2e-7      (-: plain-loop twins on the CPU tier, not the kernels)
+# Less than a factor 2 under the bar: lstm.gates (1.16 x on gfx950, 1.9 x emulated), lstm.c_seq (1.45 x on gfx950); DESIGN section 2.
+RNN_YARDSTICK = {   # float32 torch against float64 torch, largest per-slice ratio over the CPU and the GPU case lists
+    "lstm.h": 3.96e-7, "lstm.gates": 1.69e-7, "lstm.c_seq": 2.65e-7, "lstm.dx": 6.61e-6, "lstm.param": 2.90e-6,
+    "gru.h": 2.56e-7, "gru.dx": 8.04e-6, "gru.param": 6.16e-7,
+    "mix.out": 2.42e-7, "mix.g_alpha": 5.29e-6, "mix.g_base": 6.11e-7,
+    "linear.y": 1.65e-6, "linear.dx": 2.20e-5, "linear.dw": 1.24e-6, "linear.db": 6.38e-7,
+    "wgrad.wh": 7.05e-7, "wgrad.wx": 8.23e-6, "wgrad.b": 7.30e-6,
+    "regime.y": 9.32e-7, "regime.log_q": 2.43e-6, "regime.log_p": 6.48e-7, "regime.g_logits": 3.35e-5, "regime.g_init": 2.32e-5,
+}
+RNN_STEP_TOL = {k: 4.0 * v for k, v in RNN_YARDSTICK.items()}   # the bars of lstm_per_step / bigru_per_step / regime_per_step
+
+
+def _check_steps(name, got, ref, bar, out):
+    """Per-(b,t) comparison of one [B,T,...] stack against its float64 reference: every slice, none left out."""
+    ratio, where = _per_step_ratio(got.detach().cpu(), ref.detach())
+    out[name] = max(out.get(name, 0.0), ratio)
+    assert ratio < bar, (name, ratio, where, bar)
+
+
+def _check_whole(name, got, ref, bar, out):
+    ratio = rel_err(got.detach().cpu(), ref.detach())
+    out[name] = max(out.get(name, 0.0), ratio)
+    assert ratio < bar, (name, ratio, bar)
+
+
+def _upstream(w, steps):
+    """The upstream gradient on every step ("all") or on one step only ("first": t = 0, "last": t = T - 1), the others zero:
+    with a single step a dropped carry of the recurrence is the whole gradient of the other steps, not a small part of it."""
+    if steps == "all":
+        return w
+    m = torch.zeros_like(w)
+    t = 0 if steps == "first" else w.shape[1] - 1
+    m[:, t] = w[:, t]
+    return m
+
+
+def _rnn_launches(lib):
+    return [lib.dll.kvae_wemu_rnn_launches(i) for i in range(10)] if hasattr(lib.dll, "kvae_wemu_rnn_launches") else None
+
+
+def _lstm_restated(mod, x):
+    """gates [B,T,4H] (i, f, g, o after their nonlinearities), c_seq, h_seq of a single-layer nn.LSTM from a zero state, in
+    the module's dtype: what LstmSequence saves for its backward."""
+    B, T, _ = x.shape
+    H = mod.hidden_size
+    h, c = x.new_zeros(B, H), x.new_zeros(B, H)
+    gs, cs, hs = [], [], []
+    for t in range(T):
+        pre = x[:, t] @ mod.weight_ih_l0.T + mod.bias_ih_l0 + h @ mod.weight_hh_l0.T + mod.bias_hh_l0
+        i, f, g, o = pre.split(H, -1)
+        i, f, g, o = i.sigmoid(), f.sigmoid(), g.tanh(), o.sigmoid()
+        c = f * c + i * g
+        h = o * c.tanh()
+        gs.append(torch.cat([i, f, g, o], -1)), cs.append(c), hs.append(h)
+    return torch.stack(gs, 1), torch.stack(cs, 1), torch.stack(hs, 1)
+
+
+def lstm_per_step(DEV, B, T, steps="all", yardstick=False):
+    """kvae_lstm_fwd/bwd at (H, I) = (50, 2) (k_lstm_fwd_fast / k_lstm_bwd_fast) against torch.nn.LSTM in FLOAT64 on the same
+    weights and inputs: h, the saved gates and c_seq, and dx per (b,t); the parameter gradients as whole tensors.  `steps`: see
+    _upstream.  On the emulated backend the launch counters must show that the fast kernels ran.  Returns the largest ratios."""
+    from kvae import _native
+    from kvae.kalman.lgssm_ops import LstmSequence
+    torch.manual_seed(1000 * B + 10 * T + len(steps))
+    ref = torch.nn.LSTM(2, 50, batch_first=True).double()
+    names = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
+    x = torch.randn(B, T, 2, dtype=torch.float64)
+    w = _upstream(torch.randn(B, T, 50, dtype=torch.float64), steps)
+    xr = x.clone().requires_grad_(True)
+    h64 = ref(xr)[0]
+    (h64 * w).sum().backward()
+    with torch.no_grad():
+        gates64, c64, h_re = _lstm_restated(ref, x)
+    assert float((h_re - h64.detach()).abs().max()) < 1e-12   # the restatement that supplies gates / c_seq IS nn.LSTM
+    out = {}
+    if yardstick:   # float32 torch in place of the kernels
+        m32 = torch.nn.LSTM(2, 50, batch_first=True)
+        m32.load_state_dict({k: v.float() for k, v in ref.state_dict().items()})
+        xd = x.float().requires_grad_(True)
+        h = m32(xd)[0]
+        (h * w.float()).sum().backward()
+        with torch.no_grad():
+            gates, c, _ = _lstm_restated(m32, x.float())
+        pg = [getattr(m32, n).grad for n in names]
+    else:
+        lib = _native.lib_for(torch.zeros(1, device=DEV))
+        before = _rnn_launches(lib) if DEV == "cpu" else None
+        params = [getattr(ref, n).detach().float().to(DEV).requires_grad_(True) for n in names]
+        xd = x.float().to(DEV).requires_grad_(True)
+        h = LstmSequence.apply(xd, *params)
+        _, _, _, _, gates, c = h.grad_fn.saved_tensors
+        (h * w.float().to(DEV)).sum().backward()
+        pg = [q.grad for q in params]
+        if before is not None:
+            after = _rnn_launches(lib)
+            assert after[0] == before[0] + 1 and after[1] == before[1] + 1, (before, after)
+    _check_steps("lstm.h", h, h64, RNN_STEP_TOL["lstm.h"], out)
+    _check_steps("lstm.gates", gates, gates64, RNN_STEP_TOL["lstm.gates"], out)
+    _check_steps("lstm.c_seq", c, c64, RNN_STEP_TOL["lstm.c_seq"], out)
+    _check_steps("lstm.dx", xd.grad, xr.grad, RNN_STEP_TOL["lstm.dx"], out)
+    for n, got in zip(names, pg):
+        _check_whole("lstm.param", got, getattr(ref, n).grad, RNN_STEP_TOL["lstm.param"], out)
+    return out
+
+
+def bigru_per_step(DEV, B, T, steps="all", yardstick=False):
+    """kvae_bigru_fwd/bwd (k_gru_fwd_fast / k_gru_bwd_fast, grid (B, 2)) against torch.nn.GRU(bidirectional=True) in FLOAT64:
+    h (both directions' columns) and dx per (b,t), the eight parameter gradients as whole tensors."""
+    from kvae import _native
+    from kvae.kalman.lgssm_ops import BiGruSequence
+    torch.manual_seed(2000 * B + 10 * T + len(steps))
+    ref = torch.nn.GRU(2, 50, batch_first=True, bidirectional=True).double()
+    names = ["weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0", "weight_ih_l0_reverse", "weight_hh_l0_reverse",
+             "bias_ih_l0_reverse", "bias_hh_l0_reverse"]
+    x = torch.randn(B, T, 2, dtype=torch.float64)
+    w = _upstream(torch.randn(B, T, 100, dtype=torch.float64), steps)
+    xr = x.clone().requires_grad_(True)
+    h64 = ref(xr)[0]
+    (h64 * w).sum().backward()
+    out = {}
+    if yardstick:
+        m32 = torch.nn.GRU(2, 50, batch_first=True, bidirectional=True)
+        m32.load_state_dict({k: v.float() for k, v in ref.state_dict().items()})
+        xd = x.float().requires_grad_(True)
+        h = m32(xd)[0]
+        (h * w.float()).sum().backward()
+        pg = [getattr(m32, n).grad for n in names]
+    else:
+        lib = _native.lib_for(torch.zeros(1, device=DEV))
+        before = _rnn_launches(lib) if DEV == "cpu" else None
+        params = [getattr(ref, n).detach().float().to(DEV).requires_grad_(True) for n in names]
+        xd = x.float().to(DEV).requires_grad_(True)
+        h = BiGruSequence.apply(xd, *params)
+        (h * w.float().to(DEV)).sum().backward()
+        pg = [q.grad for q in params]
+        if before is not None:
+            after = _rnn_launches(lib)
+            assert after[2] == before[2] + 1 and after[3] == before[3] + 1, (before, after)
+    _check_steps("gru.h", h, h64, RNN_STEP_TOL["gru.h"], out)
+    _check_steps("gru.dx", xd.grad, xr.grad, RNN_STEP_TOL["gru.dx"], out)
+    for n, got in zip(names, pg):
+        _check_whole("gru.param", got, getattr(ref, n).grad, RNN_STEP_TOL["gru.param"], out)
+    return out
+
+
+REGIME_FAMILIES = {"grid": (4, 5), "tpp": (6, 7), "lds": (8, 9)}   # indices of kvae_wemu_rnn_launches (forward, backward)
+REGIME_HARD_GAP = 1e-3   # least top-two gap of (l + g) / tau in the float64 run for which a hard sample is compared
+
+
+def regime_per_step(DEV, B, T, K, tau, hard, family=None, tau_dev=False, seed=0, yardstick=False):
+    """kvae_regime_fwd/bwd against SwitchingDynamicsParameter.regime_chain in FLOAT64: y, log_q, log_p and g_logits per (b,t),
+    g_init per b.  `family` ("grid", "tpp", "lds"): the kernel family that must run, asserted from the launch counters of the
+    emulated backend (the GPU build has no counter: there the family is chosen by KVAE_REGIME_TPP in a fresh process).
+    `tau_dev`: tau as a one-element device tensor the kernels read.  A hard sample is compared only where float32 and float64
+    must agree on the arg-maximum: the float64 run's top-two gap of (l + g) / tau is ASSERTED above REGIME_HARD_GAP at every
+    (b,t), so a seed that does not give that fails here.  T = 1 reads no transition logits: their gradient must be exactly 0."""
+    from kvae import _native
+    from kvae.kalman.lgssm_ops import RegimeChain
+    from kvae.kalman.switch_dyn_param import StickyRegimePrior, SwitchingDynamicsParameter
+    g = torch.Generator().manual_seed(10000 * seed + 1000 * B + 10 * T + K)
+    logits = torch.randn(B, T, K, K, generator=g, dtype=torch.float64)
+    init = torch.randn(B, K, generator=g, dtype=torch.float64)
+    gum = -torch.empty(B, T, K, dtype=torch.float64).exponential_(generator=g).log()
+    w_y, w_q, w_p = (torch.randn(*sh, generator=g, dtype=torch.float64) for sh in ((B, T, K), (B, T), (B, T)))
+    # the values the kernels see are float32: the float64 run starts from the same numbers
+    logits, init, gum, w_y, w_q, w_p = (t.float().double() for t in (logits, init, gum, w_y, w_q, w_p))
+    tau = float(torch.tensor(tau, dtype=torch.float32))
+
+    def chain(dtype):
+        dyn = SwitchingDynamicsParameter(torch.eye(4).repeat(K, 1, 1), torch.zeros(K, 4, 4), torch.zeros(K, 2, 4),
+                                         prior=StickyRegimePrior(K, 0.8))
+        dyn.tau = tau
+        lr, ir = logits.to(dtype).clone().requires_grad_(True), init.to(dtype).clone().requires_grad_(True)
+        y, lq, lp = dyn.regime_chain(lr, ir, gum.to(dtype), hard)
+        ((y * w_y.to(dtype)).sum() + (lq * w_q.to(dtype)).sum() + (lp * w_p.to(dtype)).sum()).backward()
+        g_l = lr.grad if lr.grad is not None else torch.zeros_like(logits, dtype=dtype)   # T == 1: transition logits unused
+        return dyn, y.detach(), lq.detach(), lp.detach(), g_l, ir.grad
+
+    dyn, y64, lq64, lp64, gl64, gi64 = chain(torch.float64)
+    if hard and K > 1:
+        l = torch.cat([init[:, None], torch.einsum("bti,btij->btj", y64[:, :-1], logits[:, 1:])], 1)
+        top = ((l + gum) / tau).topk(2, -1).values
+        gap = float((top[..., 0] - top[..., 1]).min())
+        assert gap > REGIME_HARD_GAP, ("seed gives a near-tie of the hard sample", B, T, K, seed, gap)
+    out = {}
+    if yardstick:
+        _, y, lq, lp, g_l, g_i = chain(torch.float32)
+    else:
+        lib = _native.lib_for(torch.zeros(1, device=DEV))
+        before = _rnn_launches(lib) if DEV == "cpu" else None
+        ld, idv = logits.float().to(DEV).requires_grad_(True), init.float().to(DEV).requires_grad_(True)
+        P = dyn.prior.transition_matrix.to(DEV)
+        tau_arg = torch.tensor(tau, dtype=torch.float32, device=DEV) if tau_dev else tau
+        y, lq, lp = RegimeChain.apply(ld, idv, gum.float().to(DEV), P, tau_arg, hard)
+        ((y * w_y.float().to(DEV)).sum() + (lq * w_q.float().to(DEV)).sum() + (lp * w_p.float().to(DEV)).sum()).backward()
+        g_l, g_i = ld.grad, idv.grad
+        if before is not None and family is not None:
+            after = _rnn_launches(lib)
+            delta = [a - b for a, b in zip(after, before)][4:]
+            want = [1 if 4 + i in REGIME_FAMILIES[family] else 0 for i in range(6)]
+            assert delta == want, (family, delta)
+    _check_steps("regime.y", y, y64, RNN_STEP_TOL["regime.y"], out)
+    _check_steps("regime.log_q", lq, lq64, RNN_STEP_TOL["regime.log_q"], out)
+    _check_steps("regime.log_p", lp, lp64, RNN_STEP_TOL["regime.log_p"], out)
+    if T == 1:
+        assert float(g_l.abs().max()) == 0.0, "T = 1: the gradient of the transition logits is exactly zero"
+    else:
+        assert float(g_l[:, 0].abs().max()) == 0.0, "the transition logits of t = 0 are never read"
+        _check_steps("regime.g_logits", g_l, gl64, RNN_STEP_TOL["regime.g_logits"], out)
+    _check_steps("regime.g_init", g_i[:, None], gi64[:, None], RNN_STEP_TOL["regime.g_init"], out)
+    return out
+
+
 def n16_elbo_per_step(DEV, B, T, family, levels=(0, 0), grads=True, q_shared=False):
     """The (16,16,2) ELBO kernels (csrc/lgssm_n16_elbo.h) step by step against a FLOAT64 run of the torch oracle.
     family 2: per-step A, B, C and Q, one wavefront per (b,t) (k_elbo_n16<GRADS, HAS_GQ>) - with q_shared, ONE Q for the batch
@@ -924,6 +1148,47 @@ def rnn_wgrad_vs_torch(DEV):
     assert all(torch.equal(a, b) for r0, r1 in zip(res, run1) for a, b in zip(r0, r1) if a is not None)
 
 
+# (Bsz, T, H, I, R, shift): every k_rnn_wgrad_partial<RT> instance (RT = 1, 4, 10, 13, 16 row tiles) with a ragged last 16-row
+# tile, C = H + I + 1 = 53 or 17 columns (not a multiple of 16), N = 21 / 18 / 5 rows (not a multiple of 32), h_{t-1} and h_{t+1}
+# with T = 1 (every row is a sequence boundary: the hidden operand is zero everywhere), a problem without x and one without h
+WGRAD_ROW_CASES = [(3, 7, 50, 2, R, -1) for R in (5, 37, 150, 200, 250)] + [
+    (3, 7, 50, 2, 150, 1), (3, 7, 50, 2, 250, 1), (5, 1, 50, 2, 200, -1), (5, 1, 50, 2, 150, 1), (2, 9, 13, 3, 37, 0),
+    (3, 7, 50, 0, 150, 1), (4, 11, 0, 2, 150, 0)]
+WGRAD_ROW_CASES_LARGE = [(256, 50, 50, 2, 200, -1), (256, 50, 50, 2, 150, 1)]   # GPU tier only
+
+
+def rnn_wgrad_per_row(DEV, Bsz, T, H, I, R, shift, yardstick=False):
+    """kvae_rnn_wgrad against the float64 product D^T [h_shifted | x | 1], one OUTPUT ROW at a time (a gate row of dW_hh, dW_ih
+    and db; the floor of _per_step_ratio applies per row).  The hidden operand is a column slice of a wider [N, 2H] sequence
+    when shift = +1 (the reverse GRU direction's layout: row stride 2H)."""
+    from kvae.kalman.lgssm_ops import rnn_wgrad
+    g = torch.Generator().manual_seed(100 * R + 10 * T + shift + 1)
+    n = Bsz * T
+    d = torch.randn(n, R, generator=g)
+    h2 = torch.randn(Bsz, T, 2 * max(H, 1), generator=g)
+    x = torch.randn(n, max(I, 1), generator=g)
+    col = H if shift > 0 else 0                     # which half of the [.., 2H] sequence is the hidden operand
+    h = h2[..., col:col + H]
+    zero = torch.zeros(Bsz, 1, H)
+    hs = {-1: torch.cat([zero, h[:, :-1]], 1), 0: h, 1: torch.cat([h[:, 1:], zero], 1)}[shift].reshape(n, H)
+    dd = d.double()
+    want = (dd.t() @ hs.double(), dd.t() @ x[:, :I].double(), dd.sum(0))
+    if yardstick:
+        got = (d.t() @ hs, d.t() @ x[:, :I], d.sum(0))
+    else:
+        prob = dict(d=d.to(DEV))
+        if H:
+            prob.update(h=h2.reshape(n, -1).to(DEV)[:, col:col + H], shift=shift, T=T)
+        if I:
+            prob.update(x=x[:, :I].contiguous().to(DEV))
+        (got,) = rnn_wgrad(prob["d"], [prob])
+    out = {}
+    for name, a, b in zip(("wgrad.wh", "wgrad.wx", "wgrad.b"), got, want):
+        if a is not None and b.numel():
+            _check_steps(name, a.reshape(R, 1, -1), b.reshape(R, 1, -1), RNN_STEP_TOL[name], out)
+    return out
+
+
 def small_linear_vs_torch(DEV):
     """SmallLinear (+ fused softmax) forward, input gradient and parameter gradients against torch.nn.functional.linear /
     softmax autograd: the alpha head (K x 50, softmax), the regime posterior's heads (K^2 x 100 on [B,T,100], K x 100 on the
@@ -1025,3 +1290,67 @@ def mix_vs_torch(DEV):
                                 1, N.stream_for(alpha)) == 0
     assert rel_err((g_alpha - g_alpha0).cpu(), (gout @ base.T).cpu()) < 2e-5
     assert rel_err(g_base.cpu(), (alpha.T @ gout).cpu()) < 2e-5
+
+
+# (Bsz, T, K, E): the streaming kernels' widths with row counts that are not a multiple of the 16 rows per block of the second
+# stage (21, 37, 17, 45) and K below the instance's KMAX (2, 5, 6), a K above their limit, and the large cases of mix_vs_torch
+MIX_ROW_CASES = [(3, 7, 3, 48), (3, 7, 2, 40), (37, 1, 5, 768), (1, 17, 6, 48), (5, 9, 3, 768), (2, 5, 8, 768), (4, 6, 9, 40),
+                 (1, 1, 2, 12), (2, 3, 3, 42), (3, 7, 7, 544)]
+MIX_ROW_CASES_LARGE = [(256, 50, 3, 40), (32, 100, 7, 48), (64, 33, 3, 544)]   # GPU tier only
+
+
+def mix_per_row(DEV, Bsz, T, K, E, yardstick=False):
+    """kvae_mix_fwd / kvae_mix_bwd against the float64 products: the mixed records and g_alpha per (b,t) row, g_base per mode."""
+    from kvae.kalman.lgssm_ops import MixDynamics
+    g = torch.Generator().manual_seed(1000 * K + E + Bsz * T)
+    alpha = torch.softmax(torch.randn(Bsz, T, K, generator=g), -1)
+    base, up = torch.randn(K, E, generator=g), torch.randn(Bsz, T, E, generator=g)
+    a64, b64, u64 = alpha.double(), base.double(), up.double()
+    want = (torch.einsum("btk,ke->bte", a64, b64), torch.einsum("bte,ke->btk", u64, b64), torch.einsum("btk,bte->ke", a64, u64))
+    if yardstick:
+        got = (torch.einsum("btk,ke->bte", alpha, base), torch.einsum("bte,ke->btk", up, base), torch.einsum("btk,bte->ke", alpha, up))
+    else:
+        ad, bd = alpha.to(DEV).requires_grad_(True), base.to(DEV).requires_grad_(True)
+        o = MixDynamics.apply(ad, bd)
+        (o * up.to(DEV)).sum().backward()
+        got = (o, ad.grad, bd.grad)
+    out = {}
+    _check_steps("mix.out", got[0], want[0], RNN_STEP_TOL["mix.out"], out)
+    _check_steps("mix.g_alpha", got[1], want[1], RNN_STEP_TOL["mix.g_alpha"], out)
+    _check_steps("mix.g_base", got[2][:, None], want[2][:, None], RNN_STEP_TOL["mix.g_base"], out)
+    return out
+
+
+# (leading shape, F, O, softmax, strided): the heads of small_linear_vs_torch, single rows, and a row count of one
+LINEAR_ROW_CASES = [((6, 9), 50, 3, True, False), ((5, 8), 100, 9, False, False), ((3, 4), 100, 49, False, False),
+                    ((7,), 100, 7, False, True), ((2, 3), 17, 5, False, False), ((1, 1), 50, 7, True, False),
+                    ((3,), 100, 16, True, True)]
+LINEAR_ROW_CASES_LARGE = [((256, 50), 50, 7, True, False), ((256, 50), 100, 49, False, False)]   # GPU tier only
+
+
+def small_linear_per_row(DEV, lead, F, O, softmax, strided, yardstick=False):
+    """SmallLinear (+ fused softmax) against float64 torch: y and dx one input row at a time, dW one output row at a time, db."""
+    from kvae.kalman.lgssm_ops import SmallLinear
+    g = torch.Generator().manual_seed(100 * F + O + len(lead))
+    base = torch.randn(*lead, 6, F, generator=g)      # strided: rows 6 F apart, as h_seq[:, 0]
+    x0 = base.select(-2, 0)
+    w0, b0, up = torch.randn(O, F, generator=g) * 0.3, torch.randn(O, generator=g), torch.randn(*lead, O, generator=g)
+
+    def run(dtype, dev, kernel):
+        bs = base.to(dtype).to(dev).requires_grad_(True)
+        x = bs.select(-2, 0) if strided else bs.select(-2, 0).contiguous()
+        w, b = w0.to(dtype).to(dev).requires_grad_(True), b0.to(dtype).to(dev).requires_grad_(True)
+        if kernel:
+            y = SmallLinear.apply(x, w, b, softmax)
+        else:
+            y = torch.nn.functional.linear(x, w, b)
+            y = torch.softmax(y, -1) if softmax else y
+        (y * up.to(dtype).to(dev)).sum().backward()
+        return y.detach().reshape(-1, 1, O), bs.grad.select(-2, 0).reshape(-1, 1, F), w.grad[:, None], b.grad[None, None]
+
+    want = run(torch.float64, "cpu", False)
+    got = run(torch.float32, "cpu", False) if yardstick else run(torch.float32, DEV, True)
+    out = {}
+    for name, a, b in zip(("linear.y", "linear.dx", "linear.dw", "linear.db"), got, want):
+        _check_steps(name, a, b, RNN_STEP_TOL[name], out)
+    return out

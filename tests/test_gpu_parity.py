@@ -290,6 +290,64 @@ def test_bigru_gpu(B, T):
         assert rel_err(got.grad.cpu(), getattr(ref, n).grad) < 2e-4, n
 
 
+RNN_STEP_SHAPES = [(256, 50, "all"), (256, 50, "first"), (256, 50, "last"), (3, 7, "all"), (1, 1, "all"), (3, 2, "last"),
+                   (1, 3, "first")]
+
+
+@pytest.mark.parametrize("B,T,steps", RNN_STEP_SHAPES)
+def test_lstm_per_step_gpu(B, T, steps):
+    """k_lstm_fwd_fast / k_lstm_bwd_fast against float64 nn.LSTM, one (b,t) slice at a time (h, gates, c_seq, dx)."""
+    print(parity_cases.lstm_per_step(DEV, B, T, steps))
+
+
+@pytest.mark.parametrize("B,T,steps", RNN_STEP_SHAPES)
+def test_bigru_per_step_gpu(B, T, steps):
+    """k_gru_fwd_fast / k_gru_bwd_fast against float64 nn.GRU(bidirectional), one (b,t) slice at a time (h, dx)."""
+    print(parity_cases.bigru_per_step(DEV, B, T, steps))
+
+
+# (B, T, K, tau, hard, tau_dev): the large cases of test_regime_gpu, the edges (T = 1, K = 1, K = 8, K > 8: LDS bodies), and
+# B = 4097: one sequence above the lane-grid kernels' batch threshold, which the default dispatch hands to a thread per sequence
+REGIME_STEP_CASES = [(256, 50, 3, 1.0, False, False), (32, 100, 7, 0.7, True, False), (4, 100, 7, 0.5, False, True),
+                     (5, 9, 8, 1.3, False, True), (2, 1, 2, 0.5, False, False), (3, 4, 9, 1.0, False, False),
+                     (3, 7, 16, 0.7, False, True), (3, 10, 3, 0.7, True, False), (3, 5, 1, 0.7, False, False),
+                     (4097, 3, 3, 0.7, False, False), (4097, 2, 7, 1.3, False, True)]
+
+
+@pytest.mark.parametrize("B,T,K,tau,hard,tau_dev", REGIME_STEP_CASES)
+def test_regime_per_step_gpu(B, T, K, tau, hard, tau_dev):
+    print(parity_cases.regime_per_step(DEV, B, T, K, tau, hard, None, tau_dev))
+
+
+@pytest.mark.parametrize("B,T,K,tau,hard", [(4097, 3, 3, 0.7, False), (4097, 2, 7, 1.3, False)])
+def test_regime_gpu_above_the_grid_threshold(B, T, K, tau, hard):
+    """More than 4096 sequences: the thread-per-sequence kernels k_regime_{fwd,bwd}_tpp<K> (64 sequences per block, a ragged
+    last block with one lane in use)."""
+    parity_cases.regime_vs_torch(DEV, B, T, K, tau, hard)
+
+
+@pytest.mark.parametrize("mode", ["0", "1", "2"])
+def test_regime_switch_selects_working_kernels(mode):
+    """KVAE_REGIME_TPP (read once per process) chooses the family of the regime chain: 1 (default) the lane-grid kernels up to
+    4096 sequences and a thread per sequence above, 2 a thread per sequence always (every instance K = 2..8, at B = 65: a ragged
+    second block), 0 the LDS bodies.  The GPU build has no launch counter, so each mode runs the per-step cases in a fresh
+    process of its own, each against float64: whatever family the switch selects has to pass them."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import sys; sys.path[:0] = [%r, %r, %r]; import parity_cases as p\n"
+            "for K in range(1, 9):\n"
+            "    p.regime_per_step('cuda', 65, 3, K, 0.7, False, None, K %% 2 == 0)\n"
+            "for c in %r:\n"
+            "    p.regime_per_step('cuda', *c)\n"
+            % (root, os.path.join(root, "kalman-vae_amd"), os.path.join(root, "tests"),
+               [c[:5] + (None, c[5]) for c in REGIME_STEP_CASES]))
+    r = subprocess.run([sys.executable, "-c", code], env={**os.environ, "KVAE_REGIME_TPP": mode}, capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+
+
 @pytest.mark.parametrize("N", [1, 37, 1000, 2000])
 def test_conv_edge_gpu(N):
     """Direct decoder-head / encoder-stem kernels vs torch conv2d; 1000 / 2000 frames exercise the frame-strided weight-gradient loop."""
@@ -360,6 +418,26 @@ def test_mix_gpu():
 def test_rnn_wgrad_gpu():
     """No library GEMM on the path: LSTM / bi-GRU / head parameter gradients on the f32 matrix cores vs torch products."""
     parity_cases.rnn_wgrad_vs_torch(DEV)
+
+
+@pytest.mark.parametrize("Bsz,T,H,I,R,shift", parity_cases.WGRAD_ROW_CASES + parity_cases.WGRAD_ROW_CASES_LARGE)
+def test_rnn_wgrad_per_row_gpu(Bsz, T, H, I, R, shift):
+    """Every k_rnn_wgrad_partial<RT> instance with a ragged last row tile, ragged columns and rows, h_{t-1} / h_{t+1} at the
+    sequence boundaries (T = 1: all of them), one output row at a time against float64."""
+    print(parity_cases.rnn_wgrad_per_row(DEV, Bsz, T, H, I, R, shift))
+
+
+@pytest.mark.parametrize("Bsz,T,K,E", parity_cases.MIX_ROW_CASES + parity_cases.MIX_ROW_CASES_LARGE)
+def test_mix_per_row_gpu(Bsz, T, K, E):
+    """The streaming mixture kernels (and their element-wise fallback) one (b,t) row at a time against float64: ragged row
+    counts, K below the instance's KMAX."""
+    print(parity_cases.mix_per_row(DEV, Bsz, T, K, E))
+
+
+@pytest.mark.parametrize("lead,F,O,softmax,strided", parity_cases.LINEAR_ROW_CASES + parity_cases.LINEAR_ROW_CASES_LARGE)
+def test_small_linear_per_row_gpu(lead, F, O, softmax, strided):
+    """The four small_linear.h kernels one row at a time against float64 (contiguous rows and the strided rows of h_seq[:, 0])."""
+    print(parity_cases.small_linear_per_row(DEV, lead, F, O, softmax, strided))
 
 
 def test_small_linear_gpu():

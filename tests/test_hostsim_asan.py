@@ -45,6 +45,22 @@ parity_cases.n16_elbo_per_step("cpu", 2, 3, 2, (0, 0), True)
 parity_cases.n16_elbo_per_step("cpu", 2, 5, 3, (0, 0), True)
 parity_cases.n16_elbo_per_step("cpu", 3, 5, 2, (5, 0), True)
 assert min(lib.dll.kvae_wemu_launches(i) for i in (4, 5)) >= 3
+# the recurrent kernels on emulated workgroups (hostsim/wave_emu_rnn.cpp; their LDS arrays are heap objects of exactly their size):
+# k_lstm_*_fast / k_gru_*_fast read float4 from rows padded from 50 to 52 floats and index c_seq, h_seq and dx one step back or
+# ahead (T = 1: no neighbour at all); the lane-grid regime kernels fetch one step ahead from clamped addresses (T = 1, T = 2: the
+# last step of the last sequence ends the buffer); thread per sequence with B = 65: a second block with 63 idle lanes
+assert lib.dll.kvae_wemu_selftest() == 0
+for T in (1, 3):
+    parity_cases.lstm_per_step("cpu", 2, T)
+    parity_cases.bigru_per_step("cpu", 2, T)
+for T, K, hard in ((1, 8, False), (2, 8, True), (2, 3, False), (1, 1, False)):
+    parity_cases.regime_per_step("cpu", 2, T, K, 0.7, hard, "grid", tau_dev=hard)
+lib.dll.kvae_wemu_regime_grid_max_b(0)
+parity_cases.regime_per_step("cpu", 65, 2, 3, 0.7, False, "tpp")
+parity_cases.regime_per_step("cpu", 65, 1, 8, 0.7, False, "tpp", tau_dev=True)
+lib.dll.kvae_wemu_regime_grid_max_b(-1)
+parity_cases.regime_per_step("cpu", 2, 3, 9, 0.7, False, "lds")
+assert min(lib.dll.kvae_wemu_rnn_launches(i) for i in range(10)) > 0, [lib.dll.kvae_wemu_rnn_launches(i) for i in range(10)]
 lib.dll.kvae_hostsim_wave_emu(0)
 print("ASAN-OK")
 """

@@ -5,6 +5,7 @@ a GPU; the same comparisons run against the real gfx950 library in tests/test_gp
 import pytest
 import torch
 
+import parity_cases
 from golden_util import JITTER_CASES, LATENT_CASES, SMOOTH_KEYS, load, rel_err, sub
 from hostsim.build import build as build_hostsim
 
@@ -351,3 +352,20 @@ def test_training_phases_hostsim(name, kind, hostsim_backend):
 
     parity_cases.check_phases(g, tr.set_training_phase, run_step, lambda: {k: p.detach().clone() for k, p in model.named_parameters()},
                               steps, value_tol=1e-4)
+
+
+@pytest.mark.parametrize("Bsz,T,H,I,R,shift", parity_cases.WGRAD_ROW_CASES)
+def test_rnn_wgrad_per_row_hostsim(hostsim_backend, Bsz, T, H, I, R, shift):
+    """The plain-loop twin of kvae_rnn_wgrad at the shapes the GPU tier runs through every k_rnn_wgrad_partial<RT> instance:
+    the case function and its float64 reference are checked here before they are trusted there."""
+    parity_cases.rnn_wgrad_per_row("cpu", Bsz, T, H, I, R, shift)
+
+
+@pytest.mark.parametrize("Bsz,T,K,E", parity_cases.MIX_ROW_CASES)
+def test_mix_per_row_hostsim(hostsim_backend, Bsz, T, K, E):
+    parity_cases.mix_per_row("cpu", Bsz, T, K, E)
+
+
+@pytest.mark.parametrize("lead,F,O,softmax,strided", parity_cases.LINEAR_ROW_CASES)
+def test_small_linear_per_row_hostsim(hostsim_backend, lead, F, O, softmax, strided):
+    parity_cases.small_linear_per_row("cpu", lead, F, O, softmax, strided)
