@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 #define KVAE_MAX_DIM 16
-#define KVAE_ABI_VERSION 11
+#define KVAE_ABI_VERSION 12
 
 typedef enum {
   KVAE_OK = 0,
@@ -434,6 +434,48 @@ typedef struct {
   float *w_out;             /* [R,H,K]  alpha_h or s_h, required                                                      */
 } kvae_gen_problem;
 int kvae_lgssm_generate(const kvae_gen_problem *prob, void *stream);
+
+/* ---- imputation: joint posterior samples of latent paths (kvae/model/model.py KVAE.sample_imputations) ------------------
+ * S paths z_{0:T-1} per sequence from the smoothing posterior p(z_{0:T-1} | a_{0:T-1}, u), by backward sampling over the
+ * outputs of kvae_lgssm_filter_fwd / kvae_lgssm_filter_alpha_lstm (the smoother is not needed; no counterpart in the reference,
+ * whose KVAE.impute decodes the smoothed MEAN only, kvae/model/model.py:279-288, kvae/train/imputation.py).  For t = T-2 .. 0:
+ *   J_t = Sigma_{t|t} A_{t+1}^T Sigma_{t+1|t}^{-1}                         (the RTS gain, kalman_filter.py:221-229)
+ *   P_t = (I - J_t A_{t+1}) Sigma_{t|t} (I - J_t A_{t+1})^T + J_t Q_{t+1} J_t^T     (Joseph form), symmetrised
+ *   z_t = mu_{t|t} + J_t (z_{t+1} - mu_{t+1|t}) + chol(P_t) eps_t
+ * from z_{T-1} = mu_{T-1|T-1} + chol(Sigma_{T-1|T-1}) eps_{T-1}; a_t = C_t z_t + LR eta_t.  chol is the _safe_cholesky ladder
+ * (kalman_filter.py:282-303) applied PER (b, t) item: symmetrise, jitter 1e-6 * 10^level for level 0..4, else the clamped
+ * diagonal; levels_out[b,t] receives the level (5 = diagonal).  Indexing as in the reference: A_t maps z_{t-1} -> z_t and
+ * mus_pred[t] = mu_{t|t-1} (kalman_filter.py:151-201).  A NULL noise pointer drops that term; with eps NULL the paths are the
+ * RTS mean mu_{t|T} (kalman_filter.py:232) and a is the reference's a_imputed.  Noise is never drawn here.
+ * Three launches on `stream`: all B*T gains at once (records J | L | c in ws), the B*S paths, sequential in t (z_out), and the
+ * emission of all B*S*T rows at once (a_out).  `stages` runs a part alone: the gains once, then paths + emission any number of
+ * times (fresh draws) over the same ws. */
+#define KVAE_PSAMPLE_GAINS 1 /* fills ws and levels_out; reads neither the noise nor z_out / a_out (which may be NULL)       */
+#define KVAE_PSAMPLE_PATHS 2 /* paths + emission over a ws filled earlier for the same B, T, n; levels_out may be NULL        */
+typedef struct {
+  int32_t B, S, T;            /* sequences, paths per sequence, steps (all >= 1)                                         */
+  int32_t n, p;               /* dims of z, a                                                                            */
+  int32_t stages;             /* 0 = all launches, else KVAE_PSAMPLE_GAINS or KVAE_PSAMPLE_PATHS (or both bits)         */
+  const float *mus_filt;      /* [B,T,n]    mu_{t|t}      (kalman_filter.py:193-201), required                           */
+  const float *Sigmas_filt;   /* [B,T,n,n]  Sigma_{t|t}   required                                                       */
+  const float *mus_pred;      /* [B,T,n]    mu_{t|t-1}    required                                                       */
+  const float *Sigmas_pred;   /* [B,T,n,n]  Sigma_{t|t-1} required                                                       */
+  kvae_stack A;               /* [n,n]  A_t (kalman_filter.py:153-160), required                                         */
+  kvae_stack C;               /* [p,n]  C_t, required                                                                    */
+  kvae_stack Q;               /* [n,n]  Q_t (self.Q buffer or dyn.Q_seq), required                                       */
+  const float *LR;            /* [p,p]  Cholesky factor of R; may be NULL iff eta is NULL                                */
+  const float *eps;           /* [B,S,T,n] or NULL                                                                       */
+  const float *eta;           /* [B,S,T,p] or NULL                                                                       */
+  float *z_out;               /* [B,S,T,n] required                                                                      */
+  float *a_out;               /* [B,S,T,p] required                                                                      */
+  int32_t *levels_out;        /* [B,T]     required                                                                      */
+  float *ws;                  /* kvae_lgssm_posterior_sample_ws_floats(prob) floats, required                            */
+} kvae_psample_problem;
+/* KVAE_ERR_DIMS: B, S, T < 1 or n, p outside [1, KVAE_MAX_DIM]; KVAE_ERR_NULL: a required pointer missing, or eta without LR;
+ * KVAE_ERR_ARG: a negative stride, stages outside 0..3, or more items / paths than one grid holds. */
+int kvae_lgssm_posterior_sample(const kvae_psample_problem *prob, void *stream);
+/* B*T*(2*n*n + n); 0 for dims outside the limits.  Only B, T, n are read. */
+int64_t kvae_lgssm_posterior_sample_ws_floats(const kvae_psample_problem *prob);
 
 /* ---- misc --------------------------------------------------------------------------------- */
 int kvae_abi_version(void);

@@ -666,4 +666,5 @@ __device__ __forceinline__ void elbo_zfix_wave(const kvae_lgssm_problem &P, cons
 // emulation unit of the host simulation includes this header, and through it that one.
 #if defined(KVAE_WAVE_EMU)
 #include "lgssm_gen.h"
+#include "lgssm_post.h"   // likewise kvae_lgssm_posterior_sample
 #endif

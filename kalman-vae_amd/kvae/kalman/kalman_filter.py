@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 
 from .. import noise
+from ..noise import take as _take_noise
 from . import lgssm_ops
 from .lgssm_ops import LgssmElbo, LgssmSmooth, Slots
 
@@ -217,6 +218,39 @@ class KalmanFilter(nn.Module):
             out["y"] = y
         out.update(mu=mf[:, -1].squeeze(-1), Sigma=Sf[:, -1])
         return out
+
+    @torch.no_grad()
+    def sample_posterior(self, Y, U, mask=None, num_samples=1, noise=True, emission_noise=False):
+        """`num_samples` joint samples z_{0:T-1} per sequence from the smoothing posterior p(z_{0:T-1} | a_{0:T-1}, u) (no
+        counterpart in the reference, whose smoother returns marginals only): the eval-path filter (as filter(); lstm dynamics
+        with a mask step the alpha-network inside the filter kernel, switching dynamics draw ONE regime sequence for the pass),
+        then backward sampling over its outputs (lgssm_ops.posterior_paths; include/kvae_lgssm.h kvae_lgssm_posterior_sample).
+        The paths are conditional on that one filter pass.  Draws: kvae.noise.inject(post_z=[B,S,T,n], post_a=[B,S,T,p]) or
+        fresh ones; noise=False gives the RTS mean mu_{t|T} on every path, emission_noise adds chol(R) eta_t to a_t = C_t z_t.
+        Returns dict(z [B,S,T,n], a [B,S,T,p], levels [B,T] (ladder level of each chol(P_t)), filter = filter()'s 7-tuple,
+        state_probs)."""
+        S = int(num_samples)
+        if S < 1:
+            raise ValueError(f"sample_posterior: num_samples must be >= 1, got {num_samples}")
+        Bsz, T, _ = Y.shape
+        _, _, mf, Sf, mp, Sp = self._run(Y, U, mask, with_rts=False)
+        last = self._last
+        A_l, B_l, C_l = last["views"]
+        dev, dt = Y.device, Y.dtype
+
+        def draw(slot, d):
+            v = _take_noise(slot)
+            return torch.randn(Bsz, S, T, d, device=dev, dtype=dt) if v is None else v.to(device=dev, dtype=dt).reshape(Bsz, S, T, d)
+
+        eps = draw("post_z", self.n) if noise else None
+        eta = draw("post_a", self.p) if emission_noise else None
+        LR = lgssm_ops.safe_cholesky(self.R) if emission_noise else None
+        Q = last["Q"] if last["Q"] is not None else last["Q_view"]
+        slots = last["slots"]
+        z, a, levels = lgssm_ops.posterior_paths(mf, Sf, mp, Sp, A_l, last["C"] if last["C"] is not None else C_l, Q, S, LR, eps, eta,
+                                                 packed=last["rec"], slots=Slots(A=slots.A, C=slots.C, Q=slots.Q))
+        return {"z": z, "a": a, "levels": levels, "filter": (mf, Sf, mp, Sp, A_l, B_l, C_l),
+                "state_probs": self.dyn_params.state_seq}
 
     def emission_means(self, mus_smooth, mus_filt, C_list):
         """(C_t mu_t|T, C_t mu_t|t): the two latent read-outs KVAE.impute decodes (reference model.py:279-288), one launch."""

@@ -754,3 +754,135 @@ def rollout_torch(kind, A, Bm, Cm, mu, L0, U, LQ, LR, S, H, lstm=None, h0=None, 
         a_out.append(a), z_out.append(z), w_out.append(w)
     un = lambda lst: torch.stack(lst, 1).reshape(Bsz, S, H, -1)
     return un(a_out), un(z_out), un(w_out)
+
+
+# ------------------------------------------------------------------------------------------------
+# joint posterior samples of latent paths (kvae_lgssm_posterior_sample, csrc/lgssm_post.h)
+# ------------------------------------------------------------------------------------------------
+def posterior_supported(n, p, ref=None):
+    """Shapes / tensors kvae_lgssm_posterior_sample is built for (include/kvae_lgssm.h); the rest takes posterior_paths_torch."""
+    if ref is not None and not (N.fused_ok(ref) and ref.dtype == torch.float32):
+        return False
+    return all(1 <= d <= N.KVAE_MAX_DIM for d in (n, p))
+
+
+def safe_cholesky_items(Sigma, max_tries=5, jitter_init=1e-6):
+    """The _safe_cholesky ladder applied PER ITEM of a batch [..., n, n]: (L, levels) with levels[...] the first level 0..4
+    (jitter 1e-6 * 10^level) at which that item factorises, 5 = its clamped-diagonal fallback.  No host sync."""
+    Sigma = 0.5 * (Sigma + Sigma.mT)
+    eye = torch.eye(Sigma.shape[-1], device=Sigma.device, dtype=Sigma.dtype)
+    L = torch.diag_embed(torch.sqrt(torch.diagonal(Sigma, dim1=-2, dim2=-1).clamp(min=1e-6)))
+    levels = torch.full(Sigma.shape[:-2], max_tries, device=Sigma.device, dtype=torch.int32)
+    jitter = jitter_init
+    for lv in range(max_tries):
+        Lv, info = torch.linalg.cholesky_ex(Sigma + jitter * eye)
+        take = (levels == max_tries) & (info == 0) & torch.isfinite(Lv).all(-1).all(-1)
+        L = torch.where(take[..., None, None], Lv, L)
+        levels = torch.where(take, torch.full_like(levels, lv), levels)
+        jitter *= 10.0
+    return L, levels
+
+
+def _bt(t, Bsz, T):
+    """[B,T,r,c] view of a per-step operand given as [r,c] or [B,T,r,c]."""
+    return t.expand(Bsz, T, *t.shape[-2:]) if t.dim() == 2 else t
+
+
+def posterior_paths_torch(mus_filt, Sigmas_filt, mus_pred, Sigmas_pred, A, Cm, Q, S, LR=None, eps=None, eta=None):
+    """The recursion of csrc/lgssm_post.h in torch ops, batched over B and S, in the dtype of mus_filt: for dtypes, devices and
+    shapes the kernels are not built for - several launches per time step.  Same arguments and returns as posterior_paths."""
+    mf = mus_filt.squeeze(-1) if mus_filt.dim() == 4 else mus_filt
+    mp = mus_pred.squeeze(-1) if mus_pred.dim() == 4 else mus_pred
+    dt = mf.dtype
+    Bsz, T, n = mf.shape
+    Sf, Sp = Sigmas_filt.to(dt), Sigmas_pred.to(dt)
+    A, Cm, Q = (_bt(t.to(dt), Bsz, T) for t in (A, Cm, Q))
+    eye = torch.eye(n, device=mf.device, dtype=dt)
+    J = torch.zeros(Bsz, T, n, n, device=mf.device, dtype=dt)
+    P = Sf.clone()
+    if T > 1:
+        An, Qn = A[:, 1:], Q[:, 1:]
+        Jt = torch.linalg.solve(Sp[:, 1:].mT, (Sf[:, :-1] @ An.mT).mT).mT
+        G = eye - Jt @ An
+        J[:, :-1] = Jt
+        P[:, :-1] = G @ Sf[:, :-1] @ G.mT + Jt @ Qn @ Jt.mT
+    L, levels = safe_cholesky_items(P)
+    c = mf.clone()
+    if T > 1:
+        c[:, :-1] = mf[:, :-1] - (J[:, :-1] @ mp[:, 1:].unsqueeze(-1)).squeeze(-1)
+    z = torch.zeros(Bsz, S, n, device=mf.device, dtype=dt)
+    zs = [None] * T
+    for t in range(T - 1, -1, -1):
+        z = c[:, t, None] + z @ J[:, t].mT
+        if eps is not None:
+            z = z + eps[:, :, t].to(dt) @ L[:, t].mT
+        zs[t] = z
+    z = torch.stack(zs, 2)
+    a = (Cm[:, None] @ z.unsqueeze(-1)).squeeze(-1)
+    if eta is not None:
+        a = a + eta.to(dt) @ LR.to(dt).mT
+    return z, a, levels
+
+
+def posterior_paths(mus_filt, Sigmas_filt, mus_pred, Sigmas_pred, A, Cm, Q, S, LR=None, eps=None, eta=None, packed=None,
+                    slots=Slots(), impl=None):
+    """S joint samples z_{0:T-1} per sequence from the smoothing posterior, by backward sampling over the filter's outputs
+    (semantics: include/kvae_lgssm.h, kvae_lgssm_posterior_sample).  mus_* [B,T,n] (or [B,T,n,1]),
+    Sigmas_* [B,T,n,n]; A [n,n] | [B,T,n,n], Cm [p,n] | [B,T,p,n], Q [n,n] | [B,T,n,n], or slots of the packed step record
+    `packed` [B,T,E] at the float offsets `slots` (then A and Q are ignored; Cm is still read for p); LR [p,p] (with eta); eps [B,S,T,n],
+    eta [B,S,T,p] or None.  impl: None = the HIP kernels where built, else the torch recursion; "kernel" / "torch" force one.
+    Returns z [B,S,T,n], a [B,S,T,p], levels [B,T] (int32: the ladder level of chol(P_t), 5 = clamped diagonal)."""
+    n = Sigmas_filt.shape[-1]
+    Bsz, T = Sigmas_filt.shape[:2]
+    p = Cm.shape[-2]   # Cm is always given (a view of the record when packed): it carries p
+    use_kernel = impl == "kernel" or (impl is None and posterior_supported(n, p, Sigmas_filt))
+    if not use_kernel:
+        if packed is not None:
+            pick = lambda t, off, r, c: t if off is None else packed[..., off:off + r * c].unflatten(-1, (r, c))
+            A, Cm, Q = pick(A, slots.A, n, n), pick(Cm, slots.C, p, n), pick(Q, slots.Q, n, n)
+        return posterior_paths_torch(mus_filt, Sigmas_filt, mus_pred, Sigmas_pred, A, Cm, Q, S, LR, eps, eta)
+    call = PosteriorCall(mus_filt, Sigmas_filt, mus_pred, Sigmas_pred, A, Cm, Q, S, LR, eps, eta, packed, slots)
+    call.run()
+    return call.z, call.a, call.levels
+
+
+class PosteriorCall:
+    """The kvae_psample_problem of one posterior_paths call with its outputs and workspace, every tensor kept alive.  run(stages)
+    runs the whole call (0) or a part: GAINS once, then PATHS (paths + emission) any number of times over the same workspace (new_draws)."""
+    GAINS, PATHS = 1, 2
+
+    def __init__(self, mus_filt, Sigmas_filt, mus_pred, Sigmas_pred, A, Cm, Q, S, LR=None, eps=None, eta=None, packed=None,
+                 slots=Slots()):
+        n, p = Sigmas_filt.shape[-1], Cm.shape[-2]
+        Bsz, T = Sigmas_filt.shape[:2]
+        dev = Sigmas_filt.device
+        sq = lambda t: _f32c((t.squeeze(-1) if t.dim() == 4 else t).detach())
+        mf, mp, Sf, Sp = sq(mus_filt), sq(mus_pred), _f32c(Sigmas_filt.detach()), _f32c(Sigmas_pred.detach())
+        packed = _f32c(packed.detach()) if packed is not None else None
+        pr = N.PsampleProblem()
+        pr.B, pr.S, pr.T, pr.n, pr.p = Bsz, S, T, n, p
+        pr.mus_filt, pr.Sigmas_filt, pr.mus_pred, pr.Sigmas_pred = mf.data_ptr(), Sf.data_ptr(), mp.data_ptr(), Sp.data_ptr()
+        self.keep = [mf, mp, Sf, Sp, packed]
+        for name, t, r, c, off in (("A", A, n, n, slots.A), ("C", Cm, p, n, slots.C), ("Q", Q, n, n, slots.Q)):
+            k, st = _stack(t.detach() if (off is None and t is not None) else t, Bsz, T, r, c, packed, off)
+            self.keep.append(k)
+            setattr(pr, name, st)
+        self.pr, self.dev, self.ref = pr, dev, Sf
+        self.new_draws(LR=LR, eps=eps, eta=eta)
+        mk = lambda *s, dt=torch.float32: torch.empty(*s, device=dev, dtype=dt)
+        self.z, self.a, self.levels = mk(Bsz, S, T, n), mk(Bsz, S, T, p), mk(Bsz, T, dt=torch.int32)
+        self.lib = N.lib_for(Sf)
+        self.ws = mk(int(self.lib.dll.kvae_lgssm_posterior_sample_ws_floats(C.byref(pr))))
+        pr.z_out, pr.a_out, pr.levels_out, pr.ws = self.z.data_ptr(), self.a.data_ptr(), self.levels.data_ptr(), self.ws.data_ptr()
+
+    def new_draws(self, LR=None, eps=None, eta=None):
+        self.noise = {}
+        for name, t in (("LR", LR), ("eps", eps), ("eta", eta)):
+            self.noise[name] = _f32c(t.detach().to(self.dev)) if t is not None else None
+            setattr(self.pr, name, self.noise[name].data_ptr() if t is not None else None)
+
+    def run(self, stages=0):
+        self.pr.stages = stages
+        name = {0: "posterior_sample", 1: "posterior_gains", 2: "posterior_paths"}.get(stages, "posterior_sample")
+        self.lib.check(N.timed(name, self.ref, lambda: self.lib.dll.kvae_lgssm_posterior_sample(C.byref(self.pr), N.stream_for(self.ref))),
+                       "kvae_lgssm_posterior_sample")

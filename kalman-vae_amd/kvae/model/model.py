@@ -288,6 +288,55 @@ class KVAE(nn.Module):
                 "state_probs": out["state_probs"]}
 
     @torch.no_grad()
+    def sample_imputations(self, x, mask, num_samples=1, u=None, noise=True, emission_noise=False, decode=True):
+        """Sampled completions of hidden frames: `num_samples` COHERENT latent paths per sequence from the smoothing posterior
+        p(z_{0:T-1} | a_{0:T-1}, u), decoded (no counterpart in the reference; impute() decodes their mean, C_t mu_{t|T}).
+        B sequences of T frames, S = num_samples, mask [B,T] (1 = observed).
+
+        1. Encode x (as forward does) and run the eval-mode filter with the mask: mu_{t|t}, Sigma_{t|t}, mu_{t|t-1}, Sigma_{t|t-1},
+           A_t, C_t (and Q_t of the switching model).  The dynamics depend on the observations only, so given this pass the model
+           is linear-Gaussian and backward sampling is exact.  With switching dynamics the pass holds ONE draw of the regime
+           sequence (hard one-hot in eval mode), as impute()'s does: the S paths share it.
+        2. z_{T-1} = mu_{T-1|T-1} + chol(Sigma_{T-1|T-1}) eps_{T-1}; for t = T-2 .. 0
+               J_t = Sigma_{t|t} A_{t+1}^T Sigma_{t+1|t}^{-1}
+               P_t = (I - J_t A_{t+1}) Sigma_{t|t} (I - J_t A_{t+1})^T + J_t Q_{t+1} J_t^T      (symmetrised)
+               z_t = mu_{t|t} + J_t (z_{t+1} - mu_{t+1|t}) + chol(P_t) eps_t
+           with chol the reference's _safe_cholesky ladder applied per (b, t).  a_t = C_t z_t (+ chol(R) eta_t with
+           emission_noise).  noise=False: z_t = mu_{t|T} and a_t = impute()'s a_imputed on every path.
+        3. x = decoder(a) through the frame VAE, one pass over the B*S*T frames.
+
+        Draws are made here with torch before the two launches (kvae.noise.inject: post_z, post_a).  u: [B,T,m] or None (zeros).
+        Returns x [B,S,T,C,h,w] (None with decode=False), a [B,S,T,p], z [B,S,T,n], a_vae [B,T,p], state_probs (and levels
+        [B,T], the ladder level of each chol(P_t)).  Training mode and parameters are left as they were."""
+        num_samples = int(num_samples)
+        if num_samples < 1:
+            raise ValueError(f"sample_imputations: num_samples must be >= 1, got {num_samples}")
+        Bsz, T = x.shape[:2]
+        if mask is None or tuple(mask.shape) != (Bsz, T):
+            raise ValueError(f"sample_imputations: mask must be [B, T] = [{Bsz}, {T}], got "
+                             f"{None if mask is None else list(mask.shape)}")
+        if u is not None and (u.dim() != 3 or u.shape[0] != Bsz or u.shape[1] != T or u.shape[2] != self.u_dim):
+            raise ValueError(f"sample_imputations: u must be [B, T, m] = [{Bsz}, {T}, {self.u_dim}], got {list(u.shape)}")
+        was_training = self.training
+        self.eval()
+        try:
+            a_vae, _, _ = self.encode_sequence(x)
+            dev, dt = a_vae.device, a_vae.dtype
+            u = torch.zeros(Bsz, T, self.u_dim, device=dev, dtype=dt) if u is None else u.to(device=dev, dtype=dt)
+            self.kalman_filter.dyn_params.reset_state()
+            post = self.kalman_filter.sample_posterior(a_vae, u, mask.to(device=dev, dtype=dt), num_samples, noise=noise,
+                                                       emission_noise=emission_noise)
+            a = post["a"]
+            x_s = None
+            if decode:
+                x_s = self._to_pixels(self.decode_sequence(a.reshape(Bsz, num_samples * T, self.a_dim).to(dt))).unflatten(
+                    1, (num_samples, T))
+            return {"x": x_s, "a": a, "z": post["z"], "a_vae": a_vae, "state_probs": post["state_probs"],
+                    "levels": post["levels"]}
+        finally:
+            self.train(was_training)
+
+    @torch.no_grad()
     def generate(self, x, horizon, num_samples=1, u=None, mask=None, noise=True, decode=True):
         """Continue each sequence: `num_samples` sampled futures of `horizon` frames from the learned dynamics (no counterpart in
         the reference).  B sequences, T0 = x.shape[1] conditioning frames, S = num_samples, H = horizon.

@@ -13,10 +13,15 @@ KVAE.generate (no counterpart in the reference) draws four more, all before its 
   * gen_z       ~ N(0,1)  [B,S,H,n]   process noise of each step
   * gen_a       ~ N(0,1)  [B,S,H,p]   emission noise of each step
   * gen_gumbel  ~ Gumbel  [B,S,H,K]   regime draws of the switching dynamics
+
+KalmanFilter.sample_posterior / KVAE.sample_imputations (no counterpart either) draw two, before their two launches:
+  * post_z      ~ N(0,1)  [B,S,T,n]   the draw of each step of each posterior path (z_t = ... + chol(P_t) post_z_t)
+  * post_a      ~ N(0,1)  [B,S,T,p]   emission noise of each step (only with emission_noise=True)
 """
 import contextlib
 
-_slots = {"eps_a": None, "eps_z": None, "gumbel": None, "gen_z0": None, "gen_z": None, "gen_a": None, "gen_gumbel": None}
+_slots = {"eps_a": None, "eps_z": None, "gumbel": None, "gen_z0": None, "gen_z": None, "gen_a": None, "gen_gumbel": None,
+          "post_z": None, "post_a": None}
 
 
 def take(name):
@@ -26,9 +31,10 @@ def take(name):
 
 
 @contextlib.contextmanager
-def inject(eps_a=None, eps_z=None, gumbel=None, gen_z0=None, gen_z=None, gen_a=None, gen_gumbel=None):
+def inject(eps_a=None, eps_z=None, gumbel=None, gen_z0=None, gen_z=None, gen_a=None, gen_gumbel=None, post_z=None, post_a=None):
     old = dict(_slots)
-    _slots.update(eps_a=eps_a, eps_z=eps_z, gumbel=gumbel, gen_z0=gen_z0, gen_z=gen_z, gen_a=gen_a, gen_gumbel=gen_gumbel)
+    _slots.update(eps_a=eps_a, eps_z=eps_z, gumbel=gumbel, gen_z0=gen_z0, gen_z=gen_z, gen_a=gen_a, gen_gumbel=gen_gumbel,
+                  post_z=post_z, post_a=post_a)
     try:
         yield
     finally:

@@ -2,6 +2,7 @@
 pattern of BASELINE configs[3] ("observe, hide a block, observe again") and of masked training.  Same function
 names, arguments and results; everything else in that module (imputation plots, MSE reports) is evaluation tooling
 outside the hot path and is not shipped.  `config_block_mask` wires KVAEConfig.t_init_mask / t_steps_mask in.
+`sample_imputation_scores` (no counterpart there) scores the sampled completions of KVAE.sample_imputations.
 """
 import torch
 
@@ -35,3 +36,23 @@ def config_block_mask(config, batch_size, T, device=None):
     KVAEConfig.t_init_mask observed frames, then KVAEConfig.t_steps_mask hidden ones."""
     return mask_impute_planning(batch_size, T, t_init_mask=config.t_init_mask, t_steps_mask=config.t_steps_mask,
                                 device=device)
+
+
+def sample_imputation_scores(x, x_samples, mask):
+    """Scores of S sampled completions x_samples [B,S,T,...] of x [B,T,...] on the HIDDEN frames (mask [B,T], 1 = observed):
+    the three numbers to report next to the reference's impute_epoch MSE (of the decoded smoothed mean).
+      mse_mean   MSE of the ensemble mean frame
+      mse_best   best-of-S MSE: per sequence the sample closest to x over its hidden frames, averaged over sequences
+      std        mean per-pixel standard deviation over the S samples (0 for S = 1)
+    0-d tensors; 0 where nothing is hidden.  Pure torch, no host sync."""
+    hid = (1.0 - mask.to(device=x.device, dtype=x.dtype))                 # [B,T]
+    pix = x[0, 0].numel()
+    w = hid.reshape(*hid.shape, *([1] * (x.dim() - 2)))                   # [B,T,1,..]
+    count = (hid.sum() * pix).clamp(min=1.0)
+    err_mean = ((x_samples.mean(1) - x) ** 2 * w).sum() / count
+    per = ((x_samples - x.unsqueeze(1)) ** 2 * w.unsqueeze(1)).flatten(2).sum(-1)          # [B,S] squared error on hidden frames
+    per_count = (hid.sum(1) * pix).clamp(min=1.0)                                          # [B]
+    has = (hid.sum(1) > 0).to(x.dtype)
+    best = ((per.min(1).values / per_count) * has).sum() / has.sum().clamp(min=1.0)
+    std = x_samples.std(1, unbiased=False) if x_samples.shape[1] > 1 else torch.zeros_like(x)
+    return {"mse_mean": err_mean, "mse_best": best, "std": (std * w).sum() / count}
