@@ -910,7 +910,9 @@ def conv_edge_vs_torch(DEV, N):
     b = 0.1 * torch.randn(32, generator=g)
     up = torch.randn(N, 32, 16, 16, generator=g)
     Wr, br = (t.clone().requires_grad_(True) for t in (W, b))
-    ref = torch.relu(F.conv2d(x, Wr, br, stride=2, padding=1))
+    pre = F.conv2d(x, Wr, br, stride=2, padding=1)
+    up = up * (pre.detach().abs() > 1e-5)   # no upstream gradient where rounding picks the ReLU mask (see dec_up_vs_torch)
+    ref = torch.relu(pre)
     (ref * up).sum().backward()
     Wd, bd = (t.clone().to(DEV).requires_grad_(True) for t in (W, b))
     out = EncoderStem.apply(x.to(DEV), Wd, bd)
@@ -931,7 +933,9 @@ def enc_mid_vs_torch(DEV, N, side):
     b = 0.1 * torch.randn(32, generator=g)
     up = torch.randn(N, 32, side // 2, side // 2, generator=g)
     xr, Wr, br = (t.clone().requires_grad_(True) for t in (x, W, b))
-    ref = torch.relu(F.conv2d(xr, Wr, br, stride=2, padding=1))
+    pre = F.conv2d(xr, Wr, br, stride=2, padding=1)
+    up = up * (pre.detach().abs() > 1e-5)   # no upstream gradient where rounding picks the ReLU mask (see dec_up_vs_torch)
+    ref = torch.relu(pre)
     (ref * up).sum().backward()
     xd, Wd, bd = (t.clone().to(DEV).requires_grad_(True) for t in (x, W, b))
     out = EncoderMid.apply(xd, Wd, bd)
@@ -1354,3 +1358,481 @@ def small_linear_per_row(DEV, lead, F, O, softmax, strided, yardstick=False):
     for name, a, b in zip(("linear.y", "linear.dx", "linear.dw", "linear.db"), got, want):
         _check_steps(name, a, b, RNN_STEP_TOL[name], out)
     return out
+
+
+# ---- frame-VAE kernels (vae_conv_edge.h, vae_conv_mid.h, vae_conv_up_wino.h / vae_conv_up.h, vae_heads.h, vae_loss.h), one
+# (frame, channel) plane / one row at a time against float64 ----
+# Bars = 4 x VAE_YARDSTICK, the rule of RNN_STEP_TOL.  The yardstick of a quantity is the largest ratio of FLOAT32 TORCH ON THE CPU
+# (F.conv2d, F.pixel_shuffle, F.linear, ... run in float32 on the same inputs) against the float64 reference, over every case of both
+# tiers with at most 4099 frames (VAE_SMALL_CASES, VAE_RESIDUE_N, VAE_GRID_CASES, VAE_SCALE_CASES, the probes, VAE_HEADS_N,
+# VAE_BCE_CASES; rerun: the case functions with yardstick=True).  Ratios of the plain-loop twins and what is still unmeasured: DESIGN section 2.
+# `x`: per (frame, channel) plane / per row (_per_step_ratio); `x.whole`: the tensor as a whole (rel_err).
+VAE_LAYERS = {   # layer: (input channels, conv output channels, stride, PixelShuffle factor, ReLU, weight scale, bias scale)
+    "stem": (1, 32, 2, 1, True, 0.3, 0.1), "enc_mid": (32, 32, 2, 1, True, 0.08, 0.1),
+    "dec_up": (32, 128, 1, 2, True, 0.08, 0.1), "dec_head": (32, 4, 1, 2, False, 0.1, 1.0)}
+VAE_SIDES = {"stem": (32,), "enc_mid": (16, 8), "dec_up": (8, 4), "dec_head": (16,)}
+VAE_NEAR = 1e-5         # |float64 pre-activation| <= VAE_NEAR x frame scale: the ReLU mask is rounding's choice, no upstream gradient there
+VAE_NEAR_SHARE = 1e-4   # ... and at most this share of a case's pixels may be left out that way
+VAE_YARDSTICK = {   # float32 torch on the CPU against float64, largest ratio over the cases of both tiers with N <= 4099
+    "stem.out": 3.45e-06, "stem.out.whole": 1.75e-07, "stem.dw": 1.14e-05, "stem.dw.whole": 3.80e-06, "stem.db": 4.28e-06,
+    "enc_mid.out": 1.69e-05, "enc_mid.out.whole": 4.82e-07, "enc_mid.dx": 6.13e-07, "enc_mid.dx.whole": 3.55e-07,
+    "enc_mid.dw": 3.27e-06, "enc_mid.dw.whole": 7.72e-07, "enc_mid.db": 1.62e-06,
+    "dec_up.out": 1.73e-06, "dec_up.out.whole": 4.40e-07, "dec_up.dx": 1.04e-06, "dec_up.dx.whole": 3.07e-07,
+    "dec_up.dw": 4.81e-06, "dec_up.dw.whole": 1.16e-06, "dec_up.db": 4.62e-06,
+    "dec_head.out": 6.29e-07, "dec_head.out.whole": 4.50e-07, "dec_head.dx": 6.02e-07, "dec_head.dx.whole": 3.18e-07,
+    "dec_head.dw": 8.86e-06, "dec_head.dw.whole": 2.21e-06, "dec_head.db": 4.81e-06,
+    "enc_head.a": 2.40e-05, "enc_head.mu": 7.23e-06, "enc_head.var": 7.08e-07, "enc_head.dfeat": 1.94e-07, "enc_head.param": 7.12e-07,
+    "dec_fc.h": 1.62e-07, "dec_fc.da": 1.44e-05, "dec_fc.dw": 1.16e-05, "dec_fc.db": 1.41e-07,
+    "latent_reg.reg": 3.18e-07, "latent_reg.da": 1.95e-07, "latent_reg.dmu": 1.49e-07, "latent_reg.dvar": 2.68e-07,
+    "bce.ll": 1.66e-07, "bce.dlogits": 1.43e-07,
+}
+VAE_STEP_TOL = {k: 4.0 * v for k, v in VAE_YARDSTICK.items()}
+
+
+def _conv_ref64(x, W, b, stride, shuffle, relu):
+    """(out, pre-activation) of act(pixel_shuffle(conv3x3(x, W, padding 1, stride) + b)) WITHOUT torch's convolution: zero-pad, nine
+    shifted (strided) slices, one einsum over the input channels per tap; frames in slices of at most 4096.  Gradients: autograd."""
+    pres = []
+    for lo in range(0, x.shape[0], 4096):
+        xs = x[lo:lo + 4096]
+        n, ci, H, Wd = xs.shape
+        xp = xs.new_zeros(n, ci, H + 2, Wd + 2)
+        xp[:, :, 1:H + 1, 1:Wd + 1] = xs
+        Ho, Wo = (H - 1) // stride + 1, (Wd - 1) // stride + 1
+        acc = b.view(1, -1, 1, 1).expand(n, W.shape[0], Ho, Wo)
+        for ky in range(3):
+            for kx in range(3):
+                tap = xp[:, :, ky:ky + stride * (Ho - 1) + 1:stride, kx:kx + stride * (Wo - 1) + 1:stride]
+                acc = acc + torch.einsum("nchw,oc->nohw", tap, W[:, :, ky, kx])
+        pres.append(acc)
+    pre = torch.cat(pres)
+    if shuffle > 1:   # PixelShuffle: channel c r^2 + i r + j at (h, w) -> channel c at (h r + i, w r + j)
+        n, c, H, Wd = pre.shape
+        pre = pre.view(n, c // shuffle ** 2, shuffle, shuffle, H, Wd).permute(0, 1, 4, 2, 5, 3).reshape(
+            n, c // shuffle ** 2, H * shuffle, Wd * shuffle)
+    return (torch.relu(pre) if relu else pre), pre
+
+
+def _conv_torch(x, W, b, stride, shuffle, relu):
+    """The same layer through torch's own convolution, in the dtype of its arguments (the float32 yardstick; float64: the pin of
+    _conv_ref64)."""
+    import torch.nn.functional as F
+    pre = F.conv2d(x, W, b, stride=stride, padding=1)
+    pre = F.pixel_shuffle(pre, shuffle) if shuffle > 1 else pre
+    return (torch.relu(pre) if relu else pre), pre
+
+
+def _vae_fn(layer):
+    from kvae.vae import fused
+    return {"stem": fused.EncoderStem, "enc_mid": fused.EncoderMid, "dec_up": fused.DecoderUp, "dec_head": fused.DecoderHead}[layer]
+
+
+def _frame_sample(N, chunk=16384, seed=0):
+    """The frames of a large case that go to the host: the first one, the last 17 (the ragged tail and both sides of the last full
+    iteration / column set of every kernel: at most 8 frames each), both sides of every launch boundary, 256 seeded random ones."""
+    s = {0} | set(range(max(N - 17, 0), N))
+    for k in range(chunk, N, chunk):
+        s.update((k - 1, k))
+    s.update(torch.randint(0, N, (256,), generator=torch.Generator().manual_seed(seed)).tolist())
+    return torch.tensor(sorted(s))
+
+
+def _vae_inputs(layer, N, side, seed, gdev, scales):
+    """x [N,cin,side,side] on `gdev` (float32, non-negative like the activations the layers see, frame i scaled by
+    (1e-3, 1, 1e+2)[i % 3] with `scales`), the frame scales [N] (host), W, b (host, float32)."""
+    cin, cout, _, _, _, ws, bs = VAE_LAYERS[layer]
+    g = torch.Generator(device=gdev).manual_seed(7919 * seed + 31 * N + side)
+    x = torch.rand(N, cin, side, side, generator=g, device=gdev) if layer == "stem" else \
+        torch.relu(torch.randn(N, cin, side, side, generator=g, device=gdev))
+    s = torch.ones(N)
+    if scales:
+        s = torch.tensor([1e-3, 1.0, 1e2])[torch.arange(N) % 3]
+        x = x * s.to(gdev).view(-1, 1, 1, 1)
+    gh = torch.Generator().manual_seed(104729 * seed + 17 * N + side)
+    return x, s, ws * torch.randn(cout, cin, 3, 3, generator=gh), bs * torch.randn(cout, generator=gh), gh
+
+
+def _vae_compare(layer, got, want, out, S=None):
+    """got = (out, g_x or None, g_W, g_b) of the kernels (frames S of out / g_x), want = the float64 ones."""
+    tol = lambda k: VAE_STEP_TOL[f"{layer}.{k}"]
+    sel = (lambda t: t.detach()[S.to(t.device)].cpu()) if S is not None else (lambda t: t.detach().cpu())
+    for k, a, r, cut in (("out", got[0], want[0], True), ("dx", got[1], want[1], True), ("dw", got[2], want[2], False)):
+        if r is None:
+            assert a is None
+            continue
+        a = sel(a) if cut else a.detach().cpu()
+        _check_steps(f"{layer}.{k}", a, r, tol(k), out)
+        _check_whole(f"{layer}.{k}.whole", a, r, tol(k + ".whole"), out)
+    _check_whole(f"{layer}.db", got[3], want[3], tol("db"), out)
+
+
+def _vae_reference(layer, xs, scale_s, W, b, up_of):
+    """Float64 run on the frames xs (float32 values).  up_of(near) -> the upstream gradient (float32) given the near-threshold
+    mask.  Returns (out64, g_x64 or None, g_W64, g_b64), up, near, share."""
+    _, _, stride, shuf, relu, _, _ = VAE_LAYERS[layer]
+    xr = xs.double().requires_grad_(layer != "stem")
+    Wr, br = W.double().requires_grad_(True), b.double().requires_grad_(True)
+    out64, pre64 = _conv_ref64(xr, Wr, br, stride, shuf, relu)
+    near = (pre64.detach().abs() <= VAE_NEAR * scale_s.double().view(-1, 1, 1, 1)) if relu else torch.zeros_like(pre64, dtype=torch.bool)
+    up = up_of(near)
+    out64.backward(up.double())
+    return (out64.detach(), xr.grad, Wr.grad, br.grad), up, near
+
+
+def _vae_kernels(DEV, layer, x, W, b, up, want_dx=True):
+    """The fused Function on float32 operands already on DEV."""
+    xd = x.requires_grad_(layer != "stem" and want_dx)
+    Wd, bd = W.to(DEV).requires_grad_(True), b.to(DEV).requires_grad_(True)
+    out = _vae_fn(layer).apply(xd, Wd, bd)
+    out.backward(up)
+    return out.detach(), xd.grad, Wd.grad, bd.grad
+
+
+def _vae_check_mask(out, out64, near, S=None):
+    """Outside the near-threshold pixels the kernel's ReLU mask IS the reference's: a difference is a failure."""
+    got = out.detach()[S.to(out.device)].cpu() if S is not None else out.detach().cpu()
+    diff = ((got > 0) != (out64 > 0)) & ~near
+    assert not bool(diff.any()), ("ReLU mask differs from float64 away from the threshold", int(diff.sum()), diff.nonzero()[:4].tolist())
+
+
+def conv_layer_per_frame(DEV, layer, N, side, frames=None, seed=0, yardstick=False, scales=False):
+    """One convolution layer of the frame VAE (`layer` in VAE_LAYERS, through its kvae.vae.fused Function) against _conv_ref64:
+    the output and the data gradient per (frame, channel) plane, the weight gradient per (output channel, input channel), the bias
+    gradient as a whole; out / dx / dW also as whole tensors at bars of their own (a plane at the 1e-2 floor of _per_step_ratio turns
+    1e-7 of the tensor's maximum into 1e-5, so only the whole-tensor bar holds the full-scale values to float32's own accuracy).
+    ReLU: the upstream gradient is zero where the float64 pre-activation is within VAE_NEAR x frame scale of 0 - at most
+    VAE_NEAR_SHARE of the pixels, asserted; a case of a few frames whose first draw has more (one pixel of 2048 is 5e-4) redraws its
+    inputs, which depends on the float64 reference alone - and everywhere else the kernel's mask must equal the reference's.
+    `frames` (given, or N > 4099): x is drawn on the device, only the frames of _frame_sample reach the host; out and dx are compared
+    on them, the upstream gradient is non-zero ONLY on them - so the float64 weight / bias gradient needs no other frame, a frame the
+    kernel drops or reads from elsewhere is a whole term of it, and dx of every other frame must be exactly zero (checked on the
+    device over the whole tensor).  yardstick: float32 torch on the CPU in place of the kernels.  Returns the largest ratios."""
+    _, _, stride, shuf, relu, _, _ = VAE_LAYERS[layer]
+    assert side in VAE_SIDES[layer]
+    if frames is None and N > 4099:
+        frames = _frame_sample(N, getattr(_vae_fn(layer), "CHUNK", 16384), seed)
+    sampled = frames is not None
+    assert not (sampled and yardstick)
+    gdev = DEV if sampled else "cpu"
+    for draw in range(8):
+        x, s, W, b, gh = _vae_inputs(layer, N, side, seed + 1000 * draw, gdev, scales)
+        S = frames if sampled else torch.arange(N)
+        xs = x[S.to(x.device)].cpu()
+        want, up_s, near = _vae_reference(layer, xs, s[S], W, b, lambda near: torch.randn(near.shape, generator=gh) * ~near)
+        share = float(near.double().mean())
+        if share <= VAE_NEAR_SHARE:
+            break
+    assert share <= VAE_NEAR_SHARE, ("too many pixels at the ReLU threshold", share)
+    res = {}
+    if yardstick:
+        xr = xs.clone().requires_grad_(layer != "stem")
+        Wr, br = W.clone().requires_grad_(True), b.clone().requires_grad_(True)
+        out, _ = _conv_torch(xr, Wr, br, stride, shuf, relu)
+        out.backward(up_s)
+        got = (out.detach(), xr.grad, Wr.grad, br.grad)
+    else:
+        if sampled:
+            up = torch.zeros(N, *up_s.shape[1:], device=DEV)
+            up[S.to(DEV)] = up_s.to(DEV)
+        else:
+            up = up_s.to(DEV)
+        got = _vae_kernels(DEV, layer, x.to(DEV), W, b, up)
+        del up
+        if sampled and got[1] is not None:
+            other = got[1].abs().amax(dim=(1, 2, 3))
+            other[S.to(DEV)] = 0.0
+            assert float(other.max()) == 0.0, ("dx of a frame without upstream gradient", int(other.argmax()))
+    if relu:
+        _vae_check_mask(got[0], want[0], near, S if (sampled and not yardstick) else None)
+    _vae_compare(layer, got, want, res, S if (sampled and not yardstick) else None)
+    res["near_share"] = share
+    return res
+
+
+def _probe_positions(n):
+    """Four corners, one pixel of each edge, one interior pixel of an n x n grid (n >= 4)."""
+    h = n // 2
+    return [(0, 0), (0, n - 1), (n - 1, 0), (n - 1, n - 1), (0, h), (n - 1, h), (h, 0), (h, n - 1), (1, h)]
+
+
+def probe_frames(layer, side):
+    """(N, frames): the first and the last frame of an iteration / column set and the last frame of a ragged one, for every kernel
+    of the layer (frames per iteration: enc_mid 2 | 8; dec_up Winograd 1 | 4, direct 2 | 8; edge layers one frame per workgroup)."""
+    return {("stem", 32): (3, (0, 2)), ("dec_head", 16): (3, (0, 2)), ("enc_mid", 16): (3, (0, 1, 2)), ("enc_mid", 8): (13, (0, 7, 12)),
+            ("dec_up", 8): (3, (0, 1, 2)), ("dec_up", 4): (13, (0, 3, 7, 12))}[(layer, side)]
+
+
+def conv_probe(DEV, layer, side, kind, frame, pos, N=None, seed=0, yardstick=False):
+    """Structured inputs.  kind "upstream": dense frames, the upstream gradient on ONE output pixel `pos` of ONE frame (all channels):
+    the data gradient must match float64 inside that pixel's receptive field and be EXACTLY zero everywhere else, other frames
+    included; weight and bias gradients are that frame's term alone.  kind "input": every frame zero except the input pixel `pos` of
+    one frame (all channels): every other frame's output must be act(bias), broadcast, exactly (a zero patch gives a zero Winograd
+    product), the frame itself matches float64; dense upstream gradient."""
+    _, cout, stride, shuf, relu, _, _ = VAE_LAYERS[layer]
+    N = N or probe_frames(layer, side)[0]
+    x, s, W, b, gh = _vae_inputs(layer, N, side, seed + 50, "cpu", False)
+    so = ((side - 1) // stride + 1) * shuf
+    py, px = pos
+    if kind == "input":
+        imp = x[frame, :, py, px].clone() + 0.25
+        x = torch.zeros_like(x)
+        x[frame, :, py, px] = imp
+
+    def up_of(near):
+        up = torch.randn(near.shape, generator=gh)
+        if kind == "upstream":
+            keep = torch.zeros_like(near)
+            keep[frame, :, py, px] = True
+            up = up * keep
+        return up * ~near
+    want, up, near = _vae_reference(layer, x, s, W, b, up_of)
+    if yardstick:
+        xr = x.clone().requires_grad_(layer != "stem")
+        Wr, br = W.clone().requires_grad_(True), b.clone().requires_grad_(True)
+        out, _ = _conv_torch(xr, Wr, br, stride, shuf, relu)
+        out.backward(up)
+        got = (out.detach(), xr.grad, Wr.grad, br.grad)
+    else:
+        got = _vae_kernels(DEV, layer, x.to(DEV), W, b, up.to(DEV))
+    res = {}
+    if relu:
+        _vae_check_mask(got[0], want[0], near)
+    _vae_compare(layer, got, want, res)
+    if kind == "upstream" and got[1] is not None:
+        cy, cx = py // shuf, px // shuf
+        field = torch.zeros(N, 1, side, side, dtype=torch.bool)
+        field[frame, 0, max(stride * cy - 1, 0):stride * cy + 2, max(stride * cx - 1, 0):stride * cx + 2] = True
+        outside = ~field.expand(N, x.shape[1], side, side)
+        assert float(want[1][outside].abs().max()) == 0.0   # the geometry above is the reference's
+        leak = got[1].detach().cpu()[outside]
+        assert float(leak.abs().max()) == 0.0, ("data gradient outside the receptive field", float(leak.abs().max()))
+    if kind == "input" and not yardstick:
+        flat = b.view(1, -1, 1, 1).expand(1, cout, so // shuf, so // shuf)
+        flat = torch.nn.functional.pixel_shuffle(flat, shuf) if shuf > 1 else flat
+        flat = torch.relu(flat) if relu else flat
+        others = [i for i in range(N) if i != frame]
+        if others:
+            o = got[0].detach().cpu()[others]
+            assert torch.equal(o, flat.expand_as(o).contiguous()), "a frame of zeros does not give act(bias) exactly"
+    return res
+
+
+def conv_no_input_grad(DEV, layer, N, side):
+    """needs_input_grad[0] == False (the `g_x is None` branch of the backward): the same weight and bias gradients, bit for bit."""
+    x, s, W, b, gh = _vae_inputs(layer, N, side, 3, "cpu", False)
+    _, _, stride, shuf, _, _, _ = VAE_LAYERS[layer]
+    so = ((side - 1) // stride + 1) * shuf
+    up = torch.randn(N, VAE_LAYERS[layer][1] // shuf ** 2, so, so, generator=gh).to(DEV)
+    with_dx = _vae_kernels(DEV, layer, x.clone().to(DEV), W, b, up, want_dx=True)
+    without = _vae_kernels(DEV, layer, x.clone().to(DEV), W, b, up, want_dx=False)
+    assert with_dx[1] is not None and without[1] is None
+    assert torch.equal(with_dx[0], without[0]) and torch.equal(with_dx[2], without[2]) and torch.equal(with_dx[3], without[3])
+
+
+def _iters_cases(fpis):
+    """Frame counts that give 255, 256, 257 and 513 iterations / column sets (the last one ragged) of kernels with `fpis` frames each."""
+    return sorted({(it - 1) * f + 1 for f in fpis for it in (255, 256, 257, 513)})
+
+
+# (layer, side, N): every residue of every kernel's frames per iteration (N = 1 ... 17), and the persistent grids (256 workgroups
+# for enc_mid / dec_up, 1024 weight-gradient rows for the edge layers) one short, full, one over and past two rounds
+VAE_RESIDUE_N = list(range(1, 18))
+VAE_GRID_CASES = ([("enc_mid", 16, n) for n in _iters_cases((2,))] + [("enc_mid", 8, n) for n in _iters_cases((8,))] +
+                  [("dec_up", 8, n) for n in _iters_cases((1, 2))] + [("dec_up", 4, n) for n in _iters_cases((4, 8))] +
+                  [(l, sd, n) for l, sd in (("stem", 32), ("dec_head", 16)) for n in (1023, 1024, 1025, 2049)])
+VAE_LAYER_SIDES = [(l, sd) for l in VAE_LAYERS for sd in VAE_SIDES[l]]
+VAE_CHUNK_N = (16383, 16384, 16385, 20000)
+VAE_C5_N = 512 * 200
+# CPU tier (plain-loop twins): residues, and sampled cases of a few frames (CHUNK patched down to 16 there: three launches)
+VAE_SMALL_CASES = [(l, sd, n) for l, sd in VAE_LAYER_SIDES for n in (1, 2, 3, 5, 8, 9, 13, 17)] + [("enc_mid", 8, 64), ("dec_up", 4, 64)]
+
+
+def _rows(t):
+    return t.detach().cpu().reshape(t.shape[0], 1, -1)
+
+
+def _row_sample(N, seed=0):
+    return _frame_sample(N, 1 << 40, seed)
+
+
+def vae_heads_per_row(DEV, N, rows=None, seed=0, yardstick=False):
+    """EncoderHead (+ reparameterisation), DecoderFc and LatentReg against the float64 form of the torch expressions of
+    vae_heads_vs_torch: every output and every per-row gradient one row at a time, parameter gradients as whole tensors.  `rows`
+    (given, or N > 4099): inputs drawn on the device, the rows of _row_sample compared, upstream gradients non-zero on them alone and
+    the per-row gradients of every other row exactly zero."""
+    import torch.nn.functional as F
+    from kvae.vae.fused import DecoderFc, EncoderHead, LatentReg
+    if rows is None and N > 4099:
+        rows = _row_sample(N, seed)
+    sampled = rows is not None
+    assert not (sampled and yardstick)
+    gdev = DEV if sampled else "cpu"
+    S = rows if sampled else torch.arange(N)
+    g = torch.Generator(device=gdev).manual_seed(11 * N + seed)
+    gh = torch.Generator().manual_seed(13 * N + seed)
+    rd = lambda *sh: torch.randn(*sh, generator=g, device=gdev)
+    rh = lambda *sh: torch.randn(*sh, generator=gh)
+    ne = 0.03
+    res = {}
+    tol = VAE_STEP_TOL
+
+    def full(up_s):   # the sampled rows' upstream gradient inside zeros
+        if not sampled:
+            return up_s.to(DEV)
+        up = torch.zeros(N, *up_s.shape[1:], device=DEV)
+        up[S.to(DEV)] = up_s.to(DEV)
+        return up
+
+    def cut(t):
+        return t.detach()[S.to(t.device)].cpu() if sampled else t.detach().cpu()
+
+    def zero_elsewhere(t, name):
+        if sampled:
+            other = t.detach().abs().reshape(N, -1).amax(-1)
+            other[S.to(t.device)] = 0.0
+            assert float(other.max()) == 0.0, (name, int(other.argmax()))
+
+    # encoder head
+    feat, eps = torch.relu(rd(N, 512)), rd(N, 2)
+    par = [0.05 * rh(2, 512), 0.1 * rh(2), 0.05 * rh(2, 512), 0.1 * rh(2)]
+    ups = [rh(len(S), 2) for _ in range(3)]
+
+    def enc(dt, f, e, p):
+        mu = F.linear(f, p[0], p[1])
+        var = ne * torch.sigmoid(F.linear(f, p[2], p[3]))
+        return mu + e * torch.sqrt(var + 1e-6), mu, var
+    f64 = feat[S.to(gdev)].cpu().double().requires_grad_(True)
+    p64 = [t.double().requires_grad_(True) for t in par]
+    o64 = enc(torch.float64, f64, eps[S.to(gdev)].cpu().double(), p64)
+    sum((o * u.double()).sum() for o, u in zip(o64, ups)).backward()
+    if yardstick:
+        fd, pd = feat.clone().requires_grad_(True), [t.clone().requires_grad_(True) for t in par]
+        od = enc(torch.float32, fd, eps, pd)
+        sum((o * u).sum() for o, u in zip(od, ups)).backward()
+    else:
+        fd, pd = feat.to(DEV).requires_grad_(True), [t.to(DEV).requires_grad_(True) for t in par]
+        od = EncoderHead.apply(fd, *pd, eps.to(DEV), ne)
+        torch.autograd.backward(od, [full(u) for u in ups])
+        zero_elsewhere(fd.grad, "enc_head.dfeat")
+    for k, a, r in zip(("a", "mu", "var"), od, o64):
+        _check_steps("enc_head." + k, _rows(cut(a)), _rows(r), tol["enc_head." + k], res)
+    _check_steps("enc_head.dfeat", _rows(cut(fd.grad)), _rows(f64.grad), tol["enc_head.dfeat"], res)
+    for a, r in zip(pd, p64):
+        _check_whole("enc_head.param", a.grad, r.grad, tol["enc_head.param"], res)
+
+    # decoder fc
+    lat, W, b, up_s = rd(N, 2), 0.3 * rh(512, 2), 0.1 * rh(512), rh(len(S), 512)
+    l64, W64, b64 = lat[S.to(gdev)].cpu().double().requires_grad_(True), W.double().requires_grad_(True), b.double().requires_grad_(True)
+    h64 = F.linear(l64, W64, b64)
+    h64.backward(up_s.double())
+    if yardstick:
+        ld, Wd, bd = lat.clone().requires_grad_(True), W.clone().requires_grad_(True), b.clone().requires_grad_(True)
+        h = F.linear(ld, Wd, bd)
+        h.backward(up_s)
+    else:
+        ld, Wd, bd = lat.to(DEV).requires_grad_(True), W.to(DEV).requires_grad_(True), b.to(DEV).requires_grad_(True)
+        h = DecoderFc.apply(ld, Wd, bd)
+        h.backward(full(up_s))
+        zero_elsewhere(ld.grad, "dec_fc.da")
+    _check_steps("dec_fc.h", _rows(cut(h)), _rows(h64), tol["dec_fc.h"], res)
+    _check_steps("dec_fc.da", _rows(cut(ld.grad)), _rows(l64.grad), tol["dec_fc.da"], res)
+    _check_steps("dec_fc.dw", Wd.grad.detach().cpu()[:, None], W64.grad[:, None], tol["dec_fc.dw"], res)
+    _check_whole("dec_fc.db", bd.grad, b64.grad, tol["dec_fc.db"], res)
+
+    # latent regulariser
+    a0, m0 = rd(N, 2), rd(N, 2)
+    v0 = 0.01 + 0.05 * torch.rand(N, 2, generator=g, device=gdev)
+    w = rh(len(S))
+    lg = lambda x, mean, var: -0.5 * math.log(2 * math.pi) - 0.5 * torch.log(var) - (x - mean) ** 2 / (2 * var)
+    reg_of = lambda a, m, v: (lg(a, torch.zeros((), dtype=a.dtype), torch.ones((), dtype=a.dtype)) - lg(a, m, v)).sum(-1)
+    i64 = [t[S.to(gdev)].cpu().double().requires_grad_(True) for t in (a0, m0, v0)]
+    r64 = reg_of(*i64)
+    r64.backward(w.double())
+    if yardstick:
+        idv = [t.clone().requires_grad_(True) for t in (a0, m0, v0)]
+        reg = reg_of(*idv)
+        reg.backward(w)
+    else:
+        idv = [t.to(DEV).requires_grad_(True) for t in (a0, m0, v0)]
+        reg = LatentReg.apply(*idv)
+        reg.backward(full(w))
+        for t, k in zip(idv, ("da", "dmu", "dvar")):
+            zero_elsewhere(t.grad, "latent_reg." + k)
+    _check_steps("latent_reg.reg", _rows(cut(reg)), _rows(r64), tol["latent_reg.reg"], res)
+    for t, r, k in zip(idv, i64, ("da", "dmu", "dvar")):
+        _check_steps("latent_reg." + k, _rows(cut(t.grad)), _rows(r.grad), tol["latent_reg." + k], res)
+    return res
+
+
+def bce_frames_per_row(DEV, B, T, C=1, H=32, W=32, rows=None, seed=0, yardstick=False):
+    """BernoulliFrameLogLik against float64 -BCEWithLogits summed over the pixels: log p(x_t | a_t) and the gradient of the logits
+    one frame at a time.  `rows` (given, or B T > 4099): as in vae_heads_per_row."""
+    import torch.nn.functional as F
+    from kvae.vae.fused import BernoulliFrameLogLik
+    N = B * T
+    if rows is None and N > 4099:
+        rows = _row_sample(N, seed)
+    sampled = rows is not None
+    assert not (sampled and yardstick)
+    gdev = DEV if sampled else "cpu"
+    S = rows if sampled else torch.arange(N)
+    g = torch.Generator(device=gdev).manual_seed(17 * N + H + seed)
+    logits = 3 * torch.randn(B, T, C, H, W, generator=g, device=gdev)
+    x = (torch.rand(B, T, C, H, W, generator=g, device=gdev) < 0.2).float()
+    w_s = torch.randn(len(S), generator=torch.Generator().manual_seed(19 * N + seed))
+    l64 = logits.view(N, -1)[S.to(gdev)].cpu().double().requires_grad_(True)
+    ll64 = -F.binary_cross_entropy_with_logits(l64, x.view(N, -1)[S.to(gdev)].cpu().double(), reduction="none").sum(-1)
+    ll64.backward(w_s.double())
+    res = {}
+    if yardstick:
+        ld = logits.clone().requires_grad_(True)
+        ll = -F.binary_cross_entropy_with_logits(ld, x, reduction="none").sum(dim=(2, 3, 4))
+        ll.backward(w_s.view(B, T))
+        cut = lambda t: t.detach().reshape(N, -1)
+    else:
+        ld = logits.to(DEV).requires_grad_(True)
+        ll = BernoulliFrameLogLik.apply(ld, x.to(DEV))
+        w = torch.zeros(N, device=DEV)
+        w[S.to(DEV)] = w_s.to(DEV)
+        ll.backward(w.view(B, T))
+        if sampled:
+            other = ld.grad.abs().reshape(N, -1).amax(-1)
+            other[S.to(DEV)] = 0.0
+            assert float(other.max()) == 0.0, ("bce.dlogits of a frame without upstream gradient", int(other.argmax()))
+        cut = lambda t: t.detach().reshape(N, -1)[S.to(t.device)].cpu()
+    _check_steps("bce.ll", _rows(cut(ll)), _rows(ll64), VAE_STEP_TOL["bce.ll"], res)
+    _check_steps("bce.dlogits", _rows(cut(ld.grad)), _rows(l64.grad), VAE_STEP_TOL["bce.dlogits"], res)
+    return res
+
+
+VAE_SCALE_CASES = [(l, sd, n) for l, sd in VAE_LAYER_SIDES for n in (13, 64)]   # frames scaled by 1e-3, 1, 1e+2 in turn
+VAE_HEADS_N = (1, 2, 37, 1031, 4099)          # CPU tier: the first three
+VAE_BCE_CASES = [(1, 1), (2, 3), (7, 9), (64, 50)]   # (B, T) of 32 x 32 frames; CPU tier: the first three
+
+
+def vae_probe_cases(layer, side):
+    """(kind, frame, pos) of every structured probe of one layer: nine positions x the frames of probe_frames x both kinds."""
+    _, _, stride, shuf, _, _, _ = VAE_LAYERS[layer]
+    so = ((side - 1) // stride + 1) * shuf
+    _, frames = probe_frames(layer, side)
+    return [(kind, f, pos) for kind, n in (("upstream", so), ("input", side)) for f in frames for pos in _probe_positions(n)]
+
+
+def vae_variant_cases(DEV, layer):
+    """Every small case of one layer, the grids and one two-launch case: what a process started with a kernel switch runs."""
+    worst = {}
+
+    def take(res):
+        for k, v in res.items():
+            worst[k] = max(worst.get(k, 0.0), v)
+    for side in VAE_SIDES[layer]:
+        for N in VAE_RESIDUE_N:
+            take(conv_layer_per_frame(DEV, layer, N, side))
+        for l, sd, N in VAE_GRID_CASES + VAE_SCALE_CASES:
+            if (l, sd) == (layer, side):
+                take(conv_layer_per_frame(DEV, layer, N, side, scales=(l, sd, N) in VAE_SCALE_CASES))
+        for kind, frame, pos in vae_probe_cases(layer, side):
+            take(conv_probe(DEV, layer, side, kind, frame, pos))
+        take(conv_layer_per_frame(DEV, layer, 16385, side))
+    print(worst)
+    return worst

@@ -370,10 +370,11 @@ def test_dec_up_gpu(N, side):
 def test_conv_chunked_launches_gpu(which, side, monkeypatch):
     """20000 frames = two launches (CHUNK = 16384).  They must equal ONE launch over all frames and five independent
     4000-frame calls (a size the kernels are checked at against the CPU above): outputs and data gradients bit-identical,
-    weight gradients to fp32 summation order.  No external reference at this size: torch's CPU convolution backward
-    (fp32 and fp64 disagree with each other above 16384 frames) and MIOpen's Winograd data gradient (8e-3 off) both
-    proved unreliable here, while the three ways of running our kernels agree."""
+    weight gradients to fp32 summation order.  The external reference at this size is the nine-tap float64 restatement on
+    sampled frames (conv_layer_per_frame, also test_vae_conv_chunk_boundary_gpu): torch's CPU convolution backward (fp32 and
+    fp64 disagree with each other above 16384 frames) and MIOpen's Winograd data gradient (8e-3 off) both proved unreliable here."""
     from kvae.vae.fused import DecoderUp, EncoderMid
+    print(parity_cases.conv_layer_per_frame(DEV, which, 20000, side))
     Fn = EncoderMid if which == "enc_mid" else DecoderUp
     N, co = 20000, (32 if which == "enc_mid" else 128)
     g = torch.Generator().manual_seed(7)
@@ -579,3 +580,128 @@ def test_m4_split_and_single_launch_forms_give_the_same_bits():
         assert r.returncode == 0, r.stderr[-2000:]
         digests.append([l for l in r.stdout.splitlines() if l.startswith("DIGEST")][-1])
     assert digests[0] == digests[1]
+
+
+# ---- frame-VAE kernels per (frame, channel) plane / per row against float64 (parity_cases.conv_layer_per_frame and friends) ----
+@pytest.mark.parametrize("layer,side", parity_cases.VAE_LAYER_SIDES)
+def test_vae_conv_every_residue_gpu(layer, side):
+    """N = 1 ... 17: every residue of the frames per iteration / column set of every kernel of the layer, all frames compared."""
+    for N in parity_cases.VAE_RESIDUE_N:
+        print(N, parity_cases.conv_layer_per_frame(DEV, layer, N, side))
+
+
+@pytest.mark.parametrize("layer,side,N", parity_cases.VAE_GRID_CASES)
+def test_vae_conv_persistent_grid_gpu(layer, side, N):
+    """255, 256, 257 and 513 iterations / column sets on 256 persistent workgroups (the last one ragged); 1023 ... 2049 frames on
+    the 1024 weight-gradient rows of the edge kernels."""
+    print(parity_cases.conv_layer_per_frame(DEV, layer, N, side))
+
+
+@pytest.mark.parametrize("N", parity_cases.VAE_CHUNK_N)
+@pytest.mark.parametrize("layer,side", parity_cases.VAE_LAYER_SIDES)
+def test_vae_conv_chunk_boundary_gpu(layer, side, N):
+    """One frame short of a launch of CHUNK frames, exactly one, one frame into the second, and 20000: sampled frames against
+    float64, the upstream gradient on them alone."""
+    print(parity_cases.conv_layer_per_frame(DEV, layer, N, side))
+
+
+@pytest.mark.parametrize("layer,side", parity_cases.VAE_LAYER_SIDES)
+def test_vae_conv_c5_size_gpu(layer, side):
+    """512 x 200 frames, what bench.py --config c5 pushes through every layer: seven launches of the chunked ones, 102400
+    workgroups over tensors past 2^31 bytes in the edge kernels."""
+    print(parity_cases.conv_layer_per_frame(DEV, layer, parity_cases.VAE_C5_N, side))
+    torch.cuda.empty_cache()
+
+
+def _largest_launch(layer, side):
+    """The largest N with (N + 2048) x bytes per frame of the launch's largest tensor < 2^31 (kvae_vae.hip)."""
+    per_frame = 32 * side * side * 4 if layer == "enc_mid" else 128 * side * side * 4
+    return (1 << 31) // per_frame - 2048 - 1
+
+
+@pytest.mark.parametrize("layer,side", [("enc_mid", 16), ("enc_mid", 8), ("dec_up", 8), ("dec_up", 4)])
+def test_vae_conv_largest_single_launch_gpu(layer, side, monkeypatch):
+    """CHUNK out of the way: the largest frame count one launch accepts (63487 frames of 32 KiB, 260095 of 8 KiB), where the
+    32-bit byte offsets inside a launch come closest to wrapping."""
+    N = _largest_launch(layer, side)
+    assert N == {32768: 63487, 8192: 260095}[(32 if layer == "enc_mid" else 128) * side * side * 4]
+    monkeypatch.setattr(parity_cases._vae_fn(layer), "CHUNK", 1 << 30)
+    print(N, parity_cases.conv_layer_per_frame(DEV, layer, N, side))
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("layer,side", [("enc_mid", 16), ("dec_up", 8)])
+def test_vae_conv_one_frame_more_is_refused_gpu(layer, side):
+    """One frame above that through the raw C ABI: KVAE_ERR_ARG from the forward and the backward call, and not a byte of the
+    sentinel-filled outputs written.  Every tensor really holds N frames, so a wrong check could not leave its allocations."""
+    from kvae import _native as N_
+    lib = N_.hip_lib()
+    N = _largest_launch(layer, side) + 1
+    co, so = (32, side // 2) if layer == "enc_mid" else (128, 2 * side)
+    x = torch.zeros(N, 32, side, side, device=DEV)
+    W, b = torch.zeros(co, 32, 3, 3, device=DEV), torch.zeros(co, device=DEV)
+    out = torch.full((N, 32, so, so), 7.5, device=DEV)
+    g_x = torch.full((N, 32, side, side), 7.5, device=DEV)
+    pre = "kvae_" + layer
+    rows = getattr(lib.dll, pre + "_partial_rows")(N, side)
+    wp, bp = torch.full((rows, W.numel()), 7.5, device=DEV), torch.full((rows, co), 7.5, device=DEV)
+    st = N_.stream_for(x)
+    assert getattr(lib.dll, pre + "_fwd")(N_.ptr(x), N_.ptr(W), N_.ptr(b), N_.ptr(out), N, 32, side, st) == 4      # KVAE_ERR_ARG
+    g = torch.zeros_like(out)
+    assert getattr(lib.dll, pre + "_bwd")(N_.ptr(x), N_.ptr(W), N_.ptr(g), N_.ptr(g), N_.ptr(g_x), N_.ptr(wp), N_.ptr(bp), N, 32, side,
+                                          st) == 4
+    torch.cuda.synchronize()
+    for t in (out, g_x, wp, bp):
+        assert bool((t == 7.5).all())
+    assert getattr(lib.dll, pre + "_fwd")(N_.ptr(x), N_.ptr(W), N_.ptr(b), N_.ptr(out), N - 1, 32, side, st) == 0    # ... and N - 1 is taken
+    torch.cuda.synchronize()
+    assert bool((out[:N - 1] == 0).all()) and bool((out[N - 1] == 7.5).all())
+
+
+@pytest.mark.parametrize("layer,side", parity_cases.VAE_LAYER_SIDES)
+def test_vae_conv_probes_gpu(layer, side):
+    """Impulse upstream gradient / impulse input at corners, edges and an interior pixel, in the first and last frame of an
+    iteration / column set and of a ragged one: exact zeros outside the receptive field, act(bias) exactly in every other frame."""
+    worst = {}
+    for kind, frame, pos in parity_cases.vae_probe_cases(layer, side):
+        for k, v in parity_cases.conv_probe(DEV, layer, side, kind, frame, pos).items():
+            worst[k] = max(worst.get(k, 0.0), v)
+    print(worst)
+
+
+@pytest.mark.parametrize("layer,side,N", parity_cases.VAE_SCALE_CASES)
+def test_vae_conv_frame_scales_gpu(layer, side, N):
+    """Neighbouring frames scaled by 1e-3, 1 and 1e+2: an error of one frame cannot hide behind another frame's size."""
+    print(parity_cases.conv_layer_per_frame(DEV, layer, N, side, scales=True))
+
+
+@pytest.mark.parametrize("layer,side", [("enc_mid", 16), ("enc_mid", 8), ("dec_up", 8), ("dec_up", 4), ("dec_head", 16)])
+def test_vae_conv_without_input_gradient_gpu(layer, side):
+    parity_cases.conv_no_input_grad(DEV, layer, 13, side)
+
+
+@pytest.mark.parametrize("N", parity_cases.VAE_HEADS_N + (parity_cases.VAE_C5_N,))
+def test_vae_heads_per_row_gpu(N):
+    print(parity_cases.vae_heads_per_row(DEV, N))
+
+
+@pytest.mark.parametrize("B,T", parity_cases.VAE_BCE_CASES + [(512, 200)])
+def test_bce_frames_per_row_gpu(B, T):
+    print(parity_cases.bce_frames_per_row(DEV, B, T))
+
+
+@pytest.mark.parametrize("env,which", [({"KVAE_WINO": "0"}, "dec_up"), ({"KVAE_STEM_MFMA": "0"}, "stem"), ({"KVAE_STEM_MFMA": "2"}, "stem")])
+def test_vae_variant_kernels_per_frame(env, which):
+    """The kernels behind the switches (read once per process), each in a fresh process of its own: the direct decoder blocks
+    k_dec_up_*<8|4> (KVAE_WINO=0), the VALU stem weight gradient k_enc_stem_wrw (KVAE_STEM_MFMA=0) and the MFMA one with the mask
+    taken from `out` (k_enc_stem_wrw_mfma<false>, =2) through the residue sweep, the grids, the probes, the frame scales and one
+    16385-frame case, at the bars of the default kernels."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import sys; sys.path[:0] = [%r, %r, %r]; import parity_cases as p; p.vae_variant_cases('cuda', %r)"
+            % (root, os.path.join(root, "kalman-vae_amd"), os.path.join(root, "tests"), which))
+    r = subprocess.run([sys.executable, "-c", code], env={**os.environ, **env}, capture_output=True, text=True, timeout=900)
+    print(r.stdout[-3000:])
+    assert r.returncode == 0, r.stderr[-2000:]

@@ -369,3 +369,71 @@ def test_mix_per_row_hostsim(hostsim_backend, Bsz, T, K, E):
 @pytest.mark.parametrize("lead,F,O,softmax,strided", parity_cases.LINEAR_ROW_CASES)
 def test_small_linear_per_row_hostsim(hostsim_backend, lead, F, O, softmax, strided):
     parity_cases.small_linear_per_row("cpu", lead, F, O, softmax, strided)
+
+
+# ---- frame-VAE kernels per (frame, channel) plane / per row against float64: the case functions and their references, checked
+# on the plain-loop twins (the GPU tier runs the same functions on the kernels) ----
+@pytest.mark.parametrize("layer,side", parity_cases.VAE_LAYER_SIDES)
+def test_conv_ref64_is_float64_conv2d(layer, side):
+    """The nine-tap float64 reference == torch's own float64 convolution (+ pixel_shuffle / relu) at small N: values and every
+    gradient to 1e-12.  (F.unfold + matmul is the same code inside torch as F.conv2d; the nine shifted slices are not.)"""
+    _, cout, stride, shuf, relu, _, _ = parity_cases.VAE_LAYERS[layer]
+    for N in (1, 5):
+        x, _, W, b, gh = parity_cases._vae_inputs(layer, N, side, 0, "cpu", False)
+        res = []
+        for f in (parity_cases._conv_ref64, parity_cases._conv_torch):
+            leaves = [t.double().requires_grad_(True) for t in (x, W, b)]
+            out, pre = f(*leaves, stride, shuf, relu)
+            if not res:
+                up = torch.randn(out.shape, generator=gh, dtype=torch.float64)
+            out.backward(up)
+            res.append([out.detach(), pre.detach()] + [t.grad for t in leaves])
+        for a, r in zip(*res):
+            assert rel_err(a, r) < 1e-12
+
+
+@pytest.mark.parametrize("layer,side,N", parity_cases.VAE_SMALL_CASES)
+def test_vae_conv_per_frame_hostsim(hostsim_backend, layer, side, N, monkeypatch):
+    """Residues of every kernel's frames per iteration; at 64 frames the sampled form of the large cases (inputs drawn on the
+    device, upstream gradient on the sampled frames alone) over four launches of 16 frames."""
+    frames = None
+    if N > 17:
+        monkeypatch.setattr(parity_cases._vae_fn(layer), "CHUNK", 16)
+        frames = parity_cases._frame_sample(N, 16)[::2]
+    print(parity_cases.conv_layer_per_frame("cpu", layer, N, side, frames=frames))
+
+
+@pytest.mark.parametrize("layer,side", [("stem", 32), ("dec_head", 16)])
+def test_vae_conv_sampled_edge_layers_hostsim(hostsim_backend, layer, side):
+    print(parity_cases.conv_layer_per_frame("cpu", layer, 40, side, frames=torch.tensor([0, 1, 17, 38, 39])))
+
+
+@pytest.mark.parametrize("layer,side", parity_cases.VAE_LAYER_SIDES)
+def test_vae_conv_probes_hostsim(hostsim_backend, layer, side):
+    for kind, frame, pos in parity_cases.vae_probe_cases(layer, side):
+        parity_cases.conv_probe("cpu", layer, side, kind, frame, pos)
+
+
+@pytest.mark.parametrize("layer,side", parity_cases.VAE_LAYER_SIDES)
+def test_vae_conv_frame_scales_hostsim(hostsim_backend, layer, side):
+    print(parity_cases.conv_layer_per_frame("cpu", layer, 13, side, scales=True))
+
+
+@pytest.mark.parametrize("layer,side", [("enc_mid", 16), ("enc_mid", 8), ("dec_up", 8), ("dec_up", 4), ("dec_head", 16)])
+def test_vae_conv_without_input_gradient_hostsim(hostsim_backend, layer, side):
+    parity_cases.conv_no_input_grad("cpu", layer, 5, side)
+
+
+@pytest.mark.parametrize("N", parity_cases.VAE_HEADS_N[:3])
+def test_vae_heads_per_row_hostsim(hostsim_backend, N):
+    print(parity_cases.vae_heads_per_row("cpu", N))
+
+
+def test_vae_heads_sampled_rows_hostsim(hostsim_backend):
+    print(parity_cases.vae_heads_per_row("cpu", 300, rows=torch.tensor([0, 1, 150, 298, 299])))
+    print(parity_cases.bce_frames_per_row("cpu", 5, 8, rows=torch.tensor([0, 7, 8, 39])))
+
+
+@pytest.mark.parametrize("B,T", parity_cases.VAE_BCE_CASES[:3])
+def test_bce_frames_per_row_hostsim(hostsim_backend, B, T):
+    print(parity_cases.bce_frames_per_row("cpu", B, T))
