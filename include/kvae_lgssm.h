@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 #define KVAE_MAX_DIM 16
-#define KVAE_ABI_VERSION 12
+#define KVAE_ABI_VERSION 13
 
 typedef enum {
   KVAE_OK = 0,
@@ -206,6 +206,28 @@ int kvae_regime_fwd(const float *logits, const float *init_logits, const float *
 int kvae_regime_bwd(const float *logits, const float *init_logits, const float *gumbel, const float *P,
                     const float *y_seq, const float *g_y, const float *g_log_q, const float *g_log_p, float *g_logits,
                     float *g_init, int32_t B, int32_t T, int32_t K, float tau, const float *tau_dev, void *stream);
+
+/* Exact inference over the same chain (no sampling, no temperature).  The variational posterior is a Markov chain,
+ * q(s_0) = softmax(init_logits), q(s_t = j | s_{t-1} = i) = Q_t[i,j] with Q_t = row-softmax(logits[t]) (slice t = 0 is never
+ * read), so one forward sweep gives - each output may be NULL, its work is then skipped:
+ *   marginals [B,T,K]   m_0 = softmax(init), m_t[j] = sum_i m_{t-1}[i] Q_t[i,j]         (probability space, not renormalised)
+ *   path      [B,T]     int32, argmax over s_{0:T-1} of log q(s_{0:T-1}) by Viterbi in log space: d_0 = log_softmax(init),
+ *                       d_t[j] = max_i d_{t-1}[i] + log Q_t[i,j], backtrace from argmax_j d_{T-1}[j].  Ties: the LOWEST index
+ *                       wins, in every backpointer and in the final argmax.
+ *   path_logq [B]       log q of that path = max_j d_{T-1}[j]
+ *   kl        [B,T]     kl_0 = sum_j m_0[j] (log m_0[j] - log(1/K)),
+ *                       kl_t = sum_i m_{t-1}[i] sum_j Q_t[i,j] (log Q_t[i,j] - log max(P[i,j], 1e-8));   sum_t kl_t = KL(q || p)
+ *                       against the prior chain (uniform start, transitions P [K,K]) - the quantity of which kvae_regime_fwd's
+ *                       log_q - log_p is a one-sample estimate.
+ * All floating-point operands fp32, contiguous, finite.  One launch, one wavefront per sequence (csrc/regime_decode.h).
+ * ws: kvae_regime_decode_ws_bytes(B, T, K) bytes, 8-byte aligned - the Viterbi backpointers (4 bits per target state: one 32-bit
+ * word per (b,t) for K <= 8, one 64-bit word above); required when path or path_logq is requested.
+ * Errors: logits, init_logits or P NULL -> KVAE_ERR_NULL; B < 1, T < 1 or K > 16 -> KVAE_ERR_DIMS; K < 1 -> KVAE_ERR_ARG;
+ * ws NULL while path or path_logq is requested -> KVAE_ERR_NULL. */
+int kvae_regime_decode(const float *logits, const float *init_logits, const float *P, float *marginals, int32_t *path,
+                       float *path_logq, float *kl, void *ws, int32_t B, int32_t T, int32_t K, void *stream);
+/* bytes of workspace kvae_regime_decode needs (0 for dimensions it refuses) */
+int64_t kvae_regime_decode_ws_bytes(int64_t B, int32_t T, int32_t K);
 
 /* ---- bidirectional GRU of the regime posterior ("switching" dynamics) ------------------------- */
 

@@ -17,7 +17,7 @@ LIB_PATH = _HERE / "lib" / "libkvae_lgssm.so"
 KVAE_MAX_DIM = 16
 KVAE_MAX_K = 16
 LSTM_MAX_H, LSTM_MAX_I = 52, 16
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 _STATUS = {1: "KVAE_ERR_DIMS (n, m, p must be in [1,16]; B, T >= 1)", 2: "KVAE_ERR_NULL", 3: "KVAE_ERR_LAUNCH",
            4: "KVAE_ERR_ARG"}
@@ -67,7 +67,7 @@ class InputGrads(C.Structure):  # kvae_lgssm_input_grads
 
 SYMBOLS = ("kvae_lgssm_filter_alpha_lstm", "kvae_lgssm_alpha_lstm_bwd", "kvae_lgssm_filter_fwd", "kvae_lgssm_rts_fwd", "kvae_lgssm_smooth_fwd", "kvae_lgssm_smooth_bwd",
            "kvae_lgssm_elbo", "kvae_mix_fwd", "kvae_mix_bwd", "kvae_mix_bwd_partials", "kvae_lstm_fwd",
-           "kvae_lstm_bwd", "kvae_bias_shuffle_act_fwd", "kvae_bias_shuffle_act_bwd", "kvae_bias_partial_rows", "kvae_colsum", "kvae_colsum2", "kvae_clip_adam", "kvae_regime_fwd", "kvae_regime_bwd", "kvae_bigru_fwd", "kvae_bigru_bwd", "kvae_bce_frames_fwd", "kvae_bce_frames_bwd",
+           "kvae_lstm_bwd", "kvae_bias_shuffle_act_fwd", "kvae_bias_shuffle_act_bwd", "kvae_bias_partial_rows", "kvae_colsum", "kvae_colsum2", "kvae_clip_adam", "kvae_regime_fwd", "kvae_regime_bwd", "kvae_regime_decode", "kvae_regime_decode_ws_bytes", "kvae_bigru_fwd", "kvae_bigru_bwd", "kvae_bce_frames_fwd", "kvae_bce_frames_bwd",
            "kvae_dec_head_fwd", "kvae_dec_head_bwd", "kvae_enc_stem_fwd", "kvae_enc_stem_bwd", "kvae_conv_edge_partial_rows",
            "kvae_enc_mid_fwd", "kvae_enc_mid_bwd", "kvae_enc_mid_partial_rows",
            "kvae_dec_up_fwd", "kvae_dec_up_bwd", "kvae_dec_up_partial_rows", "kvae_dec_up_set_workgroups",
@@ -124,6 +124,10 @@ class LgssmLib:
         d.kvae_regime_fwd.restype = C.c_int
         d.kvae_regime_bwd.argtypes = [vp] * 10 + [C.c_int32] * 3 + [C.c_float, vp, vp]
         d.kvae_regime_bwd.restype = C.c_int
+        d.kvae_regime_decode.argtypes = [vp] * 8 + [C.c_int32] * 3 + [vp]
+        d.kvae_regime_decode.restype = C.c_int
+        d.kvae_regime_decode_ws_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+        d.kvae_regime_decode_ws_bytes.restype = C.c_int64
         d.kvae_bigru_fwd.argtypes = [vp] * 7 + [C.c_int32] * 4 + [vp]
         d.kvae_bigru_fwd.restype = C.c_int
         d.kvae_bigru_bwd.argtypes = [vp] * 8 + [C.c_int32] * 4 + [vp]

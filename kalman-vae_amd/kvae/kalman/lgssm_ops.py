@@ -451,6 +451,93 @@ class RegimeChain(torch.autograd.Function):
         return g_logits, g_init, None, None, None, None
 
 
+def regime_decode_supported(K, ref=None):
+    """Shapes / dtypes kvae_regime_decode is built for (include/kvae_lgssm.h: fp32, K <= 16); the rest takes regime_decode_torch.
+    The device is not asked about: fp32 host tensors go to the kernel's binding, which raises (kvae._native.lib_for)."""
+    if ref is not None and ref.dtype != torch.float32:
+        return False
+    return 1 <= K <= N.KVAE_MAX_K
+
+
+_DECODE_OUTPUTS = ("marginals", "path", "kl")
+
+
+def _decode_want(want):
+    want = (want,) if isinstance(want, str) else tuple(want)
+    bad = [w for w in want if w not in _DECODE_OUTPUTS]
+    if bad or not want:
+        raise ValueError(f"regime_decode: want must name some of {_DECODE_OUTPUTS}, got {want}")
+    return want
+
+
+def regime_decode(logits, init_logits, P, want=_DECODE_OUTPUTS, impl=None):
+    """Exact inference over the Markov regime posterior q(s_0) = softmax(init_logits), q(s_t | s_{t-1}) = row-softmax(logits[t])
+    (semantics: include/kvae_lgssm.h, kvae_regime_decode).  logits [B,T,K,K] (slice 0 unused), init_logits
+    [B,K], P [K,K] the prior's transition matrix.  want: which of "marginals", "path", "kl" to compute.  Returns a dict with
+    marginals [B,T,K], path [B,T] (int64: the most likely regime sequence, lowest index on ties) and path_logq [B] (its log q),
+    kl [B,T] (sum over t = KL(q || p)); entries not asked for are None.  One launch, no host synchronisation.
+    impl: None = the HIP kernel where it is built (fp32, K <= 16), else regime_decode_torch; "kernel" / "torch" force one."""
+    want = _decode_want(want)
+    Bsz, T, K, _ = logits.shape
+    use_kernel = impl == "kernel" or (impl is None and regime_decode_supported(K, logits))
+    if not use_kernel:
+        return regime_decode_torch(logits, init_logits, P, want)
+    dev = logits.device
+    logits, init_logits, P = (_f32c(t.detach().to(dev)) for t in (logits, init_logits, P))
+    mk = lambda *s, dt=torch.float32: torch.empty(*s, device=dev, dtype=dt)
+    marg = mk(Bsz, T, K) if "marginals" in want else None
+    kl = mk(Bsz, T) if "kl" in want else None
+    path = plq = ws = None
+    lib = N.lib_for(logits)
+    if "path" in want:
+        path, plq = mk(Bsz, T, dt=torch.int32), mk(Bsz)
+        ws = mk((lib.dll.kvae_regime_decode_ws_bytes(Bsz, T, K) + 7) // 8, dt=torch.int64)   # 8-byte aligned
+    lib.check(N.timed("regime_decode", logits, lambda: lib.dll.kvae_regime_decode(
+        N.ptr(logits), N.ptr(init_logits), N.ptr(P), N.ptr(marg), N.ptr(path), N.ptr(plq), N.ptr(kl), N.ptr(ws), Bsz, T, K,
+        N.stream_for(logits))), "kvae_regime_decode")
+    return {"marginals": marg, "path": None if path is None else path.long(), "path_logq": plq, "kl": kl}
+
+
+def regime_decode_torch(logits, init_logits, P, want=_DECODE_OUTPUTS):
+    """The equations of kvae_regime_decode in torch ops, in the dtype of the logits: K > 16 and non-fp32 tensors, and (in float64)
+    the reference the kernel is tested against.  Ties take the lowest index, in every backpointer and in the final argmax
+    (an argmax over (value == max), whose first hit torch returns).  T - 1 iterations of about ten small launches."""
+    want = _decode_want(want)
+    Bsz, T, K, _ = logits.shape
+    dt = logits.dtype
+    init_logits, P = init_logits.to(dt), P.to(device=logits.device, dtype=dt)
+    first = lambda v: (v == v.max(-1, keepdim=True).values).to(torch.int8).argmax(-1)   # lowest index among the maxima
+    ls0 = torch.log_softmax(init_logits, -1)
+    m, d = torch.softmax(init_logits, -1), ls0
+    log_p = torch.log(P.clamp_min(1e-8))
+    ms, kls, bps = [m], [(m * (ls0 - torch.full_like(ls0, 1.0 / K).log())).sum(-1)], []
+    for t in range(1, T):
+        lq = torch.log_softmax(logits[:, t], -1)              # [B, i, j]
+        Q = torch.softmax(logits[:, t], -1)
+        if "marginals" in want or "kl" in want:
+            kls.append((m * (Q * (lq - log_p)).sum(-1)).sum(-1))
+            m = torch.einsum("bi,bij->bj", m, Q)
+            ms.append(m)
+        if "path" in want:
+            cand = (d.unsqueeze(-1) + lq).transpose(1, 2)      # [B, j, i]
+            bps.append(first(cand))
+            d = cand.max(-1).values
+    out = {"marginals": None, "path": None, "path_logq": None, "kl": None}
+    if "marginals" in want:
+        out["marginals"] = torch.stack(ms, 1)
+    if "kl" in want:
+        out["kl"] = torch.stack(kls, 1)
+    if "path" in want:
+        out["path_logq"] = d.max(-1).values
+        s = first(d)
+        path = [s]
+        for bp in reversed(bps):
+            s = bp.gather(1, s.unsqueeze(1)).squeeze(1)
+            path.append(s)
+        out["path"] = torch.stack(path[::-1], 1)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # bidirectional GRU of the regime posterior
 # ------------------------------------------------------------------------------------------------

@@ -8,13 +8,15 @@ the Gumbel-softmax regime chain is `kvae_regime_fwd/bwd`, and the mixing einsums
 `kvae_mix_fwd/bwd` producing one packed A|B|Q step record; the two linear heads are `kvae_linear_fwd/bwd_input`.  Other GRU shapes
 take nn.GRU (MIOpen).  Gumbel noise can be injected (kvae.noise.inject) for parity tests.
 """
+import contextlib
+
 import torch
 import torch.nn as nn
 from torch.distributions import Multinomial
 
 from .. import noise
 from .. import _native
-from .lgssm_ops import BiGruSequence, RegimeChain, Slots, mix_dynamics, small_linear
+from .lgssm_ops import BiGruSequence, RegimeChain, Slots, mix_dynamics, regime_decode, small_linear
 
 
 def _gumbel_softmax(logits, g, tau, hard):
@@ -45,6 +47,7 @@ class SwitchingDynamicsParameter(nn.Module):
         self.hidden_size = hidden_lstm
         self.state_seq = None
         self._record = self._slots = None
+        self._pinned = None
 
     # The Gumbel-softmax temperature.  The reference's epoch loop assigns `dyn_params.tau = max(tau_min, tau * rate)`
     # (kvae/train/train.py:270-274); here the value is mirrored into a device scalar that the regime-chain kernels read
@@ -98,6 +101,42 @@ class SwitchingDynamicsParameter(nn.Module):
             y = y_t
         return torch.stack(ys, 1), torch.stack(lq, 1), torch.stack(lp, 1)
 
+    @contextlib.contextmanager
+    def pinned(self, y_seq):
+        """Inside the block compute_batch uses the given one-hot regime sequence y_seq [B,T,K] in place of a draw of the
+        Gumbel chain (no noise is taken); log_qseq / log_pseq are those of that sequence.  Outside it nothing differs."""
+        old, self._pinned = self._pinned, y_seq
+        try:
+            yield self
+        finally:
+            self._pinned = old
+
+    def _pinned_terms(self, y, logits, init_logits):
+        """log q_t and log p_t of a GIVEN regime sequence, by the formulas of regime_chain (every y_{t-1} is known: no loop)."""
+        K = self.K
+        P = self._prior_matrix(logits.device, logits.dtype)
+        l = torch.cat([init_logits.unsqueeze(1), torch.einsum("bti,btij->btj", y[:, :-1], logits[:, 1:])], 1)
+        lq = (y * torch.log_softmax(l, dim=-1)).sum(-1)
+        lp0 = (y[:, :1] * torch.full_like(y[:, :1], 1.0 / K).log()).sum(-1)
+        lp = (y[:, 1:] * torch.log((y[:, :-1] @ P).clamp_min(1e-8))).sum(-1)
+        return lq, torch.cat([lp0, lp], 1)
+
+    @torch.no_grad()
+    def decode(self, a_seq):
+        """Exact inference over the regime posterior of a_seq [B,T,p] (lgssm_ops.regime_decode over the bi-GRU's logits: one
+        launch, no sampling, tau plays no part): regime_probs [B,T,K] the marginals q(s_t), regimes [B,T] (int64) the most
+        likely regime path, regimes_logq [B] its log q, regime_kl [B,T] the per-step KL against the sticky prior."""
+        Bsz, T, _ = a_seq.size()
+        dev, dt = a_seq.device, a_seq.dtype
+        if self.K == 1:
+            return {"regime_probs": torch.ones(Bsz, T, 1, device=dev, dtype=dt),
+                    "regimes": torch.zeros(Bsz, T, device=dev, dtype=torch.long),
+                    "regimes_logq": torch.zeros(Bsz, device=dev, dtype=dt), "regime_kl": torch.zeros(Bsz, T, device=dev, dtype=dt)}
+        logits, init_logits = self.markov_regime_posterior(a_seq)
+        out = regime_decode(logits, init_logits, self._prior_matrix(dev, dt))
+        return {"regime_probs": out["marginals"], "regimes": out["path"], "regimes_logq": out["path_logq"],
+                "regime_kl": out["kl"]}
+
     def compute_batch(self, a_seq, is_training=True):
         Bsz, T, _ = a_seq.size()
         dev, dt = a_seq.device, a_seq.dtype
@@ -110,12 +149,20 @@ class SwitchingDynamicsParameter(nn.Module):
             self._record = self._slots = None
             return ex(self.A), ex(self.B), ex(self.C), self.Q_seq
         logits, init_logits = self.markov_regime_posterior(a_seq)
-        gumbel = noise.take("gumbel")
-        if gumbel is None:
-            gumbel = -torch.empty(Bsz, T, self.K, device=dev, dtype=dt).exponential_().log()
+        if self._pinned is not None:
+            gumbel = None
         else:
-            gumbel = gumbel.to(device=dev, dtype=dt)
-        if _native.fused_ok(logits) and self.K <= 16:   # one HIP launch (csrc/regime.h) instead of the T-1 step loop
+            gumbel = noise.take("gumbel")
+            if gumbel is None:
+                gumbel = -torch.empty(Bsz, T, self.K, device=dev, dtype=dt).exponential_().log()
+            else:
+                gumbel = gumbel.to(device=dev, dtype=dt)
+        if self._pinned is not None:   # a given regime sequence (KVAE.decode_regimes: the most likely path)
+            y_seq = self._pinned.to(device=dev, dtype=dt)
+            if tuple(y_seq.shape) != (Bsz, T, self.K):
+                raise ValueError(f"pinned regime sequence must be [B, T, K] = [{Bsz}, {T}, {self.K}], got {list(y_seq.shape)}")
+            self.log_qseq, self.log_pseq = self._pinned_terms(y_seq, logits, init_logits)
+        elif _native.fused_ok(logits) and self.K <= 16:   # one HIP launch (csrc/regime.h) instead of the T-1 step loop
             P = self._prior_matrix(dev, dt)
             tau = self.tau_scalar(dev) if logits.is_cuda else self.tau
             y_seq, self.log_qseq, self.log_pseq = RegimeChain.apply(logits, init_logits, gumbel, P, tau, not is_training)

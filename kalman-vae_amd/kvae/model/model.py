@@ -111,10 +111,11 @@ class KVAE(nn.Module):
         eps = torch.randn_like(std) if eps is None else eps.to(device=std.device, dtype=std.dtype).reshape(std.shape)
         return mu + eps * std
 
-    def encode_sequence(self, x):
+    def encode_sequence(self, x, sample=True):
+        """`sample=False`: a = a_mu (the heads kernel with eps = 0, no draw taken)."""
         lead = x.shape[:2]
         feat = self.encoder.features(x.flatten(0, 1))
-        eps = noise.take("eps_a")
+        eps = noise.take("eps_a") if sample else torch.zeros(feat.shape[0], self.config.a_dim, device=feat.device, dtype=feat.dtype)
         if eps is None:
             eps = torch.randn(feat.shape[0], self.config.a_dim, device=feat.device, dtype=feat.dtype)
         else:
@@ -131,7 +132,9 @@ class KVAE(nn.Module):
     # -- full pass ------------------------------------------------------------------------------
     def forward(self, x, u=None, mask=None, with_recon=True):
         """`with_recon=False` (addition over the reference) skips sigmoid(x_logits): the training loss only
-        needs the logits, so the step saves one full pass over the frame tensor."""
+        needs the logits, so the step saves one full pass over the frame tensor.
+        With switching dynamics `state_probs` is a single draw of the regime chain (one-hot in eval mode), not
+        probabilities: decode_regimes() gives the marginals and the most likely path."""
         a_samples, a_mu, a_var = self.encode_sequence(x)
         if u is None:
             u = torch.zeros(x.shape[0], x.shape[1], self.u_dim, device=x.device, dtype=x.dtype)
@@ -272,7 +275,9 @@ class KVAE(nn.Module):
 
     @torch.no_grad()
     def impute(self, x, mask, u=None):
-        """Eval-mode imputation: decode C_t mu_{t|T} (smoothed) and C_t mu_{t|t} (filtered)."""
+        """Eval-mode imputation: decode C_t mu_{t|T} (smoothed) and C_t mu_{t|t} (filtered).
+        With switching dynamics `state_probs` is a single draw of the regime chain (a hard one-hot sequence), not
+        probabilities: decode_regimes() gives the marginals and the most likely path."""
         self.eval()
         mask = mask.to(device=x.device, dtype=x.dtype)
         out = self.forward(x, u=u, mask=mask)
@@ -333,6 +338,53 @@ class KVAE(nn.Module):
                     1, (num_samples, T))
             return {"x": x_s, "a": a, "z": post["z"], "a_vae": a_vae, "state_probs": post["state_probs"],
                     "levels": post["levels"]}
+        finally:
+            self.train(was_training)
+
+    @torch.no_grad()
+    def decode_regimes(self, x, u=None, mask=None, sample_a=False, smooth=True, decode=False):
+        """Segment each sequence into regimes, exactly (switching dynamics only; no counterpart in the reference, whose
+        plot_state_probabilities is fed single Gumbel draws).  The regime posterior is a Markov chain, q(s_0) = softmax(init),
+        q(s_t | s_{t-1}) = row-softmax(logits[t]) with the evidence already folded into the logits by the bi-GRU, so its
+        marginals, its most likely path and its KL against the sticky prior are one forward sweep (kvae_regime_decode).
+
+        1. Encode x.  sample_a=False: a = a_mu, the call is deterministic; True: a is drawn as forward() draws it.
+        2. regime_probs [B,T,K] = q(s_t); regimes [B,T] (int64) = argmax over paths of log q(s_{0:T-1}) (Viterbi, lowest index
+           on ties); regimes_logq [B] = its log q; regime_kl [B,T], summing to KL(q || p), the quantity the ELBO estimates from
+           one sample.
+        3. smooth=True: the eval-mode smoother with A_t, B_t, Q_t of the most likely path (mask [B,T] optional, 1 = observed;
+           u [B,T,m] or None = zeros): mus_smooth, Sigmas_smooth, mus_filt, ABC and a_imputed = C_t mu_{t|T}.
+        4. decode=True (needs smooth): x_imputed = decoder(a_imputed).
+        Also returns a_vae.  Training mode, tau and parameters are left as they were."""
+        dyn = self.kalman_filter.dyn_params
+        if not dyn.is_switching_dynamics:
+            raise ValueError('decode_regimes needs a model with dynamics = "switching" (config.dynamics_model); this one has '
+                             f'"{self.config.dynamics_model}"')
+        Bsz, T = x.shape[:2]
+        if mask is not None and tuple(mask.shape) != (Bsz, T):
+            raise ValueError(f"decode_regimes: mask must be [B, T] = [{Bsz}, {T}], got {list(mask.shape)}")
+        if u is not None and (u.dim() != 3 or u.shape[0] != Bsz or u.shape[1] != T or u.shape[2] != self.u_dim):
+            raise ValueError(f"decode_regimes: u must be [B, T, m] = [{Bsz}, {T}, {self.u_dim}], got {list(u.shape)}")
+        if decode and not smooth:
+            raise ValueError("decode_regimes: decode=True needs smooth=True (x_imputed is decoded from the smoothed latents)")
+        was_training = self.training
+        self.eval()
+        try:
+            a_vae, _, _ = self.encode_sequence(x, sample=bool(sample_a))
+            dev, dt = a_vae.device, a_vae.dtype
+            dyn.reset_state()
+            out = dict(dyn.decode(a_vae), a_vae=a_vae)
+            if smooth:
+                u = torch.zeros(Bsz, T, self.u_dim, device=dev, dtype=dt) if u is None else u.to(device=dev, dtype=dt)
+                y_map = torch.nn.functional.one_hot(out["regimes"], self.K).to(dt)
+                with dyn.pinned(y_map):
+                    sm = self.kalman_filter.smooth(a_vae, u, mask=None if mask is None else mask.to(device=dev, dtype=dt))
+                ms, Ss, mf, _, _, _, A_list, B_list, C_list = sm
+                a_imputed, _ = self.kalman_filter.emission_means(ms, mf, C_list)
+                out.update(mus_smooth=ms, Sigmas_smooth=Ss, mus_filt=mf, ABC=(A_list, B_list, C_list), a_imputed=a_imputed)
+                if decode:
+                    out["x_imputed"] = self._to_pixels(self.decode_sequence(a_imputed))
+            return out
         finally:
             self.train(was_training)
 
