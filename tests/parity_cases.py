@@ -1836,3 +1836,527 @@ def vae_variant_cases(DEV, layer):
         take(conv_layer_per_frame(DEV, layer, 16385, side))
     print(worst)
     return worst
+
+
+# ---- the linear-Gaussian sweeps (LgssmSmooth) and the coupled alpha-network kernels, one (b,t) slice at a time ----
+# Bars = 4 x YARDSTICK, as RNN_STEP_TOL: the yardstick of a quantity is the largest per-slice ratio (whole-tensor ratio for the
+# summed gradients of broadcast operands, ".sum") of the FLOAT32 run of oracle/torch_oracle.py against its own float64 run over
+# the case lists of both tiers (LGSSM_*_CASES, ALPHA_LSTM_CASES below; rerun: the case functions with yardstick=True).  Keys:
+# "<family>.<quantity>", family n4 = (4,4,2), n16 = (16,16,2), rt = run-time dimensions, alpha = the coupled kernels.
+# The largest ratios of the emulated / generic bodies and of gfx950 against the same float64 runs: the table of DESIGN section 2.
+# Less than a factor 2 under the bar: n4.mus_smooth (1.5 x on the CPU tiers, 1.7 x on gfx950), n16.mus_smooth (1.9 x), n16.gQ
+# (1.5 x on gfx950).
+LGSSM_YARDSTICK = {   # float32 torch oracle against its float64 run, largest ratio over the case lists of both tiers
+    "n4.Sigmas_filt": 1.88e-06, "n4.Sigmas_pred": 1.41e-06, "n4.Sigmas_smooth": 8.49e-06, "n4.gA": 4.71e-05, "n4.gB": 9.51e-06,
+    "n4.gC": 5.88e-06, "n4.gC.sum": 2.16e-06, "n4.gQ": 3.48e-05, "n4.gQ.sum": 4.91e-07, "n4.gU": 1.28e-05, "n4.gY": 1.28e-05,
+    "n4.g_Sigma0": 9.37e-05, "n4.g_Sigma0.sum": 2.13e-06, "n4.g_mu0": 9.54e-06, "n4.g_mu0.sum": 2.81e-06,
+    "n4.mus_filt": 8.61e-06, "n4.mus_pred": 7.22e-06, "n4.mus_smooth": 1.01e-05,
+    "n16.Sigmas_filt": 8.28e-07, "n16.Sigmas_pred": 9.37e-07, "n16.Sigmas_smooth": 4.69e-06, "n16.gA": 5.59e-06,
+    "n16.gB": 3.42e-06, "n16.gC": 3.85e-06, "n16.gC.sum": 1.24e-06, "n16.gQ": 3.15e-05, "n16.gQ.sum": 2.12e-06,
+    "n16.gU": 4.17e-06, "n16.gY": 1.05e-05, "n16.g_Sigma0": 2.37e-06, "n16.g_Sigma0.sum": 4.18e-06, "n16.g_mu0": 1.51e-06,
+    "n16.g_mu0.sum": 2.58e-06, "n16.mus_filt": 2.01e-06, "n16.mus_pred": 2.01e-06, "n16.mus_smooth": 2.22e-06,
+    "rt.Sigmas_filt": 1.18e-06, "rt.Sigmas_pred": 7.61e-07, "rt.Sigmas_smooth": 2.77e-06, "rt.gA": 3.03e-05, "rt.gB": 4.01e-06,
+    "rt.gC": 3.51e-06, "rt.gC.sum": 1.78e-06, "rt.gQ": 9.19e-06, "rt.gU": 2.70e-06, "rt.gY": 1.79e-05, "rt.g_Sigma0": 2.31e-06,
+    "rt.g_Sigma0.sum": 7.34e-06, "rt.g_mu0": 1.15e-06, "rt.g_mu0.sum": 2.55e-06, "rt.mus_filt": 2.75e-06,
+    "rt.mus_pred": 2.70e-06, "rt.mus_smooth": 2.79e-06,
+    "alpha.Sigmas_filt": 7.17e-06, "alpha.Sigmas_pred": 6.94e-06, "alpha.Sigmas_smooth": 4.27e-05, "alpha.alpha": 7.16e-06,
+    "alpha.c_seq": 4.75e-06, "alpha.gU": 1.84e-04, "alpha.gY": 1.00e-03, "alpha.g_A": 4.89e-05, "alpha.g_B": 1.62e-05,
+    "alpha.g_C": 1.32e-04, "alpha.g_S0": 5.61e-06, "alpha.g_head_w.bias": 2.54e-04, "alpha.g_head_w.weight": 2.79e-04,
+    "alpha.g_lstm.bias_hh_l0": 3.45e-04, "alpha.g_lstm.bias_ih_l0": 3.45e-04, "alpha.g_lstm.weight_hh_l0": 4.92e-04,
+    "alpha.g_lstm.weight_ih_l0": 6.38e-05, "alpha.g_mu0": 1.48e-05, "alpha.h_seq": 5.38e-06, "alpha.mus_filt": 3.09e-05,
+    "alpha.mus_pred": 3.15e-05, "alpha.mus_smooth": 5.08e-05, "alpha.record": 7.16e-07,
+}
+LGSSM_STEP_TOL = {k: 4.0 * v for k, v in LGSSM_YARDSTICK.items()}
+LGSSM_STACKS = ("mus_smooth", "Sigmas_smooth", "mus_filt", "Sigmas_filt", "mus_pred", "Sigmas_pred")
+
+
+def _lgssm_family(n, m, p):
+    return {(4, 4, 2): "n4", (16, 16, 2): "n16"}.get((n, m, p), "rt")
+
+
+def _lgssm_bar(key, yardstick):
+    return float("inf") if yardstick else LGSSM_STEP_TOL[key]
+
+
+def _step_mask(kind, B, T, g):
+    """[B,T] float64 mask (1 = observed) or None.  ones; t0_hidden: t = 0 of every sequence (odd sequences also t = 1);
+    last_hidden: t = T-1 of every sequence (odd sequences also t = T-2); all_hidden: sequence B // 2 entirely, the others a
+    seeded random pattern; block: the reference's t_init / t_steps block, t_init = 1 + b; alternating: (t + b) odd observed;
+    random: seeded, per sequence.  Except for ones the patterns differ between the sequences of a batch."""
+    if kind is None:
+        return None
+    mk = torch.ones(B, T, dtype=torch.float64)
+    odd = torch.arange(B) % 2 == 1
+    if kind == "t0_hidden":
+        mk[:, 0] = 0.0
+        if T > 2:
+            mk[odd, 1] = 0.0
+    elif kind == "last_hidden":
+        mk[:, T - 1] = 0.0
+        if T > 2:
+            mk[odd, T - 2] = 0.0
+    elif kind == "all_hidden":
+        mk = (torch.rand(B, T, generator=g, dtype=torch.float64) > 0.3).double()
+        mk[B // 2] = 0.0
+    elif kind == "block":
+        for b in range(B):
+            t0 = min(T - 1, 1 + b)
+            mk[b, t0:t0 + max(1, T // 3)] = 0.0
+    elif kind == "alternating":
+        mk = ((torch.arange(T)[None, :] + torch.arange(B)[:, None]) % 2).double()
+    elif kind == "random":
+        mk = (torch.rand(B, T, generator=g, dtype=torch.float64) > 0.4).double()
+    else:
+        assert kind == "ones", kind
+    return mk
+
+
+def _device_leaf(t, DEV, odd=False):
+    """(tensor to pass, function returning its gradient): a float32 leaf on DEV - odd: the same values 4 bytes off a 16-byte
+    boundary (a view of a leaf one float longer, as unaligned_fallback builds it; .clone() would re-align it)."""
+    t = t.float().to(DEV)
+    if not odd:
+        leaf = t.clone().requires_grad_(True)
+        return leaf, (lambda: leaf.grad)
+    base = torch.empty(t.numel() + 1, device=DEV)
+    with torch.no_grad():
+        base[1:].copy_(t.reshape(-1))
+    base.requires_grad_(True)
+    view = base[1:].view(t.shape)
+    assert view.data_ptr() % 16 != 0 and base.data_ptr() % 16 == 0
+    return view, (lambda: None if base.grad is None else base.grad[1:].view(t.shape))
+
+
+def _sweeps_oracle(ops, mask, w, with_rts, dtype):
+    """The recursion of O.filter_step / O.smooth_step in `dtype` on the CPU over per-step operands ([B,T,r,c] stacks or one
+    broadcast matrix; mu0 [n] or [B,n], S0 [n,n] or [B,n,n]); gradients of sum_i <w_i, stack_i> (w_i None: no upstream gradient)
+    by autograd.  Returns (stacks, {operand: gradient})."""
+    from oracle import torch_oracle as O
+    c = lambda t: t.detach().cpu().to(dtype)
+    lv = {k: c(ops[k]).clone().requires_grad_(True) for k in ("Y", "U", "A", "B", "C", "Q", "mu0", "S0")}
+    R = c(ops["R"])
+    B, T = lv["Y"].shape[:2]
+    at = lambda M, t: M[:, t] if M.dim() == 4 else M
+    mk = torch.ones(B, T, dtype=dtype) if mask is None else c(mask)
+    mu, Sig = lv["mu0"].expand(B, -1).unsqueeze(-1), lv["S0"].expand(B, -1, -1)
+    mfs, Sfs, mps, Sps = [], [], [], []
+    for t in range(T):
+        mu, Sig, mu_p, Sig_p = O.filter_step(mu, Sig, lv["Y"][:, t], lv["U"][:, t], at(lv["A"], t), at(lv["B"], t), at(lv["C"], t),
+                                             at(lv["Q"], t), R, mk[:, t])
+        mfs.append(mu), Sfs.append(Sig), mps.append(mu_p), Sps.append(Sig_p)
+    st = lambda v: torch.stack(v, 1)
+    outs = [st(mfs).squeeze(-1), st(Sfs), st(mps).squeeze(-1), st(Sps)]
+    if with_rts:
+        mus, Sigs = [mfs[-1]], [Sfs[-1]]
+        for t in range(T - 2, -1, -1):
+            m_s, S_s = O.smooth_step(Sfs[t], Sps[t + 1], Sigs[0], mfs[t], mps[t + 1], mus[0], at(lv["A"], t + 1))
+            mus.insert(0, m_s), Sigs.insert(0, S_s)
+        outs = [st(mus).squeeze(-1), st(Sigs)] + outs
+    sum((o * c(wi)).sum() for o, wi in zip(outs, w) if wi is not None).backward()
+    return [o.detach() for o in outs], {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in lv.items()}
+
+
+def lgssm_sweeps_per_step(DEV, B, T, n, m, p, layout="plain", up="smooth", steps="all", mask_kind=None, prior="shared",
+                          misalign=False, only_b=None, q_grad=False, single_launch=False, emulated=False, seed=0, yardstick=False):
+    """LgssmSmooth (kvae_lgssm_filter_fwd / _smooth_fwd / _smooth_bwd) against a FLOAT64 run of O.filter_step / O.smooth_step on
+    per-step operands that are leaves of their own, one (b,t) slice at a time (_per_step_ratio): the six stacks (up="filter": the
+    four filter stacks, with_rts = 0), gY, gU, the per-step gradients gA, gB, gC and gQ, g_mu0 / g_Sigma0 per sequence with
+    prior="per_seq"; the summed gradients of broadcast operands (a stride-0 Q or C, a shared mu0 / Sigma0) as whole tensors.
+    layout: "abc" one packed record A|B|C and a Q shared by the batch (lstm layout; q_grad: with the gradient of that Q);
+    "abq" one packed record A|B|Q and a broadcast C (switching layout, HAS_GQ); "plain" four [B,T,r,c] stacks.
+    up: the upstream gradient on the smoothed stacks only ("smooth", HAS_FP off), on all six ("all", HAS_FP), or on the
+    filtered and predicted stacks with with_rts = 0 ("filter"); steps: see _upstream; only_b: on ONE sequence only.
+    mask_kind: None or a kind of _step_mask.  misalign: one operand (the record, or the A stack) 4 bytes off a 16-byte boundary,
+    which sends (4,4,2) to k_smooth_*_n4 and (16,16,2) to k_smooth_*_wide / the one-wavefront bodies.  single_launch: the
+    single-launch form of the (4,4,2) kernels (host tier: the split hook; GPU: B above the split or KVAE_M4_SPLIT_MAX_B=0).
+    emulated: the host tier runs on emulated wavefronts - the launch counters must show which kernels ran.
+    Exact, on the kernel's output: gY and a per-step gC are 0 at every hidden (b,t); with up="filter" and the upstream gradient on
+    step s only, gY, gU and every per-step operand gradient are 0 at t > s; with only_b, they are 0 for every other sequence.
+    Q is dense SPD (asserted on the float64 inputs: the natural-order solves).  Returns {quantity: largest ratio}."""
+    from kvae import _native
+    from kvae.kalman.lgssm_ops import LgssmSmooth, Slots
+    assert layout in ("abc", "abq", "plain") and up in ("smooth", "all", "filter") and prior in ("shared", "per_seq")
+    fam = _lgssm_family(n, m, p)
+    with_rts = up != "filter"
+    g = torch.Generator().manual_seed(7919 * seed + 1000 * B + 10 * T + n + len(layout) + len(up))
+    rn = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
+    eye = torch.eye(n, dtype=torch.float64)
+    per_b = (B,) if prior == "per_seq" else ()
+    A, Bm = eye + 0.08 * rn(B, T, n, n), 0.1 * rn(B, T, n, m)          # as _random_problem draws its modes
+    C = 0.3 * (rn(p, n) if layout == "abq" else rn(B, T, p, n))
+    Wq = 0.05 * rn(*(() if layout == "abc" else (B, T)), n, n)
+    Q = 0.02 * eye + Wq @ Wq.mT
+    Y, U = rn(B, T, p), 0.3 * rn(B, T, m)
+    R = 0.03 * torch.eye(p, dtype=torch.float64)
+    mu0 = 0.1 * rn(*per_b, n)                                            # the finite prior of tests/test_wave_emu.py
+    S0 = 2.0 * eye
+    if per_b:
+        W0 = 0.3 * rn(B, n, n)
+        S0 = S0 + W0 @ W0.mT
+    mask = _step_mask(mask_kind, B, T, g)
+    shapes = [(B, T, n), (B, T, n, n)] * (3 if with_rts else 2)
+    w = [_upstream(rn(*s), steps) for s in shapes]
+    if only_b is not None:
+        for wi in w:
+            wi[torch.arange(B) != only_b] = 0.0
+    if up == "smooth":
+        w = w[:2] + [None] * 4
+    # the float32 values are the problem: the float64 reference runs on exactly them
+    r32 = lambda t: None if t is None else t.float().double()
+    A, Bm, C, Q, Y, U, R, mu0, S0, mask = (r32(t) for t in (A, Bm, C, Q, Y, U, R, mu0, S0, mask))
+    w = [r32(wi) for wi in w]
+    assert float(torch.linalg.eigvalsh(Q).min()) > 0.0
+    ops = dict(Y=Y, U=U, A=A, B=Bm, C=C, Q=Q, R=R, mu0=mu0, S0=S0)
+    outs64, g64 = _sweeps_oracle(ops, mask, w, with_rts, torch.float64)
+    if yardstick:
+        outs, grads = _sweeps_oracle(ops, mask, w, with_rts, torch.float32)
+        if layout == "abc" and not q_grad:
+            grads["Q"] = None
+    else:
+        lib = _native.lib_for(torch.zeros(1, device=DEV))
+        d = lambda t: None if t is None else t.float().to(DEV)
+        before = [lib.dll.kvae_wemu_launches(i) for i in range(4)] if emulated else None
+        Yl, gY = _device_leaf(Y, DEV)
+        Ul, gU = _device_leaf(U, DEV)
+        m0l, gm0 = _device_leaf(mu0, DEV)
+        S0l, gS0 = _device_leaf(S0, DEV)
+        nn, nm = n * n, n * m
+        fl = lambda t: t.reshape(B, T, -1)
+        if layout == "plain":
+            Al, gA = _device_leaf(A, DEV, odd=misalign)
+            (Bl, gB), (Cl, gC), (Ql, gQ) = (_device_leaf(t, DEV) for t in (Bm, C, Q))
+            args, slots = (None, Al, Bl, Cl, Ql), Slots()
+        else:
+            third = C if layout == "abc" else Q
+            rec, grec = _device_leaf(torch.cat([fl(A), fl(Bm), fl(third)], -1), DEV, odd=misalign)
+            part = lambda lo, hi, sh: (lambda: grec()[..., lo:hi].reshape(B, T, *sh))
+            gA, gB, g3 = part(0, nn, (n, n)), part(nn, nn + nm, (n, m)), part(nn + nm, None, (p, n) if layout == "abc" else (n, n))
+            if layout == "abc":
+                if q_grad:
+                    Ql, gQ = _device_leaf(Q, DEV)
+                else:
+                    Ql, gQ = d(Q), (lambda: None)
+                gC = g3
+                args, slots = (rec, None, None, None, Ql), Slots(A=0, B=nn, C=nn + nm)
+            else:
+                Cl, gC = _device_leaf(C, DEV)
+                gQ = g3
+                args, slots = (rec, None, None, Cl, None), Slots(A=0, B=nn, Q=nn + nm)
+        hook = DEV == "cpu" and single_launch and fam == "n4"
+        if single_launch and DEV != "cpu":
+            import os
+            assert B > 2048 or os.environ.get("KVAE_M4_SPLIT_MAX_B") == "0", "the single-launch form was asked for"
+        if hook:
+            lib.dll.kvae_wemu_m4_split_max_b(0)
+        try:
+            outs = LgssmSmooth.apply(Yl, Ul, d(mask), *args, d(R), m0l, S0l, slots, with_rts)
+            sum((o * d(wi)).sum() for o, wi in zip(outs, w) if wi is not None).backward()
+        finally:
+            if hook:
+                lib.dll.kvae_wemu_m4_split_max_b(-1)
+        grads = dict(Y=gY(), U=gU(), A=gA(), B=gB(), C=gC(), Q=gQ(), mu0=gm0(), S0=gS0())
+        if emulated:
+            after = [lib.dll.kvae_wemu_launches(i) for i in range(4)]
+            delta = [a - b_ for a, b_ in zip(after, before)]
+            f, bw = {"n4": (0, 1), "n16": (2, 3)}[fam]
+            want = [0, 0, 0, 0]
+            if not misalign:
+                want[f], want[bw] = 1, (1 if with_rts else 0)   # (the filter-only adjoint is the one-wavefront body on every tier)
+            assert delta == want, ("emulated launches", delta, want)
+    out = {}
+    names = LGSSM_STACKS if with_rts else LGSSM_STACKS[2:]
+    for k, got, ref in zip(names, outs, outs64):
+        _check_steps(f"{fam}.{k}", got, ref, _lgssm_bar(f"{fam}.{k}", yardstick), out)
+    cpu = lambda t: t.detach().cpu()
+    per_step = []   # (name, kernel's gradient [B,T,...]) for the exact assertions
+    for k, name in (("Y", "gY"), ("U", "gU"), ("A", "gA"), ("B", "gB"), ("C", "gC"), ("Q", "gQ")):
+        if grads[k] is None:
+            assert k == "Q"
+            continue
+        key = f"{fam}.{name}"
+        if g64[k].dim() == 2:   # a broadcast operand: the summed gradient
+            _check_whole(key + ".sum", grads[k], g64[k], _lgssm_bar(key + ".sum", yardstick), out)
+        else:
+            _check_steps(key, grads[k], g64[k], _lgssm_bar(key, yardstick), out)
+            per_step.append((name, cpu(grads[k])))
+    for k, name in (("mu0", "g_mu0"), ("S0", "g_Sigma0")):
+        key = f"{fam}.{name}"
+        if per_b:
+            _check_steps(key, grads[k][:, None], g64[k][:, None], _lgssm_bar(key, yardstick), out)
+        else:
+            _check_whole(key + ".sum", grads[k], g64[k], _lgssm_bar(key + ".sum", yardstick), out)
+    # ---- exact zeros, on what the kernels wrote ----
+    if mask is not None:
+        hidden = mask == 0
+        for name, got in per_step:
+            if name in ("gY", "gC") and bool(hidden.any()):
+                assert float(got[hidden].abs().max()) == 0.0, (name, "not exactly zero at a hidden step")
+    if up == "filter" and steps in ("first", "last"):
+        s = 0 if steps == "first" else T - 1
+        for name, got in per_step:
+            if s + 1 < T:
+                assert float(got[:, s + 1:].abs().max()) == 0.0, (name, "not exactly zero after the only step with an upstream gradient")
+    if only_b is not None and B > 1:
+        others = torch.arange(B) != only_b
+        for name, got in per_step:
+            assert float(got[others].abs().max()) == 0.0, (name, "another sequence's gradient is not exactly zero", only_b)
+    return out
+
+
+def _lg(B, T, layout, up, steps, mask_kind, prior="shared", **kw):
+    return dict(B=B, T=T, layout=layout, up=up, steps=steps, mask_kind=mask_kind, prior=prior, **kw)
+
+
+# (4,4,2), aligned: k_smooth_fwd_m4 / k_smooth_bwd_m4 in the split form (B <= 2048) and k_rts_bwd_items_m4; up="filter" takes
+# k_smooth_fwd_m4 forward and the one-wavefront k_smooth_bwd_n4 backward (with_rts = 0).  Every B with a short and a long T, every
+# T = 1 ... 5 with B = 17 (one sequence in the ragged second wavefront).
+LGSSM_N4_CASES = [
+    _lg(1, 1, "abc", "smooth", "all", None),
+    _lg(1, 24, "abq", "all", "first", "random", "per_seq"),
+    _lg(15, 2, "plain", "filter", "first", "ones"),
+    _lg(15, 24, "abc", "all", "last", "t0_hidden", "per_seq", q_grad=True),
+    _lg(16, 3, "abq", "smooth", "first", "last_hidden"),
+    _lg(16, 24, "plain", "all", "all", "all_hidden", "per_seq"),
+    _lg(17, 1, "abq", "all", "all", "t0_hidden", "per_seq"),
+    _lg(17, 2, "abc", "all", "last", "last_hidden"),
+    _lg(17, 3, "plain", "smooth", "first", "random", "per_seq"),
+    _lg(17, 4, "abq", "filter", "first", "all_hidden"),
+    _lg(17, 5, "abc", "smooth", "last", "random", "per_seq"),
+    _lg(17, 24, "abq", "smooth", "all", "random"),
+    _lg(33, 4, "plain", "all", "last", None, "per_seq"),
+    _lg(33, 24, "abc", "filter", "last", "random"),
+    _lg(33, 5, "abq", "filter", "all", "last_hidden", "per_seq"),
+]
+# ... the single-launch form of the same kernels (host tier: the split hook; GPU tier: a fresh process with KVAE_M4_SPLIT_MAX_B=0)
+LGSSM_N4_SINGLE_CASES = [
+    _lg(17, 1, "abc", "all", "all", "t0_hidden", "per_seq", single_launch=True),
+    _lg(17, 2, "abq", "smooth", "first", "last_hidden", single_launch=True),
+    _lg(17, 3, "plain", "all", "last", "random", "per_seq", single_launch=True),
+    _lg(33, 5, "abq", "all", "all", "all_hidden", single_launch=True),
+    _lg(16, 24, "abc", "smooth", "first", None, single_launch=True, seed=1),
+]
+LGSSM_N4_LARGE_CASE = _lg(2049, 3, "abq", "all", "all", "random", "per_seq", single_launch=True)   # GPU tier: its natural size
+# ... one operand 4 bytes off a 16-byte boundary: k_smooth_fwd_n4 / k_smooth_bwd_n4, one wavefront per sequence
+LGSSM_N4_ODD_CASES = [
+    _lg(17, 3, "abc", "all", "all", "random", "per_seq", misalign=True),
+    _lg(3, 24, "abq", "smooth", "first", "t0_hidden", misalign=True),
+    _lg(1, 1, "plain", "filter", "all", None, misalign=True),
+    _lg(5, 2, "plain", "all", "last", "last_hidden", "per_seq", misalign=True),
+    _lg(4, 5, "abq", "filter", "first", "all_hidden", misalign=True),
+    _lg(2, 4, "abc", "smooth", "last", "ones", misalign=True, q_grad=True),
+]
+# the upstream gradient on ONE sequence: the first, the last, and both sides of the wavefront boundary at sixteen sequences
+LGSSM_N4_ISOLATION_CASES = [
+    _lg(33, 3, "abq", "all", "all", "random", "per_seq", only_b=0),
+    _lg(33, 3, "abc", "smooth", "all", "random", only_b=32),
+    _lg(33, 2, "plain", "all", "all", None, "per_seq", only_b=15),
+    _lg(33, 2, "abq", "smooth", "all", "ones", only_b=16),
+    _lg(17, 3, "plain", "filter", "all", "random", only_b=16),
+    _lg(17, 1, "abc", "all", "all", "t0_hidden", only_b=15),
+    _lg(17, 3, "abq", "all", "last", "random", "per_seq", only_b=16, single_launch=True),
+]
+# (16,16,2), aligned: k_smooth_fwd_n16 / k_smooth_bwd_n16 (up="filter": the 256-thread k_smooth_bwd<D> body backward)
+LGSSM_N16_CASES = [
+    _lg(1, 1, "abc", "smooth", "all", None),
+    _lg(1, 2, "abq", "all", "first", "last_hidden", "per_seq"),
+    _lg(1, 3, "plain", "filter", "first", "t0_hidden"),
+    _lg(1, 5, "abq", "smooth", "last", "random"),
+    _lg(1, 12, "abc", "all", "all", "random", "per_seq", q_grad=True),
+    _lg(3, 1, "abq", "all", "all", "t0_hidden", "per_seq"),
+    _lg(3, 2, "plain", "all", "last", "all_hidden"),
+    _lg(3, 3, "abc", "smooth", "first", "ones", "per_seq"),
+    _lg(3, 5, "abq", "filter", "last", "all_hidden", "per_seq"),
+    _lg(3, 12, "plain", "smooth", "all", "last_hidden"),
+    _lg(3, 3, "abq", "all", "all", "random", only_b=0),
+    _lg(3, 2, "abc", "all", "all", None, "per_seq", only_b=2),
+]
+# ... misaligned: k_smooth_fwd_wide and the 256-thread k_smooth_bwd<D> body
+LGSSM_N16_ODD_CASES = [
+    _lg(1, 1, "plain", "all", "all", "t0_hidden", "per_seq", misalign=True),
+    _lg(3, 2, "abc", "smooth", "first", "random", misalign=True),
+    _lg(1, 3, "abq", "filter", "first", None, "per_seq", misalign=True),
+    _lg(3, 5, "abq", "all", "last", "last_hidden", misalign=True),
+    _lg(3, 12, "abc", "smooth", "all", "all_hidden", "per_seq", misalign=True, q_grad=True),
+    _lg(1, 12, "plain", "all", "all", "ones", misalign=True, only_b=0),
+]
+# run-time dimensions: (2,1,1), (5,3,2), (8,8,3) on the one-wavefront bodies k_smooth_fwd<D> / k_smooth_bwd<D>; (12,12,2) and (16,8,2)
+# on the 256-thread bodies (k_smooth_fwd_wide).  B = 3, T = 1, 2, 7.
+_RT_OPTS = [("abc", "smooth", "all", None, "shared"), ("abq", "all", "first", "random", "per_seq"), ("plain", "filter", "first", "t0_hidden", "shared"),
+            ("plain", "all", "last", "last_hidden", "per_seq"), ("abq", "filter", "all", "all_hidden", "shared"), ("abc", "smooth", "last", "ones", "per_seq")]
+LGSSM_RT_CASES = [dict(n=n, m=m, p=p, **_lg(3, T, *_RT_OPTS[(2 * i + j) % 6], **({"only_b": 1} if (i + j) % 4 == 3 else {})))
+                  for i, (n, m, p) in enumerate([(2, 1, 1), (5, 3, 2), (8, 8, 3), (12, 12, 2), (16, 8, 2)]) for j, T in enumerate((1, 2, 7))]
+LGSSM_RT_CASES.append(dict(n=12, m=12, p=2, **_lg(3, 7, "abc", "all", "last", "ones", "per_seq")))   # (a mask of ones on the 256-thread bodies)
+
+
+ALPHA_PARAMS = ("A", "B", "C", "lstm.weight_ih_l0", "lstm.weight_hh_l0", "lstm.bias_ih_l0", "lstm.bias_hh_l0", "head_w.weight", "head_w.bias")
+ALPHA_MARGIN = 0.25  # alpha's per-step maximum must exceed (1 + ALPHA_MARGIN) / K somewhere in every sequence of the float64 run
+
+
+def _alpha_oracle(dyn, ops, mask, w, with_rts, dtype):
+    """O.lgssm_filter / O.lgssm_smooth(kind="lstm") in `dtype` on the CPU, with the masked feedback into the cell.  Returns
+    ([stacks..., record A|B|C, alpha], h_seq, c_seq, {name: gradient}) for the loss sum_i <w_i, out_i>."""
+    from oracle import torch_oracle as O
+    c = lambda t: t.detach().cpu().to(dtype)
+    dl = {k: c(v).clone().requires_grad_(True) for k, v in dyn.items()}
+    lv = {k: c(ops[k]).clone().requires_grad_(True) for k in ("Y", "U", "mu0", "S0")}
+    mk = c(mask)
+    o = (O.lgssm_smooth if with_rts else O.lgssm_filter)(lv["Y"], lv["U"], mk, dl, "lstm", c(ops["Q"]), c(ops["R"]), lv["mu0"], lv["S0"])
+    keys = LGSSM_STACKS if with_rts else LGSSM_STACKS[2:]
+    outs = [o[k].squeeze(-1) if k.startswith("mus") else o[k] for k in keys]
+    outs += [torch.cat([o[k].flatten(2) for k in ("A_list", "B_list", "C_list")], -1), o["state_seq"]]
+    sum((x * c(wi)).sum() for x, wi in zip(outs, w)).backward()
+    with torch.no_grad():   # the cell over the inputs the filter fed it (kalman_filter.py:142, 183-185 of the reference)
+        y_pred = (o["C_list"] @ o["mus_pred"]).squeeze(-1)
+        y_dyn = mk.unsqueeze(-1) * lv["Y"] + (1.0 - mk.unsqueeze(-1)) * y_pred
+        x = torch.cat([torch.zeros_like(y_dyn[:, :1]), y_dyn[:, :-1]], 1)
+        state, hs, cs = None, [], []
+        for t in range(x.shape[1]):
+            _, state = O.lstm_cell(x[:, t], state, dl["lstm.weight_ih_l0"], dl["lstm.weight_hh_l0"], dl["lstm.bias_ih_l0"], dl["lstm.bias_hh_l0"])
+            hs.append(state[0]), cs.append(state[1])
+    grads = {k: v.grad for k, v in list(dl.items()) + list(lv.items())}
+    return [x_.detach() for x_ in outs], torch.stack(hs, 1), torch.stack(cs, 1), grads
+
+
+def alpha_lstm_per_step(DEV, B, T, n, m, K, mask_kind, steps, with_rts, yardstick=False):
+    """AlphaLstmSmooth (k_filter_alpha_lstm + k_alpha_lstm_bwd: LSTM cell, head, softmax, mixing and a filter step in one time
+    loop, the coupled adjoint in one launch; (n, m) = (4, 4): the SDims<4,4,2> instance, else RDims) against a FLOAT64 run of
+    O.lgssm_filter / O.lgssm_smooth(kind="lstm") on the module's parameters.  Per (b,t): alpha, the record A|B|C, the six stacks
+    (with_rts = False: the four filter stacks), h_seq and c_seq (a second, no-grad call with keep_cell=True), gY, gU; whole
+    tensors: the gradients of the nine network and mode parameters and of mu0 / Sigma0.  The upstream gradient sits on the
+    stacks, the record and alpha (`steps`: see _upstream); mask_kind: see _step_mask.  The model's modes are perturbed and its
+    head scaled so that alpha is far from uniform - asserted on the float64 run.  mask_kind "ones": the same problem through the
+    precomputed-alpha path of mask=None (kvae_lstm_fwd, the head, kvae_mix_fwd, LgssmSmooth) meets the same bars - no feedback
+    term in gC.  with_rts = False and steps = "first": gY and gU of t = T-1 are exactly zero.
+    ON A HOST DEVICE THIS DOES NOT CHECK THE KERNELS: the coupled kernels exist on the GPU only, and the product's per-step
+    differentiable path (KalmanFilter._filter_stepwise on the host simulation) runs in their place - that checks this case
+    function, the float64 reference and the yardstick before the card."""
+    from kvae.kalman.lgssm_ops import AlphaLstmSmooth, LgssmSmooth, Slots
+    from kvae.model.model import KVAE
+    from kvae.utils.config import KVAEConfig
+    torch.manual_seed(100000 + 1000 * K + 10 * n + T)
+    model = KVAE(KVAEConfig(dynamics_model="lstm", num_modes=K, z_dim=n, u_dim=m))
+    kf = model.kalman_filter
+    dyn = kf.dyn_params
+    with torch.no_grad():   # as test_alpha_lstm_masked_matches_stepwise, the head scaled until the assertion below holds
+        dyn.A.add_(0.05 * torch.randn_like(dyn.A))
+        dyn.head_w.bias.zero_()
+        dyn.head_w.weight.mul_(60.0)
+    p = 2
+    g = torch.Generator().manual_seed(31 * B + 7 * T + K + len(mask_kind) + len(steps))
+    rn = lambda *s: torch.randn(*s, generator=g)
+    Y, U = rn(B, T, p), 0.3 * rn(B, T, m)
+    mask = _step_mask(mask_kind, B, T, g)
+    E = n * n + n * m + p * n
+    shapes = [(B, T, n), (B, T, n, n)] * (3 if with_rts else 2) + [(B, T, E), (B, T, K)]
+    w = [_upstream(rn(*s), steps) for s in shapes]
+    w[-2] *= 0.1   # (the record's entries are O(1): keep its share of the loss next to the stacks')
+    params = {k: v.detach().clone() for k, v in dyn.named_parameters()}
+    assert tuple(params) == ALPHA_PARAMS, tuple(params)
+    ops = dict(Y=Y, U=U, Q=kf.Q.detach().clone(), R=kf.R.detach().clone(), mu0=kf.mu0.detach().clone(), S0=kf.Sigma0.detach().clone())
+    outs64, h64, c64, g64 = _alpha_oracle(params, ops, mask, w, with_rts, torch.float64)
+    peak = outs64[-1].amax(-1).amax(1)
+    assert float(peak.min()) > (1.0 + ALPHA_MARGIN) / K, ("alpha is close to uniform in some sequence", peak.tolist(), K)
+    gnames = ALPHA_PARAMS + ("mu0", "S0")
+    nogC = None
+    if yardstick:
+        outs, h_seq, c_seq, grads = _alpha_oracle(params, ops, mask, w, with_rts, torch.float32)
+    else:
+        kf = kf.to(DEV).train()
+        d = lambda t: t.float().to(DEV)
+        Yl, Ul, mu0l, S0l = (d(ops[k]).clone().requires_grad_(True) for k in ("Y", "U", "mu0", "S0"))
+        mk, wd = d(mask), [d(wi) for wi in w]
+        plist = [dyn.get_parameter(k) for k in ALPHA_PARAMS]
+        leaves = [Yl, Ul] + plist + [mu0l, S0l]
+        if str(DEV).startswith("cuda"):
+            net = [dyn.get_parameter(k) for k in ALPHA_PARAMS[3:]] + plist[:3]
+            outs = AlphaLstmSmooth.apply(Yl, Ul, mk, *net, kf.Q, kf.R, mu0l, S0l, with_rts)
+            with torch.no_grad():
+                h_seq, c_seq = AlphaLstmSmooth.apply(Yl, Ul, mk, *net, kf.Q, kf.R, mu0l, S0l, with_rts, True)[-2:]
+        else:   # the per-step differentiable path in the kernels' place (see the docstring)
+            kf.mu0, kf.Sigma0 = mu0l, S0l
+            dyn.reset_state()
+            mf, Sf, mp, Sp, A_l, B_l, C_l = kf._filter_stepwise(Yl, Ul, mk)
+            alpha = dyn.state_seq
+            stacks = [mf.squeeze(-1), Sf, mp.squeeze(-1), Sp]
+            if with_rts:
+                stacks = list(LgssmSmooth.apply(Yl, Ul, mk, None, A_l, B_l, C_l, kf.Q, kf.R, mu0l, S0l, Slots(), True))
+            outs = stacks + [torch.cat([A_l.flatten(2), B_l.flatten(2), C_l.flatten(2)], -1), alpha]
+            with torch.no_grad():
+                y_dyn = mk.unsqueeze(-1) * Yl + (1.0 - mk.unsqueeze(-1)) * (C_l @ mp).squeeze(-1)
+                _, c_seq, h_seq = _lstm_restated(dyn.lstm, torch.cat([torch.zeros_like(y_dyn[:, :1]), y_dyn[:, :-1]], 1))
+        gl = torch.autograd.grad(sum((o * wi).sum() for o, wi in zip(outs, wd)), leaves, allow_unused=True)
+        grads = dict(zip(("Y", "U") + gnames, gl))
+        if mask_kind == "ones":   # the same problem without a mask: precomputed alpha, no cell inside the filter
+            dyn.reset_state()
+            a_seq = dyn.alpha_sequence(Yl)
+            rec, slots, _ = dyn.step_record(a_seq)
+            o2 = LgssmSmooth.apply(Yl, Ul, None, rec, None, None, None, kf.Q, kf.R, mu0l, S0l, slots, with_rts)
+            outs_nomask = list(o2) + [rec, a_seq]
+            gl2 = torch.autograd.grad(sum((o * wi).sum() for o, wi in zip(outs_nomask, wd)), leaves, allow_unused=True)
+            nogC = (outs_nomask, dict(zip(("Y", "U") + gnames, gl2)))
+    out = {}
+    bar = lambda k: _lgssm_bar("alpha." + k, yardstick)
+    names = (LGSSM_STACKS if with_rts else LGSSM_STACKS[2:]) + ("record", "alpha")
+
+    def compare(outs_, grads_):
+        for k, got, ref in zip(names, outs_, outs64):
+            _check_steps("alpha." + k, got, ref, bar(k), out)
+        _check_steps("alpha.gY", grads_["Y"], g64["Y"], bar("gY"), out)
+        _check_steps("alpha.gU", grads_["U"], g64["U"], bar("gU"), out)
+        for k in gnames:
+            ref = g64[k] if g64[k] is not None else torch.zeros_like(params.get(k, ops.get(k)), dtype=torch.float64)
+            got = grads_[k] if grads_[k] is not None else torch.zeros_like(ref)
+            if float(ref.abs().max()) == 0.0:   # (T = 1: the cell's input and previous state are zero vectors)
+                assert float(got.abs().max()) == 0.0, (k, "the float64 gradient is exactly zero")
+            else:
+                _check_whole("alpha.g_" + k, got, ref, bar("g_" + k), out)
+
+    compare(outs, grads)
+    _check_steps("alpha.h_seq", h_seq, h64, bar("h_seq"), out)
+    _check_steps("alpha.c_seq", c_seq, c64, bar("c_seq"), out)
+    if nogC is not None:
+        compare(*nogC)
+    if not yardstick and not with_rts and steps == "first" and T > 1:
+        for k in ("Y", "U"):
+            assert float(g64[k][:, T - 1].abs().max()) == 0.0   # ... of the float64 run
+            assert float(grads[k][:, T - 1].abs().max()) == 0.0, (k, "t = T-1 is not exactly zero")
+    return out
+
+
+# (B, T, n, m, K, mask_kind, steps, with_rts): (4,4) takes the SDims<4,4,2> instance, (5,3) and (16,16) RDims
+ALPHA_LSTM_CASES = [
+    (1, 1, 4, 4, 2, "ones", "all", True), (5, 1, 5, 3, 3, "t0_hidden", "all", False), (1, 1, 16, 16, 16, "all_hidden", "all", True),
+    (5, 2, 4, 4, 3, "t0_hidden", "first", True), (1, 2, 5, 3, 16, "last_hidden", "first", False), (5, 2, 16, 16, 2, "alternating", "last", True),
+    (5, 3, 4, 4, 16, "last_hidden", "first", False), (5, 3, 5, 3, 2, "all_hidden", "last", True), (1, 3, 16, 16, 3, "t0_hidden", "all", False),
+    (5, 3, 4, 4, 2, "all_hidden", "all", True), (5, 3, 16, 16, 3, "block", "first", True), (1, 3, 4, 4, 3, "random", "last", False),
+    (5, 20, 4, 4, 3, "t0_hidden", "all", True), (5, 20, 4, 4, 3, "all_hidden", "first", False), (5, 20, 4, 4, 2, "block", "last", True),
+    (5, 20, 4, 4, 16, "alternating", "all", False), (1, 20, 4, 4, 3, "random", "first", True), (5, 20, 4, 4, 3, "ones", "all", False),
+    (5, 20, 4, 4, 2, "last_hidden", "first", False), (5, 20, 4, 4, 3, "last_hidden", "last", True),
+    (5, 20, 5, 3, 3, "all_hidden", "all", True), (5, 20, 5, 3, 16, "t0_hidden", "last", False), (1, 20, 5, 3, 2, "block", "all", False),
+    (5, 20, 5, 3, 3, "ones", "first", True), (5, 20, 5, 3, 2, "random", "all", True), (5, 20, 5, 3, 3, "alternating", "first", False),
+    (5, 20, 16, 16, 3, "all_hidden", "all", False), (5, 20, 16, 16, 2, "t0_hidden", "first", True), (1, 20, 16, 16, 16, "last_hidden", "all", True),
+    (5, 20, 16, 16, 3, "random", "last", False), (5, 20, 16, 16, 3, "ones", "last", True), (5, 20, 16, 16, 2, "alternating", "all", False),
+]
+
+
+def lgssm_case_id(c):
+    dims = "%d-%d-%d_" % (c["n"], c["m"], c["p"]) if "n" in c else ""
+    extra = "".join("_%s%s" % (k, "" if v is True else v) for k, v in c.items() if k in ("misalign", "only_b", "q_grad", "single_launch", "seed"))
+    return "%sB%d_T%d_%s_%s_%s_%s_%s%s" % (dims, c["B"], c["T"], c["layout"], c["up"], c["steps"], c["mask_kind"], c["prior"], extra)
+
+
+def run_lgssm_case(DEV, case, dims=None, **kw):
+    """One entry of the LGSSM_*_CASES lists through lgssm_sweeps_per_step ((n, m, p) from the entry, else `dims`)."""
+    c = dict(case)
+    n, m, p = (c.pop(k) for k in ("n", "m", "p")) if "n" in c else dims
+    return lgssm_sweeps_per_step(DEV, c.pop("B"), c.pop("T"), n, m, p, **c, **kw)
+
+
+def lgssm_single_launch_cases(DEV):
+    """What a process started with KVAE_M4_SPLIT_MAX_B=0 runs: the single-launch form of the (4,4,2) kernels below the split."""
+    worst = {}
+    for c in LGSSM_N4_SINGLE_CASES + [x for x in LGSSM_N4_ISOLATION_CASES if x.get("single_launch")]:
+        for k, v in run_lgssm_case(DEV, c, (4, 4, 2)).items():
+            worst[k] = max(worst.get(k, 0.0), v)
+    print(worst)
+    return worst

@@ -705,3 +705,69 @@ def test_vae_variant_kernels_per_frame(env, which):
     r = subprocess.run([sys.executable, "-c", code], env={**os.environ, **env}, capture_output=True, text=True, timeout=900)
     print(r.stdout[-3000:])
     assert r.returncode == 0, r.stderr[-2000:]
+
+
+# ---- the sweeps and the coupled alpha-network kernels one (b,t) slice at a time against float64 ----
+def _fresh_process(call, env):
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import sys; sys.path[:0] = [%r, %r, %r]; import parity_cases as p; %s"
+            % (root, os.path.join(root, "kalman-vae_amd"), os.path.join(root, "tests"), call))
+    r = subprocess.run([sys.executable, "-c", code], env={**os.environ, **env}, capture_output=True, text=True, timeout=600)
+    print(r.stdout[-3000:])
+    assert r.returncode == 0, r.stderr[-2000:]
+
+
+@pytest.mark.parametrize("case", parity_cases.LGSSM_N4_CASES + parity_cases.LGSSM_N4_ISOLATION_CASES[:6], ids=parity_cases.lgssm_case_id)
+def test_lgssm_sweeps_per_step_n4_gpu(case):
+    """(4,4,2), every operand on a 16-byte boundary, B <= 2048: k_smooth_fwd_m4 and k_smooth_bwd_m4 in the split form (chain sweeps
+    + k_rts_bwd_items_m4), sixteen sequences per wavefront, B = 15 / 17 / 33 with a ragged last wavefront; up="filter" runs
+    k_smooth_fwd_m4 forward and k_smooth_bwd_n4 backward (with_rts = 0).  only_b: the upstream gradient on one sequence."""
+    print(parity_cases.run_lgssm_case(DEV, case, (4, 4, 2)))
+
+
+def test_lgssm_sweeps_per_step_n4_single_launch_natural_size_gpu():
+    """B = 2049, one sequence above the split: the single-launch k_smooth_fwd_m4 / k_smooth_bwd_m4 at their natural size (129
+    wavefronts, the last with one sequence), packed A|B|Q, upstream gradients on all six stacks, per-sequence priors."""
+    print(parity_cases.run_lgssm_case(DEV, parity_cases.LGSSM_N4_LARGE_CASE, (4, 4, 2)))
+
+
+def test_lgssm_sweeps_per_step_n4_single_launch_fresh_process_gpu():
+    """The single-launch form below the split (KVAE_M4_SPLIT_MAX_B=0 is read once per process): B = 16, 17, 33, T = 1 ... 5, 24."""
+    _fresh_process("p.lgssm_single_launch_cases('cuda')", {"KVAE_M4_SPLIT_MAX_B": "0"})
+
+
+@pytest.mark.parametrize("case", parity_cases.LGSSM_N4_ODD_CASES, ids=parity_cases.lgssm_case_id)
+def test_lgssm_sweeps_per_step_n4_misaligned_gpu(case):
+    """(4,4,2) with the packed record / the A stack 4 bytes off a 16-byte boundary: k_smooth_fwd_n4 / k_smooth_bwd_n4."""
+    print(parity_cases.run_lgssm_case(DEV, case, (4, 4, 2)))
+
+
+@pytest.mark.parametrize("case", parity_cases.LGSSM_N16_CASES, ids=parity_cases.lgssm_case_id)
+def test_lgssm_sweeps_per_step_n16_gpu(case):
+    """(16,16,2), aligned: k_smooth_fwd_n16 / k_smooth_bwd_n16 on the matrix cores (up="filter": k_smooth_fwd_n16 forward, the
+    run-time-dimension k_smooth_bwd<D> backward)."""
+    print(parity_cases.run_lgssm_case(DEV, case, (16, 16, 2)))
+
+
+@pytest.mark.parametrize("case", parity_cases.LGSSM_N16_ODD_CASES, ids=parity_cases.lgssm_case_id)
+def test_lgssm_sweeps_per_step_n16_misaligned_gpu(case):
+    """(16,16,2) with one operand 4 bytes off a 16-byte boundary: k_smooth_fwd_wide (256 threads) and k_smooth_bwd<D>."""
+    print(parity_cases.run_lgssm_case(DEV, case, (16, 16, 2)))
+
+
+@pytest.mark.parametrize("case", parity_cases.LGSSM_RT_CASES, ids=parity_cases.lgssm_case_id)
+def test_lgssm_sweeps_per_step_runtime_dims_gpu(case):
+    """(2,1,1), (5,3,2), (8,8,3): k_smooth_fwd<D> / k_smooth_bwd<D>, one wavefront per sequence; (12,12,2), (16,8,2): n > 8 takes
+    k_smooth_fwd_wide."""
+    print(parity_cases.run_lgssm_case(DEV, case))
+
+
+@pytest.mark.parametrize("B,T,n,m,K,mask_kind,steps,with_rts", parity_cases.ALPHA_LSTM_CASES)
+def test_alpha_lstm_per_step_gpu(B, T, n, m, K, mask_kind, steps, with_rts):
+    """k_filter_alpha_lstm / k_alpha_lstm_bwd per (b,t) against a float64 run of O.lgssm_smooth(kind="lstm"): (n, m) = (4, 4) the
+    SDims<4,4,2> instance, (5, 3) and (16, 16) RDims; t = 0 hidden (the cell's next input is C_0 mu_0|-1), the last step hidden
+    (no feedback leaves the sequence), a whole sequence hidden (the feedback chain runs T deep)."""
+    print(parity_cases.alpha_lstm_per_step(DEV, B, T, n, m, K, mask_kind, steps, with_rts))

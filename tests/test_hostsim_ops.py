@@ -437,3 +437,21 @@ def test_vae_heads_sampled_rows_hostsim(hostsim_backend):
 @pytest.mark.parametrize("B,T", parity_cases.VAE_BCE_CASES[:3])
 def test_bce_frames_per_row_hostsim(hostsim_backend, B, T):
     print(parity_cases.bce_frames_per_row("cpu", B, T))
+
+
+# ---- the sweeps and the alpha-network path one (b,t) slice at a time against float64 ----
+@pytest.mark.parametrize("case", parity_cases.LGSSM_RT_CASES, ids=parity_cases.lgssm_case_id)
+def test_lgssm_sweeps_per_step_hostsim(hostsim_backend, case):
+    """LgssmSmooth at run-time dimensions on the generic bodies (lgssm_fwd.h / lgssm_bwd.h: what k_smooth_fwd<D>, k_smooth_bwd<D> and
+    the 256-thread kernels wrap): values, gY, gU, the per-step operand gradients and the priors' gradients per (b,t) against a
+    float64 run of O.filter_step / O.smooth_step, and the exact zeros of parity_cases.lgssm_sweeps_per_step."""
+    print(parity_cases.run_lgssm_case("cpu", case))
+
+
+@pytest.mark.parametrize("B,T,n,m,K,mask_kind,steps,with_rts", parity_cases.ALPHA_LSTM_CASES)
+def test_alpha_lstm_per_step_hostsim(hostsim_backend, B, T, n, m, K, mask_kind, steps, with_rts):
+    """NOT a test of k_filter_alpha_lstm / k_alpha_lstm_bwd, which exist on the GPU only (the host simulation returns KVAE_ERR_DIMS):
+    the product's per-step differentiable path (KalmanFilter._filter_stepwise on the host simulation) runs in their place.  This
+    checks the case function, the float64 reference O.lgssm_smooth(kind="lstm") with its masked feedback, and the yardstick
+    before the card (tests/test_gpu_parity.py::test_alpha_lstm_per_step_gpu runs the same cases on the kernels)."""
+    print(parity_cases.alpha_lstm_per_step("cpu", B, T, n, m, K, mask_kind, steps, with_rts))

@@ -123,3 +123,57 @@ def test_wave_n4_split_and_single_launch_forms_give_the_same_bits(wave_emu_backe
         wave_emu_backend.dll.kvae_wemu_m4_split_max_b(-1)
     for a, b in zip(split, single):
         assert torch.equal(a, b)
+
+
+# ---- the sweeps one (b,t) slice at a time against float64 (parity_cases.lgssm_sweeps_per_step), on emulated wavefronts ----
+def _short(cases):
+    """T <= 5 keeps an emulated case within a few seconds; B = 17 with T = 1, 2, 3 and B = 33 stay."""
+    return [c for c in cases if c["T"] <= 5]
+
+
+N4_EMU = _short(parity_cases.LGSSM_N4_CASES + parity_cases.LGSSM_N4_SINGLE_CASES + parity_cases.LGSSM_N4_ISOLATION_CASES)
+N16_EMU = _short(parity_cases.LGSSM_N16_CASES)
+
+
+@pytest.mark.parametrize("case", N4_EMU, ids=parity_cases.lgssm_case_id)
+def test_lgssm_sweeps_per_step_n4_emulated(wave_emu_backend, case):
+    """k_smooth_fwd_m4 / k_smooth_bwd_m4 (split form, and the single-launch form through kvae_wemu_m4_split_max_b) and
+    k_rts_bwd_items_m4 on emulated wavefronts: values and every gradient per (b,t) against float64, the exact zeros of hidden
+    steps, of the steps after the only one with an upstream gradient and of the sequences without one.  The launch counters must
+    show one emulated forward launch and - with the smoother - one emulated backward launch (asserted in the case function)."""
+    print(parity_cases.run_lgssm_case("cpu", case, (4, 4, 2), emulated=True))
+
+
+@pytest.mark.parametrize("case", N16_EMU, ids=parity_cases.lgssm_case_id)
+def test_lgssm_sweeps_per_step_n16_emulated(wave_emu_backend, case):
+    """k_smooth_fwd_n16 / k_smooth_bwd_n16 (lgssm_n16.h) on emulated wavefronts, as above."""
+    print(parity_cases.run_lgssm_case("cpu", case, (16, 16, 2), emulated=True))
+
+
+@pytest.mark.parametrize("dims,case", [((4, 4, 2), c) for c in parity_cases.LGSSM_N4_ODD_CASES] +
+                         [((16, 16, 2), c) for c in parity_cases.LGSSM_N16_ODD_CASES],
+                         ids=lambda v: parity_cases.lgssm_case_id(v) if isinstance(v, dict) else "n%d" % v[0])
+def test_lgssm_sweeps_per_step_misaligned_leave_the_wave_kernels(wave_emu_backend, dims, case):
+    """One operand 4 bytes off a 16-byte boundary: the gates of the dispatch must send the call to the one-wavefront bodies
+    (k_smooth_*_n4 at (4,4,2), the run-time-dimension bodies at (16,16,2)) - no emulated launch - and those must meet the same bars."""
+    print(parity_cases.run_lgssm_case("cpu", case, dims, emulated=True))
+
+
+def test_lgssm_case_lists_cover_every_option():
+    """Every list uses each value of each option at least once in each kernel family, and the emulated lists keep B = 17 with
+    T = 1, 2, 3 and every kernel variant (HAS_FP x HAS_GQ)."""
+    opts = dict(layout={"abc", "abq", "plain"}, up={"smooth", "all", "filter"}, steps={"all", "first", "last"},
+                mask_kind={None, "ones", "t0_hidden", "last_hidden", "all_hidden", "random"}, prior={"shared", "per_seq"})
+    rt = parity_cases.LGSSM_RT_CASES
+    lists = [parity_cases.LGSSM_N4_CASES, parity_cases.LGSSM_N4_ODD_CASES, parity_cases.LGSSM_N16_CASES, parity_cases.LGSSM_N16_ODD_CASES,
+             [c for c in rt if c["n"] <= 8], [c for c in rt if c["n"] > 8], N4_EMU, N16_EMU]
+    for cases in lists:
+        for k, want in opts.items():
+            assert {c[k] for c in cases} == want, (k, {c[k] for c in cases})
+    assert {c["T"] for c in N4_EMU if c["B"] == 17} >= {1, 2, 3}
+    assert {c["B"] for c in parity_cases.LGSSM_N4_CASES} == {1, 15, 16, 17, 33}
+    assert {c["T"] for c in parity_cases.LGSSM_N4_CASES if c["B"] == 17} == {1, 2, 3, 4, 5, 24}
+    assert {(c["B"], c["only_b"]) for c in parity_cases.LGSSM_N4_ISOLATION_CASES} >= {(33, 0), (33, 32), (33, 15), (33, 16)}
+    for cases in (N4_EMU, N16_EMU):   # HAS_FP x HAS_GQ of the emulated backward
+        assert {(c["up"] == "all", c["layout"] != "abc" or bool(c.get("q_grad"))) for c in cases if c["up"] != "filter"} == \
+            {(False, False), (False, True), (True, False), (True, True)}
