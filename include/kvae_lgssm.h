@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 #define KVAE_MAX_DIM 16
-#define KVAE_ABI_VERSION 13
+#define KVAE_ABI_VERSION 14
 
 typedef enum {
   KVAE_OK = 0,
@@ -498,6 +498,42 @@ typedef struct {
 int kvae_lgssm_posterior_sample(const kvae_psample_problem *prob, void *stream);
 /* B*T*(2*n*n + n); 0 for dims outside the limits.  Only B, T, n are read. */
 int64_t kvae_lgssm_posterior_sample_ws_floats(const kvae_psample_problem *prob);
+
+/* ---- predictive density of the latents (kvae/model/model.py KVAE.score, KVAE.log_likelihood) ---------------------------------
+ * The prediction-error decomposition over the outputs of kvae_lgssm_filter_fwd / kvae_lgssm_filter_alpha_lstm, with the
+ * conventions of the reference filter (kalman_filter.py:62-79, 151-185; it computes S_t and r_t and keeps neither, and has no
+ * likelihood call: its kalman_prediction_test, kvae/train/testing.py:100-177, predicts from smoothed means).  For every (b, t):
+ *   a_pred_t = C_t mu_{t|t-1}
+ *   S_t      = sym(C_t Sigma_{t|t-1} C_t^T + R)              (0.5 (S + S^T), kalman_filter.py:78-79)
+ *   r_t      = y_t - a_pred_t
+ *   nis_t    = r_t^T S_t^{-1} r_t                            (normalised innovation squared: chi^2_p under the model)
+ *   ll_t     = -0.5 (nis_t + log det S_t + p log 2 pi)       = log p(a_t | a_{0:t-1}, u)
+ *   seq_ll_b = sum_t mask_t ll_t                             = log p(observed a of sequence b)
+ * log det and the solve go through the Cholesky factor of S_t found by the _safe_cholesky ladder (kalman_filter.py:282-303)
+ * applied PER (b, t) item: jitter 1e-6 * 10^level for level 0..4, else the clamped diagonal; levels[b,t] receives the level
+ * (5 = diagonal).  On hidden steps (mask == 0) ll_t = nis_t = 0; a_pred_t and S_t are still written (the forecast of the hidden
+ * frame), as is the level.  Indexing as in the reference: mus_pred[t] = mu_{t|t-1} (kalman_filter.py:151-201).
+ * Built for p == 2 (as the filter kernels); n == 4 and n == 16 have bodies of their own, other n <= 16 and operands that are
+ * not 16-byte aligned take a run-time-dimension body (csrc/lgssm_pred.h).  Two launches on `stream`: all B*T items at once, then
+ * one wavefront per sequence sums ll[b, 0:T] in a fixed order (no atomics; two calls give the same bits). */
+typedef struct {
+  int32_t B, T, n, p;         /* sequences, steps (>= 1); dims of z, a                                                   */
+  const float *mus_pred;      /* [B,T,n]    mu_{t|t-1}    required                                                       */
+  const float *Sigmas_pred;   /* [B,T,n,n]  Sigma_{t|t-1} required                                                       */
+  kvae_stack C;               /* [p,n]  C_t, per step out of the packed record or shared, required                       */
+  const float *R;             /* [p,p]  observation noise (kalman_filter.py:23), required                                */
+  const float *y;             /* [B,T,p] observations a_t, required                                                      */
+  const float *mask;          /* [B,T] 1 = observed, 0 = missing; NULL = all observed                                    */
+  float *ll;                  /* [B,T]     outputs: each may be NULL, its work is then skipped and the others keep the   */
+  float *nis;                 /* [B,T]     bits of the full call (seq_ll reads ll: it needs ll)                          */
+  float *a_pred;              /* [B,T,p]                                                                                 */
+  float *S_out;               /* [B,T,p,p]                                                                               */
+  int32_t *levels;            /* [B,T]                                                                                   */
+  float *seq_ll;              /* [B]                                                                                     */
+} kvae_pred_problem;
+/* KVAE_ERR_DIMS: B, T < 1, n or p outside [1, KVAE_MAX_DIM], or p != 2; KVAE_ERR_NULL: a required input missing, or seq_ll
+ * without ll; KVAE_ERR_ARG: a negative stride, or more items than one grid holds. */
+int kvae_lgssm_predictive(const kvae_pred_problem *prob, void *stream);
 
 /* ---- misc --------------------------------------------------------------------------------- */
 int kvae_abi_version(void);

@@ -252,6 +252,22 @@ class KalmanFilter(nn.Module):
         return {"z": z, "a": a, "levels": levels, "filter": (mf, Sf, mp, Sp, A_l, B_l, C_l),
                 "state_probs": self.dyn_params.state_seq}
 
+    @torch.no_grad()
+    def predictive(self, Y, U, mask=None, want=("ll", "nis", "a_pred", "S", "levels", "seq_ll")):
+        """log p(a_t | a_{0:t-1}, u) of every step, exactly: the eval-path filter (as sample_posterior runs it - lstm dynamics
+        with a mask step the alpha-network inside the filter kernel, switching dynamics hold ONE regime sequence for the pass),
+        then the prediction-error decomposition over its one-step-ahead beliefs (lgssm_ops.predictive; include/kvae_lgssm.h
+        kvae_lgssm_predictive).  The filter's (mu0, Sigma0) is the belief before step 0 (reference kalman_filter.py:124-168).
+        Returns dict(ll [B,T], nis [B,T], a_pred [B,T,p], S [B,T,p,p], levels [B,T], seq_ll [B], filter = filter()'s 7-tuple,
+        state_probs); ll and nis are 0 on hidden steps, a_pred and S are the forecast of every step."""
+        _, _, mf, Sf, mp, Sp = self._run(Y, U, mask, with_rts=False)
+        last = self._last
+        A_l, B_l, C_l = last["views"]
+        out = lgssm_ops.predictive(mp, Sp, last["C"] if last["C"] is not None else C_l, self.R, Y, self._mask(mask, Y),
+                                   packed=last["rec"], slots=Slots(C=last["slots"].C), want=want)
+        out.update(filter=(mf, Sf, mp, Sp, A_l, B_l, C_l), state_probs=self.dyn_params.state_seq)
+        return out
+
     def emission_means(self, mus_smooth, mus_filt, C_list):
         """(C_t mu_t|T, C_t mu_t|t): the two latent read-outs KVAE.impute decodes (reference model.py:279-288), one launch."""
         last = self._last

@@ -973,3 +973,100 @@ class PosteriorCall:
         name = {0: "posterior_sample", 1: "posterior_gains", 2: "posterior_paths"}.get(stages, "posterior_sample")
         self.lib.check(N.timed(name, self.ref, lambda: self.lib.dll.kvae_lgssm_posterior_sample(C.byref(self.pr), N.stream_for(self.ref))),
                        "kvae_lgssm_posterior_sample")
+
+
+# ------------------------------------------------------------------------------------------------
+# predictive density of the latents (kvae_lgssm_predictive, csrc/lgssm_pred.h)
+# ------------------------------------------------------------------------------------------------
+_PRED_OUTPUTS = ("ll", "nis", "a_pred", "S", "levels", "seq_ll")
+_LOG_2PI = 1.8378770664093453
+
+
+def predictive_supported(n, p, ref=None):
+    """Shapes / tensors kvae_lgssm_predictive is built for (include/kvae_lgssm.h: fp32, p == 2, n <= 16); the rest takes
+    predictive_torch."""
+    if ref is not None and not (N.fused_ok(ref) and ref.dtype == torch.float32):
+        return False
+    return p == 2 and 1 <= n <= N.KVAE_MAX_DIM
+
+
+def _pred_want(want):
+    want = (want,) if isinstance(want, str) else tuple(want)
+    bad = [w for w in want if w not in _PRED_OUTPUTS]
+    if bad or not want:
+        raise ValueError(f"predictive: want must name some of {_PRED_OUTPUTS}, got {want}")
+    return want
+
+
+def predictive_torch(mus_pred, Sigmas_pred, Cm, R, Y, mask=None, want=_PRED_OUTPUTS):
+    """The equations of kvae_lgssm_predictive in torch ops, batched over (b, t), in the dtype of Sigmas_pred: other a_dim than 2,
+    non-fp32 and host tensors, and (in float64) the reference the kernel is tested against.  The factor of S_t is found by the
+    per-item ladder (safe_cholesky_items).  Same arguments and returns as predictive (without packed / slots)."""
+    want = _pred_want(want)
+    mp = mus_pred.squeeze(-1) if mus_pred.dim() == 4 else mus_pred
+    dt = Sigmas_pred.dtype
+    Bsz, T, n = mp.shape
+    p = Cm.shape[-2]
+    mp, Cm, R, Y = mp.to(dt), _bt(Cm.to(dt), Bsz, T), R.to(dt), Y.to(dt)
+    a_pred = (Cm @ mp.unsqueeze(-1)).squeeze(-1)
+    S = Cm @ Sigmas_pred @ Cm.mT + R
+    S = 0.5 * (S + S.mT)
+    L, levels = safe_cholesky_items(S)
+    w = torch.linalg.solve_triangular(L, (Y - a_pred).unsqueeze(-1), upper=False).squeeze(-1)
+    nis = (w * w).sum(-1)
+    logdet = 2.0 * torch.log(torch.diagonal(L, dim1=-2, dim2=-1)).sum(-1)
+    ll = -0.5 * (nis + logdet + p * _LOG_2PI)
+    if mask is not None:
+        observed = mask.to(device=ll.device).reshape(Bsz, T) != 0
+        ll, nis = torch.where(observed, ll, torch.zeros_like(ll)), torch.where(observed, nis, torch.zeros_like(nis))
+    full = {"ll": ll, "nis": nis, "a_pred": a_pred, "S": S, "levels": levels, "seq_ll": ll.sum(1)}
+    return {k: (v if k in want else None) for k, v in full.items()}
+
+
+@torch.no_grad()
+def predictive(mus_pred, Sigmas_pred, Cm, R, Y, mask=None, packed=None, slots=Slots(), want=_PRED_OUTPUTS, impl=None):
+    """log p(a_t | a_{0:t-1}, u) of every step from the filter's one-step-ahead beliefs (semantics: include/kvae_lgssm.h,
+    kvae_lgssm_predictive).  mus_pred [B,T,n] (or [B,T,n,1]), Sigmas_pred [B,T,n,n]; Cm [p,n] | [B,T,p,n],
+    or the C slot of the packed step record `packed` [B,T,E] at the float offset slots.C (Cm is still read for p); R [p,p];
+    Y [B,T,p]; mask [B,T] (1 = observed) or None.  want: which of "ll", "nis", "a_pred", "S", "levels", "seq_ll" to compute.
+    Returns a dict: ll [B,T], nis [B,T] (both 0 on hidden steps), a_pred [B,T,p], S [B,T,p,p], levels [B,T] (int32: the ladder
+    level of chol(S_t), 5 = clamped diagonal), seq_ll [B] = sum_t ll; entries not asked for are None.  Two launches, no host
+    synchronisation.  impl: None = the HIP kernels where built (fp32, p == 2), else predictive_torch; "kernel" / "torch" force one."""
+    want = _pred_want(want)
+    n = Sigmas_pred.shape[-1]
+    Bsz, T = Sigmas_pred.shape[:2]
+    p = Cm.shape[-2]
+    use_kernel = impl == "kernel" or (impl is None and predictive_supported(n, p, Sigmas_pred))
+    if not use_kernel:
+        if packed is not None and slots.C is not None:
+            Cm = packed[..., slots.C:slots.C + p * n].unflatten(-1, (p, n))
+        return predictive_torch(mus_pred, Sigmas_pred, Cm, R, Y, mask, want)
+    dev = Sigmas_pred.device
+    mp = _f32c((mus_pred.squeeze(-1) if mus_pred.dim() == 4 else mus_pred).detach())
+    Sp, R, Y = _f32c(Sigmas_pred.detach()), _f32c(R.detach().to(dev)), _f32c(Y.detach())
+    mask = None if mask is None else _f32c(mask.detach().to(dev).reshape(Bsz, T))
+    packed = _f32c(packed.detach()) if packed is not None else None
+    pr = N.PredProblem()
+    pr.B, pr.T, pr.n, pr.p = Bsz, T, n, p
+    pr.mus_pred, pr.Sigmas_pred, pr.R, pr.y, pr.mask = mp.data_ptr(), Sp.data_ptr(), R.data_ptr(), Y.data_ptr(), N.ptr(mask)
+    keep, pr.C = _stack(Cm.detach() if slots.C is None else Cm, Bsz, T, p, n, packed, slots.C)
+    mk = lambda *s, dt=torch.float32: torch.empty(*s, device=dev, dtype=dt)
+    out = {k: None for k in _PRED_OUTPUTS}
+    ll = mk(Bsz, T) if ("ll" in want or "seq_ll" in want) else None   # the sequence sums read ll
+    out["ll"] = ll if "ll" in want else None
+    if "nis" in want:
+        out["nis"] = mk(Bsz, T)
+    if "a_pred" in want:
+        out["a_pred"] = mk(Bsz, T, p)
+    if "S" in want:
+        out["S"] = mk(Bsz, T, p, p)
+    if "levels" in want:
+        out["levels"] = mk(Bsz, T, dt=torch.int32)
+    if "seq_ll" in want:
+        out["seq_ll"] = mk(Bsz)
+    pr.ll, pr.nis, pr.a_pred, pr.S_out = N.ptr(ll), N.ptr(out["nis"]), N.ptr(out["a_pred"]), N.ptr(out["S"])
+    pr.levels, pr.seq_ll = N.ptr(out["levels"]), N.ptr(out["seq_ll"])
+    lib = N.lib_for(Sp)
+    lib.check(N.timed("predictive", Sp, lambda: lib.dll.kvae_lgssm_predictive(C.byref(pr), N.stream_for(Sp))), "kvae_lgssm_predictive")
+    del keep
+    return out

@@ -6,6 +6,7 @@ signatures and output dictionaries.  For the reference's default shapes every la
 hand-written HIP kernels of csrc/vae_*.h (kvae/vae/fused.py; other shapes: MIOpen + fused epilogues), and everything
 between `a_samples` and the LGSSM ELBO runs in the HIP kernels behind `self.kalman_filter`.
 """
+import math
 import os
 
 import torch
@@ -16,7 +17,7 @@ from kvae.kalman import dyn_param as base_dyn_param
 from kvae.kalman import lgssm_ops, switch_dyn_param
 from kvae.kalman.kalman_filter import KalmanFilter
 from kvae.noise import take as _take_noise
-from kvae.vae.losses import LinearScheduler, count_active_units, vae_loss
+from kvae.vae.losses import LinearScheduler, count_active_units, log_gaussian, vae_loss
 from kvae.vae.vae import Decoder, Encoder
 
 
@@ -385,6 +386,124 @@ class KVAE(nn.Module):
                 if decode:
                     out["x_imputed"] = self._to_pixels(self.decode_sequence(a_imputed))
             return out
+        finally:
+            self.train(was_training)
+
+    def _check_mask_u(self, who, x, mask, u):
+        Bsz, T = x.shape[:2]
+        if mask is not None and tuple(mask.shape) != (Bsz, T):
+            raise ValueError(f"{who}: mask must be [B, T] = [{Bsz}, {T}], got {list(mask.shape)}")
+        if u is not None and (u.dim() != 3 or u.shape[0] != Bsz or u.shape[1] != T or u.shape[2] != self.u_dim):
+            raise ValueError(f"{who}: u must be [B, T, m] = [{Bsz}, {T}, {self.u_dim}], got {list(u.shape)}")
+
+    @torch.no_grad()
+    def score(self, x, u=None, mask=None, sample_a=False, regimes="map", decode=False):
+        """How probable the encoded sequence is under the learned dynamics, exactly (no counterpart in the reference, whose only
+        likelihood-like number is the one-sample training ELBO): the prediction-error decomposition of the linear-Gaussian
+        state-space model over the eval-mode filter's own outputs (kvae_lgssm_predictive).
+
+        1. Encode x.  sample_a=False: a = a_mu, the call is deterministic; True: a is drawn as forward() draws it.
+        2. Dynamics.  lstm: the alpha-network, as the filter runs it (`regimes` is ignored).  switching, regimes="map": the most
+           likely regime path (decode_regimes' Viterbi path) is pinned and the density is conditional on it - the result carries
+           `regimes` [B,T] and `regimes_logq` [B]; regimes="draw": one eval-mode draw of the regime chain.
+        3. For every step: a_pred_t = C_t mu_{t|t-1}, S_t = sym(C_t Sigma_{t|t-1} C_t^T + R), nis_t = r_t^T S_t^{-1} r_t with
+           r_t = a_t - a_pred_t, log_lik_t = -0.5 (nis_t + log det S_t + p log 2 pi) = log p(a_t | a_{0:t-1}, u); log_lik_seq =
+           sum_t mask_t log_lik_t = log p(observed a).  mask [B,T] optional (1 = observed): hidden steps have log_lik = nis = 0,
+           a_pred and S are still the model's forecast of the hidden frame.  u [B,T,m] or None = zeros.
+        4. decode=True: x_pred = decoder(a_pred), the one-step-ahead predicted frames.
+        Returns log_lik [B,T], log_lik_seq [B], nis [B,T], a_pred [B,T,p], S [B,T,p,p], levels [B,T] (ladder level of each
+        chol(S_t)), a_vae, state_probs, n_obs [B].  No host synchronisation: the call can be captured into a hipGraph.
+        Training mode, tau and parameters are left as they were."""
+        if regimes not in ("map", "draw"):
+            raise ValueError(f'score: regimes must be "map" or "draw", got {regimes!r}')
+        self._check_mask_u("score", x, mask, u)
+        dyn = self.kalman_filter.dyn_params
+        Bsz, T = x.shape[:2]
+        was_training = self.training
+        self.eval()
+        try:
+            a_vae, _, _ = self.encode_sequence(x, sample=bool(sample_a))
+            dev, dt = a_vae.device, a_vae.dtype
+            u = torch.zeros(Bsz, T, self.u_dim, device=dev, dtype=dt) if u is None else u.to(device=dev, dtype=dt)
+            mk = None if mask is None else mask.to(device=dev, dtype=dt)
+            dyn.reset_state()
+            out = {}
+            if dyn.is_switching_dynamics and regimes == "map":
+                dec = dyn.decode(a_vae)
+                with dyn.pinned(torch.nn.functional.one_hot(dec["regimes"], self.K).to(dt)):
+                    pred = self.kalman_filter.predictive(a_vae, u, mk)
+                out.update(regimes=dec["regimes"], regimes_logq=dec["regimes_logq"])
+            else:
+                pred = self.kalman_filter.predictive(a_vae, u, mk)
+            n_obs = torch.full((Bsz,), float(T), device=dev, dtype=dt) if mk is None else mk.sum(1)
+            out.update(log_lik=pred["ll"], log_lik_seq=pred["seq_ll"], nis=pred["nis"], a_pred=pred["a_pred"], S=pred["S"],
+                       levels=pred["levels"], a_vae=a_vae, state_probs=pred["state_probs"], n_obs=n_obs)
+            if decode:
+                out["x_pred"] = self._to_pixels(self.decode_sequence(pred["a_pred"].to(dt)))
+            return out
+        finally:
+            self.train(was_training)
+
+    @torch.no_grad()
+    def log_likelihood(self, x, num_samples=1, u=None, mask=None):
+        """Importance-weighted bound on log p(x_observed) per sequence under the generative model p(x | a) p_LGSSM(a), with the
+        encoder as proposal (no counterpart in the reference).  B sequences of T frames, S = num_samples.
+
+        1. Encode once: a_mu, a_var [B,T,p].  a_s = a_mu + sqrt(a_var) eps_s, eps from kvae.noise.inject(ll_a=[B,S,T,p]) or fresh.
+        2. The B*S rows go through the eval-mode filter (mask and u repeated per sample) and kvae_lgssm_predictive:
+           log_pa [B,S] = log p_LGSSM(observed a_s), exact.  Switching dynamics take one hard draw of the regime chain per row;
+           argmax(logits + Gumbel) is an exact sample of q whatever tau is, so log_ps_qs [B,S] = sum_t (log p(s_t | s_{t-1}) -
+           log q(s_t | s_{t-1})) is a valid importance weight.  lstm dynamics give zeros.
+        3. One decoder pass over the B*S*T frames: log_px_a [B,S] = sum_t mask_t log p(x_t | a_{s,t}) with the frame model of
+           config.out_distr, UNWEIGHTED (scale_reconstruction and beta are training weights and play no part).
+        4. log_qa [B,S] = sum_t mask_t log N(a_{s,t}; a_mu_t, a_var_t);  log_w = log_px_a + log_pa - log_qa + log_ps_qs.
+        Returns log_px [B] = logsumexp_s log_w - log S, elbo [B] = mean_s log_w (<= log_px), log_w and its four parts [B,S],
+        ess [B] = exp(2 lse(log_w) - lse(2 log_w)) in [1, S], n_obs [B].  Training mode and parameters are left as they were."""
+        S = int(num_samples)
+        if S < 1:
+            raise ValueError(f"log_likelihood: num_samples must be >= 1, got {num_samples}")
+        self._check_mask_u("log_likelihood", x, mask, u)
+        dyn = self.kalman_filter.dyn_params
+        Bsz, T = x.shape[:2]
+        was_training = self.training
+        self.eval()
+        try:
+            _, a_mu, a_var = self.encode_sequence(x, sample=False)
+            dev, dt = a_mu.device, a_mu.dtype
+            eps = _take_noise("ll_a")
+            eps = (torch.randn(Bsz, S, T, self.a_dim, device=dev, dtype=dt) if eps is None
+                   else eps.to(device=dev, dtype=dt).reshape(Bsz, S, T, self.a_dim))
+            a_s = a_mu.unsqueeze(1) + torch.sqrt(a_var).unsqueeze(1) * eps                      # [B,S,T,p]
+            rows = a_s.reshape(Bsz * S, T, self.a_dim)
+            u = torch.zeros(Bsz, T, self.u_dim, device=dev, dtype=dt) if u is None else u.to(device=dev, dtype=dt)
+            mk = torch.ones(Bsz, T, device=dev, dtype=dt) if mask is None else mask.to(device=dev, dtype=dt)
+            rep = lambda t: t.repeat_interleave(S, 0)
+            dyn.reset_state()
+            pred = self.kalman_filter.predictive(rows, rep(u), None if mask is None else rep(mk), want=("seq_ll",))
+            log_pa = pred["seq_ll"].to(dt).view(Bsz, S)
+            if dyn.is_switching_dynamics:
+                lq, lp = dyn.elbo_terms()
+                log_ps_qs = (lp - lq).sum(-1).view(Bsz, S)
+            else:
+                log_ps_qs = torch.zeros(Bsz, S, device=dev, dtype=dt)
+            x_logits = self.decode_sequence(rows)
+            x_rep = x.to(dt).unsqueeze(1).expand(Bsz, S, *x.shape[1:]).reshape(Bsz * S, *x.shape[1:])
+            if self.config.out_distr.lower() == "bernoulli":
+                if _native.fused_ok(x_logits) and x_logits.dtype == torch.float32 and x_rep.dtype == torch.float32:
+                    from kvae.vae.fused import BernoulliFrameLogLik
+                    lpx = BernoulliFrameLogLik.apply(x_logits, x_rep)
+                else:
+                    lpx = -torch.nn.functional.binary_cross_entropy_with_logits(x_logits, x_rep, reduction="none").sum(dim=(2, 3, 4))
+            else:
+                x_var = torch.tensor(self.config.noise_pixel_var, device=dev, dtype=dt)
+                lpx = log_gaussian(x_rep, x_logits, x_var).sum(dim=(2, 3, 4))
+            log_px_a = (lpx.to(dt).view(Bsz, S, T) * mk.unsqueeze(1)).sum(-1)
+            log_qa = (log_gaussian(a_s, a_mu.unsqueeze(1), a_var.unsqueeze(1)).sum(-1) * mk.unsqueeze(1)).sum(-1)
+            log_w = log_px_a + log_pa - log_qa + log_ps_qs
+            lse = torch.logsumexp(log_w, 1)
+            return {"log_px": lse - math.log(S), "elbo": log_w.mean(1), "log_w": log_w, "log_px_a": log_px_a, "log_pa": log_pa,
+                    "log_qa": log_qa, "log_ps_qs": log_ps_qs, "ess": torch.exp(2.0 * lse - torch.logsumexp(2.0 * log_w, 1)),
+                    "n_obs": mk.sum(1)}
         finally:
             self.train(was_training)
 

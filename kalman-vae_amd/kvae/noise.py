@@ -17,11 +17,15 @@ KVAE.generate (no counterpart in the reference) draws four more, all before its 
 KalmanFilter.sample_posterior / KVAE.sample_imputations (no counterpart either) draw two, before their two launches:
   * post_z      ~ N(0,1)  [B,S,T,n]   the draw of each step of each posterior path (z_t = ... + chol(P_t) post_z_t)
   * post_a      ~ N(0,1)  [B,S,T,p]   emission noise of each step (only with emission_noise=True)
+
+KVAE.log_likelihood (no counterpart either) draws one, before the filter runs:
+  * ll_a        ~ N(0,1)  [B,S,T,p]   the proposal draws a_s = a_mu + sqrt(a_var) ll_a_s (its regime draws take `gumbel`,
+                                      one row per (b, s): [B*S,T,K])
 """
 import contextlib
 
 _slots = {"eps_a": None, "eps_z": None, "gumbel": None, "gen_z0": None, "gen_z": None, "gen_a": None, "gen_gumbel": None,
-          "post_z": None, "post_a": None}
+          "post_z": None, "post_a": None, "ll_a": None}
 
 
 def take(name):
@@ -31,10 +35,11 @@ def take(name):
 
 
 @contextlib.contextmanager
-def inject(eps_a=None, eps_z=None, gumbel=None, gen_z0=None, gen_z=None, gen_a=None, gen_gumbel=None, post_z=None, post_a=None):
+def inject(eps_a=None, eps_z=None, gumbel=None, gen_z0=None, gen_z=None, gen_a=None, gen_gumbel=None, post_z=None, post_a=None,
+           ll_a=None):
     old = dict(_slots)
     _slots.update(eps_a=eps_a, eps_z=eps_z, gumbel=gumbel, gen_z0=gen_z0, gen_z=gen_z, gen_a=gen_a, gen_gumbel=gen_gumbel,
-                  post_z=post_z, post_a=post_a)
+                  post_z=post_z, post_a=post_a, ll_a=ll_a)
     try:
         yield
     finally:

@@ -1,0 +1,37 @@
+"""One-step-ahead prediction diagnostics: the shipped counterpart of the reference's kalman_prediction_test
+(kvae/train/testing.py:100-177 there), which its epoch loop calls every five epochs to report the one-step-ahead MSE of the
+latents against a persistence baseline.  The reference predicts from SMOOTHED means, which have seen the future; this one
+predicts from the FILTER (KVAE.score: a_pred_t = C_t mu_{t|t-1} has seen a_{0:t-1} only), and adds the exact predictive
+log-likelihood and the mean normalised innovation squared (2 = a_dim for a calibrated model).
+"""
+import torch
+
+
+@torch.no_grad()
+def prediction_scores(model, batch_or_x, mask=None, u=None):
+    """Scores of the filter's one-step-ahead predictions on x [B,T,...] (or a batch: a dict with "images", or a tuple whose
+    first entry is x); mask [B,T] (1 = observed) and u [B,T,m] optional.  Predictions come from the filter, not from smoothed
+    means.  Python floats:
+      mse_kf            mean squared error of a_pred_t against the encoding a_vae_t over observed steps t >= 1
+      mse_naive         the same for the persistence prediction a_vae_{t-1}
+      log_lik_per_step  sum of log p(a_t | a_{0:t-1}, u) over observed steps / their number
+      nis_mean          mean normalised innovation squared over observed steps"""
+    if isinstance(batch_or_x, dict):
+        x = batch_or_x["images"]
+    elif isinstance(batch_or_x, (tuple, list)):
+        x = batch_or_x[0]
+    else:
+        x = batch_or_x
+    dev = next(model.parameters()).device
+    x = x.to(dev)
+    sc = model.score(x, u=u, mask=mask)
+    a, a_pred = sc["a_vae"], sc["a_pred"].to(sc["a_vae"].dtype)
+    Bsz, T = a.shape[:2]
+    mk = torch.ones(Bsz, T, device=a.device, dtype=a.dtype) if mask is None else mask.to(device=a.device, dtype=a.dtype)
+    w = mk[:, 1:]
+    count = (w.sum() * a.shape[-1]).clamp(min=1.0)
+    mse_kf = (((a_pred[:, 1:] - a[:, 1:]) ** 2).sum(-1) * w).sum() / count
+    mse_naive = (((a[:, :-1] - a[:, 1:]) ** 2).sum(-1) * w).sum() / count
+    n_obs = mk.sum().clamp(min=1.0)
+    return {"mse_kf": float(mse_kf), "mse_naive": float(mse_naive), "log_lik_per_step": float(sc["log_lik"].sum() / n_obs),
+            "nis_mean": float(sc["nis"].sum() / n_obs)}
