@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 #define KVAE_MAX_DIM 16
-#define KVAE_ABI_VERSION 14
+#define KVAE_ABI_VERSION 15
 
 typedef enum {
   KVAE_OK = 0,
@@ -534,6 +534,30 @@ typedef struct {
 /* KVAE_ERR_DIMS: B, T < 1, n or p outside [1, KVAE_MAX_DIM], or p != 2; KVAE_ERR_NULL: a required input missing, or seq_ll
  * without ll; KVAE_ERR_ARG: a negative stride, or more items than one grid holds. */
 int kvae_lgssm_predictive(const kvae_pred_problem *prob, void *stream);
+
+/* Adjoint of kvae_lgssm_predictive (lgssm_ops.PredictiveLogLik, KalmanFilter.log_marginal): the gradient of
+ *   sum_{b,t} g_ll[b,t] ll[b,t] + sum_b g_seq[b] seq_ll[b]
+ * w.r.t. mu_{t|t-1}, Sigma_{t|t-1}, C_t and y_t, in ONE launch over the B*T items (nothing recurrent: feed g_mus_pred /
+ * g_Sigmas_pred to kvae_lgssm_smooth_bwd / kvae_lgssm_alpha_lstm_bwd as the upstream of the one-step-ahead beliefs to reach the
+ * dynamics).  `prob` is the forward's problem; its output pointers are ignored.  Per item, with w = g_ll[b,t] + g_seq[b],
+ * S~ = S_t + jitter(level) I at the level the forward found (recomputed with the forward's own statements: the same bits),
+ * v = S~^-1 r_t and G = 0.5 (v v^T - S~^-1):
+ *   g_mu = w C^T v     g_Sigma = w C^T G C     gC = w (v mu^T + G C (Sigma + Sigma^T))     gY = -w v
+ * At level 5 (clamped diagonal, d_i = max(s_ii, 1e-6)) the gradient reaches s_ii only where s_ii >= 1e-6 (as torch.clamp's
+ * backward) and s_01 gets none.  Hidden items (mask == 0) get exact zeros in every output.  R is a buffer of the model: NO
+ * gradient for R is produced.  No atomics, every output element written exactly once (the items of gC must not overlap), two calls
+ * give the same bits, and a NULL output leaves the bits of the others unchanged. */
+typedef struct {
+  const float *g_ll;          /* [B,T] upstream of ll, or NULL                 at least one of the two                        */
+  const float *g_seq;         /* [B]   upstream of seq_ll, or NULL                                                           */
+  float *g_mus_pred;          /* [B,T,n]    outputs: each may be NULL, its work is then skipped                              */
+  float *g_Sigmas_pred;       /* [B,T,n,n]                                                                                   */
+  float *gY;                  /* [B,T,p]                                                                                     */
+  kvae_gstack gC;             /* [p,n] per item: a [B,T,p,n] buffer or the C slot of a packed gradient record (ptr NULL: skipped) */
+} kvae_pred_grads;
+/* The error codes of kvae_lgssm_predictive over the inputs of `prob`; in addition KVAE_ERR_NULL: g NULL, or g_ll and g_seq
+ * both NULL; KVAE_ERR_ARG: a negative stride of gC. */
+int kvae_lgssm_predictive_bwd(const kvae_pred_problem *prob, const kvae_pred_grads *g, void *stream);
 
 /* ---- misc --------------------------------------------------------------------------------- */
 int kvae_abi_version(void);

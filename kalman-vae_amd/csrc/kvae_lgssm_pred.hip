@@ -1,5 +1,5 @@
 // kvae_lgssm_pred.hip — kvae_lgssm_predictive (include/kvae_lgssm.h): the predictive density of every (b, t) item in one launch,
-// the per-sequence sums in a second.  The bodies are csrc/lgssm_pred.h (also run on emulated wavefronts by the CPU tier); this
+// the per-sequence sums in a second (its adjoint: kvae_lgssm_pred_bwd.hip).  The bodies are csrc/lgssm_pred.h (also run on emulated wavefronts by the CPU tier); this
 // unit holds the __global__ wrappers and the entry point.
 #include <hip/hip_runtime.h>
 

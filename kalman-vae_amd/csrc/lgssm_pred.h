@@ -24,6 +24,9 @@
 // stores nothing, so control flow around the DPP moves is uniform.  Every multiply-add is an explicit fmaf: the bits do not
 // depend on which outputs are requested, and the n = 4 and run-time bodies sum in the same order.
 //
+// The adjoint (kvae_lgssm_predictive_bwd, KalmanFilter.log_marginal, the "marginal" training objective) is the second half of this
+// header: one (b, t)-parallel launch, the same three bodies, S, r and the level recomputed by the statements above.
+//
 // Cross-lane traffic: DPP quad_perm / row_half_mirror / row_mirror in the n = 16 items, __shfl_xor in the sequence sums - all of
 // which the wavefront emulator (tests/hostsim/wave_emu.h) runs unchanged.
 #pragma once
@@ -56,6 +59,7 @@ __device__ __forceinline__ float jitter_of(int level) {
 struct Tail {
   float ll, nis;
   int level;
+  float l00, l10, l11;   // the factor the level found (the adjoint below solves with it again)
 };
 // S = [[s00, s01], [s01, s11]] (symmetrised), r = y - a_pred
 __device__ __forceinline__ Tail pred_tail(float s00, float s01, float s11, float r0, float r1) {
@@ -81,6 +85,7 @@ __device__ __forceinline__ Tail pred_tail(float s00, float s01, float s11, float
   const float logdet = 2.0f * (logf(l00) + logf(l11));
   out.ll = -0.5f * ((out.nis + logdet) + 2.0f * LOG_2PI);
   out.level = level;
+  out.l00 = l00, out.l10 = l10, out.l11 = l11;
   return out;
 }
 
@@ -229,13 +234,13 @@ __device__ inline void seq_wave(const kvae_pred_problem &P) {
 }
 
 // ---- what both entry points (kvae_lgssm_pred.hip, the host simulation below) share -------------------------------------------
-inline int pred_check(const kvae_pred_problem *P) {
+inline int pred_check(const kvae_pred_problem *P, bool outputs = true) {   // outputs false: the adjoint ignores the output pointers
   if (!P) return KVAE_ERR_NULL;
   const auto bad = [](int v) { return v < 1 || v > KVAE_MAX_DIM; };
   if (P->B < 1 || P->T < 1 || bad(P->n) || bad(P->p)) return KVAE_ERR_DIMS;
   if (P->p != 2) return KVAE_ERR_DIMS;   // the only emission width built
   if (!P->mus_pred || !P->Sigmas_pred || !P->C.ptr || !P->R || !P->y) return KVAE_ERR_NULL;
-  if (P->seq_ll && !P->ll) return KVAE_ERR_NULL;   // the sequence sums read ll
+  if (outputs && P->seq_ll && !P->ll) return KVAE_ERR_NULL;   // the sequence sums read ll
   if (P->C.sb < 0 || P->C.st < 0) return KVAE_ERR_ARG;
   if ((int64_t)P->B * P->T > (int64_t)INT32_MAX) return KVAE_ERR_ARG;   // grid limit
   return KVAE_OK;
@@ -250,6 +255,252 @@ inline int pred_kind(const kvae_pred_problem &P) {
 }
 inline unsigned pred_item_grid(const kvae_pred_problem &P) {
   const int64_t items = (int64_t)P.B * P.T, per = pred_kind(P) == 1 ? 4 : 64;
+  return (unsigned)((items + per - 1) / per);
+}
+
+// ==== the adjoint: kvae_lgssm_predictive_bwd =====================================================================================
+// Per item, with the weight w = g_ll[b,t] + g_seq[b] (0 on hidden steps), S~ = S + jitter(level) I, v = S~^-1 r, G = 0.5 (v v^T - S~^-1):
+//     g_mu = w C^T v      g_Sigma = w C^T G C      gC = w (v mu^T + G C (Sigma + Sigma^T))      gY = -w v
+// S, r and the level are recomputed by the forward's own statements (the same bits), v and S~^-1 from the factor pred_tail hands back.
+// Level 5 (clamped diagonal, d_i = max(s_ii, 1e-6)): G_01 = 0 and G_ii = 0 where s_ii < 1e-6 (the backward of torch.clamp).
+// Nothing recurrent: every item is independent, every output element is written by exactly one lane, once - no atomics, two calls
+// give the same bits; an output that is NULL is skipped and the others keep their bits (every multiply-add is written out).
+// The three bodies mirror the forward's; every element is formed by the same expression in all three:
+//     h_a[k] = fmaf(G_a1, C[1][k], G_a0 C[0][k])                                  (H = G C, 2 x n)
+//     g_mu[j] = w fmaf(C[1][j], v1, C[0][j] v0)        g_Sigma[i][j] = w fmaf(C[1][i], h_1[j], C[0][i] h_0[j])
+//     gC[a][j] = w (v_a mu[j] + sum_k h_a[k] (Sigma[k][j] + Sigma[j][k])), k ascending in one fmaf chain
+struct Adj {
+  float v0, v1, g00, g01, g11;
+};
+__device__ __forceinline__ Adj pred_adjoint(const Tail &tl, float s00, float s11, float r0, float r1) {
+  const float w0 = r0 / tl.l00;
+  const float w1 = fmaf(-tl.l10, w0, r1) / tl.l11;   // L w = r, as pred_tail
+  Adj a;
+  a.v1 = w1 / tl.l11;                                // L^T v = w
+  a.v0 = fmaf(-tl.l10, a.v1, w0) / tl.l00;
+  const float q = 1.0f / tl.l00, e = 1.0f / tl.l11;  // L^-1 = [[q, 0], [m, e]],  S~^-1 = L^-T L^-1
+  const float m = -(tl.l10 * q) * e;
+  const float i00 = fmaf(m, m, q * q), i01 = m * e, i11 = e * e;
+  a.g00 = 0.5f * (a.v0 * a.v0 - i00), a.g01 = 0.5f * (a.v0 * a.v1 - i01), a.g11 = 0.5f * (a.v1 * a.v1 - i11);
+  if (tl.level == LEVELS) {   // the clamped diagonal: s_01 is not read, and s_ii only where the clamp lets it through
+    a.g01 = 0.0f;
+    if (!(s00 >= 1e-6f)) a.g00 = 0.0f;
+    if (!(s11 >= 1e-6f)) a.g11 = 0.0f;
+  }
+  return a;
+}
+__device__ __forceinline__ float *gstack_at(const kvae_gstack &s, int64_t b, int64_t t) { return s.ptr + b * s.sb + t * s.st; }
+// (observed, w) of one item
+__device__ __forceinline__ float item_weight(const kvae_pred_problem &P, const kvae_pred_grads &G, int64_t it, int64_t b, bool &observed) {
+  observed = !P.mask || P.mask[it] != 0.0f;
+  return (G.g_ll ? G.g_ll[it] : 0.0f) + (G.g_seq ? G.g_seq[b] : 0.0f);
+}
+
+__device__ inline void bwd_n4_wave(const kvae_pred_problem &P, const kvae_pred_grads &G) {
+  const int T = P.T;
+  const int64_t items = (int64_t)P.B * T;
+  int64_t it = (int64_t)blockIdx.x * 64 + (int)(threadIdx.x & 63);
+  const bool live = it < items;
+  if (!live) it = items - 1;   // a lane past the end repeats the last item and stores nothing
+  const int64_t b = it / T;
+  const int t = (int)(it - b * T);
+  const f4 *Sg = reinterpret_cast<const f4 *>(P.Sigmas_pred + it * 16);
+  const f4 *Cp = reinterpret_cast<const f4 *>(stack_at(P.C, b, t));
+  const f4 sg0 = Sg[0], sg1 = Sg[1], sg2 = Sg[2], sg3 = Sg[3];
+  const f4 mu = *reinterpret_cast<const f4 *>(P.mus_pred + it * 4);
+  const f4 c0 = Cp[0], c1 = Cp[1];
+  const f2 y = *reinterpret_cast<const f2 *>(P.y + it * 2);
+  // S, r and the level: the statements of items_n4_wave
+  const float a0 = dot4(c0, mu), a1 = dot4(c1, mu);
+  const f4 g0 = {dot4(sg0, c0), dot4(sg1, c0), dot4(sg2, c0), dot4(sg3, c0)};
+  const f4 g1 = {dot4(sg0, c1), dot4(sg1, c1), dot4(sg2, c1), dot4(sg3, c1)};
+  const float S00 = dot4(c0, g0) + P.R[0], S01 = dot4(c0, g1) + P.R[1], S10 = dot4(c1, g0) + P.R[2], S11 = dot4(c1, g1) + P.R[3];
+  const float s01 = 0.5f * (S01 + S10);
+  const float r0 = y[0] - a0, r1 = y[1] - a1;
+  const Tail tl = pred_tail(S00, s01, S11, r0, r1);
+  const Adj ad = pred_adjoint(tl, S00, S11, r0, r1);
+  bool observed;
+  const float w = item_weight(P, G, it, b, observed);
+  if (!live) return;
+  const f4 zero = {0.f, 0.f, 0.f, 0.f};
+  if (G.gY) *reinterpret_cast<f2 *>(G.gY + it * 2) = observed ? f2{-(w * ad.v0), -(w * ad.v1)} : f2{0.f, 0.f};
+  if (G.g_mus_pred) {
+    f4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = w * fmaf(c1[j], ad.v1, c0[j] * ad.v0);
+    *reinterpret_cast<f4 *>(G.g_mus_pred + it * 4) = observed ? o : zero;
+  }
+  if (!G.g_Sigmas_pred && !G.gC.ptr) return;
+  f4 h0, h1;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) h0[k] = fmaf(ad.g01, c1[k], ad.g00 * c0[k]), h1[k] = fmaf(ad.g11, c1[k], ad.g01 * c0[k]);
+  if (G.g_Sigmas_pred) {
+    f4 *o = reinterpret_cast<f4 *>(G.g_Sigmas_pred + it * 16);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      f4 row;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) row[j] = w * fmaf(c1[i], h1[j], c0[i] * h0[j]);
+      o[i] = observed ? row : zero;
+    }
+  }
+  if (G.gC.ptr) {
+    const f4 sg[4] = {sg0, sg1, sg2, sg3};   // indexed by unrolled constants only: registers
+    f4 o0, o1;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float e0 = ad.v0 * mu[j], e1 = ad.v1 * mu[j];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float ss = sg[k][j] + sg[j][k];
+        e0 = fmaf(h0[k], ss, e0), e1 = fmaf(h1[k], ss, e1);
+      }
+      o0[j] = w * e0, o1[j] = w * e1;
+    }
+    f4 *o = reinterpret_cast<f4 *>(gstack_at(G.gC, b, t));
+    o[0] = observed ? o0 : zero, o[1] = observed ? o1 : zero;
+  }
+}
+
+__device__ inline void bwd_n16_wave(const kvae_pred_problem &P, const kvae_pred_grads &G) {
+  const int T = P.T, lane = (int)(threadIdx.x & 63), i = lane & 15;
+  const int64_t items = (int64_t)P.B * T;
+  int64_t it = (int64_t)blockIdx.x * 4 + (lane >> 4);
+  const bool live = it < items;
+  if (!live) it = items - 1;   // uniform control flow: every lane of every row reaches the DPP moves
+  const int64_t b = it / T;
+  const int t = (int)(it - b * T);
+  const float *Ct = stack_at(P.C, b, t);
+  const float *Sit = P.Sigmas_pred + it * 256;
+  const f4 *Sr = reinterpret_cast<const f4 *>(Sit + 16 * i);
+  const f4 *C0 = reinterpret_cast<const f4 *>(Ct), *C1 = reinterpret_cast<const f4 *>(Ct + 16);
+  f4 sg[4], c0[4], c1[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) sg[q] = Sr[q], c0[q] = C0[q], c1[q] = C1[q];
+  const float ci0 = Ct[i], ci1 = Ct[16 + i], mui = P.mus_pred[it * 16 + i];
+  const float y0 = P.y[it * 2], y1 = P.y[it * 2 + 1];
+  // S, r and the level: the statements of items_n16_wave
+  const float a0 = row_sum(ci0 * mui), a1 = row_sum(ci1 * mui);
+  const float g0 = dot16(sg, c0), g1 = dot16(sg, c1);
+  const float S00 = row_sum(ci0 * g0) + P.R[0], S01 = row_sum(ci0 * g1) + P.R[1];
+  const float S10 = row_sum(ci1 * g0) + P.R[2], S11 = row_sum(ci1 * g1) + P.R[3];
+  const float s01 = 0.5f * (S01 + S10);
+  const float r0 = y0 - a0, r1 = y1 - a1;
+  const Tail tl = pred_tail(S00, s01, S11, r0, r1);      // the same in every lane of the row
+  const Adj ad = pred_adjoint(tl, S00, S11, r0, r1);
+  bool observed;
+  const float w = item_weight(P, G, it, b, observed);
+  if (!live) return;                                     // no cross-lane traffic below
+  const f4 zero = {0.f, 0.f, 0.f, 0.f};
+  if (G.gY && i < 2) G.gY[it * 2 + i] = observed ? -(w * (i == 0 ? ad.v0 : ad.v1)) : 0.0f;
+  if (G.g_mus_pred) G.g_mus_pred[it * 16 + i] = observed ? w * fmaf(ci1, ad.v1, ci0 * ad.v0) : 0.0f;
+  if (!G.g_Sigmas_pred && !G.gC.ptr) return;
+  f4 h0[4], h1[4];                                       // H = G C, whole in every lane
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      h0[q][k] = fmaf(ad.g01, c1[q][k], ad.g00 * c0[q][k]), h1[q][k] = fmaf(ad.g11, c1[q][k], ad.g01 * c0[q][k]);
+  }
+  if (G.g_Sigmas_pred) {                                 // lane i: row i, 64 contiguous bytes
+    f4 *o = reinterpret_cast<f4 *>(G.g_Sigmas_pred + it * 256 + 16 * i);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      f4 row;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) row[k] = w * fmaf(ci1, h1[q][k], ci0 * h0[q][k]);
+      o[q] = observed ? row : zero;
+    }
+  }
+  if (G.gC.ptr) {                                        // lane i: column i of gC; Sigma[k][i] read again (the 16 lanes of a row
+    float e0 = ad.v0 * mui, e1 = ad.v1 * mui;            // read 64 contiguous bytes per k, lines this row has just loaded)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float ss = Sit[(4 * q + k) * 16 + i] + sg[q][k];
+        e0 = fmaf(h0[q][k], ss, e0), e1 = fmaf(h1[q][k], ss, e1);
+      }
+    }
+    float *o = gstack_at(G.gC, b, t);
+    o[i] = observed ? w * e0 : 0.0f, o[16 + i] = observed ? w * e1 : 0.0f;
+  }
+}
+
+__device__ inline void bwd_rt_wave(const kvae_pred_problem &P, const kvae_pred_grads &G) {
+  const int T = P.T, n = P.n;
+  const int64_t items = (int64_t)P.B * T;
+  int64_t it = (int64_t)blockIdx.x * 64 + (int)(threadIdx.x & 63);
+  if (it >= items) return;   // no cross-lane traffic in this body
+  const int64_t b = it / T;
+  const int t = (int)(it - b * T);
+  const float *Sg = P.Sigmas_pred + it * n * n, *mu = P.mus_pred + it * n, *Ct = stack_at(P.C, b, t);
+  // S, r and the level: the statements of items_rt_wave
+  float a0 = 0.f, a1 = 0.f;
+  for (int j = 0; j < n; ++j) a0 = fmaf(Ct[j], mu[j], a0), a1 = fmaf(Ct[n + j], mu[j], a1);
+  float S00 = 0.f, S01 = 0.f, S10 = 0.f, S11 = 0.f;
+  for (int i = 0; i < n; ++i) {
+    float g0 = 0.f, g1 = 0.f;
+    for (int j = 0; j < n; ++j) {
+      const float s = Sg[i * n + j];
+      g0 = fmaf(s, Ct[j], g0), g1 = fmaf(s, Ct[n + j], g1);
+    }
+    S00 = fmaf(Ct[i], g0, S00), S01 = fmaf(Ct[i], g1, S01), S10 = fmaf(Ct[n + i], g0, S10), S11 = fmaf(Ct[n + i], g1, S11);
+  }
+  S00 += P.R[0], S01 += P.R[1], S10 += P.R[2], S11 += P.R[3];
+  const float s01 = 0.5f * (S01 + S10);
+  const float r0 = P.y[it * 2] - a0, r1 = P.y[it * 2 + 1] - a1;
+  const Tail tl = pred_tail(S00, s01, S11, r0, r1);
+  const Adj ad = pred_adjoint(tl, S00, S11, r0, r1);
+  bool observed;
+  const float w = item_weight(P, G, it, b, observed);
+  if (G.gY) G.gY[it * 2] = observed ? -(w * ad.v0) : 0.0f, G.gY[it * 2 + 1] = observed ? -(w * ad.v1) : 0.0f;
+  if (G.g_mus_pred)
+    for (int j = 0; j < n; ++j) G.g_mus_pred[it * n + j] = observed ? w * fmaf(Ct[n + j], ad.v1, Ct[j] * ad.v0) : 0.0f;
+  if (G.g_Sigmas_pred) {
+    float *o = G.g_Sigmas_pred + it * n * n;
+    for (int i = 0; i < n; ++i)
+      for (int j = 0; j < n; ++j) {
+        const float h0 = fmaf(ad.g01, Ct[n + j], ad.g00 * Ct[j]), h1 = fmaf(ad.g11, Ct[n + j], ad.g01 * Ct[j]);
+        o[i * n + j] = observed ? w * fmaf(Ct[n + i], h1, Ct[i] * h0) : 0.0f;
+      }
+  }
+  if (G.gC.ptr) {
+    float *o = gstack_at(G.gC, b, t);
+    for (int j = 0; j < n; ++j) {
+      float e0 = ad.v0 * mu[j], e1 = ad.v1 * mu[j];
+      for (int k = 0; k < n; ++k) {
+        const float h0 = fmaf(ad.g01, Ct[n + k], ad.g00 * Ct[k]), h1 = fmaf(ad.g11, Ct[n + k], ad.g01 * Ct[k]);
+        const float ss = Sg[k * n + j] + Sg[j * n + k];
+        e0 = fmaf(h0, ss, e0), e1 = fmaf(h1, ss, e1);
+      }
+      o[j] = observed ? w * e0 : 0.0f, o[n + j] = observed ? w * e1 : 0.0f;
+    }
+  }
+}
+
+// ---- what both entry points of the adjoint share --------------------------------------------------------------------------------
+inline int pred_bwd_check(const kvae_pred_problem *P, const kvae_pred_grads *G) {
+  const int rc = pred_check(P, false);
+  if (rc) return rc;
+  if (!G || (!G->g_ll && !G->g_seq)) return KVAE_ERR_NULL;
+  if (G->gC.sb < 0 || G->gC.st < 0) return KVAE_ERR_ARG;
+  return KVAE_OK;
+}
+inline bool pred_bwd_wants(const kvae_pred_grads &G) { return G.g_mus_pred || G.g_Sigmas_pred || G.gY || G.gC.ptr; }
+// pred_kind over the inputs (the forward's output pointers are ignored), then the alignment of what this call writes
+inline int pred_bwd_kind(const kvae_pred_problem &P, const kvae_pred_grads &G) {
+  kvae_pred_problem in = P;
+  in.a_pred = nullptr, in.S_out = nullptr;
+  const int kind = pred_kind(in);
+  if (kind == 0 && aligned(G.g_mus_pred, 16) && aligned(G.g_Sigmas_pred, 16) && aligned(G.gY, 8) && aligned(G.gC.ptr, 16) &&
+      G.gC.sb % 4 == 0 && G.gC.st % 4 == 0)
+    return 0;
+  if (kind == 1 && aligned(G.g_Sigmas_pred, 16)) return 1;
+  return 2;
+}
+inline unsigned pred_bwd_grid(const kvae_pred_problem &P, const kvae_pred_grads &G) {
+  const int64_t items = (int64_t)P.B * P.T, per = pred_bwd_kind(P, G) == 1 ? 4 : 64;
   return (unsigned)((items + per - 1) / per);
 }
 
@@ -288,4 +539,30 @@ extern "C" int kvae_lgssm_predictive(const kvae_pred_problem *prob, void *) {
   return KVAE_OK;
 }
 extern "C" int kvae_wemu_predictive_launches(int which) { return which >= 0 && which < 4 ? kvae_pred::emu_launches()[which] : -1; }
+
+// ---- the host simulation's kvae_lgssm_predictive_bwd: the same grids and body choice, launches counted per body -------------
+namespace kvae_pred {
+inline int *emu_bwd_launches() {
+  static int n[3] = {0, 0, 0};   // 0 n = 4, 1 n = 16, 2 run-time n
+  return n;
+}
+}  // namespace kvae_pred
+
+extern "C" int kvae_lgssm_predictive_bwd(const kvae_pred_problem *prob, const kvae_pred_grads *g, void *) {
+  using namespace kvae_pred;
+  const int rc = pred_bwd_check(prob, g);
+  if (rc) return rc;
+  const kvae_pred_problem &P = *prob;
+  const kvae_pred_grads &G = *g;
+  if (!pred_bwd_wants(G)) return KVAE_OK;
+  const int kind = pred_bwd_kind(P, G);
+  emu_bwd_launches()[kind] += 1;
+  switch (kind) {
+    case 0: wemu::launch(pred_bwd_grid(P, G), [&] { bwd_n4_wave(P, G); }); break;
+    case 1: wemu::launch(pred_bwd_grid(P, G), [&] { bwd_n16_wave(P, G); }); break;
+    default: wemu::launch(pred_bwd_grid(P, G), [&] { bwd_rt_wave(P, G); }); break;
+  }
+  return KVAE_OK;
+}
+extern "C" int kvae_wemu_predictive_bwd_launches(int which) { return which >= 0 && which < 3 ? kvae_pred::emu_bwd_launches()[which] : -1; }
 #endif

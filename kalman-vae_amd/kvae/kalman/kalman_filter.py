@@ -6,6 +6,8 @@ argument order, tuple layouts and tensor shapes:
     filter(Y,U,mask)  -> (mus_filt[B,T,n,1], Sigmas_filt[B,T,n,n], mus_pred, Sigmas_pred, A_list, B_list, C_list)
     smooth(Y,U,mask)  -> (mus_smooth, Sigmas_smooth) + the seven above
     elbo(mu,Sigma,y,u,A_list,B_list,C_list,Q_list=None,mask=None) -> 0-d tensor
+Additions over the reference: condition, sample_posterior, predictive (exact log p(a_t | a_{0:t-1}, u), no tape) and
+log_marginal / marginal (the same density, differentiable: the exact LGSSM training objective).
 What differs is the execution: one launch (one wavefront per sequence, the whole T loop and the
 RTS sweep inside the kernel) replaces ~580 aten calls per time step, and the backward is a
 hand-derived adjoint kernel instead of an autograd tape.  Inputs must live on a HIP device.
@@ -267,6 +269,41 @@ class KalmanFilter(nn.Module):
                                    packed=last["rec"], slots=Slots(C=last["slots"].C), want=want)
         out.update(filter=(mf, Sf, mp, Sp, A_l, B_l, C_l), state_probs=self.dyn_params.state_seq)
         return out
+
+    def log_marginal(self, Y, U, mask=None):
+        """log p(a | u), exactly and DIFFERENTIABLY: the filter (training or eval dynamics as self.training says; no RTS sweep),
+        then lgssm_ops.log_marginal over its one-step-ahead beliefs - C_t out of the packed step record where there is one.
+        predictive() is the eval-only, no-grad read-out of the same density.  Gradients reach Y, U, A / B / C, the alpha-LSTM
+        and the switching model's bi-GRU and regime chain through the filter's own Functions (the in-kernel alpha-LSTM path takes
+        the C-slot gradient as the upstream of its record).  Returns dict(ll [B,T], seq_ll [B], levels [B,T], filter = filter()'s
+        7-tuple, state_probs); ll is 0 on hidden steps."""
+        _, _, mf, Sf, mp, Sp = self._run(Y, U, mask, with_rts=False)
+        A_l, B_l, C_l = self._last["views"]
+        out = self._log_marginal(mp, Sp, Y, C_l, mask)
+        out.update(filter=(mf, Sf, mp, Sp, A_l, B_l, C_l), state_probs=self.dyn_params.state_seq)
+        return out
+
+    def _log_marginal(self, mus_pred, Sigmas_pred, y_t, C_list, mask=None):
+        last = self._last
+        mask = self._mask(mask, y_t)
+        if last is not None and C_list is last["views"][2]:
+            return lgssm_ops.log_marginal(mus_pred, Sigmas_pred, last["C"] if last["C"] is not None else C_list, self.R, y_t, mask,
+                                          packed=last["rec"], slots=Slots(C=last["slots"].C))
+        return lgssm_ops.log_marginal(mus_pred, Sigmas_pred, C_list, self.R, y_t, mask)
+
+    def marginal(self, mus_pred, Sigmas_pred, y_t, C_list, mask=None):
+        """The exact LGSSM objective, normalised as elbo(): (sum_b log p(a_b | u_b) [+ log_p - log_q of the regime chain]) / num_el,
+        over the filter's one-step-ahead beliefs - no smoothed stacks, no eps_z draw."""
+        Bsz, T = y_t.size(0), y_t.size(1)
+        mask = self._mask(mask, y_t)
+        out = self._log_marginal(mus_pred, Sigmas_pred, y_t, C_list, mask)
+        self.last_marginal_levels = out["levels"]
+        total = out["seq_ll"].sum()
+        if self.dyn_params.is_switching_dynamics:
+            log_q, log_p = self.dyn_params.elbo_terms()
+            total = total + log_p.sum() - log_q.sum()
+        num_el = mask.sum().clamp(min=1.0) if mask is not None else float(Bsz * T)
+        return total / num_el
 
     def emission_means(self, mus_smooth, mus_filt, C_list):
         """(C_t mu_t|T, C_t mu_t|t): the two latent read-outs KVAE.impute decodes (reference model.py:279-288), one launch."""

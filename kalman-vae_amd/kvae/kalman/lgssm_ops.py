@@ -1070,3 +1070,141 @@ def predictive(mus_pred, Sigmas_pred, Cm, R, Y, mask=None, packed=None, slots=Sl
     lib.check(N.timed("predictive", Sp, lambda: lib.dll.kvae_lgssm_predictive(C.byref(pr), N.stream_for(Sp))), "kvae_lgssm_predictive")
     del keep
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# log p(a | u), differentiable (kvae_lgssm_predictive + kvae_lgssm_predictive_bwd, csrc/lgssm_pred.h)
+# ------------------------------------------------------------------------------------------------
+def _pred_problem(mp, Sp, Cm, packed, R, Y, mask, slots):
+    """(kvae_pred_problem, tensors to keep alive) over contiguous fp32 inputs; the output pointers are left NULL."""
+    Bsz, T, n = mp.shape
+    p = Y.shape[-1]
+    pr = N.PredProblem()
+    pr.B, pr.T, pr.n, pr.p = Bsz, T, n, p
+    pr.mus_pred, pr.Sigmas_pred, pr.R, pr.y, pr.mask = mp.data_ptr(), Sp.data_ptr(), R.data_ptr(), Y.data_ptr(), N.ptr(mask)
+    keep, pr.C = _stack(Cm, Bsz, T, p, n, packed, slots.C)
+    return pr, (mp, Sp, R, Y, mask, keep)
+
+
+class PredictiveLogLik(torch.autograd.Function):
+    """(ll [B,T], seq_ll [B], levels [B,T]) of kvae_lgssm_predictive with the adjoint kvae_lgssm_predictive_bwd: one call each
+    way.  Gradients for mus_pred, Sigmas_pred, Cm (or `packed`: a zero-filled record with the C slot written) and Y; a shared
+    2-D Cm is reduced over the items.  R is a buffer of the model: no gradient."""
+
+    @staticmethod
+    def forward(ctx, mus_pred, Sigmas_pred, Cm, packed, R, Y, mask, slots):
+        mp, Sp, Rc, Yc, mk = _f32c(mus_pred), _f32c(Sigmas_pred), _f32c(R), _f32c(Y), _f32c(mask)
+        pk = _f32c(packed)
+        Bsz, T, _ = mp.shape
+        dev = Sp.device
+        pr, keep = _pred_problem(mp, Sp, Cm, pk, Rc, Yc, mk, slots)
+        ll = torch.empty(Bsz, T, device=dev, dtype=torch.float32)
+        seq = torch.empty(Bsz, device=dev, dtype=torch.float32)
+        levels = torch.empty(Bsz, T, device=dev, dtype=torch.int32)
+        pr.ll, pr.seq_ll, pr.levels = ll.data_ptr(), seq.data_ptr(), levels.data_ptr()
+        lib = N.lib_for(Sp)
+        lib.check(N.timed("predictive", Sp, lambda: lib.dll.kvae_lgssm_predictive(C.byref(pr), N.stream_for(Sp))), "kvae_lgssm_predictive")
+        del keep
+        ctx.slots = slots
+        ctx.mark_non_differentiable(levels)
+        ctx.set_materialize_grads(False)   # an output nobody differentiates arrives as None: NULL upstream, its loads skipped
+        ctx.save_for_backward(mus_pred, Sigmas_pred, Cm, packed, R, Y, mask)
+        return ll, seq, levels
+
+    @staticmethod
+    def backward(ctx, g_ll, g_seq, _g_levels):
+        if g_ll is None and g_seq is None:
+            return (None,) * 8
+        mus_pred, Sigmas_pred, Cm, packed, R, Y, mask = ctx.saved_tensors
+        slots, need = ctx.slots, ctx.needs_input_grad
+        mp, Sp, Rc, Yc, mk = _f32c(mus_pred), _f32c(Sigmas_pred), _f32c(R), _f32c(Y), _f32c(mask)
+        pk = _f32c(packed)
+        Bsz, T, n = mp.shape
+        p = Yc.shape[-1]
+        dev = Sp.device
+        pr, keep = _pred_problem(mp, Sp, Cm, pk, Rc, Yc, mk, slots)
+        g_ll, g_seq = _f32c(g_ll), _f32c(g_seq)
+        g = N.PredGrads()
+        g.g_ll, g.g_seq = N.ptr(g_ll), N.ptr(g_seq)
+        g_mp = torch.empty_like(mp) if need[0] else None
+        g_Sp = torch.empty_like(Sp) if need[1] else None
+        gY = torch.empty_like(Yc) if need[5] else None
+        g.g_mus_pred, g.g_Sigmas_pred, g.gY = N.ptr(g_mp), N.ptr(g_Sp), N.ptr(gY)
+        g_packed = g_Cbuf = None
+        if slots.C is not None:
+            if need[3]:
+                g_packed = torch.zeros_like(pk)
+                E = pk.shape[-1]
+                g.gC = N.Stack(g_packed.data_ptr() + 4 * slots.C, T * E, E)
+        elif need[2]:
+            g_Cbuf = torch.empty(Bsz, T, p, n, device=dev, dtype=torch.float32)
+            g.gC = N.Stack(g_Cbuf.data_ptr(), T * p * n, p * n)
+        lib = N.lib_for(Sp)
+        lib.check(N.timed("predictive_bwd", Sp, lambda: lib.dll.kvae_lgssm_predictive_bwd(C.byref(pr), C.byref(g), N.stream_for(Sp))),
+                  "kvae_lgssm_predictive_bwd")
+        del keep
+        gC = None
+        if g_Cbuf is not None:   # reduced to the shape the caller passed in, as _GradSink.operand_grad
+            if Cm.dim() == 2:
+                gC = g_Cbuf.sum((0, 1))
+            else:
+                gC = g_Cbuf.sum_to_size(Cm.shape) if tuple(Cm.shape) != tuple(g_Cbuf.shape) else g_Cbuf
+        return (g_mp.reshape(mus_pred.shape) if g_mp is not None else None, g_Sp, gC, g_packed, None, gY, None, None)
+
+
+def log_marginal_torch(mus_pred, Sigmas_pred, Cm, R, Y, mask=None):
+    """log_marginal in torch ops, differentiable, in the dtype of Sigmas_pred: other a_dim than 2, non-fp32 and host tensors, and
+    (in float64) the reference the adjoint kernel is tested against.  The values are predictive_torch's.  Nothing is
+    differentiated through safe_cholesky_items (its torch.where over failed cholesky_ex attempts turns into NaN * 0 in the
+    backward): the levels are found without a tape, then S + jitter[level] I - for level-5 items the clamped diagonal matrix - is
+    factorised once."""
+    mp = mus_pred.squeeze(-1) if mus_pred.dim() == 4 else mus_pred
+    dt = Sigmas_pred.dtype
+    Bsz, T, n = mp.shape
+    p = Cm.shape[-2]
+    mp, Cm, R, Y = mp.to(dt), _bt(Cm.to(dt), Bsz, T), R.to(dt), Y.to(dt)
+    a_pred = (Cm @ mp.unsqueeze(-1)).squeeze(-1)
+    S = Cm @ Sigmas_pred @ Cm.mT + R
+    S = 0.5 * (S + S.mT)
+    with torch.no_grad():
+        _, levels = safe_cholesky_items(S)
+    jit, j = [], 1e-6
+    for _ in range(5):
+        jit.append(j)
+        j *= 10.0
+    jitter = torch.tensor(jit + [0.0], device=S.device, dtype=torch.float64)[levels.long()]
+    eye = torch.eye(p, device=S.device, dtype=dt)
+    St = S + (jitter[..., None, None] * eye.double()).to(dt)
+    clamped = torch.diag_embed(torch.diagonal(S, dim1=-2, dim2=-1).clamp(min=1e-6))
+    St = torch.where((levels == 5)[..., None, None], clamped, St)
+    L = torch.linalg.cholesky(St)
+    w = torch.linalg.solve_triangular(L, (Y - a_pred).unsqueeze(-1), upper=False).squeeze(-1)
+    nis = (w * w).sum(-1)
+    logdet = 2.0 * torch.log(torch.diagonal(L, dim1=-2, dim2=-1)).sum(-1)
+    ll = -0.5 * (nis + logdet + p * _LOG_2PI)
+    if mask is not None:
+        observed = mask.to(device=ll.device).reshape(Bsz, T) != 0
+        ll = torch.where(observed, ll, torch.zeros_like(ll))
+    return {"ll": ll, "seq_ll": ll.sum(1), "levels": levels}
+
+
+def log_marginal(mus_pred, Sigmas_pred, Cm, R, Y, mask=None, packed=None, slots=Slots(), impl=None):
+    """log p(a_t | a_{0:t-1}, u) of every step and its per-sequence sum log p(a | u), DIFFERENTIABLE w.r.t. mus_pred, Sigmas_pred,
+    C (Cm, or the C slot of `packed`) and Y (predictive is the no-grad read-out with more outputs).  Arguments as predictive.
+    Returns dict(ll [B,T], seq_ll [B], levels [B,T] int32).  Forward two launches, backward one (kvae_lgssm_predictive_bwd), no
+    host synchronisation.  impl: None = the HIP kernels where built (fp32, p == 2), else log_marginal_torch; "kernel" / "torch"
+    force one."""
+    n = Sigmas_pred.shape[-1]
+    Bsz, T = Sigmas_pred.shape[:2]
+    p = Cm.shape[-2]
+    use_kernel = impl == "kernel" or (impl is None and predictive_supported(n, p, Sigmas_pred))
+    if not use_kernel:
+        if packed is not None and slots.C is not None:
+            Cm = packed[..., slots.C:slots.C + p * n].unflatten(-1, (p, n))
+        return log_marginal_torch(mus_pred, Sigmas_pred, Cm, R, Y, mask)
+    dev = Sigmas_pred.device
+    mp = mus_pred.squeeze(-1) if mus_pred.dim() == 4 else mus_pred
+    mask = None if mask is None else mask.detach().to(dev).reshape(Bsz, T)
+    ll, seq, levels = PredictiveLogLik.apply(mp, Sigmas_pred, Cm, packed if slots.C is not None else None, R.detach().to(dev), Y,
+                                             mask, Slots(C=slots.C))
+    return {"ll": ll, "seq_ll": seq, "levels": levels}

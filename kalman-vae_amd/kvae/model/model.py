@@ -65,6 +65,10 @@ class KVAE(nn.Module):
     early_kf_backward = False
     lgssm_stream = None     # second HIP stream for the LGSSM chain: it is latency-bound (256 of ~8000 wave slots at configs[1])
     #                         and independent of the decoder, so it overlaps with the decoder convolutions; compute_loss() joins
+    # The LGSSM term of the objective: "elbo" = the reference's one-sample ELBO (z_t drawn from the smoothing marginals), "marginal"
+    # = the exact log p(a | u) of the prediction-error decomposition (KalmanFilter.marginal: zero variance, no RTS sweep, no eps_z).
+    # With "marginal" a TRAINING-mode forward runs the filter only: outputs["mus_smooth"] / ["Sigmas_smooth"] are None.
+    kf_objective = "elbo"
     kf_value_only = False   # "vae" phase (reference train.py:246-250: kf_weight = 0, every LGSSM parameter frozen): the chain runs
     #                         forward only, without a tape, for the logged elbo_kf; nothing of it is differentiated
 
@@ -127,6 +131,12 @@ class KVAE(nn.Module):
     def decode_sequence(self, a):
         return self.decoder(a.flatten(0, 1)).unflatten(0, a.shape[:2])
 
+    def _kf_objective(self, value=None):
+        value = self.kf_objective if value is None else value
+        if value not in ("elbo", "marginal"):
+            raise ValueError(f"kf_objective must be 'elbo' or 'marginal', got {value!r}")
+        return value
+
     def _to_pixels(self, logits):
         return torch.sigmoid(logits) if self.config.out_distr.lower() == "bernoulli" else logits
 
@@ -143,6 +153,11 @@ class KVAE(nn.Module):
         side = self.lgssm_stream if (self.training and a_samples.is_cuda) else None
         a_side = None
         value_only = self.kf_value_only and self.training
+        kf = self.kalman_filter
+        if self._kf_objective() == "marginal" and self.training:   # the exact objective reads the one-step-ahead beliefs only
+            run = lambda y, uu, mask=None: (None, None) + kf.filter(y, uu, mask=mask)
+        else:
+            run = kf.smooth
         if side is not None:
             side.wait_stream(torch.cuda.current_stream())
             a_lgssm = a_samples.detach() if value_only else a_samples
@@ -150,12 +165,12 @@ class KVAE(nn.Module):
                 a_side = a_lgssm = a_samples.detach().requires_grad_(True)
                 a_samples = _SideGradJoin.apply(a_samples, {"a_side": a_side, "side": side})
             with torch.cuda.stream(side), torch.set_grad_enabled(torch.is_grad_enabled() and not value_only):
-                smoothed = self.kalman_filter.smooth(a_lgssm, u, mask=mask)
+                smoothed = run(a_lgssm, u, mask=mask)
         elif value_only:
             with torch.no_grad():
-                smoothed = self.kalman_filter.smooth(a_samples.detach(), u, mask=mask)
+                smoothed = run(a_samples.detach(), u, mask=mask)
         else:
-            smoothed = self.kalman_filter.smooth(a_samples, u, mask=mask)
+            smoothed = run(a_samples, u, mask=mask)
         (mus_smooth, Sigmas_smooth, mus_filt, Sigmas_filt, mus_pred, Sigmas_pred, A_list, B_list, C_list) = smoothed
         x_logits = self.decode_sequence(a_samples)
         return {
@@ -168,12 +183,17 @@ class KVAE(nn.Module):
             "state_probs": self.kalman_filter.dyn_params.state_seq,
         }
 
-    def compute_loss(self, x, outputs, kf_weight=1.0, vae_weight=1.0, mask=None, with_metrics=True, weights_dev=None):
+    def compute_loss(self, x, outputs, kf_weight=1.0, vae_weight=1.0, mask=None, with_metrics=True, weights_dev=None,
+                     kf_objective=None):
         """`with_metrics` (addition over the reference): True = the reference's behaviour (active-unit count and the
         two latent variances as Python numbers: three host syncs); "device" = the same statistics as device tensors
         (`active_units`, `latent_variances`), no sync, capturable into a hipGraph; False = skip them.
         `weights_dev` (addition): fp32 device tensor (vae_weight, kf_weight) that replaces the two floats - the kernels read it
-        at run time, so a step captured into a hipGraph follows the reference's phase weights (train.py:246-260)."""
+        at run time, so a step captured into a hipGraph follows the reference's phase weights (train.py:246-260).
+        `kf_objective` (addition): None = self.kf_objective; "elbo" = the reference's one-sample ELBO; "marginal" = elbo_kf is the
+        exact (seq_ll.sum() [+ switching: log_p.sum() - log_q.sum()]) / num_el over outputs["mus_pred"], ["Sigmas_pred"], ["ABC"] and
+        a_samples (KalmanFilter.marginal), num_el as in KalmanFilter.elbo."""
+        objective = self._kf_objective(kf_objective)
         if weights_dev is not None:
             vae_weight, kf_weight = weights_dev[0], weights_dev[1]
         B, T = x.shape[:2]
@@ -191,21 +211,23 @@ class KVAE(nn.Module):
             variances = a_mu.detach().reshape(-1, a_mu.shape[-1]).var(dim=0)
             stats = ((variances > 1e-2).sum(), variances)
 
+        def kf_term(a_in):
+            if objective == "marginal":
+                return self.kalman_filter.marginal(outputs["mus_pred"], outputs["Sigmas_pred"], a_in, C_list, mask=mask)
+            return self.kalman_filter.elbo(outputs["mus_smooth"], outputs["Sigmas_smooth"], a_in, u, A_list, B_list, C_list, mask=mask)
+
         def kf_elbo():
             if self.kf_value_only and self.training:   # no tape, nothing to differentiate: the value for the log
                 with torch.no_grad():
                     if side is None:
-                        return self.kalman_filter.elbo(outputs["mus_smooth"], outputs["Sigmas_smooth"], a.detach(), u, A_list,
-                                                       B_list, C_list, mask=mask)
+                        return kf_term(a.detach())
                     with torch.cuda.stream(side):
-                        v = self.kalman_filter.elbo(outputs["mus_smooth"], outputs["Sigmas_smooth"], a.detach(), u, A_list,
-                                                    B_list, C_list, mask=mask)
+                        v = kf_term(a.detach())
                     torch.cuda.current_stream().wait_stream(side)
                     return v
             if a_side is not None:   # early_kf_backward: value and gradients of the LGSSM term on the side stream, now
                 with torch.cuda.stream(side):
-                    v = self.kalman_filter.elbo(outputs["mus_smooth"], outputs["Sigmas_smooth"], a_side, u, A_list, B_list,
-                                                C_list, mask=mask)
+                    v = kf_term(a_side)
                     done = torch.cuda.Event()
                     done.record(side)
                     # d loss / d elbo_kf = -kf_weight
@@ -213,11 +235,9 @@ class KVAE(nn.Module):
                 torch.cuda.current_stream().wait_event(done)   # the value only; _SideGradJoin waits for the gradients
                 return v.detach()
             if side is None:
-                return self.kalman_filter.elbo(outputs["mus_smooth"], outputs["Sigmas_smooth"], a, u, A_list, B_list, C_list,
-                                               mask=mask)
+                return kf_term(a)
             with torch.cuda.stream(side):
-                v = self.kalman_filter.elbo(outputs["mus_smooth"], outputs["Sigmas_smooth"], a, u, A_list, B_list, C_list,
-                                            mask=mask)
+                v = kf_term(a)
             torch.cuda.current_stream().wait_stream(side)   # join before the two ELBOs are combined
             return v
 

@@ -91,11 +91,17 @@ def phase_for_epoch(epoch, pretrain_vae_epochs=5, warmup_epochs=10):
 
 class Trainer:
     def __init__(self, model, lr=7e-3, weight_decay=0.0, grad_clip_norm=10.0, kf_weight=1.0, vae_weight=1.0,
-                 use_graph=True, world_size=1, overlap_lgssm=True, reference_logging=False, graph_allreduce=False):
+                 use_graph=True, world_size=1, overlap_lgssm=True, reference_logging=False, graph_allreduce=False,
+                 kf_objective="elbo"):
         """reference_logging: also compute what the reference's step computes for logging only - sigmoid(x_logits)
         (model.py:165-168 there) and the active-unit statistics (model.py:229) - as device tensors in `self.out`.
         graph_allreduce: with world_size > 1, capture the RCCL all-reduce into the step's hipGraph (one replay per step)
-        instead of cutting the graph around an eager call."""
+        instead of cutting the graph around an eager call.
+        kf_objective: the LGSSM term of this trainer's steps - "elbo" (the reference's one-sample ELBO) or "marginal" (the exact
+        log p(a | u): KVAE.kf_objective); carried by the model only inside the trainer's own forward+backward (_schedule)."""
+        if kf_objective not in ("elbo", "marginal"):
+            raise ValueError(f"kf_objective must be 'elbo' or 'marginal', got {kf_objective!r}")
+        self.kf_objective = kf_objective
         self.model, self.clip = model, grad_clip_norm
         self.world = world_size
         self.reference_logging = bool(reference_logging)
@@ -208,6 +214,8 @@ class Trainer:
         inside the trainer's own forward+backward: a plain model(x) / compute_loss / backward outside is the reference's."""
         m = self.model
         saved = (m.lgssm_stream, m.early_kf_backward, m.kf_value_only)
+        saved_objective = m.__dict__.get("kf_objective")   # None: the class attribute is what the model reads
+        m.kf_objective = self.kf_objective
         value_only = self._kf_value_only()
         m.lgssm_stream = self.lgssm_stream
         m.early_kf_backward = self.early_kf_backward and not value_only
@@ -216,6 +224,10 @@ class Trainer:
             yield
         finally:
             m.lgssm_stream, m.early_kf_backward, m.kf_value_only = saved
+            if saved_objective is None:
+                m.__dict__.pop("kf_objective", None)
+            else:
+                m.kf_objective = saved_objective
 
     # -- the three segments of a step ---------------------------------------------------------------
     def _forward_backward(self, x, mask=None):
