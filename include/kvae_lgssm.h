@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 #define KVAE_MAX_DIM 16
-#define KVAE_ABI_VERSION 15
+#define KVAE_ABI_VERSION 16
 
 typedef enum {
   KVAE_OK = 0,
@@ -558,6 +558,59 @@ typedef struct {
 /* The error codes of kvae_lgssm_predictive over the inputs of `prob`; in addition KVAE_ERR_NULL: g NULL, or g_ll and g_seq
  * both NULL; KVAE_ERR_ARG: a negative stride of gC. */
 int kvae_lgssm_predictive_bwd(const kvae_pred_problem *prob, const kvae_pred_grads *g, void *stream);
+
+/* ---- causal switching Kalman filter, GPB2 (kvae/model/model.py KVAE.filter_regimes) --------------------------------------------
+ * The generative switching model filtered on its own: s_0 ~ uniform(K), s_t | s_{t-1} ~ P[s_{t-1}, :] (unclamped: a zero is an
+ * impossible transition), z_t = A_{s_t} z_{t-1} + B_{s_t} u_t + N(0, Q_{s_t}), a_t = C z_t + N(0, R).  The carried belief is one
+ * Gaussian per regime with its log weight, (log w(i), mu^i, Sigma^i), i < K.  Every step t (t = 0 included: predict first, as
+ * kvae_lgssm_filter_fwd) runs all K^2 (previous regime i, current regime j) Kalman steps - the statements of the filter kernels:
+ * symmetrised S, gain times mask_t, Joseph form, symmetrised Sigma - with the pair likelihood l_ij = log N(a_t; C mu_pred, S) by
+ * the ladder of kvae_lgssm_predictive (0 on a hidden step), then
+ *   log c_ij = log w(i) + log P[i,j] + l_ij          ll_t = logsumexp_ij log c_ij   (0 on a hidden step)
+ *   regime_pred_t(j) = sum_i w(i) P[i,j]             log w'(j) = logsumexp_i log c_ij - logsumexp_ij log c_ij
+ *   regime_filt_t(j) = exp(log w'(j))                W_{i|j} = softmax_i log c_ij   (one-hot at i = j where the column is all -inf)
+ *   mu'^j = sum_i W_{i|j} mu_ij                      Sigma'^j = sum_i W_{i|j} (Sigma_ij + (mu_ij - mu'^j)(mu_ij - mu'^j)^T)
+ * mus_filt_t / Sigmas_filt_t: the moment match of the K collapsed Gaussians under w'; a_pred_t / S_t: the moment match of the K^2
+ * pair forecasts under the prior weights w(i) P[i,j]; levels_t: the largest ladder level over the pairs of non-zero prior weight.
+ * Without a carried state the first step starts every regime at (mu0, Sigma0) with w = 1/K and the uniform matrix 1/K in place
+ * of P (exact); with one (state_log_w / state_mu / state_Sigma: all three or none) the first step uses P.  out_* is the state
+ * after the last step.  Built for fp32, K <= 8, n <= 4, m <= 4, p == 2: one wavefront per sequence, lane (i, j) of an 8 x 8
+ * grid owns pair (i, j), everything in registers (csrc/lgssm_swf.h).  One launch for the sweep, a second for seq_ll (which
+ * reads ll).  No atomics, every output element written once, two calls give the same bits; any output may be NULL and the bits of
+ * the others do not depend on it. */
+typedef struct {
+  int32_t B, T, K, n, m, p;
+  const float *A;             /* [K,n,n]                                                                                 */
+  const float *Bm;            /* [K,n,m]                                                                                 */
+  const float *Q;             /* [K,n,n]                                                                                 */
+  const float *C;             /* [p,n]                                                                                   */
+  const float *R;             /* [p,p]                                                                                   */
+  const float *P;             /* [K,K]    transition matrix, rows sum to 1                                               */
+  const float *mu0;           /* [n]      read only without a carried state                                              */
+  const float *Sigma0;        /* [n,n]                                                                                   */
+  const float *y;             /* [B,T,p]                                                                                 */
+  const float *u;             /* [B,T,m]                                                                                 */
+  const float *mask;          /* [B,T] 1 = observed, or NULL: every step observed                                        */
+  const float *state_log_w;   /* [B,K]     carried state in: all three or none                                           */
+  const float *state_mu;      /* [B,K,n]                                                                                 */
+  const float *state_Sigma;   /* [B,K,n,n]                                                                               */
+  float *regime_filt;         /* [B,T,K]   outputs: each may be NULL                                                     */
+  float *regime_pred;         /* [B,T,K]                                                                                 */
+  float *ll;                  /* [B,T]                                                                                   */
+  float *seq_ll;              /* [B]       sum_t ll[b,t] in a fixed order; needs ll                                      */
+  float *a_pred;              /* [B,T,p]                                                                                 */
+  float *S_out;               /* [B,T,p,p]                                                                               */
+  float *mus_filt;            /* [B,T,n]                                                                                 */
+  float *Sigmas_filt;         /* [B,T,n,n]                                                                               */
+  int32_t *levels;            /* [B,T]                                                                                   */
+  float *out_log_w;           /* [B,K]     carried state out                                                             */
+  float *out_mu;              /* [B,K,n]                                                                                 */
+  float *out_Sigma;           /* [B,K,n,n]                                                                               */
+} kvae_swf_problem;
+/* KVAE_ERR_NULL: prob or a required input NULL, or seq_ll without ll; KVAE_ERR_DIMS: B or T < 1; KVAE_ERR_ARG: a shape outside
+ * what is built (K outside [1,8], n or m outside [1,4], p != 2), a partly given carried state, or more sequences than one grid
+ * holds.  Nothing is written on error. */
+int kvae_lgssm_switching_filter(const kvae_swf_problem *prob, void *stream);
 
 /* ---- misc --------------------------------------------------------------------------------- */
 int kvae_abi_version(void);

@@ -669,4 +669,5 @@ __device__ __forceinline__ void elbo_zfix_wave(const kvae_lgssm_problem &P, cons
 #include "lgssm_post.h"   // likewise kvae_lgssm_posterior_sample
 #include "regime_decode.h"   // likewise kvae_regime_decode
 #include "lgssm_pred.h"   // likewise kvae_lgssm_predictive
+#include "lgssm_swf.h"    // likewise kvae_lgssm_switching_filter
 #endif

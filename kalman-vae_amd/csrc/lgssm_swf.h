@@ -1,0 +1,367 @@
+// lgssm_swf.h — the causal switching Kalman filter with second-order generalised pseudo-Bayes collapse (GPB2, Murphy 1998) of the
+// switching dynamics (include/kvae_lgssm.h kvae_lgssm_switching_filter, lgssm_ops.switching_filter, KalmanFilter.filter_regimes,
+// KVAE.filter_regimes).  The equations are in the header of the C ABI; this file is their layout on a wavefront.
+//
+// One wavefront per sequence, laid out as the 8 x 8 grid of regime_grid.h / regime_decode.h: lane = 8 g + k owns the pair
+// (previous regime i = k, current regime j = g).  A_j, B_j, Q_j, C, R and log P[i,j] are loaded once, padded with zeros to
+// 4 x 4 (run-time n, m <= 4), and stay in registers for the whole sweep; only y_t, u_t, mask_t are streamed, one step ahead of
+// the step that uses them, from a clamped address (the last step fetches itself again).
+//   per step, on every lane: the filter step of pair (i, j) from (mu^i, Sigma^i) - the statements of filter_gain /
+//     filter_step_core (csrc/lgssm_fwd.h), the 2 x 2 solve by elimination without pivoting (S is positive definite) - and the
+//     pair density by pred_tail (csrc/lgssm_pred.h).
+//   reductions over i inside a column j: the eight lanes of group g, three DPP moves each (rgrid::oct_sum / oct_max): the column
+//     maximum, the softmax weights W_{i|j}, log w'(j) and the fourteen sums of the collapse.  Every lane of the group ends with
+//     the same bits ("on the groups").
+//   reductions over j, and over all pairs: the eight groups, two DPP mirrors and two permlane swaps (rdec::xg8) - the step's
+//     log-likelihood, the moment match of the K collapsed Gaussians and (after a group reduction) of the K^2 pair forecasts.
+//   hand-over: lane (i = k, j = g) of the next step needs regime k's collapsed belief, which group k holds: fifteen __shfl from
+//     lane 8 k - the transpose of the grid.
+// Padding lanes (k >= K or g >= K) hold zero operands, log c = -inf and weight 0: every value on them is finite, they take every
+// branch the live lanes take (all branches test kernel arguments only), and they store nothing.  No per-lane array is indexed at
+// run time (every loop below is unrolled over constants), no LDS, no scratch.  Every multiply-add is an explicit fmaf and the
+// unit is compiled with contraction off, so the bits of an output do not depend on which others are requested.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/kvae_lgssm.h"
+#include "lgssm_pred.h"
+#include "regime_decode.h"
+
+namespace kvae_swf {
+
+using kvae::rdec::xg8;
+using kvae::rgrid::oct_max;
+using kvae::rgrid::oct_sum;
+
+constexpr int MAX_K = 8, MAX_N = 4, MAX_M = 4;
+
+// all 64 lanes: the eight lanes of a group, then the eight groups
+__device__ __forceinline__ float wave_sum(float x) { return xg8<0>(oct_sum(x)); }
+__device__ __forceinline__ float wave_max(float x) { return xg8<1>(oct_max(x)); }
+
+// element (r, c) of a row-major [rows, cols] matrix padded to 4 x 4: loaded from a valid address, selected afterwards
+__device__ __forceinline__ float padded(const float *M, int rows, int cols, int r, int c, bool live) {
+  const bool in = live && r < rows && c < cols;
+  const float v = M[in ? r * cols + c : 0];
+  return in ? v : 0.0f;
+}
+
+__device__ inline void sweep_wave(const kvae_swf_problem &P) {
+  const int lane = (int)(threadIdx.x & 63), k = lane & 7, g = lane >> 3;
+  const int T = P.T, K = P.K, n = P.n, m = P.m;
+  const int64_t b = blockIdx.x;
+  const bool vk = k < K, vg = g < K, ve = vk && vg;
+  const int kc = vk ? k : 0, gc = vg ? g : 0;
+  // ---- operands of the sweep: regime j = g's dynamics, the shared emission, log P[i = k, j = g] ----
+  float A[4][4], Bm[4][4], Q[4][4], C[2][4], R[2][2];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      A[r][c] = padded(P.A + gc * n * n, n, n, r, c, vg);
+      Bm[r][c] = padded(P.Bm + gc * n * m, n, m, r, c, vg);
+      Q[r][c] = padded(P.Q + gc * n * n, n, n, r, c, vg);
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) C[q][c] = padded(P.C, 2, n, q, c, true);
+    R[q][0] = P.R[2 * q], R[q][1] = P.R[2 * q + 1];
+  }
+  const float Pr = P.P[ve ? k * K + g : 0];
+  const float Pij = ve ? Pr : 0.0f, lPij = ve ? logf(Pr) : -INFINITY;
+  const float Puni = 1.0f / (float)K, lPuni = logf(Puni);
+  // ---- the carried belief of regime i = k ("along the lanes") ----
+  const bool carried = P.state_log_w != nullptr;
+  float mu[4], Sg[4][4], lw;
+  {
+    const float *m0 = carried ? P.state_mu + (b * K + kc) * n : P.mu0;
+    const float *S0 = carried ? P.state_Sigma + (b * K + kc) * n * n : P.Sigma0;
+    const float *w0 = carried ? P.state_log_w + b * K + kc : P.R;   // a valid address either way
+    const float lw0 = *w0;
+    lw = vk ? (carried ? lw0 : lPuni) : -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      mu[r] = padded(m0, 1, n, 0, r, vk);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) Sg[r][c] = padded(S0, n, n, r, c, vk);
+    }
+  }
+  // ---- y_0, u_0, mask_0 ----
+  const int64_t q0 = b * T;
+  const float *maskp = P.mask ? P.mask + q0 : P.R;   // always a valid address (the note at mask_addr, csrc/lgssm_fwd.h)
+  const int mstep = P.mask ? 1 : 0;
+  float yn0 = P.y[q0 * 2], yn1 = P.y[q0 * 2 + 1], mkn = maskp[0], un[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) un[c] = padded(P.u + q0 * m, 1, m, 0, c, true);
+
+  for (int t = 0; t < T; ++t) {
+    const int64_t q = q0 + t;
+    const float y0 = yn0, y1 = yn1, mk = P.mask ? mkn : 1.0f;
+    const float u[4] = {un[0], un[1], un[2], un[3]};
+    {   // the next step's, in flight while this one computes
+      const int tn = t + 1 < T ? t + 1 : t;
+      const int64_t qn = q0 + tn;
+      yn0 = P.y[qn * 2], yn1 = P.y[qn * 2 + 1], mkn = maskp[tn * mstep];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) un[c] = padded(P.u + qn * m, 1, m, 0, c, true);
+    }
+    const bool observed = mk != 0.0f, first = t == 0 && !carried;
+    // ---- the Kalman step of pair (i, j): predict ----
+    float mp[4], AS[4][4], Sp[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float acc = 0.f;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc = fmaf(A[r][c], mu[c], acc);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc = fmaf(Bm[r][c], u[c], acc);
+      mp[r] = acc;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        float s = 0.f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s = fmaf(A[r][e], Sg[e][c], s);
+        AS[r][c] = s;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        float s = 0.f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s = fmaf(AS[r][e], A[c][e], s);
+        Sp[r][c] = s + Q[r][c];
+      }
+    }
+    // ---- forecast of the pair, S, the pair density ----
+    float ap[2], res[2], CP[2][4], PCT[4][2];
+#pragma unroll
+    for (int qq = 0; qq < 2; ++qq) {
+      float acc = 0.f;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc = fmaf(C[qq][e], mp[e], acc);
+      ap[qq] = acc;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s1 = fmaf(C[qq][e], Sp[e][c], s1), s2 = fmaf(Sp[c][e], C[qq][e], s2);
+        CP[qq][c] = s1, PCT[c][qq] = s2;
+      }
+    }
+    res[0] = y0 - ap[0], res[1] = y1 - ap[1];
+    float s00 = 0.f, s01a = 0.f, s01b = 0.f, s11 = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      s00 = fmaf(CP[0][e], C[0][e], s00), s01a = fmaf(CP[0][e], C[1][e], s01a);
+      s01b = fmaf(CP[1][e], C[0][e], s01b), s11 = fmaf(CP[1][e], C[1][e], s11);
+    }
+    const float S00 = s00 + R[0][0], S11 = s11 + R[1][1];   // 0.5 (x + x) = x
+    const float S01 = 0.5f * ((s01a + R[0][1]) + (s01b + R[1][0]));
+    const kvae_pred::Tail tl = kvae_pred::pred_tail(S00, S01, S11, res[0], res[1]);
+    // ---- gain (S^-1 PCT^T by elimination), update, Joseph form ----
+    const float el = S01 / S00, ed = fmaf(-el, S01, S11);
+    float Kg[4][2];   // K = mask * Kt^T
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float x1 = fmaf(-el, PCT[r][0], PCT[r][1]) / ed;
+      const float x0 = fmaf(-S01, x1, PCT[r][0]) / S00;
+      Kg[r][0] = mk * x0, Kg[r][1] = mk * x1;
+    }
+    float IKC[4][4], KR[4][2], muf[4], T1[4][4], Sf[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) IKC[r][c] = (r == c ? 1.0f : 0.0f) - fmaf(Kg[r][1], C[1][c], Kg[r][0] * C[0][c]);
+      KR[r][0] = fmaf(Kg[r][1], R[1][0], Kg[r][0] * R[0][0]), KR[r][1] = fmaf(Kg[r][1], R[1][1], Kg[r][0] * R[0][1]);
+      muf[r] = fmaf(Kg[r][1], res[1], fmaf(Kg[r][0], res[0], mp[r]));
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        float s = 0.f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s = fmaf(IKC[r][e], Sp[e][c], s);
+        T1[r][c] = s;
+      }
+    }
+    float F0[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        float s = 0.f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s = fmaf(T1[r][e], IKC[c][e], s);
+        F0[r][c] = s + fmaf(KR[r][1], Kg[c][1], KR[r][0] * Kg[c][0]);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+#pragma unroll
+      for (int c = r; c < 4; ++c) Sf[r][c] = 0.5f * (F0[r][c] + F0[c][r]);   // the upper triangle: the lower has the same bits
+    }
+    // ---- weights: log c_ij, the prior weight w(i) P[i,j], the column softmax ----
+    const float lPt = first ? (ve ? lPuni : -INFINITY) : lPij, Pt = first ? (ve ? Puni : 0.0f) : Pij;
+    const float lij = observed ? tl.ll : 0.0f;
+    const float logc = ve ? (lw + lPt) + lij : -INFINITY;
+    const float pw = ve ? expf(lw) * Pt : 0.0f;
+    const float rp = oct_sum(pw);                                   // regime_pred(j), on the groups
+    const float cmx = oct_max(logc);
+    const bool dead = !(cmx > -INFINITY);                           // an impossible regime: W one-hot at i = j
+    const float ex = dead ? (k == g ? 1.0f : 0.0f) : expf(logc - cmx);
+    const float se = oct_sum(ex);
+    const float W = ex / se;
+    const float mx = xg8<1>(cmx);
+    const float tot = mx + logf(xg8<0>(vg ? se * expf(cmx - mx) : 0.0f));   // logsumexp_ij; a dead column adds 1 * exp(-inf) = 0
+    const float lwn = (cmx + logf(se)) - tot;                       // log w'(j), on the groups
+    const float rf = vg ? expf(lwn) : 0.0f;
+    // ---- collapse over i ----
+    float mc[4], Sc[4][4], d[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      mc[r] = oct_sum(W * muf[r]);
+      d[r] = muf[r] - mc[r];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+#pragma unroll
+      for (int c = r; c < 4; ++c) Sc[r][c] = oct_sum(W * fmaf(d[r], d[c], Sf[r][c]));
+    }
+    // ---- the step's outputs ----
+    if (P.regime_pred && vg && k == 0) P.regime_pred[q * K + g] = rp;
+    if (P.regime_filt && vg && k == 0) P.regime_filt[q * K + g] = rf;
+    if (P.ll && lane == 0) P.ll[q] = observed ? tot : 0.0f;
+    if (P.levels) {
+      const float lv = wave_max(pw > 0.0f ? (float)tl.level : 0.0f);
+      if (lane == 0) P.levels[q] = (int32_t)lv;
+    }
+    if (P.a_pred || P.S_out) {   // moment match of the K^2 pair forecasts under the prior weights
+      const float a0 = wave_sum(pw * ap[0]), a1 = wave_sum(pw * ap[1]);
+      if (P.a_pred && lane == 0) P.a_pred[q * 2] = a0, P.a_pred[q * 2 + 1] = a1;
+      if (P.S_out) {
+        const float e0 = ap[0] - a0, e1 = ap[1] - a1;
+        const float o00 = wave_sum(pw * fmaf(e0, e0, S00)), o01 = wave_sum(pw * fmaf(e0, e1, S01));
+        const float o11 = wave_sum(pw * fmaf(e1, e1, S11));
+        if (lane == 0) {
+          float *o = P.S_out + q * 4;
+          o[0] = o00, o[1] = o01, o[2] = o01, o[3] = o11;
+        }
+      }
+    }
+    if (P.mus_filt || P.Sigmas_filt) {   // moment match of the K collapsed Gaussians under w': the operands are already equal
+      const float wj = rf;               // inside a group (rf = 0 on the groups past K), so the sum over the groups is all there is
+      float mm[4], dd[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        mm[r] = xg8<0>(wj * mc[r]);
+        dd[r] = mc[r] - mm[r];
+        if (P.mus_filt && lane == 0 && r < n) P.mus_filt[q * n + r] = mm[r];
+      }
+      if (P.Sigmas_filt) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+#pragma unroll
+          for (int c = r; c < 4; ++c) {
+            const float v = xg8<0>(wj * fmaf(dd[r], dd[c], Sc[r][c]));
+            if (lane == 0 && c < n) P.Sigmas_filt[q * n * n + r * n + c] = v, P.Sigmas_filt[q * n * n + c * n + r] = v;
+          }
+        }
+      }
+    }
+    if (t == T - 1) {   // the carried state out: regime j = g, one lane per group
+      const bool w = vg && k == 0;
+      const int64_t s = b * K + g;
+      if (P.out_log_w && w) P.out_log_w[s] = lwn;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if (P.out_mu && w && r < n) P.out_mu[s * n + r] = mc[r];
+#pragma unroll
+        for (int c = r; c < 4; ++c)
+          if (P.out_Sigma && w && c < n) P.out_Sigma[(s * n + r) * n + c] = Sc[r][c], P.out_Sigma[(s * n + c) * n + r] = Sc[r][c];
+      }
+    }
+    // ---- hand-over: lane (i = k, j = g) takes regime k's belief from group k ----
+    const int src = k << 3;
+    const float lwA = __shfl(lwn, src, 64);
+    lw = vk ? lwA : -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float v = __shfl(mc[r], src, 64);
+      mu[r] = vk ? v : 0.0f;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+#pragma unroll
+      for (int c = r; c < 4; ++c) {
+        const float v = __shfl(Sc[r][c], src, 64);
+        Sg[r][c] = vk ? v : 0.0f;
+        Sg[c][r] = Sg[r][c];
+      }
+    }
+  }
+}
+
+// ---- seq_ll[b] = sum_t ll[b, t]: one wavefront per sequence, lane-strided partial sums in ascending t, then a fixed butterfly ----
+__device__ inline void seq_wave(const kvae_swf_problem &P) {
+  const int T = P.T, lane = (int)(threadIdx.x & 63);
+  const int64_t b = blockIdx.x;
+  const float *ll = P.ll + b * T;
+  float acc = 0.f;
+  for (int t = lane; t < T; t += 64) acc += ll[t];   // hidden steps hold 0
+  for (int s = 32; s >= 1; s >>= 1) acc += __shfl_xor(acc, s, 64);
+  if (lane == 0) P.seq_ll[b] = acc;
+}
+
+// ---- what both entry points (kvae_lgssm_swf.hip, the host simulation below) share --------------------------------------------
+inline int swf_check(const kvae_swf_problem *P) {
+  if (!P) return KVAE_ERR_NULL;
+  if (!P->A || !P->Bm || !P->Q || !P->C || !P->R || !P->P || !P->y || !P->u) return KVAE_ERR_NULL;
+  const bool any = P->state_log_w || P->state_mu || P->state_Sigma, all = P->state_log_w && P->state_mu && P->state_Sigma;
+  if (!any && (!P->mu0 || !P->Sigma0)) return KVAE_ERR_NULL;
+  if (P->seq_ll && !P->ll) return KVAE_ERR_NULL;   // the sequence sums read ll
+  if (P->B < 1 || P->T < 1) return KVAE_ERR_DIMS;
+  if (P->K < 1 || P->K > MAX_K || P->n < 1 || P->n > MAX_N || P->m < 1 || P->m > MAX_M || P->p != 2) return KVAE_ERR_ARG;
+  if (any && !all) return KVAE_ERR_ARG;
+  return KVAE_OK;
+}
+inline bool swf_wants_sweep(const kvae_swf_problem &P) {
+  return P.regime_filt || P.regime_pred || P.ll || P.a_pred || P.S_out || P.mus_filt || P.Sigmas_filt || P.levels || P.out_log_w ||
+         P.out_mu || P.out_Sigma;
+}
+
+}  // namespace kvae_swf
+
+#if defined(KVAE_WAVE_EMU)
+// ---- the host simulation's kvae_lgssm_switching_filter (TEST-ONLY: tests/hostsim/wave_emu.h defines KVAE_WAVE_EMU) -----------
+// The kernel bodies on emulated wavefronts, with the grids of kvae_lgssm_swf.hip; the launches are counted per body so that tests
+// can assert which one ran.  Include this header with KVAE_WAVE_EMU in ONE translation unit per binary.
+namespace kvae_swf {
+inline int *emu_launches() {
+  static int n[2] = {0, 0};   // 0 the sweep, 1 the sequence sums
+  return n;
+}
+}  // namespace kvae_swf
+
+extern "C" int kvae_lgssm_switching_filter(const kvae_swf_problem *prob, void *) {
+  using namespace kvae_swf;
+  const int rc = swf_check(prob);
+  if (rc) return rc;
+  const kvae_swf_problem &P = *prob;
+  if (swf_wants_sweep(P)) {
+    emu_launches()[0] += 1;
+    wemu::launch((unsigned)P.B, [&] { sweep_wave(P); });
+  }
+  if (P.seq_ll) {
+    emu_launches()[1] += 1;
+    wemu::launch((unsigned)P.B, [&] { seq_wave(P); });
+  }
+  return KVAE_OK;
+}
+extern "C" int kvae_wemu_switching_filter_launches(int which) { return which == 0 || which == 1 ? kvae_swf::emu_launches()[which] : -1; }
+#endif

@@ -17,7 +17,7 @@ LIB_PATH = _HERE / "lib" / "libkvae_lgssm.so"
 KVAE_MAX_DIM = 16
 KVAE_MAX_K = 16
 LSTM_MAX_H, LSTM_MAX_I = 52, 16
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 _STATUS = {1: "KVAE_ERR_DIMS (n, m, p must be in [1,16]; B, T >= 1)", 2: "KVAE_ERR_NULL", 3: "KVAE_ERR_LAUNCH",
            4: "KVAE_ERR_ARG"}
@@ -70,6 +70,13 @@ class PredGrads(C.Structure):  # kvae_pred_grads
     _fields_ = [(k, C.c_void_p) for k in ("g_ll", "g_seq", "g_mus_pred", "g_Sigmas_pred", "gY")] + [("gC", Stack)]
 
 
+class SwfProblem(C.Structure):  # kvae_swf_problem
+    _fields_ = ([(k, C.c_int32) for k in ("B", "T", "K", "n", "m", "p")]
+                + [(k, C.c_void_p) for k in ("A", "Bm", "Q", "C", "R", "P", "mu0", "Sigma0", "y", "u", "mask", "state_log_w", "state_mu",
+                                             "state_Sigma", "regime_filt", "regime_pred", "ll", "seq_ll", "a_pred", "S_out", "mus_filt",
+                                             "Sigmas_filt", "levels", "out_log_w", "out_mu", "out_Sigma")])
+
+
 class InputGrads(C.Structure):  # kvae_lgssm_input_grads
     _fields_ = [("gA", Stack), ("gB", Stack), ("gC", Stack), ("gQ", Stack),
                 ("gY", C.c_void_p), ("gU", C.c_void_p), ("g_mu0", C.c_void_p), ("g_Sigma0", C.c_void_p)]
@@ -83,7 +90,7 @@ SYMBOLS = ("kvae_lgssm_filter_alpha_lstm", "kvae_lgssm_alpha_lstm_bwd", "kvae_lg
            "kvae_dec_up_fwd", "kvae_dec_up_bwd", "kvae_dec_up_partial_rows", "kvae_dec_up_set_workgroups",
            "kvae_enc_head_fwd", "kvae_enc_head_bwd", "kvae_dec_fc_fwd", "kvae_dec_fc_bwd", "kvae_head_partial_rows",
            "kvae_latent_reg_fwd", "kvae_latent_reg_bwd", "kvae_loss_head_fwd", "kvae_loss_head_bwd",
-           "kvae_lgssm_emission_means", "kvae_lgssm_generate", "kvae_lgssm_posterior_sample", "kvae_lgssm_posterior_sample_ws_floats", "kvae_lgssm_predictive", "kvae_lgssm_predictive_bwd", "kvae_rnn_wgrad", "kvae_rnn_wgrad_ws_floats", "kvae_linear_fwd", "kvae_linear_bwd_input",
+           "kvae_lgssm_emission_means", "kvae_lgssm_generate", "kvae_lgssm_posterior_sample", "kvae_lgssm_posterior_sample_ws_floats", "kvae_lgssm_predictive", "kvae_lgssm_predictive_bwd", "kvae_lgssm_switching_filter", "kvae_rnn_wgrad", "kvae_rnn_wgrad_ws_floats", "kvae_linear_fwd", "kvae_linear_bwd_input",
            "kvae_abi_version",
            "kvae_last_error", "kvae_build_info")
 
@@ -116,6 +123,8 @@ class LgssmLib:
         d.kvae_lgssm_predictive.restype = C.c_int
         d.kvae_lgssm_predictive_bwd.argtypes = [C.POINTER(PredProblem), C.POINTER(PredGrads), vp]
         d.kvae_lgssm_predictive_bwd.restype = C.c_int
+        d.kvae_lgssm_switching_filter.argtypes = [C.POINTER(SwfProblem), vp]
+        d.kvae_lgssm_switching_filter.restype = C.c_int
         d.kvae_lgssm_smooth_bwd.argtypes = [P, S, S, G, vp, C.c_int, vp]
         d.kvae_lgssm_smooth_bwd.restype = C.c_int
         d.kvae_lgssm_elbo.argtypes = [P, vp, vp, vp, vp, vp, vp, vp, vp, G, vp]

@@ -6,8 +6,9 @@ argument order, tuple layouts and tensor shapes:
     filter(Y,U,mask)  -> (mus_filt[B,T,n,1], Sigmas_filt[B,T,n,n], mus_pred, Sigmas_pred, A_list, B_list, C_list)
     smooth(Y,U,mask)  -> (mus_smooth, Sigmas_smooth) + the seven above
     elbo(mu,Sigma,y,u,A_list,B_list,C_list,Q_list=None,mask=None) -> 0-d tensor
-Additions over the reference: condition, sample_posterior, predictive (exact log p(a_t | a_{0:t-1}, u), no tape) and
-log_marginal / marginal (the same density, differentiable: the exact LGSSM training objective).
+Additions over the reference: condition, sample_posterior, predictive (exact log p(a_t | a_{0:t-1}, u), no tape),
+log_marginal / marginal (the same density, differentiable: the exact LGSSM training objective) and filter_regimes (the causal
+switching Kalman filter over the generative switching model).
 What differs is the execution: one launch (one wavefront per sequence, the whole T loop and the
 RTS sweep inside the kernel) replaces ~580 aten calls per time step, and the backward is a
 hand-derived adjoint kernel instead of an autograd tape.  Inputs must live on a HIP device.
@@ -269,6 +270,24 @@ class KalmanFilter(nn.Module):
                                    packed=last["rec"], slots=Slots(C=last["slots"].C), want=want)
         out.update(filter=(mf, Sf, mp, Sp, A_l, B_l, C_l), state_probs=self.dyn_params.state_seq)
         return out
+
+    @torch.no_grad()
+    def filter_regimes(self, Y, U, mask=None, state=None, want=lgssm_ops._SWF_OUTPUTS):
+        """The generative switching model filtered on its own, causally (switching dynamics only): the switching Kalman filter
+        with GPB2 collapse over (A_k, B_k, Q_k), the shared C and R, the prior's transition matrix P (unclamped) and
+        (mu0, Sigma0) - lgssm_ops.switching_filter; include/kvae_lgssm.h kvae_lgssm_switching_filter.  The regime posterior
+        network plays no part and no regime is drawn.  state: the "state" entry of an earlier call continues that stream.
+        Returns switching_filter's dict: regime_filt / regime_pred [B,T,K] = p(s_t | a_{0:t}) / p(s_t | a_{0:t-1}), log_lik [B,T]
+        = log p(a_t | a_{0:t-1}, u) with the regimes summed out (0 on hidden steps), log_lik_seq [B], a_pred, S, mus_filt,
+        Sigmas_filt, levels, state; entries not named in `want` are None."""
+        dyn = self.dyn_params
+        if not dyn.is_switching_dynamics:
+            raise ValueError("filter_regimes needs switching dynamics (SwitchingDynamicsParameter): the alpha-network of the lstm "
+                             "dynamics has no regime chain to filter")
+        dev, dt = Y.device, Y.dtype
+        return lgssm_ops.switching_filter(dyn.A.detach(), dyn.B.detach(), dyn.Q.detach(), dyn.C[0].detach(), self.R,
+                                          dyn._prior_matrix(dev, dt), self.mu0, self.Sigma0, Y, U, self._mask(mask, Y), want=want,
+                                          state=state)
 
     def log_marginal(self, Y, U, mask=None):
         """log p(a | u), exactly and DIFFERENTIABLY: the filter (training or eval dynamics as self.training says; no RTS sweep),

@@ -1208,3 +1208,175 @@ def log_marginal(mus_pred, Sigmas_pred, Cm, R, Y, mask=None, packed=None, slots=
     ll, seq, levels = PredictiveLogLik.apply(mp, Sigmas_pred, Cm, packed if slots.C is not None else None, R.detach().to(dev), Y,
                                              mask, Slots(C=slots.C))
     return {"ll": ll, "seq_ll": seq, "levels": levels}
+
+
+# ------------------------------------------------------------------------------------------------
+# causal switching Kalman filter, GPB2 (kvae_lgssm_switching_filter, csrc/lgssm_swf.h)
+# ------------------------------------------------------------------------------------------------
+_SWF_OUTPUTS = ("regime_filt", "regime_pred", "log_lik", "log_lik_seq", "a_pred", "S", "mus_filt", "Sigmas_filt", "levels", "state")
+SWF_SUPPORTED = dict(max_K=8, max_n=4, max_m=4, p=2)
+
+
+def switching_filter_supported(K, n, m, p, ref=None):
+    """Shapes / tensors kvae_lgssm_switching_filter is built for (include/kvae_lgssm.h: fp32, K <= 8, n <= 4, m <= 4, p == 2, a HIP
+    device - or the host simulation a test injected); the rest takes switching_filter_torch."""
+    if ref is not None and not (N.fused_ok(ref) and ref.dtype == torch.float32):
+        return False
+    s = SWF_SUPPORTED
+    return 1 <= K <= s["max_K"] and 1 <= n <= s["max_n"] and 1 <= m <= s["max_m"] and p == s["p"]
+
+
+def _swf_want(want):
+    want = (want,) if isinstance(want, str) else tuple(want)
+    bad = [w for w in want if w not in _SWF_OUTPUTS]
+    if bad or not want:
+        raise ValueError(f"switching_filter: want must name some of {_SWF_OUTPUTS}, got {want}")
+    return want
+
+
+def _swf_state(state, Bsz, K, n):
+    if state is None:
+        return None
+    lw, mu, Sig = state["log_w"], state["mu"], state["Sigma"]
+    if lw.shape != (Bsz, K) or mu.shape != (Bsz, K, n) or Sig.shape != (Bsz, K, n, n):
+        raise ValueError(f"switching_filter: state must hold log_w [{Bsz},{K}], mu [{Bsz},{K},{n}], Sigma [{Bsz},{K},{n},{n}], got "
+                         f"{tuple(lw.shape)}, {tuple(mu.shape)}, {tuple(Sig.shape)}")
+    return lw, mu, Sig
+
+
+@torch.no_grad()
+def switching_filter_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, state=None, want=_SWF_OUTPUTS):
+    """The equations of kvae_lgssm_switching_filter (include/kvae_lgssm.h) in torch ops, vectorised over (B, i, j), in the dtype of
+    A: shapes outside the kernel's, non-fp32 and host tensors, and (in float64) the reference the kernel is tested against.
+    T steps of about thirty small launches.  Same arguments and returns as switching_filter."""
+    want = _swf_want(want)
+    dt, dev = A.dtype, Y.device
+    K, n = A.shape[0], A.shape[1]
+    Bsz, T, p = Y.shape
+    A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U = (t.detach().to(device=dev, dtype=dt) for t in (A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U))
+    mask = None if mask is None else mask.detach().to(device=dev, dtype=dt).reshape(Bsz, T)
+    st = _swf_state(state, Bsz, K, n)
+    if st is None:
+        lw = torch.full((Bsz, K), 1.0 / K, device=dev, dtype=dt).log()
+        mu, Sig = mu0.expand(Bsz, K, n), Sigma0.expand(Bsz, K, n, n)
+    else:
+        lw, mu, Sig = (t.detach().to(device=dev, dtype=dt) for t in st)
+    eye = torch.eye(n, device=dev, dtype=dt)
+    eyeK = torch.eye(K, device=dev, dtype=dt)
+    uniform = torch.full((K, K), 1.0 / K, device=dev, dtype=dt)
+    ninf = torch.full((), -float("inf"), device=dev, dtype=dt)
+    outs = {k: [] for k in ("regime_filt", "regime_pred", "log_lik", "a_pred", "S", "mus_filt", "Sigmas_filt", "levels")}
+    for t in range(T):
+        Pt = uniform if (t == 0 and st is None) else P
+        mk = torch.ones(Bsz, device=dev, dtype=dt) if mask is None else mask[:, t]
+        observed = mk != 0
+        # ---- the K^2 filter steps: [B, i, j, ...] ----
+        mp = torch.einsum("jrc,bic->bijr", A, mu) + torch.einsum("jrc,bc->bjr", Bm, U[:, t]).unsqueeze(1)
+        Sp = torch.einsum("jre,biec,jdc->bijrd", A, Sig, A) + Q
+        ap = mp @ Cm.mT
+        res = Y[:, t, None, None, :] - ap
+        S = Cm @ Sp @ Cm.mT + R
+        S = 0.5 * (S + S.mT)
+        L, lv = safe_cholesky_items(S)
+        wv = torch.linalg.solve_triangular(L, res.unsqueeze(-1), upper=False).squeeze(-1)
+        logdet = 2.0 * torch.log(torch.diagonal(L, dim1=-2, dim2=-1)).sum(-1)
+        lij = -0.5 * ((wv * wv).sum(-1) + logdet + p * _LOG_2PI)
+        lij = torch.where(observed[:, None, None], lij, torch.zeros_like(lij))
+        Kg = torch.linalg.solve(S, Cm @ Sp).mT * mk[:, None, None, None, None]      # S^-1 (Sigma_pred C^T)^T, transposed
+        muf = mp + (Kg @ res.unsqueeze(-1)).squeeze(-1)
+        IKC = eye - Kg @ Cm
+        Sf = IKC @ Sp @ IKC.mT + Kg @ R @ Kg.mT
+        Sf = 0.5 * (Sf + Sf.mT)
+        # ---- weights ----
+        logc = lw.unsqueeze(-1) + Pt.log() + lij                                     # [B, i, j]
+        pw = lw.exp().unsqueeze(-1) * Pt
+        cmx = logc.amax(1)                                                           # [B, j]
+        dead = cmx == ninf
+        ex = torch.where(dead.unsqueeze(1), eyeK.expand(Bsz, K, K), (logc - torch.where(dead, torch.zeros_like(cmx), cmx).unsqueeze(1)).exp())
+        se = ex.sum(1)
+        W = ex / se.unsqueeze(1)
+        mx = cmx.amax(-1, keepdim=True)
+        tot = mx.squeeze(-1) + (se * (cmx - mx).exp()).sum(-1).log()
+        lw = (cmx + se.log()) - tot.unsqueeze(-1)
+        rf = lw.exp()
+        # ---- collapse over i ----
+        mu = (W.unsqueeze(-1) * muf).sum(1)                                          # [B, j, n]
+        d = muf - mu.unsqueeze(1)
+        Sig = (W[..., None, None] * (Sf + d.unsqueeze(-1) * d.unsqueeze(-2))).sum(1)
+        Sig = 0.5 * (Sig + Sig.mT)
+        # ---- outputs of the step ----
+        outs["regime_pred"].append(pw.sum(1))
+        outs["regime_filt"].append(rf)
+        outs["log_lik"].append(torch.where(observed, tot, torch.zeros_like(tot)))
+        outs["levels"].append(torch.where(pw > 0, lv, torch.zeros_like(lv)).amax((1, 2)))
+        a = (pw.unsqueeze(-1) * ap).sum((1, 2))
+        e = ap - a[:, None, None, :]
+        outs["a_pred"].append(a)
+        outs["S"].append((pw[..., None, None] * (S + e.unsqueeze(-1) * e.unsqueeze(-2))).sum((1, 2)))
+        m_ = (rf.unsqueeze(-1) * mu).sum(1)
+        dd = mu - m_.unsqueeze(1)
+        outs["mus_filt"].append(m_)
+        outs["Sigmas_filt"].append((rf[..., None, None] * (Sig + dd.unsqueeze(-1) * dd.unsqueeze(-2))).sum(1))
+    full = {k: torch.stack(v, 1) for k, v in outs.items()}
+    full["log_lik_seq"] = full["log_lik"].sum(1)
+    full["state"] = {"log_w": lw, "mu": mu, "Sigma": Sig}
+    return {k: (full[k] if k in want else None) for k in _SWF_OUTPUTS}
+
+
+@torch.no_grad()
+def switching_filter(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, want=_SWF_OUTPUTS, state=None, impl=None):
+    """The causal switching Kalman filter with GPB2 collapse over the generative switching model (semantics: include/kvae_lgssm.h,
+    kvae_lgssm_switching_filter; DESIGN.md section 14).  A [K,n,n], Bm [K,n,m], Q [K,n,n] per regime; Cm [p,n], R [p,p] shared;
+    P [K,K] the transition matrix (unclamped: a zero is an impossible transition); mu0 [n], Sigma0 [n,n]; Y [B,T,p]; U [B,T,m];
+    mask [B,T] (1 = observed) or None.  state: None (s_0 uniform, every regime starts at (mu0, Sigma0)) or the "state" entry of an
+    earlier call, which continues that stream.  want: which of "regime_filt", "regime_pred" [B,T,K], "log_lik" [B,T],
+    "log_lik_seq" [B], "a_pred" [B,T,p], "S" [B,T,p,p], "mus_filt" [B,T,n], "Sigmas_filt" [B,T,n,n], "levels" [B,T] (int32),
+    "state" (dict log_w [B,K], mu [B,K,n], Sigma [B,K,n,n] after the last step) to compute; entries not asked for are None.
+    One launch for the sweep (one more for log_lik_seq), no host synchronisation, no gradients.
+    impl: None = the HIP kernel where it is built (switching_filter_supported), else switching_filter_torch; "hip" / "torch" force one."""
+    want = _swf_want(want)
+    if impl not in (None, "hip", "torch"):
+        raise ValueError(f"switching_filter: impl must be None, 'hip' or 'torch', got {impl!r}")
+    K, n, m = A.shape[0], A.shape[1], Bm.shape[2]
+    Bsz, T, p = Y.shape
+    supported = switching_filter_supported(K, n, m, p, Y)
+    if impl == "hip" and not supported:
+        raise ValueError(f"switching_filter: impl='hip' needs fp32 tensors on a HIP device and K <= {SWF_SUPPORTED['max_K']}, "
+                         f"n <= {SWF_SUPPORTED['max_n']}, m <= {SWF_SUPPORTED['max_m']}, p == {SWF_SUPPORTED['p']}; got K = {K}, "
+                         f"n = {n}, m = {m}, p = {p}, {Y.dtype} on {Y.device}")
+    if impl == "torch" or not supported:
+        return switching_filter_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, state, want)
+    dev = Y.device
+    A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U = (_f32c(t.detach().to(dev)) for t in (A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U))
+    mask = None if mask is None else _f32c(mask.detach().to(dev).reshape(Bsz, T))
+    st = _swf_state(state, Bsz, K, n)
+    if st is not None:
+        st = tuple(_f32c(t.detach().to(dev)) for t in st)
+    mk = lambda *s, dt=torch.float32: torch.empty(*s, device=dev, dtype=dt)
+    out = {k: None for k in _SWF_OUTPUTS}
+    ll = mk(Bsz, T) if ("log_lik" in want or "log_lik_seq" in want) else None   # the sequence sums read log_lik
+    out["log_lik"] = ll if "log_lik" in want else None
+    shapes = dict(regime_filt=(Bsz, T, K), regime_pred=(Bsz, T, K), log_lik_seq=(Bsz,), a_pred=(Bsz, T, p), S=(Bsz, T, p, p),
+                  mus_filt=(Bsz, T, n), Sigmas_filt=(Bsz, T, n, n))
+    for k, s in shapes.items():
+        if k in want:
+            out[k] = mk(*s)
+    if "levels" in want:
+        out["levels"] = mk(Bsz, T, dt=torch.int32)
+    if "state" in want:
+        out["state"] = {"log_w": mk(Bsz, K), "mu": mk(Bsz, K, n), "Sigma": mk(Bsz, K, n, n)}
+    pr = N.SwfProblem()
+    pr.B, pr.T, pr.K, pr.n, pr.m, pr.p = Bsz, T, K, n, m, p
+    pr.A, pr.Bm, pr.Q, pr.C, pr.R, pr.P = (t.data_ptr() for t in (A, Bm, Q, Cm, R, P))
+    pr.mu0, pr.Sigma0, pr.y, pr.u, pr.mask = mu0.data_ptr(), Sigma0.data_ptr(), Y.data_ptr(), U.data_ptr(), N.ptr(mask)
+    if st is not None:
+        pr.state_log_w, pr.state_mu, pr.state_Sigma = (t.data_ptr() for t in st)
+    pr.regime_filt, pr.regime_pred, pr.ll, pr.seq_ll = N.ptr(out["regime_filt"]), N.ptr(out["regime_pred"]), N.ptr(ll), N.ptr(out["log_lik_seq"])
+    pr.a_pred, pr.S_out, pr.mus_filt, pr.Sigmas_filt = N.ptr(out["a_pred"]), N.ptr(out["S"]), N.ptr(out["mus_filt"]), N.ptr(out["Sigmas_filt"])
+    pr.levels = N.ptr(out["levels"])
+    if out["state"] is not None:
+        pr.out_log_w, pr.out_mu, pr.out_Sigma = (out["state"][k].data_ptr() for k in ("log_w", "mu", "Sigma"))
+    lib = N.lib_for(Y)
+    lib.check(N.timed("switching_filter", Y, lambda: lib.dll.kvae_lgssm_switching_filter(C.byref(pr), N.stream_for(Y))),
+              "kvae_lgssm_switching_filter")
+    return out

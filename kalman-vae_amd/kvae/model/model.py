@@ -465,6 +465,50 @@ class KVAE(nn.Module):
             self.train(was_training)
 
     @torch.no_grad()
+    def filter_regimes(self, x, u=None, mask=None, sample_a=False, state=None, decode=False):
+        """What the generative switching model believes on its own, causally (switching dynamics only; no counterpart in the
+        reference): the switching Kalman filter with second-order generalised pseudo-Bayes collapse (GPB2) over A_k, B_k, Q_k,
+        the shared C and R, the sticky prior P (unclamped) and (mu0, Sigma0) - kvae_lgssm_switching_filter.  The bidirectional
+        regime posterior network, which reads the whole sequence, plays no part: every output of step t has seen a_{0:t} only.
+
+        1. Encode x.  sample_a=False: a = a_mu, the call is deterministic; True: a is drawn as forward() draws it.
+        2. regime_filt [B,T,K] = p(s_t | a_{0:t}), regime_pred [B,T,K] = p(s_t | a_{0:t-1}), regimes [B,T] (int64) = argmax of
+           regime_filt (lowest index on ties).
+        3. log_lik [B,T] = log p(a_t | a_{0:t-1}, u) with the regimes summed out (0 on hidden steps; mask [B,T] optional,
+           1 = observed), log_lik_seq [B] its sum; a_pred [B,T,p], S [B,T,p,p] the moment-matched one-step-ahead forecast;
+           mus_filt [B,T,n], Sigmas_filt [B,T,n,n] the moment-matched filtered belief; levels [B,T] the largest ladder level of
+           the pair densities.  u [B,T,m] or None = zeros.
+        4. state: the K collapsed Gaussians and their log weights after the last step; state=prev["state"] continues a stream,
+           and the outputs of the chunks, concatenated, are the bits of the whole-sequence call.
+        5. decode=True: x_pred = decoder(a_pred), the one-step-ahead predicted frames.
+        Also returns a_vae and n_obs [B].  Exact through t = 1, at every step when P is the identity or when all regimes share
+        A, B, Q; otherwise the GPB2 approximation.  No host synchronisation.  Training mode, tau and
+        parameters are left as they were."""
+        dyn = self.kalman_filter.dyn_params
+        if not dyn.is_switching_dynamics:
+            raise ValueError('filter_regimes needs a model with dynamics = "switching" (config.dynamics_model); this one has '
+                             f'"{self.config.dynamics_model}"')
+        self._check_mask_u("filter_regimes", x, mask, u)
+        Bsz, T = x.shape[:2]
+        was_training = self.training
+        self.eval()
+        try:
+            a_vae, _, _ = self.encode_sequence(x, sample=bool(sample_a))
+            dev, dt = a_vae.device, a_vae.dtype
+            u = torch.zeros(Bsz, T, self.u_dim, device=dev, dtype=dt) if u is None else u.to(device=dev, dtype=dt)
+            mk = None if mask is None else mask.to(device=dev, dtype=dt)
+            out = self.kalman_filter.filter_regimes(a_vae, u, mk, state=state)
+            rf = out["regime_filt"]
+            out["regimes"] = (rf == rf.max(-1, keepdim=True).values).to(torch.int8).argmax(-1)   # lowest index among the maxima
+            out["a_vae"] = a_vae
+            out["n_obs"] = torch.full((Bsz,), float(T), device=dev, dtype=dt) if mk is None else mk.sum(1)
+            if decode:
+                out["x_pred"] = self._to_pixels(self.decode_sequence(out["a_pred"].to(dt)))
+            return out
+        finally:
+            self.train(was_training)
+
+    @torch.no_grad()
     def log_likelihood(self, x, num_samples=1, u=None, mask=None):
         """Importance-weighted bound on log p(x_observed) per sequence under the generative model p(x | a) p_LGSSM(a), with the
         encoder as proposal (no counterpart in the reference).  B sequences of T frames, S = num_samples.

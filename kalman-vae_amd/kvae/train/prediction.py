@@ -35,3 +35,33 @@ def prediction_scores(model, batch_or_x, mask=None, u=None):
     n_obs = mk.sum().clamp(min=1.0)
     return {"mse_kf": float(mse_kf), "mse_naive": float(mse_naive), "log_lik_per_step": float(sc["log_lik"].sum() / n_obs),
             "nis_mean": float(sc["nis"].sum() / n_obs)}
+
+
+@torch.no_grad()
+def regime_filter_scores(model, batch_or_x, mask=None, u=None):
+    """The generative switching model against its amortised regime posterior on x [B,T,...] (or a batch, as prediction_scores
+    takes it): KVAE.filter_regimes - causal, the regimes summed out - next to KVAE.score and KVAE.decode_regimes, which go
+    through the bidirectional posterior network.  Switching dynamics only.  Python floats:
+      log_lik_per_step       sum of the regime-marginal log p(a_t | a_{0:t-1}, u) over observed steps / their number
+      log_lik_per_step_map   the same for score(): the density conditional on the posterior's most likely regime path
+      regime_agreement       share of steps whose causal argmax regime equals decode_regimes' path
+      regime_kl              mean over steps of KL(q(s_t) || p(s_t | a_{0:t})), q(s_t) the posterior network's marginals"""
+    if isinstance(batch_or_x, dict):
+        x = batch_or_x["images"]
+    elif isinstance(batch_or_x, (tuple, list)):
+        x = batch_or_x[0]
+    else:
+        x = batch_or_x
+    dev = next(model.parameters()).device
+    x = x.to(dev)
+    fr = model.filter_regimes(x, u=u, mask=mask)
+    sc = model.score(x, u=u, mask=mask, regimes="map")
+    dec = model.decode_regimes(x, u=u, mask=mask, smooth=False)
+    n_obs = fr["n_obs"].sum().clamp(min=1.0)
+    q, pf = dec["regime_probs"].double(), fr["regime_filt"].double()
+    tiny = torch.finfo(torch.float32).tiny
+    kl = (q * (q.clamp_min(tiny).log() - pf.clamp_min(tiny).log())).sum(-1)
+    return {"log_lik_per_step": float(fr["log_lik_seq"].sum() / n_obs),
+            "log_lik_per_step_map": float(sc["log_lik_seq"].sum() / n_obs),
+            "regime_agreement": float((fr["regimes"] == dec["regimes"]).double().mean()),
+            "regime_kl": float(kl.mean())}

@@ -1,0 +1,163 @@
+"""CPU tier of kvae_lgssm_switching_filter / lgssm_ops.switching_filter / KalmanFilter.filter_regimes / KVAE.filter_regimes: the
+host simulation injected (as tests/test_regime_decode.py does), so the kernel body of csrc/lgssm_swf.h runs on emulated
+wavefronts (tests/hostsim/wave_emu.h); the launch counters say which body ran.  Against the float64 restatement per (b, t)
+(tests/swf_cases.py), the enumeration of every regime path, the existing filter, chunked streams, partial outputs, the C ABI, the
+model level, the resource report of the gfx950 kernels, and the body under ASan + UBSan."""
+import os
+import re
+import subprocess
+from pathlib import Path
+
+import pytest
+import torch
+
+import swf_cases as cases
+from hostsim.build import build as build_hostsim
+
+torch.set_num_threads(4)
+ROOT = Path(__file__).resolve().parents[1]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def wave_emu_backend():
+    from kvae import _native
+    lib = _native.LgssmLib(build_hostsim())
+    _native._set_test_backend(lib)
+    lib.dll.kvae_hostsim_wave_emu(1)
+    yield lib
+    lib.dll.kvae_hostsim_wave_emu(0)
+    _native._set_test_backend(None)
+
+
+def launches(lib):
+    """emulated launches so far (csrc/lgssm_swf.h, KVAE_WAVE_EMU section): [the sweep, the sequence sums]"""
+    return [lib.dll.kvae_wemu_switching_filter_launches(i) for i in (0, 1)]
+
+
+@pytest.mark.parametrize("case", cases.CASES + [cases.LONG_CASE], ids=str)
+def test_per_step_vs_float64(wave_emu_backend, case):
+    before = launches(wave_emu_backend)
+    cases.per_step("cpu", case)
+    assert [a - b for a, b in zip(launches(wave_emu_backend), before)] == [1, 1]
+
+
+def test_yardsticks_are_what_float32_torch_gives():
+    """The constants the bars derive from: the float32 restatement against the float64 one, remeasured.  Each is the largest of
+    a few hundred rounding samples and moves with the host's vector width and libm: within a factor 3 either way."""
+    for k, v in cases.yardsticks().items():
+        assert v / 3 <= cases.YARDSTICK[k] <= v * 3, (k, v, cases.YARDSTICK[k])
+
+
+def test_model_yardsticks_are_what_float32_torch_gives(wave_emu_backend):
+    for k, v in cases.model_yardsticks().items():
+        assert v / 3 <= cases.MODEL_YARDSTICK[k] <= v * 3, (k, v, cases.MODEL_YARDSTICK[k])
+
+
+@pytest.mark.parametrize("K,T", [(2, 2), (3, 2), (2, 6)])
+def test_restatement_is_exact_through_step_one(K, T):
+    cases.exact_first_steps(K, T)
+
+
+def test_restatement_is_exact_under_an_identity_prior():
+    cases.exact_identity_prior()
+
+
+def test_restatement_is_exact_for_shared_dynamics():
+    cases.exact_shared_dynamics()
+
+
+def test_identity_prior_on_the_kernel(wave_emu_backend):
+    before = launches(wave_emu_backend)
+    cases.identity_prior_on_kernel("cpu")
+    assert launches(wave_emu_backend)[0] == before[0] + 1
+
+
+@pytest.mark.parametrize("K", [1, 3])
+def test_identical_regimes_are_the_existing_filter(wave_emu_backend, K):
+    before = launches(wave_emu_backend)
+    cases.vs_existing_filter("cpu", K)
+    assert launches(wave_emu_backend)[0] == before[0] + 1
+
+
+@pytest.mark.parametrize("case", [c for c in cases.CASES if c[5] and c[1] >= 8], ids=str)
+def test_streaming_is_bit_identical(wave_emu_backend, case):
+    cases.streaming("cpu", case)
+
+
+def test_partial_outputs_and_repeatability(wave_emu_backend):
+    before = launches(wave_emu_backend)
+    cases.partial_outputs("cpu", (3, 5, 3, 4, 2, True))
+    assert [a - b for a, b in zip(launches(wave_emu_backend), before)] == [2 + 10, 2 + 1]   # every output sweeps (log_lik_seq reads log_lik)
+
+
+def test_routing(wave_emu_backend):
+    before = launches(wave_emu_backend)
+    cases.routing("cpu")
+    assert [a - b for a, b in zip(launches(wave_emu_backend), before)] == [1, 1]   # only the last, supported, call
+
+
+def test_host_tensors_raise_without_a_backend(wave_emu_backend):
+    """fp32 host tensors of a supported shape are not routed to the kernel when no test backend is injected: they take the
+    restatement, as float64 ones do; impl="hip" raises."""
+    from kvae import _native
+    args, mask = cases.inputs(2, 3, 2)
+    _native._set_test_backend(None)
+    try:
+        before = launches(wave_emu_backend)
+        out = cases.run("cpu", args, mask)
+        assert out["regime_filt"].dtype == torch.float32 and launches(wave_emu_backend) == before
+        assert cases.run("cpu", tuple(a.double() for a in args), mask)["regime_filt"].dtype == torch.float64
+        with pytest.raises(ValueError, match="impl='hip'"):
+            cases.run("cpu", args, mask, impl="hip")
+    finally:
+        _native._set_test_backend(wave_emu_backend)
+
+
+def test_c_abi(wave_emu_backend):
+    cases.c_abi(wave_emu_backend, "cpu")
+
+
+def test_model_level(wave_emu_backend):
+    before = launches(wave_emu_backend)
+    cases.model_level("cpu")
+    assert launches(wave_emu_backend)[0] > before[0]
+
+
+def test_model_errors(wave_emu_backend):
+    before = launches(wave_emu_backend)
+    cases.model_errors("cpu")
+    assert launches(wave_emu_backend) == before
+
+
+def test_regime_filter_scores(wave_emu_backend):
+    cases.filter_scores("cpu")
+
+
+def test_kernels_have_no_scratch():
+    """The resource report of every kernel of the unit (gfx950 cross-compile): 0 bytes of scratch per lane, no LDS."""
+    src = ROOT / "kalman-vae_amd" / "csrc" / "kvae_lgssm_swf.hip"
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-mllvm", "-amdgpu-mfma-vgpr-form", "-c",
+                        str(src), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    names = re.findall(r"Function Name: (\S*k_swf_\S*)", r.stderr)
+    scratch = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
+    lds = [int(v) for v in re.findall(r"LDS Size \[bytes/block\]: (\d+)", r.stderr)]
+    assert len(names) == 2 and len(scratch) == 2 and len(lds) == 2, (names, scratch, lds)
+    assert all(s == 0 for s in scratch), list(zip(names, scratch))
+    assert all(v == 0 for v in lds), list(zip(names, lds))
+
+
+def test_kernel_body_under_sanitizers():
+    """A standalone driver of csrc/lgssm_swf.h (tests/hostsim/swf_asan_driver.cpp), built with -fsanitize=address,undefined and
+    run as a child process: T = 1, K = 5 and K = 7 padding lanes, run-time n and m below 4, NULL outputs, a carried state."""
+    out = ROOT / "tests" / "hostsim" / "swf_asan_driver"
+    src = ROOT / "tests" / "hostsim" / "swf_asan_driver.cpp"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-pthread", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
+                    "-fno-sanitize-recover=undefined", "-I", str(ROOT / "tests" / "hostsim" / "stub"), "-o", str(out), str(src)],
+                   check=True, cwd=ROOT)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1:verify_asan_link_order=0",
+               UBSAN_OPTIONS="halt_on_error=1")
+    r = subprocess.run([str(out)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "SWF-ASAN-OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
