@@ -82,17 +82,22 @@ class InputGrads(C.Structure):  # kvae_lgssm_input_grads
                 ("gY", C.c_void_p), ("gU", C.c_void_p), ("g_mu0", C.c_void_p), ("g_Sigma0", C.c_void_p)]
 
 
-SYMBOLS = ("kvae_lgssm_filter_alpha_lstm", "kvae_lgssm_alpha_lstm_bwd", "kvae_lgssm_filter_fwd", "kvae_lgssm_rts_fwd", "kvae_lgssm_smooth_fwd", "kvae_lgssm_smooth_bwd",
-           "kvae_lgssm_elbo", "kvae_mix_fwd", "kvae_mix_bwd", "kvae_mix_bwd_partials", "kvae_lstm_fwd",
-           "kvae_lstm_bwd", "kvae_bias_shuffle_act_fwd", "kvae_bias_shuffle_act_bwd", "kvae_bias_partial_rows", "kvae_colsum", "kvae_colsum2", "kvae_clip_adam", "kvae_regime_fwd", "kvae_regime_bwd", "kvae_regime_decode", "kvae_regime_decode_ws_bytes", "kvae_bigru_fwd", "kvae_bigru_bwd", "kvae_bce_frames_fwd", "kvae_bce_frames_bwd",
-           "kvae_dec_head_fwd", "kvae_dec_head_bwd", "kvae_enc_stem_fwd", "kvae_enc_stem_bwd", "kvae_conv_edge_partial_rows",
-           "kvae_enc_mid_fwd", "kvae_enc_mid_bwd", "kvae_enc_mid_partial_rows",
-           "kvae_dec_up_fwd", "kvae_dec_up_bwd", "kvae_dec_up_partial_rows", "kvae_dec_up_set_workgroups",
-           "kvae_enc_head_fwd", "kvae_enc_head_bwd", "kvae_dec_fc_fwd", "kvae_dec_fc_bwd", "kvae_head_partial_rows",
-           "kvae_latent_reg_fwd", "kvae_latent_reg_bwd", "kvae_loss_head_fwd", "kvae_loss_head_bwd",
-           "kvae_lgssm_emission_means", "kvae_lgssm_generate", "kvae_lgssm_posterior_sample", "kvae_lgssm_posterior_sample_ws_floats", "kvae_lgssm_predictive", "kvae_lgssm_predictive_bwd", "kvae_lgssm_switching_filter", "kvae_rnn_wgrad", "kvae_rnn_wgrad_ws_floats", "kvae_linear_fwd", "kvae_linear_bwd_input",
-           "kvae_abi_version",
-           "kvae_last_error", "kvae_build_info")
+SYMBOLS = (
+    "kvae_lgssm_filter_alpha_lstm", "kvae_lgssm_alpha_lstm_bwd", "kvae_lgssm_filter_fwd", "kvae_lgssm_rts_fwd",
+    "kvae_lgssm_smooth_fwd", "kvae_lgssm_smooth_bwd", "kvae_lgssm_elbo", "kvae_mix_fwd", "kvae_mix_bwd",
+    "kvae_mix_bwd_partials", "kvae_lstm_fwd", "kvae_lstm_bwd", "kvae_bias_shuffle_act_fwd",
+    "kvae_bias_shuffle_act_bwd", "kvae_bias_partial_rows", "kvae_colsum", "kvae_colsum2", "kvae_clip_adam",
+    "kvae_regime_fwd", "kvae_regime_bwd", "kvae_regime_decode", "kvae_regime_decode_ws_bytes", "kvae_bigru_fwd",
+    "kvae_bigru_bwd", "kvae_bce_frames_fwd", "kvae_bce_frames_bwd", "kvae_dec_head_fwd", "kvae_dec_head_bwd",
+    "kvae_enc_stem_fwd", "kvae_enc_stem_bwd", "kvae_conv_edge_partial_rows", "kvae_enc_mid_fwd", "kvae_enc_mid_bwd",
+    "kvae_enc_mid_partial_rows", "kvae_dec_up_fwd", "kvae_dec_up_bwd", "kvae_dec_up_partial_rows",
+    "kvae_dec_up_set_workgroups", "kvae_enc_head_fwd", "kvae_enc_head_bwd", "kvae_dec_fc_fwd", "kvae_dec_fc_bwd",
+    "kvae_head_partial_rows", "kvae_latent_reg_fwd", "kvae_latent_reg_bwd", "kvae_loss_head_fwd",
+    "kvae_loss_head_bwd", "kvae_lgssm_emission_means", "kvae_lgssm_generate", "kvae_lgssm_posterior_sample",
+    "kvae_lgssm_posterior_sample_ws_floats", "kvae_lgssm_predictive", "kvae_lgssm_predictive_bwd",
+    "kvae_lgssm_switching_filter", "kvae_rnn_wgrad", "kvae_rnn_wgrad_ws_floats", "kvae_linear_fwd",
+    "kvae_linear_bwd_input", "kvae_abi_version", "kvae_last_error", "kvae_build_info",
+)
 
 
 class LgssmLib:
@@ -312,7 +317,6 @@ def timed(name, t, thunk):
 
 
 def _colsum_raw(p2):
-    import torch
     out = torch.empty(p2.shape[1], device=p2.device, dtype=torch.float32)
     lib = lib_for(p2)
     lib.check(lib.dll.kvae_colsum(ptr(p2), ptr(out), p2.shape[0], p2.shape[1], stream_for(p2)), "kvae_colsum")
@@ -322,7 +326,6 @@ def _colsum_raw(p2):
 def colsum_pair(a, b):
     """(colsum(a), colsum(b)) in one launch when neither needs the two-pass folding of tall inputs (k_colsum_v4_pair): the
     weight- and bias-gradient partials of one layer."""
-    import torch
     a2, b2 = a.reshape(a.shape[0], -1).contiguous(), b.reshape(b.shape[0], -1).contiguous()
     tall = [p.shape[0] >= 1024 and p.shape[1] < 4096 for p in (a2, b2)]
     if a2.device != b2.device or tall[0] != tall[1] or (tall[0] and (a2.shape[0] != b2.shape[0] or a2.shape[0] % 64)):

@@ -12,6 +12,8 @@ switching Kalman filter over the generative switching model).
 What differs is the execution: one launch (one wavefront per sequence, the whole T loop and the
 RTS sweep inside the kernel) replaces ~580 aten calls per time step, and the backward is a
 hand-derived adjoint kernel instead of an autograd tape.  Inputs must live on a HIP device.
+Everything native is reached through lgssm_ops (the bridge; it also lays out the packed step record: Slots, alpha_lstm_slots,
+slot_view); the read-outs' torch restatements it falls back to are lgssm_torch's.
 """
 import torch
 import torch.nn as nn
@@ -142,11 +144,11 @@ class KalmanFilter(nn.Module):
                                                    self.Q, self.R, self.mu0, self.Sigma0, with_rts)
             rec, alpha = outs[-2], outs[-1]
             n, m, p = self.n, self.m, self.p
-            views = (rec[..., :n * n].unflatten(-1, (n, n)), rec[..., n * n:n * n + n * m].unflatten(-1, (n, m)),
-                     rec[..., n * n + n * m:].unflatten(-1, (p, n)))
+            slots, _ = lgssm_ops.alpha_lstm_slots(n, m, p)
+            views = (lgssm_ops.slot_view(rec, slots.A, n, n), lgssm_ops.slot_view(rec, slots.B, n, m),
+                     lgssm_ops.slot_view(rec, slots.C, p, n))
             dyn.state_seq = alpha
-            self._last = dict(rec=rec, slots=Slots(A=0, B=n * n, C=n * n + n * m), A=None, B=None, C=None, Q=self.Q,
-                              views=views, Q_view=None)
+            self._last = dict(rec=rec, slots=slots, A=None, B=None, C=None, Q=self.Q, views=views, Q_view=None)
             if with_rts:
                 ms, Ss, mf, Sf, mp, Sp = outs[:6]
                 return u1(ms), Ss, u1(mf), Sf, u1(mp), Sp
@@ -197,8 +199,8 @@ class KalmanFilter(nn.Module):
             mf, Sf, mp, Sp, rec, alpha, h_seq, c_seq = lgssm_ops.AlphaLstmSmooth.apply(
                 Y, U, m, dyn.lstm.weight_ih_l0, dyn.lstm.weight_hh_l0, dyn.lstm.bias_ih_l0, dyn.lstm.bias_hh_l0,
                 dyn.head_w.weight, dyn.head_w.bias, dyn.A, dyn.B, dyn.C, self.Q, self.R, self.mu0, self.Sigma0, False, True)
-            n, mm = self.n, self.m
-            C_last = rec[:, -1, n * n + n * mm:].unflatten(-1, (self.p, n))
+            slots, _ = lgssm_ops.alpha_lstm_slots(self.n, self.m, self.p)
+            C_last = lgssm_ops.slot_view(rec[:, -1], slots.C, self.p, self.n)
             dyn.state_seq = alpha
             out.update(h=h_seq[:, -1], c=c_seq[:, -1])
             mf, mp = mf.unsqueeze(-1), mp.unsqueeze(-1)

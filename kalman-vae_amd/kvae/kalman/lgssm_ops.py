@@ -9,6 +9,10 @@ Per-step operands (A_t, B_t, C_t, Q_t) reach the kernels as strided "stacks": ei
 packed record tensor [B,T,E] produced by `mix_dynamics` (mixture-of-K case: a single launch writes
 a whole step record, a single tensor carries its gradient) or a plain tensor that is broadcast
 ([r,c]) or per-step ([B,T,r,c]).
+
+This module is the bridge only.  The read-outs (regime_decode, rollout, posterior_paths, predictive, log_marginal,
+switching_filter) dispatch between their kernel and its restatement in torch ops; the restatements - also the float64 references
+of the tests - and safe_cholesky / safe_cholesky_items live in lgssm_torch (no native library behind it) and are re-exported here.
 """
 import ctypes as C
 from typing import NamedTuple, Optional
@@ -16,6 +20,9 @@ from typing import NamedTuple, Optional
 import torch
 
 from .. import _native as N
+from .lgssm_torch import (_DECODE_OUTPUTS, _LOG_2PI, _PRED_OUTPUTS, _SWF_OUTPUTS, _bt, _swf_state, _want,  # noqa: F401 (re-exported)
+                          log_marginal_torch, posterior_paths_torch, predictive_torch, regime_decode_torch, rollout_torch,
+                          safe_cholesky, safe_cholesky_items, switching_filter_torch)
 
 
 class Slots(NamedTuple):
@@ -24,6 +31,26 @@ class Slots(NamedTuple):
     B: Optional[int] = None
     C: Optional[int] = None
     Q: Optional[int] = None
+
+
+def alpha_lstm_slots(n, m, p):
+    """(Slots, record width E) of the step record A | B | C the in-kernel alpha-LSTM writes (AlphaLstmSmooth)."""
+    return Slots(A=0, B=n * n, C=n * n + n * m), n * n + n * m + p * n
+
+
+def slot_view(packed, off, r, c):
+    """The [..., r, c] view of the slot at float offset `off` of a packed step record [..., E]."""
+    return packed[..., off:off + r * c].unflatten(-1, (r, c))
+
+
+def _empty(dev, *shape, dt=torch.float32):
+    return torch.empty(*shape, device=dev, dtype=dt)
+
+
+def _wanted(dev, outputs, want, shapes):
+    """{name: a fresh tensor of shapes[name] if the name is wanted, else None} over `outputs`; "levels" is int32."""
+    return {k: _empty(dev, *shapes[k], dt=torch.int32 if k == "levels" else torch.float32) if (k in want and k in shapes) else None
+            for k in outputs}
 
 
 def _f32c(t):
@@ -89,10 +116,17 @@ def _states(mf, Sf, mp, Sp, ms=None, Ss=None, aux=None):
     return st
 
 
-class _GradSink:
-    """Gradient buffers for the per-step operands + the autograd return values built from them."""
+def _reduce_to(buf, t):
+    """The per-step gradient buf [B,T,r,c] reduced to the shape of the operand t the caller passed in."""
+    if t.dim() == 2:
+        return buf.sum((0, 1))
+    return buf.sum_to_size(t.shape) if tuple(t.shape) != tuple(buf.shape) else buf
 
-    def __init__(self, call, packed, A, Bm, Cm, Q, slots, need_q):
+
+class _GradSink:
+    """Gradient buffers for the per-step operands (and, where asked for, the prior) + the autograd return values built from them."""
+
+    def __init__(self, call, packed, A, Bm, Cm, Q, slots, need_q, need_mu0=False, need_Sigma0=False):
         Bsz, T, n, m, p = call.dims
         dev = call.Y.device
         self.g = N.InputGrads()
@@ -106,23 +140,28 @@ class _GradSink:
             elif name == "gQ" and not need_q:
                 setattr(self.g, name, N.Stack(None, 0, 0))
             else:
-                buf = torch.empty(Bsz, T, r, c, device=dev, dtype=torch.float32)
+                buf = _empty(dev, Bsz, T, r, c)
                 self.out[name] = (buf, t)
                 setattr(self.g, name, N.Stack(buf.data_ptr(), T * r * c, r * c))
         self.gY = torch.empty_like(call.Y)
         self.gU = torch.empty_like(call.U)
         self.g.gY, self.g.gU = self.gY.data_ptr(), self.gU.data_ptr()
+        self.g_mu0 = _empty(dev, Bsz, n) if need_mu0 else None
+        self.g_Sigma0 = _empty(dev, Bsz, n, n) if need_Sigma0 else None
+        self.g.g_mu0, self.g.g_Sigma0 = N.ptr(self.g_mu0), N.ptr(self.g_Sigma0)
+        self.shared_prior = (call.mu0.dim() == 1, call.Sigma0.dim() == 2)
 
     def operand_grad(self, name, scale=None):
         """Gradient for a non-packed operand, reduced to the shape the caller passed in."""
         if name not in self.out:
             return None
         buf, t = self.out[name]
-        if scale is not None:
-            buf = buf * scale
-        if t.dim() == 2:
-            return buf.sum((0, 1))
-        return buf.sum_to_size(t.shape) if tuple(t.shape) != tuple(buf.shape) else buf
+        return _reduce_to(buf if scale is None else buf * scale, t)
+
+    def prior_grads(self):
+        """(g_mu0, g_Sigma0) once the launch has written them per sequence: summed over the batch where the prior was shared."""
+        return tuple(N.colsum(g) if (g is not None and shared) else g
+                     for g, shared in zip((self.g_mu0, self.g_Sigma0), self.shared_prior))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -136,11 +175,10 @@ class LgssmSmooth(torch.autograd.Function):
         call = _Call(Y, U, mask, packed, A, Bm, Cm, Q, R, mu0, Sigma0, slots)
         Bsz, T, n, m, p = call.dims
         dev = call.Y.device
-        mk = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
-        mf, Sf, mp, Sp = mk(Bsz, T, n), mk(Bsz, T, n, n), mk(Bsz, T, n), mk(Bsz, T, n, n)
-        ms, Ss = (mk(Bsz, T, n), mk(Bsz, T, n, n)) if with_rts else (None, None)
+        mf, Sf, mp, Sp = _empty(dev, Bsz, T, n), _empty(dev, Bsz, T, n, n), _empty(dev, Bsz, T, n), _empty(dev, Bsz, T, n, n)
+        ms, Ss = (_empty(dev, Bsz, T, n), _empty(dev, Bsz, T, n, n)) if with_rts else (None, None)
         # gains (K | S | J) kept for the backward; consumed by the n=4,p=2 fused-phase kernels
-        aux = mk(Bsz, T, n * p + p * p + n * n) if any(ctx.needs_input_grad) else None
+        aux = _empty(dev, Bsz, T, n * p + p * p + n * n) if any(ctx.needs_input_grad) else None
         st = _states(mf, Sf, mp, Sp, ms, Ss, aux)
         fn = call.lib.dll.kvae_lgssm_smooth_fwd if with_rts else call.lib.dll.kvae_lgssm_filter_fwd
         call.lib.check(N.timed("smooth_fwd" if with_rts else "filter_fwd", call.Y,
@@ -167,24 +205,14 @@ class LgssmSmooth(torch.autograd.Function):
             g_ms = g_Ss = None
         need = ctx.needs_input_grad
         need_q = slots.Q is not None or (Q is not None and need[7])
-        sink = _GradSink(call, packed, A, Bm, Cm, Q, slots, need_q)
-        g0 = S0 = None
-        if need[9]:
-            g0 = torch.empty(Bsz, n, device=Y.device, dtype=torch.float32)
-            sink.g.g_mu0 = g0.data_ptr()
-        if need[10]:
-            S0 = torch.empty(Bsz, n, n, device=Y.device, dtype=torch.float32)
-            sink.g.g_Sigma0 = S0.data_ptr()
-        ws = torch.empty(Bsz, T, 2 * (n + n * n), device=Y.device, dtype=torch.float32)
+        sink = _GradSink(call, packed, A, Bm, Cm, Q, slots, need_q, need[9], need[10])
+        ws = _empty(Y.device, Bsz, T, 2 * (n + n * n))
         saved = _states(mf, Sf, mp, Sp, ms, Ss, aux)
         up = _states(g_mf, g_Sf, g_mp, g_Sp, g_ms, g_Ss)
         call.lib.check(N.timed("smooth_bwd", call.Y, lambda: call.lib.dll.kvae_lgssm_smooth_bwd(
             C.byref(call.prob), C.byref(saved), C.byref(up), C.byref(sink.g), N.ptr(ws), int(with_rts), call.stream)),
             "kvae_lgssm_smooth_bwd")
-        if g0 is not None and mu0.dim() == 1:
-            g0 = N.colsum(g0)
-        if S0 is not None and Sigma0.dim() == 2:
-            S0 = N.colsum(S0)
+        g0, S0 = sink.prior_grads()
         return (sink.gY if need[0] else None, sink.gU if need[1] else None, None, sink.gpacked,
                 sink.operand_grad("gA"), sink.operand_grad("gB"), sink.operand_grad("gC"),
                 sink.operand_grad("gQ") if need_q else None, None, g0, S0, None, None)
@@ -207,9 +235,9 @@ class LgssmElbo(torch.autograd.Function):
         dev = call.Y.device
         mus_c = _f32c(mus.reshape(Bsz, T, n))
         Sigs_c, eps_c = _f32c(Sigs), _f32c(eps)
-        terms = torch.empty(Bsz, T, 4, device=dev, dtype=torch.float32)
-        levels = torch.empty(3, device=dev, dtype=torch.int32)   # (level of Sigma_s, level of Q_t, kernel family of the launch)
-        ws_lz = torch.empty(Bsz, T, n, device=dev, dtype=torch.float32)   # z_t parked by the probe launch
+        terms = _empty(dev, Bsz, T, 4)
+        levels = _empty(dev, 3, dt=torch.int32)   # (level of Sigma_s, level of Q_t, kernel family of the launch)
+        ws_lz = _empty(dev, Bsz, T, n)   # z_t parked by the probe launch
         want = any(ctx.needs_input_grad)
         g_mus = g_Sigs = sink = None
         if want:
@@ -252,7 +280,7 @@ class MixDynamics(torch.autograd.Function):
         a, bs = _f32c(alpha), _f32c(base)
         Bsz, T, K = a.shape
         E = bs.shape[1]
-        out = torch.empty(Bsz, T, E, device=a.device, dtype=torch.float32)
+        out = _empty(a.device, Bsz, T, E)
         lib = N.lib_for(a)
         lib.check(lib.dll.kvae_mix_fwd(N.ptr(a), N.ptr(bs), N.ptr(out), Bsz * T, K, E, N.stream_for(a)), "kvae_mix_fwd")
         ctx.save_for_backward(a, bs)
@@ -260,17 +288,19 @@ class MixDynamics(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_out):
-        a, bs = ctx.saved_tensors
-        g = _f32c(g_out)
-        Bsz, T, K = a.shape
-        E = bs.shape[1]
-        lib = N.lib_for(a)
-        nblk = lib.dll.kvae_mix_bwd_partials(Bsz * T)
-        partials = torch.empty(nblk, K, E, device=a.device, dtype=torch.float32)
-        g_alpha, g_base = torch.empty_like(a), torch.empty_like(bs)
-        lib.check(lib.dll.kvae_mix_bwd(N.ptr(a), N.ptr(bs), N.ptr(g), N.ptr(g_alpha), N.ptr(g_base), N.ptr(partials),
-                                       Bsz * T, K, E, 0, N.stream_for(a)), "kvae_mix_bwd")
-        return g_alpha, g_base
+        return _mix_bwd(*ctx.saved_tensors, _f32c(g_out))
+
+
+def _mix_bwd(alpha, base, g_rec):
+    """(g_alpha, g_base) of record = sum_k alpha_k base_k from g_rec [B,T,E]: kvae_mix_bwd with its partials workspace."""
+    Bsz, T, K = alpha.shape
+    E = base.shape[1]
+    lib = N.lib_for(alpha)
+    partials = _empty(alpha.device, lib.dll.kvae_mix_bwd_partials(Bsz * T), K, E)
+    g_alpha, g_base = torch.empty_like(alpha), torch.empty_like(base)
+    lib.check(lib.dll.kvae_mix_bwd(N.ptr(alpha), N.ptr(base), N.ptr(g_rec), N.ptr(g_alpha), N.ptr(g_base), N.ptr(partials),
+                                   Bsz * T, K, E, 0, N.stream_for(alpha)), "kvae_mix_bwd")
+    return g_alpha, g_base
 
 
 def mix_dynamics(alpha, mats):
@@ -279,10 +309,9 @@ def mix_dynamics(alpha, mats):
     rec = MixDynamics.apply(alpha, base)
     offs, views, o = [], [], 0
     for mt in mats:
-        e = mt.shape[1] * mt.shape[2]
         offs.append(o)
-        views.append(rec[..., o:o + e].unflatten(-1, (mt.shape[1], mt.shape[2])))
-        o += e
+        views.append(slot_view(rec, o, mt.shape[1], mt.shape[2]))
+        o += mt.shape[1] * mt.shape[2]
     return rec, offs, views
 
 
@@ -301,9 +330,9 @@ def rnn_wgrad(ref, problems):
         n_rows, R = d.shape
         assert d.stride(1) == 1 and (h is None or h.stride(1) == 1) and (x is None or x.stride(1) == 1)
         H, I, bias = (h.shape[1] if h is not None else 0), (x.shape[1] if x is not None else 0), int(bool(pr.get("bias", True)))
-        g_wh = torch.empty(R, H, device=d.device, dtype=torch.float32) if H else None
-        g_wx = torch.empty(R, I, device=d.device, dtype=torch.float32) if I else None
-        g_b = torch.empty(R, device=d.device, dtype=torch.float32) if bias else None
+        g_wh = _empty(d.device, R, H) if H else None
+        g_wx = _empty(d.device, R, I) if I else None
+        g_b = _empty(d.device, R) if bias else None
         slot.d, slot.h, slot.x = d.data_ptr(), (h.data_ptr() if H else None), (x.data_ptr() if I else None)
         slot.g_wh, slot.g_wx, slot.g_b = (t.data_ptr() if t is not None else None for t in (g_wh, g_wx, g_b))
         slot.d_stride, slot.h_stride, slot.x_stride = d.stride(0), (h.stride(0) if H else 0), (x.stride(0) if I else 0)
@@ -311,7 +340,7 @@ def rnn_wgrad(ref, problems):
         slot.T, slot.shift = int(pr.get("T", 1)), int(pr.get("shift", 0))
         outs.append((g_wh, g_wx, g_b))
         keep += [d, h, x]
-    ws = torch.empty(int(lib.dll.kvae_rnn_wgrad_ws_floats(arr, len(problems))), device=ref.device, dtype=torch.float32)
+    ws = _empty(ref.device, int(lib.dll.kvae_rnn_wgrad_ws_floats(arr, len(problems))))
     lib.check(N.timed("rnn_wgrad", ref, lambda: lib.dll.kvae_rnn_wgrad(arr, len(problems), N.ptr(ws), N.stream_for(ref))),
               "kvae_rnn_wgrad")
     return outs
@@ -335,7 +364,7 @@ class SmallLinear(torch.autograd.Function):
         w, b = _f32c(weight), _f32c(bias)
         O, F = w.shape
         x2 = x if x.dim() == 2 else x.reshape(-1, F)
-        y = torch.empty(x2.shape[0], O, device=x.device, dtype=torch.float32)
+        y = _empty(x.device, x2.shape[0], O)
         lib = N.lib_for(x)
         lib.check(N.timed("linear_fwd", x, lambda: lib.dll.kvae_linear_fwd(
             N.ptr(x2), x2.stride(0), x2.shape[0], F, N.ptr(w), N.ptr(b), O, int(softmax), N.ptr(y), N.stream_for(x))), "kvae_linear_fwd")
@@ -352,7 +381,7 @@ class SmallLinear(torch.autograd.Function):
         need_x, need_w, need_b = ctx.needs_input_grad[:3]
         dx = gl = None
         if need_x or ctx.softmax:
-            dx = torch.empty(x2.shape[0], F, device=g2.device, dtype=torch.float32)
+            dx = _empty(g2.device, x2.shape[0], F)
             gl = torch.empty_like(g2) if ctx.softmax else None
             lib.check(N.timed("linear_bwd", g2, lambda: lib.dll.kvae_linear_bwd_input(
                 N.ptr(g2), N.ptr(y), x2.shape[0], F, N.ptr(w), O, N.ptr(gl), N.ptr(dx), F, N.stream_for(g2))), "kvae_linear_bwd_input")
@@ -382,8 +411,7 @@ class LstmSequence(torch.autograd.Function):
         x, w_ih, w_hh, b_ih, b_hh = (_f32c(t) for t in (x, w_ih, w_hh, b_ih, b_hh))
         Bsz, T, I = x.shape
         H = w_hh.shape[1]
-        mk = lambda *s: torch.empty(*s, device=x.device, dtype=torch.float32)
-        h, gates, c = mk(Bsz, T, H), mk(Bsz, T, 4 * H), mk(Bsz, T, H)
+        h, gates, c = _empty(x.device, Bsz, T, H), _empty(x.device, Bsz, T, 4 * H), _empty(x.device, Bsz, T, H)
         lib = N.lib_for(x)
         lib.check(N.timed("lstm_fwd", x, lambda: lib.dll.kvae_lstm_fwd(
             N.ptr(x), N.ptr(w_ih), N.ptr(w_hh), N.ptr(b_ih), N.ptr(b_hh), N.ptr(h), N.ptr(gates), N.ptr(c),
@@ -397,7 +425,7 @@ class LstmSequence(torch.autograd.Function):
         g_h = _f32c(g_h)
         Bsz, T, I = x.shape
         H = w_hh.shape[1]
-        d_pre = torch.empty(Bsz, T, 4 * H, device=x.device, dtype=torch.float32)
+        d_pre = _empty(x.device, Bsz, T, 4 * H)
         dx = torch.empty_like(x)
         lib = N.lib_for(x)
         lib.check(N.timed("lstm_bwd", x, lambda: lib.dll.kvae_lstm_bwd(
@@ -423,8 +451,7 @@ class RegimeChain(torch.autograd.Function):
         at run time - the form that follows the reference's tau schedule (train.py:270-274) under hipGraph replay."""
         logits, init_logits, gumbel, P = (_f32c(t) for t in (logits, init_logits, gumbel, P))
         Bsz, T, K, _ = logits.shape
-        mk = lambda *s: torch.empty(*s, device=logits.device, dtype=torch.float32)
-        y, lq, lp = mk(Bsz, T, K), mk(Bsz, T), mk(Bsz, T)
+        y, lq, lp = _empty(logits.device, Bsz, T, K), _empty(logits.device, Bsz, T), _empty(logits.device, Bsz, T)
         lib = N.lib_for(logits)
         tau_t = tau if isinstance(tau, torch.Tensor) else None
         if tau_t is not None and (tau_t.device != logits.device or tau_t.dtype != torch.float32 or tau_t.numel() != 1):
@@ -459,17 +486,6 @@ def regime_decode_supported(K, ref=None):
     return 1 <= K <= N.KVAE_MAX_K
 
 
-_DECODE_OUTPUTS = ("marginals", "path", "kl")
-
-
-def _decode_want(want):
-    want = (want,) if isinstance(want, str) else tuple(want)
-    bad = [w for w in want if w not in _DECODE_OUTPUTS]
-    if bad or not want:
-        raise ValueError(f"regime_decode: want must name some of {_DECODE_OUTPUTS}, got {want}")
-    return want
-
-
 def regime_decode(logits, init_logits, P, want=_DECODE_OUTPUTS, impl=None):
     """Exact inference over the Markov regime posterior q(s_0) = softmax(init_logits), q(s_t | s_{t-1}) = row-softmax(logits[t])
     (semantics: include/kvae_lgssm.h, kvae_regime_decode).  logits [B,T,K,K] (slice 0 unused), init_logits
@@ -477,65 +493,24 @@ def regime_decode(logits, init_logits, P, want=_DECODE_OUTPUTS, impl=None):
     marginals [B,T,K], path [B,T] (int64: the most likely regime sequence, lowest index on ties) and path_logq [B] (its log q),
     kl [B,T] (sum over t = KL(q || p)); entries not asked for are None.  One launch, no host synchronisation.
     impl: None = the HIP kernel where it is built (fp32, K <= 16), else regime_decode_torch; "kernel" / "torch" force one."""
-    want = _decode_want(want)
+    want = _want("regime_decode", _DECODE_OUTPUTS, want)
     Bsz, T, K, _ = logits.shape
     use_kernel = impl == "kernel" or (impl is None and regime_decode_supported(K, logits))
     if not use_kernel:
         return regime_decode_torch(logits, init_logits, P, want)
     dev = logits.device
     logits, init_logits, P = (_f32c(t.detach().to(dev)) for t in (logits, init_logits, P))
-    mk = lambda *s, dt=torch.float32: torch.empty(*s, device=dev, dtype=dt)
-    marg = mk(Bsz, T, K) if "marginals" in want else None
-    kl = mk(Bsz, T) if "kl" in want else None
+    marg = _empty(dev, Bsz, T, K) if "marginals" in want else None
+    kl = _empty(dev, Bsz, T) if "kl" in want else None
     path = plq = ws = None
     lib = N.lib_for(logits)
     if "path" in want:
-        path, plq = mk(Bsz, T, dt=torch.int32), mk(Bsz)
-        ws = mk((lib.dll.kvae_regime_decode_ws_bytes(Bsz, T, K) + 7) // 8, dt=torch.int64)   # 8-byte aligned
+        path, plq = _empty(dev, Bsz, T, dt=torch.int32), _empty(dev, Bsz)
+        ws = _empty(dev, (lib.dll.kvae_regime_decode_ws_bytes(Bsz, T, K) + 7) // 8, dt=torch.int64)   # 8-byte aligned
     lib.check(N.timed("regime_decode", logits, lambda: lib.dll.kvae_regime_decode(
         N.ptr(logits), N.ptr(init_logits), N.ptr(P), N.ptr(marg), N.ptr(path), N.ptr(plq), N.ptr(kl), N.ptr(ws), Bsz, T, K,
         N.stream_for(logits))), "kvae_regime_decode")
     return {"marginals": marg, "path": None if path is None else path.long(), "path_logq": plq, "kl": kl}
-
-
-def regime_decode_torch(logits, init_logits, P, want=_DECODE_OUTPUTS):
-    """The equations of kvae_regime_decode in torch ops, in the dtype of the logits: K > 16 and non-fp32 tensors, and (in float64)
-    the reference the kernel is tested against.  Ties take the lowest index, in every backpointer and in the final argmax
-    (an argmax over (value == max), whose first hit torch returns).  T - 1 iterations of about ten small launches."""
-    want = _decode_want(want)
-    Bsz, T, K, _ = logits.shape
-    dt = logits.dtype
-    init_logits, P = init_logits.to(dt), P.to(device=logits.device, dtype=dt)
-    first = lambda v: (v == v.max(-1, keepdim=True).values).to(torch.int8).argmax(-1)   # lowest index among the maxima
-    ls0 = torch.log_softmax(init_logits, -1)
-    m, d = torch.softmax(init_logits, -1), ls0
-    log_p = torch.log(P.clamp_min(1e-8))
-    ms, kls, bps = [m], [(m * (ls0 - torch.full_like(ls0, 1.0 / K).log())).sum(-1)], []
-    for t in range(1, T):
-        lq = torch.log_softmax(logits[:, t], -1)              # [B, i, j]
-        Q = torch.softmax(logits[:, t], -1)
-        if "marginals" in want or "kl" in want:
-            kls.append((m * (Q * (lq - log_p)).sum(-1)).sum(-1))
-            m = torch.einsum("bi,bij->bj", m, Q)
-            ms.append(m)
-        if "path" in want:
-            cand = (d.unsqueeze(-1) + lq).transpose(1, 2)      # [B, j, i]
-            bps.append(first(cand))
-            d = cand.max(-1).values
-    out = {"marginals": None, "path": None, "path_logq": None, "kl": None}
-    if "marginals" in want:
-        out["marginals"] = torch.stack(ms, 1)
-    if "kl" in want:
-        out["kl"] = torch.stack(kls, 1)
-    if "path" in want:
-        out["path_logq"] = d.max(-1).values
-        s = first(d)
-        path = [s]
-        for bp in reversed(bps):
-            s = bp.gather(1, s.unsqueeze(1)).squeeze(1)
-            path.append(s)
-        out["path"] = torch.stack(path[::-1], 1)
-    return out
 
 
 # ------------------------------------------------------------------------------------------------
@@ -556,8 +531,8 @@ class BiGruSequence(torch.autograd.Function):
         ws = [_f32c(t) for t in (wi0, wh0, bi0, bh0, wi1, wh1, bi1, bh1)]
         Bsz, T, I = x.shape
         H = ws[1].shape[1]
-        h = torch.empty(Bsz, T, 2 * H, device=x.device, dtype=torch.float32)
-        gates = torch.empty(2, Bsz, T, 4 * H, device=x.device, dtype=torch.float32)
+        h = _empty(x.device, Bsz, T, 2 * H)
+        gates = _empty(x.device, 2, Bsz, T, 4 * H)
         lib = N.lib_for(x)
         lib.check(N.timed("bigru_fwd", x, lambda: lib.dll.kvae_bigru_fwd(
             N.ptr(x), _ptr2(ws[0], ws[4]), _ptr2(ws[1], ws[5]), _ptr2(ws[2], ws[6]), _ptr2(ws[3], ws[7]), N.ptr(h),
@@ -571,8 +546,7 @@ class BiGruSequence(torch.autograd.Function):
         g_h = _f32c(g_h)
         Bsz, T, I = x.shape
         H = wh0.shape[1]
-        mk = lambda *s: torch.empty(*s, device=x.device, dtype=torch.float32)
-        dpi, dph, dx = mk(2, Bsz, T, 3 * H), mk(2, Bsz, T, 3 * H), mk(2, Bsz, T, I)
+        dpi, dph, dx = _empty(x.device, 2, Bsz, T, 3 * H), _empty(x.device, 2, Bsz, T, 3 * H), _empty(x.device, 2, Bsz, T, I)
         lib = N.lib_for(x)
         lib.check(N.timed("bigru_bwd", x, lambda: lib.dll.kvae_bigru_bwd(
             N.ptr(g_h), N.ptr(gates), N.ptr(h), _ptr2(wi0, wi1), _ptr2(wh0, wh1), N.ptr(dpi), N.ptr(dph), N.ptr(dx),
@@ -619,18 +593,17 @@ class AlphaLstmSmooth(torch.autograd.Function):
         Bsz, T, p = Y.shape
         K, n, m = A.shape[0], A.shape[1], Bm.shape[2]
         H = w_hh.shape[1]
-        E = n * n + n * m + p * n
+        slots, E = alpha_lstm_slots(n, m, p)
         dev = Y.device
-        mk = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
-        mf, Sf, mp, Sp = mk(Bsz, T, n), mk(Bsz, T, n, n), mk(Bsz, T, n), mk(Bsz, T, n, n)
-        record, alpha = mk(Bsz, T, E), mk(Bsz, T, K)
+        mf, Sf, mp, Sp = _empty(dev, Bsz, T, n), _empty(dev, Bsz, T, n, n), _empty(dev, Bsz, T, n), _empty(dev, Bsz, T, n, n)
+        record, alpha = _empty(dev, Bsz, T, E), _empty(dev, Bsz, T, K)
         need = any(ctx.needs_input_grad)
-        gates, c_seq, h_seq, x_seq = (mk(Bsz, T, 4 * H), mk(Bsz, T, H), mk(Bsz, T, H), mk(Bsz, T, p)) if need else (None,) * 4
+        gates, c_seq, h_seq, x_seq = ((_empty(dev, Bsz, T, 4 * H), _empty(dev, Bsz, T, H), _empty(dev, Bsz, T, H), _empty(dev, Bsz, T, p))
+                                      if need else (None,) * 4)
         if keep_cell and not need:
-            c_seq, h_seq = mk(Bsz, T, H), mk(Bsz, T, H)
-        slots = Slots(A=0, B=n * n, C=n * n + n * m)
+            c_seq, h_seq = _empty(dev, Bsz, T, H), _empty(dev, Bsz, T, H)
         call = _Call(Y, U, mask, record, None, None, None, Q, R, mu0, Sigma0, slots)
-        ms, Ss = (mk(Bsz, T, n), mk(Bsz, T, n, n)) if with_rts else (None, None)
+        ms, Ss = (_empty(dev, Bsz, T, n), _empty(dev, Bsz, T, n, n)) if with_rts else (None, None)
         st = _states(mf, Sf, mp, Sp, ms, Ss)
         call.lib.check(N.timed("alpha_lstm_fwd", Y, lambda: call.lib.dll.kvae_lgssm_filter_alpha_lstm(
             C.byref(call.prob), C.byref(st), *[N.ptr(w) for w in ws_], K, H, N.ptr(record), N.ptr(alpha), N.ptr(gates),
@@ -659,17 +632,8 @@ class AlphaLstmSmooth(torch.autograd.Function):
         K, H = A.shape[0], w_hh.shape[1]
         dev = Y.device
         need = ctx.needs_input_grad
-        sink = _GradSink(call, record, None, None, None, Q, slots, False)   # gA|gB|gC land in one g_record buffer
-        g0 = S0 = None
-        if need[14]:
-            g0 = torch.empty(Bsz, n, device=dev, dtype=torch.float32)
-            sink.g.g_mu0 = g0.data_ptr()
-        if need[15]:
-            S0 = torch.empty(Bsz, n, n, device=dev, dtype=torch.float32)
-            sink.g.g_Sigma0 = S0.data_ptr()
-        ws = torch.empty(Bsz, T, 2 * (n + n * n), device=dev, dtype=torch.float32)
-        d_pre = torch.empty(Bsz, T, 4 * H, device=dev, dtype=torch.float32)
-        g_logit = torch.empty(Bsz, T, K, device=dev, dtype=torch.float32)
+        sink = _GradSink(call, record, None, None, None, Q, slots, False, need[14], need[15])   # gA|gB|gC land in one g_record buffer
+        ws, d_pre, g_logit = _empty(dev, Bsz, T, 2 * (n + n * n)), _empty(dev, Bsz, T, 4 * H), _empty(dev, Bsz, T, K)
         saved = _states(mf, Sf, mp, Sp, ms, Ss)
         up = _states(g_mf, g_Sf, g_mp, g_Sp, g_ms, g_Ss)
         call.lib.check(N.timed("alpha_lstm_bwd", Y, lambda: call.lib.dll.kvae_lgssm_alpha_lstm_bwd(
@@ -683,19 +647,10 @@ class AlphaLstmSmooth(torch.autograd.Function):
             (g_whh, g_wih, g_b), (g_hw, _, g_hb) = rnn_wgrad(Y, [
                 dict(d=d_pre.reshape(Bsz * T, 4 * H), h=h2, shift=-1, T=T, x=x_seq.reshape(Bsz * T, p)),
                 dict(d=g_logit.reshape(Bsz * T, K), h=h2)])
-        base = torch.cat([t.reshape(K, -1) for t in (A, Bm, Cm)], dim=1)
-        nblk = call.lib.dll.kvae_mix_bwd_partials(Bsz * T)
-        E = base.shape[1]
-        partials = torch.empty(nblk, K, E, device=dev, dtype=torch.float32)
-        g_alpha_scratch, g_base = torch.empty_like(alpha), torch.empty_like(base)
-        call.lib.check(call.lib.dll.kvae_mix_bwd(N.ptr(alpha), N.ptr(base), N.ptr(sink.gpacked), N.ptr(g_alpha_scratch), N.ptr(g_base),
-                                                 N.ptr(partials), Bsz * T, K, E, 0, call.stream), "kvae_mix_bwd")
+        _, g_base = _mix_bwd(alpha, torch.cat([t.reshape(K, -1) for t in (A, Bm, Cm)], dim=1), sink.gpacked)
         gA, gB, gC = g_base.split([n * n, n * m, p * n], dim=1)
         gA, gB, gC = (g.reshape(t.shape) if nd else None for g, t, nd in zip((gA, gB, gC), (A, Bm, Cm), need[9:12]))
-        if g0 is not None and mu0.dim() == 1:
-            g0 = N.colsum(g0)
-        if S0 is not None and Sigma0.dim() == 2:
-            S0 = N.colsum(S0)
+        g0, S0 = sink.prior_grads()
         return (sink.gY if need[0] else None, sink.gU if need[1] else None, None, g_wih, g_whh, g_b, g_b, g_hw, g_hb,
                 gA, gB, gC, None, None, g0, S0, None, None)
 
@@ -710,7 +665,7 @@ def emission_means(mus_smooth, mus_filt, C_view, packed=None, c_off=None):
     prob = N.Problem()
     prob.B, prob.T, prob.n, prob.m, prob.p = Bsz, T, n, n, p
     keep, prob.C = _stack(C_view, Bsz, T, p, n, packed, c_off)
-    a_s, a_f = torch.empty(Bsz, T, p, device=ms.device, dtype=torch.float32), torch.empty(Bsz, T, p, device=ms.device, dtype=torch.float32)
+    a_s, a_f = _empty(ms.device, Bsz, T, p), _empty(ms.device, Bsz, T, p)
     lib = N.lib_for(ms)
     lib.check(lib.dll.kvae_lgssm_emission_means(C.byref(prob), N.ptr(ms), N.ptr(mf), N.ptr(a_s), N.ptr(a_f), N.stream_for(ms)),
               "kvae_lgssm_emission_means")
@@ -730,20 +685,6 @@ def rts_only(Y, U, mask, packed, A, Bm, Cm, Q, R, mu0, Sigma0, slots, mf, Sf, mp
 # ------------------------------------------------------------------------------------------------
 # generation: the closed-loop rollout of KVAE.generate (kvae_lgssm_generate, csrc/lgssm_gen.h)
 # ------------------------------------------------------------------------------------------------
-def safe_cholesky(Sigma, max_tries=5, jitter_init=1e-6):
-    """The reference's _safe_cholesky ladder (kalman_filter.py:282-303 there) over a batch [..., n, n]: symmetrise, add
-    jitter 1e-6 * 10^level until the WHOLE batch factorises (levels 0..4), else the clamped-diagonal fallback."""
-    Sigma = 0.5 * (Sigma + Sigma.mT)
-    eye = torch.eye(Sigma.shape[-1], device=Sigma.device, dtype=Sigma.dtype)
-    jitter = jitter_init
-    for _ in range(max_tries):
-        L, info = torch.linalg.cholesky_ex(Sigma + jitter * eye)
-        if not bool((info != 0).any()):
-            return L
-        jitter *= 10.0
-    return torch.diag_embed(torch.sqrt(torch.diagonal(Sigma, dim1=-2, dim2=-1).clamp(min=1e-6)))
-
-
 GEN_LSTM = dict(hidden=50, p=2)   # the alpha-network shape csrc/lgssm_gen.h holds in LDS
 
 
@@ -771,8 +712,7 @@ def rollout(kind, A, Bm, Cm, mu, L0, U, LQ, LR, S, H, lstm=None, h0=None, c0=Non
         return rollout_torch(kind, A, Bm, Cm, mu, L0, U, LQ, LR, S, H, lstm, h0, c0, y0, P, s0, eps0, eps_z, eps_a, gumbel)
     Bsz = mu.shape[0]
     dev = mu.device
-    mk = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
-    a, z, w = mk(Bsz, S, H, p), mk(Bsz, S, H, n), mk(Bsz, S, H, K)
+    a, z, w = _empty(dev, Bsz, S, H, p), _empty(dev, Bsz, S, H, n), _empty(dev, Bsz, S, H, K)
     keep = {}
     pr = N.GenProblem()
     pr.B, pr.S, pr.H, pr.n, pr.m, pr.p, pr.K = Bsz, S, H, n, m, p, K
@@ -792,57 +732,6 @@ def rollout(kind, A, Bm, Cm, mu, L0, U, LQ, LR, S, H, lstm=None, h0=None, c0=Non
     return a, z, w
 
 
-def rollout_torch(kind, A, Bm, Cm, mu, L0, U, LQ, LR, S, H, lstm=None, h0=None, c0=None, y0=None, P=None, s0=None,
-                  eps0=None, eps_z=None, eps_a=None, gumbel=None):
-    """The same recursion as csrc/lgssm_gen.h in torch ops, in the dtype of mu (fp32 on the product path): the shapes the
-    kernel is not built for (alpha-network hidden != 50 or a_dim != 2) - about fifteen launches per step."""
-    K = A.shape[0]
-    Bsz = mu.shape[0]
-    rep = lambda t: t.repeat_interleave(S, 0)
-    flat = lambda t: None if t is None else t.reshape(Bsz * S, *t.shape[2:]).to(mu.dtype)
-    eps0, eps_z, eps_a, gumbel = flat(eps0), flat(eps_z), flat(eps_a), flat(gumbel)
-    z = rep(mu)
-    if eps0 is not None:
-        z = z + (rep(L0) @ eps0.unsqueeze(-1)).squeeze(-1)
-    R = z.shape[0]
-    if kind == "switching":
-        s = rep(s0)
-    elif K == 1:
-        w = z.new_ones(R, 1)
-    else:
-        w_ih, w_hh, b_ih, b_hh, head_w, head_b = lstm
-        h, c, y = rep(h0), rep(c0), rep(y0)
-    a_out, z_out, w_out = [], [], []
-    for t in range(H):
-        if kind == "switching":
-            pi = s @ P
-            if gumbel is not None:
-                s = torch.nn.functional.one_hot((pi.log() + gumbel[:, t]).argmax(-1), K).to(pi.dtype)
-            else:
-                s = pi
-            w = s
-        elif K > 1:
-            gi, gf, gg, go = (y @ w_ih.T + h @ w_hh.T + b_ih + b_hh).chunk(4, -1)
-            c = torch.sigmoid(gf) * c + torch.sigmoid(gi) * torch.tanh(gg)
-            h = torch.sigmoid(go) * torch.tanh(c)
-            w = torch.softmax(h @ head_w.T + head_b, -1)
-        zn = torch.einsum("rk,kij,rj->ri", w, A, z)
-        if U is not None:
-            zn = zn + torch.einsum("rk,kij,rj->ri", w, Bm, rep(U[:, t]))
-        if eps_z is not None:
-            LQt = torch.einsum("rk,kij->rij", w, LQ) if kind == "switching" else LQ
-            zn = zn + (LQt @ eps_z[:, t].unsqueeze(-1)).squeeze(-1)
-        z = zn
-        a = Cm[0] @ z.unsqueeze(-1) if kind == "switching" else torch.einsum("rk,kij,rj->ri", w, Cm, z).unsqueeze(-1)
-        a = a.squeeze(-1)
-        if eps_a is not None:
-            a = a + (LR @ eps_a[:, t].unsqueeze(-1)).squeeze(-1)
-        y = a
-        a_out.append(a), z_out.append(z), w_out.append(w)
-    un = lambda lst: torch.stack(lst, 1).reshape(Bsz, S, H, -1)
-    return un(a_out), un(z_out), un(w_out)
-
-
 # ------------------------------------------------------------------------------------------------
 # joint posterior samples of latent paths (kvae_lgssm_posterior_sample, csrc/lgssm_post.h)
 # ------------------------------------------------------------------------------------------------
@@ -851,64 +740,6 @@ def posterior_supported(n, p, ref=None):
     if ref is not None and not (N.fused_ok(ref) and ref.dtype == torch.float32):
         return False
     return all(1 <= d <= N.KVAE_MAX_DIM for d in (n, p))
-
-
-def safe_cholesky_items(Sigma, max_tries=5, jitter_init=1e-6):
-    """The _safe_cholesky ladder applied PER ITEM of a batch [..., n, n]: (L, levels) with levels[...] the first level 0..4
-    (jitter 1e-6 * 10^level) at which that item factorises, 5 = its clamped-diagonal fallback.  No host sync."""
-    Sigma = 0.5 * (Sigma + Sigma.mT)
-    eye = torch.eye(Sigma.shape[-1], device=Sigma.device, dtype=Sigma.dtype)
-    L = torch.diag_embed(torch.sqrt(torch.diagonal(Sigma, dim1=-2, dim2=-1).clamp(min=1e-6)))
-    levels = torch.full(Sigma.shape[:-2], max_tries, device=Sigma.device, dtype=torch.int32)
-    jitter = jitter_init
-    for lv in range(max_tries):
-        Lv, info = torch.linalg.cholesky_ex(Sigma + jitter * eye)
-        take = (levels == max_tries) & (info == 0) & torch.isfinite(Lv).all(-1).all(-1)
-        L = torch.where(take[..., None, None], Lv, L)
-        levels = torch.where(take, torch.full_like(levels, lv), levels)
-        jitter *= 10.0
-    return L, levels
-
-
-def _bt(t, Bsz, T):
-    """[B,T,r,c] view of a per-step operand given as [r,c] or [B,T,r,c]."""
-    return t.expand(Bsz, T, *t.shape[-2:]) if t.dim() == 2 else t
-
-
-def posterior_paths_torch(mus_filt, Sigmas_filt, mus_pred, Sigmas_pred, A, Cm, Q, S, LR=None, eps=None, eta=None):
-    """The recursion of csrc/lgssm_post.h in torch ops, batched over B and S, in the dtype of mus_filt: for dtypes, devices and
-    shapes the kernels are not built for - several launches per time step.  Same arguments and returns as posterior_paths."""
-    mf = mus_filt.squeeze(-1) if mus_filt.dim() == 4 else mus_filt
-    mp = mus_pred.squeeze(-1) if mus_pred.dim() == 4 else mus_pred
-    dt = mf.dtype
-    Bsz, T, n = mf.shape
-    Sf, Sp = Sigmas_filt.to(dt), Sigmas_pred.to(dt)
-    A, Cm, Q = (_bt(t.to(dt), Bsz, T) for t in (A, Cm, Q))
-    eye = torch.eye(n, device=mf.device, dtype=dt)
-    J = torch.zeros(Bsz, T, n, n, device=mf.device, dtype=dt)
-    P = Sf.clone()
-    if T > 1:
-        An, Qn = A[:, 1:], Q[:, 1:]
-        Jt = torch.linalg.solve(Sp[:, 1:].mT, (Sf[:, :-1] @ An.mT).mT).mT
-        G = eye - Jt @ An
-        J[:, :-1] = Jt
-        P[:, :-1] = G @ Sf[:, :-1] @ G.mT + Jt @ Qn @ Jt.mT
-    L, levels = safe_cholesky_items(P)
-    c = mf.clone()
-    if T > 1:
-        c[:, :-1] = mf[:, :-1] - (J[:, :-1] @ mp[:, 1:].unsqueeze(-1)).squeeze(-1)
-    z = torch.zeros(Bsz, S, n, device=mf.device, dtype=dt)
-    zs = [None] * T
-    for t in range(T - 1, -1, -1):
-        z = c[:, t, None] + z @ J[:, t].mT
-        if eps is not None:
-            z = z + eps[:, :, t].to(dt) @ L[:, t].mT
-        zs[t] = z
-    z = torch.stack(zs, 2)
-    a = (Cm[:, None] @ z.unsqueeze(-1)).squeeze(-1)
-    if eta is not None:
-        a = a + eta.to(dt) @ LR.to(dt).mT
-    return z, a, levels
 
 
 def posterior_paths(mus_filt, Sigmas_filt, mus_pred, Sigmas_pred, A, Cm, Q, S, LR=None, eps=None, eta=None, packed=None,
@@ -925,7 +756,7 @@ def posterior_paths(mus_filt, Sigmas_filt, mus_pred, Sigmas_pred, A, Cm, Q, S, L
     use_kernel = impl == "kernel" or (impl is None and posterior_supported(n, p, Sigmas_filt))
     if not use_kernel:
         if packed is not None:
-            pick = lambda t, off, r, c: t if off is None else packed[..., off:off + r * c].unflatten(-1, (r, c))
+            pick = lambda t, off, r, c: t if off is None else slot_view(packed, off, r, c)
             A, Cm, Q = pick(A, slots.A, n, n), pick(Cm, slots.C, p, n), pick(Q, slots.Q, n, n)
         return posterior_paths_torch(mus_filt, Sigmas_filt, mus_pred, Sigmas_pred, A, Cm, Q, S, LR, eps, eta)
     call = PosteriorCall(mus_filt, Sigmas_filt, mus_pred, Sigmas_pred, A, Cm, Q, S, LR, eps, eta, packed, slots)
@@ -956,10 +787,9 @@ class PosteriorCall:
             setattr(pr, name, st)
         self.pr, self.dev, self.ref = pr, dev, Sf
         self.new_draws(LR=LR, eps=eps, eta=eta)
-        mk = lambda *s, dt=torch.float32: torch.empty(*s, device=dev, dtype=dt)
-        self.z, self.a, self.levels = mk(Bsz, S, T, n), mk(Bsz, S, T, p), mk(Bsz, T, dt=torch.int32)
+        self.z, self.a, self.levels = _empty(dev, Bsz, S, T, n), _empty(dev, Bsz, S, T, p), _empty(dev, Bsz, T, dt=torch.int32)
         self.lib = N.lib_for(Sf)
-        self.ws = mk(int(self.lib.dll.kvae_lgssm_posterior_sample_ws_floats(C.byref(pr))))
+        self.ws = _empty(dev, int(self.lib.dll.kvae_lgssm_posterior_sample_ws_floats(C.byref(pr))))
         pr.z_out, pr.a_out, pr.levels_out, pr.ws = self.z.data_ptr(), self.a.data_ptr(), self.levels.data_ptr(), self.ws.data_ptr()
 
     def new_draws(self, LR=None, eps=None, eta=None):
@@ -978,10 +808,6 @@ class PosteriorCall:
 # ------------------------------------------------------------------------------------------------
 # predictive density of the latents (kvae_lgssm_predictive, csrc/lgssm_pred.h)
 # ------------------------------------------------------------------------------------------------
-_PRED_OUTPUTS = ("ll", "nis", "a_pred", "S", "levels", "seq_ll")
-_LOG_2PI = 1.8378770664093453
-
-
 def predictive_supported(n, p, ref=None):
     """Shapes / tensors kvae_lgssm_predictive is built for (include/kvae_lgssm.h: fp32, p == 2, n <= 16); the rest takes
     predictive_torch."""
@@ -990,91 +816,6 @@ def predictive_supported(n, p, ref=None):
     return p == 2 and 1 <= n <= N.KVAE_MAX_DIM
 
 
-def _pred_want(want):
-    want = (want,) if isinstance(want, str) else tuple(want)
-    bad = [w for w in want if w not in _PRED_OUTPUTS]
-    if bad or not want:
-        raise ValueError(f"predictive: want must name some of {_PRED_OUTPUTS}, got {want}")
-    return want
-
-
-def predictive_torch(mus_pred, Sigmas_pred, Cm, R, Y, mask=None, want=_PRED_OUTPUTS):
-    """The equations of kvae_lgssm_predictive in torch ops, batched over (b, t), in the dtype of Sigmas_pred: other a_dim than 2,
-    non-fp32 and host tensors, and (in float64) the reference the kernel is tested against.  The factor of S_t is found by the
-    per-item ladder (safe_cholesky_items).  Same arguments and returns as predictive (without packed / slots)."""
-    want = _pred_want(want)
-    mp = mus_pred.squeeze(-1) if mus_pred.dim() == 4 else mus_pred
-    dt = Sigmas_pred.dtype
-    Bsz, T, n = mp.shape
-    p = Cm.shape[-2]
-    mp, Cm, R, Y = mp.to(dt), _bt(Cm.to(dt), Bsz, T), R.to(dt), Y.to(dt)
-    a_pred = (Cm @ mp.unsqueeze(-1)).squeeze(-1)
-    S = Cm @ Sigmas_pred @ Cm.mT + R
-    S = 0.5 * (S + S.mT)
-    L, levels = safe_cholesky_items(S)
-    w = torch.linalg.solve_triangular(L, (Y - a_pred).unsqueeze(-1), upper=False).squeeze(-1)
-    nis = (w * w).sum(-1)
-    logdet = 2.0 * torch.log(torch.diagonal(L, dim1=-2, dim2=-1)).sum(-1)
-    ll = -0.5 * (nis + logdet + p * _LOG_2PI)
-    if mask is not None:
-        observed = mask.to(device=ll.device).reshape(Bsz, T) != 0
-        ll, nis = torch.where(observed, ll, torch.zeros_like(ll)), torch.where(observed, nis, torch.zeros_like(nis))
-    full = {"ll": ll, "nis": nis, "a_pred": a_pred, "S": S, "levels": levels, "seq_ll": ll.sum(1)}
-    return {k: (v if k in want else None) for k, v in full.items()}
-
-
-@torch.no_grad()
-def predictive(mus_pred, Sigmas_pred, Cm, R, Y, mask=None, packed=None, slots=Slots(), want=_PRED_OUTPUTS, impl=None):
-    """log p(a_t | a_{0:t-1}, u) of every step from the filter's one-step-ahead beliefs (semantics: include/kvae_lgssm.h,
-    kvae_lgssm_predictive; DESIGN.md section 12).  mus_pred [B,T,n] (or [B,T,n,1]), Sigmas_pred [B,T,n,n]; Cm [p,n] | [B,T,p,n],
-    or the C slot of the packed step record `packed` [B,T,E] at the float offset slots.C (Cm is still read for p); R [p,p];
-    Y [B,T,p]; mask [B,T] (1 = observed) or None.  want: which of "ll", "nis", "a_pred", "S", "levels", "seq_ll" to compute.
-    Returns a dict: ll [B,T], nis [B,T] (both 0 on hidden steps), a_pred [B,T,p], S [B,T,p,p], levels [B,T] (int32: the ladder
-    level of chol(S_t), 5 = clamped diagonal), seq_ll [B] = sum_t ll; entries not asked for are None.  Two launches, no host
-    synchronisation.  impl: None = the HIP kernels where built (fp32, p == 2), else predictive_torch; "kernel" / "torch" force one."""
-    want = _pred_want(want)
-    n = Sigmas_pred.shape[-1]
-    Bsz, T = Sigmas_pred.shape[:2]
-    p = Cm.shape[-2]
-    use_kernel = impl == "kernel" or (impl is None and predictive_supported(n, p, Sigmas_pred))
-    if not use_kernel:
-        if packed is not None and slots.C is not None:
-            Cm = packed[..., slots.C:slots.C + p * n].unflatten(-1, (p, n))
-        return predictive_torch(mus_pred, Sigmas_pred, Cm, R, Y, mask, want)
-    dev = Sigmas_pred.device
-    mp = _f32c((mus_pred.squeeze(-1) if mus_pred.dim() == 4 else mus_pred).detach())
-    Sp, R, Y = _f32c(Sigmas_pred.detach()), _f32c(R.detach().to(dev)), _f32c(Y.detach())
-    mask = None if mask is None else _f32c(mask.detach().to(dev).reshape(Bsz, T))
-    packed = _f32c(packed.detach()) if packed is not None else None
-    pr = N.PredProblem()
-    pr.B, pr.T, pr.n, pr.p = Bsz, T, n, p
-    pr.mus_pred, pr.Sigmas_pred, pr.R, pr.y, pr.mask = mp.data_ptr(), Sp.data_ptr(), R.data_ptr(), Y.data_ptr(), N.ptr(mask)
-    keep, pr.C = _stack(Cm.detach() if slots.C is None else Cm, Bsz, T, p, n, packed, slots.C)
-    mk = lambda *s, dt=torch.float32: torch.empty(*s, device=dev, dtype=dt)
-    out = {k: None for k in _PRED_OUTPUTS}
-    ll = mk(Bsz, T) if ("ll" in want or "seq_ll" in want) else None   # the sequence sums read ll
-    out["ll"] = ll if "ll" in want else None
-    if "nis" in want:
-        out["nis"] = mk(Bsz, T)
-    if "a_pred" in want:
-        out["a_pred"] = mk(Bsz, T, p)
-    if "S" in want:
-        out["S"] = mk(Bsz, T, p, p)
-    if "levels" in want:
-        out["levels"] = mk(Bsz, T, dt=torch.int32)
-    if "seq_ll" in want:
-        out["seq_ll"] = mk(Bsz)
-    pr.ll, pr.nis, pr.a_pred, pr.S_out = N.ptr(ll), N.ptr(out["nis"]), N.ptr(out["a_pred"]), N.ptr(out["S"])
-    pr.levels, pr.seq_ll = N.ptr(out["levels"]), N.ptr(out["seq_ll"])
-    lib = N.lib_for(Sp)
-    lib.check(N.timed("predictive", Sp, lambda: lib.dll.kvae_lgssm_predictive(C.byref(pr), N.stream_for(Sp))), "kvae_lgssm_predictive")
-    del keep
-    return out
-
-
-# ------------------------------------------------------------------------------------------------
-# log p(a | u), differentiable (kvae_lgssm_predictive + kvae_lgssm_predictive_bwd, csrc/lgssm_pred.h)
-# ------------------------------------------------------------------------------------------------
 def _pred_problem(mp, Sp, Cm, packed, R, Y, mask, slots):
     """(kvae_pred_problem, tensors to keep alive) over contiguous fp32 inputs; the output pointers are left NULL."""
     Bsz, T, n = mp.shape
@@ -1086,6 +827,44 @@ def _pred_problem(mp, Sp, Cm, packed, R, Y, mask, slots):
     return pr, (mp, Sp, R, Y, mask, keep)
 
 
+@torch.no_grad()
+def predictive(mus_pred, Sigmas_pred, Cm, R, Y, mask=None, packed=None, slots=Slots(), want=_PRED_OUTPUTS, impl=None):
+    """log p(a_t | a_{0:t-1}, u) of every step from the filter's one-step-ahead beliefs (semantics: include/kvae_lgssm.h,
+    kvae_lgssm_predictive; DESIGN.md section 12).  mus_pred [B,T,n] (or [B,T,n,1]), Sigmas_pred [B,T,n,n]; Cm [p,n] | [B,T,p,n],
+    or the C slot of the packed step record `packed` [B,T,E] at the float offset slots.C (Cm is still read for p); R [p,p];
+    Y [B,T,p]; mask [B,T] (1 = observed) or None.  want: which of "ll", "nis", "a_pred", "S", "levels", "seq_ll" to compute.
+    Returns a dict: ll [B,T], nis [B,T] (both 0 on hidden steps), a_pred [B,T,p], S [B,T,p,p], levels [B,T] (int32: the ladder
+    level of chol(S_t), 5 = clamped diagonal), seq_ll [B] = sum_t ll; entries not asked for are None.  Two launches, no host
+    synchronisation.  impl: None = the HIP kernels where built (fp32, p == 2), else predictive_torch; "kernel" / "torch" force one."""
+    want = _want("predictive", _PRED_OUTPUTS, want)
+    n = Sigmas_pred.shape[-1]
+    Bsz, T = Sigmas_pred.shape[:2]
+    p = Cm.shape[-2]
+    use_kernel = impl == "kernel" or (impl is None and predictive_supported(n, p, Sigmas_pred))
+    if not use_kernel:
+        if packed is not None and slots.C is not None:
+            Cm = slot_view(packed, slots.C, p, n)
+        return predictive_torch(mus_pred, Sigmas_pred, Cm, R, Y, mask, want)
+    dev = Sigmas_pred.device
+    mp = _f32c((mus_pred.squeeze(-1) if mus_pred.dim() == 4 else mus_pred).detach())
+    Sp, R, Y = _f32c(Sigmas_pred.detach()), _f32c(R.detach().to(dev)), _f32c(Y.detach())
+    mask = None if mask is None else _f32c(mask.detach().to(dev).reshape(Bsz, T))
+    packed = _f32c(packed.detach()) if packed is not None else None
+    pr, keep = _pred_problem(mp, Sp, Cm.detach() if slots.C is None else Cm, packed, R, Y, mask, slots)
+    out = _wanted(dev, _PRED_OUTPUTS, want, dict(nis=(Bsz, T), a_pred=(Bsz, T, p), S=(Bsz, T, p, p), levels=(Bsz, T), seq_ll=(Bsz,)))
+    ll = _empty(dev, Bsz, T) if ("ll" in want or "seq_ll" in want) else None   # the sequence sums read ll
+    out["ll"] = ll if "ll" in want else None
+    pr.ll, pr.nis, pr.a_pred, pr.S_out = N.ptr(ll), N.ptr(out["nis"]), N.ptr(out["a_pred"]), N.ptr(out["S"])
+    pr.levels, pr.seq_ll = N.ptr(out["levels"]), N.ptr(out["seq_ll"])
+    lib = N.lib_for(Sp)
+    lib.check(N.timed("predictive", Sp, lambda: lib.dll.kvae_lgssm_predictive(C.byref(pr), N.stream_for(Sp))), "kvae_lgssm_predictive")
+    del keep
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# log p(a | u), differentiable (kvae_lgssm_predictive + kvae_lgssm_predictive_bwd, csrc/lgssm_pred.h)
+# ------------------------------------------------------------------------------------------------
 class PredictiveLogLik(torch.autograd.Function):
     """(ll [B,T], seq_ll [B], levels [B,T]) of kvae_lgssm_predictive with the adjoint kvae_lgssm_predictive_bwd: one call each
     way.  Gradients for mus_pred, Sigmas_pred, Cm (or `packed`: a zero-filled record with the C slot written) and Y; a shared
@@ -1098,9 +877,7 @@ class PredictiveLogLik(torch.autograd.Function):
         Bsz, T, _ = mp.shape
         dev = Sp.device
         pr, keep = _pred_problem(mp, Sp, Cm, pk, Rc, Yc, mk, slots)
-        ll = torch.empty(Bsz, T, device=dev, dtype=torch.float32)
-        seq = torch.empty(Bsz, device=dev, dtype=torch.float32)
-        levels = torch.empty(Bsz, T, device=dev, dtype=torch.int32)
+        ll, seq, levels = _empty(dev, Bsz, T), _empty(dev, Bsz), _empty(dev, Bsz, T, dt=torch.int32)
         pr.ll, pr.seq_ll, pr.levels = ll.data_ptr(), seq.data_ptr(), levels.data_ptr()
         lib = N.lib_for(Sp)
         lib.check(N.timed("predictive", Sp, lambda: lib.dll.kvae_lgssm_predictive(C.byref(pr), N.stream_for(Sp))), "kvae_lgssm_predictive")
@@ -1137,55 +914,14 @@ class PredictiveLogLik(torch.autograd.Function):
                 E = pk.shape[-1]
                 g.gC = N.Stack(g_packed.data_ptr() + 4 * slots.C, T * E, E)
         elif need[2]:
-            g_Cbuf = torch.empty(Bsz, T, p, n, device=dev, dtype=torch.float32)
+            g_Cbuf = _empty(dev, Bsz, T, p, n)
             g.gC = N.Stack(g_Cbuf.data_ptr(), T * p * n, p * n)
         lib = N.lib_for(Sp)
         lib.check(N.timed("predictive_bwd", Sp, lambda: lib.dll.kvae_lgssm_predictive_bwd(C.byref(pr), C.byref(g), N.stream_for(Sp))),
                   "kvae_lgssm_predictive_bwd")
         del keep
-        gC = None
-        if g_Cbuf is not None:   # reduced to the shape the caller passed in, as _GradSink.operand_grad
-            if Cm.dim() == 2:
-                gC = g_Cbuf.sum((0, 1))
-            else:
-                gC = g_Cbuf.sum_to_size(Cm.shape) if tuple(Cm.shape) != tuple(g_Cbuf.shape) else g_Cbuf
+        gC = _reduce_to(g_Cbuf, Cm) if g_Cbuf is not None else None
         return (g_mp.reshape(mus_pred.shape) if g_mp is not None else None, g_Sp, gC, g_packed, None, gY, None, None)
-
-
-def log_marginal_torch(mus_pred, Sigmas_pred, Cm, R, Y, mask=None):
-    """log_marginal in torch ops, differentiable, in the dtype of Sigmas_pred: other a_dim than 2, non-fp32 and host tensors, and
-    (in float64) the reference the adjoint kernel is tested against.  The values are predictive_torch's.  Nothing is
-    differentiated through safe_cholesky_items (its torch.where over failed cholesky_ex attempts turns into NaN * 0 in the
-    backward): the levels are found without a tape, then S + jitter[level] I - for level-5 items the clamped diagonal matrix - is
-    factorised once."""
-    mp = mus_pred.squeeze(-1) if mus_pred.dim() == 4 else mus_pred
-    dt = Sigmas_pred.dtype
-    Bsz, T, n = mp.shape
-    p = Cm.shape[-2]
-    mp, Cm, R, Y = mp.to(dt), _bt(Cm.to(dt), Bsz, T), R.to(dt), Y.to(dt)
-    a_pred = (Cm @ mp.unsqueeze(-1)).squeeze(-1)
-    S = Cm @ Sigmas_pred @ Cm.mT + R
-    S = 0.5 * (S + S.mT)
-    with torch.no_grad():
-        _, levels = safe_cholesky_items(S)
-    jit, j = [], 1e-6
-    for _ in range(5):
-        jit.append(j)
-        j *= 10.0
-    jitter = torch.tensor(jit + [0.0], device=S.device, dtype=torch.float64)[levels.long()]
-    eye = torch.eye(p, device=S.device, dtype=dt)
-    St = S + (jitter[..., None, None] * eye.double()).to(dt)
-    clamped = torch.diag_embed(torch.diagonal(S, dim1=-2, dim2=-1).clamp(min=1e-6))
-    St = torch.where((levels == 5)[..., None, None], clamped, St)
-    L = torch.linalg.cholesky(St)
-    w = torch.linalg.solve_triangular(L, (Y - a_pred).unsqueeze(-1), upper=False).squeeze(-1)
-    nis = (w * w).sum(-1)
-    logdet = 2.0 * torch.log(torch.diagonal(L, dim1=-2, dim2=-1)).sum(-1)
-    ll = -0.5 * (nis + logdet + p * _LOG_2PI)
-    if mask is not None:
-        observed = mask.to(device=ll.device).reshape(Bsz, T) != 0
-        ll = torch.where(observed, ll, torch.zeros_like(ll))
-    return {"ll": ll, "seq_ll": ll.sum(1), "levels": levels}
 
 
 def log_marginal(mus_pred, Sigmas_pred, Cm, R, Y, mask=None, packed=None, slots=Slots(), impl=None):
@@ -1200,7 +936,7 @@ def log_marginal(mus_pred, Sigmas_pred, Cm, R, Y, mask=None, packed=None, slots=
     use_kernel = impl == "kernel" or (impl is None and predictive_supported(n, p, Sigmas_pred))
     if not use_kernel:
         if packed is not None and slots.C is not None:
-            Cm = packed[..., slots.C:slots.C + p * n].unflatten(-1, (p, n))
+            Cm = slot_view(packed, slots.C, p, n)
         return log_marginal_torch(mus_pred, Sigmas_pred, Cm, R, Y, mask)
     dev = Sigmas_pred.device
     mp = mus_pred.squeeze(-1) if mus_pred.dim() == 4 else mus_pred
@@ -1213,7 +949,6 @@ def log_marginal(mus_pred, Sigmas_pred, Cm, R, Y, mask=None, packed=None, slots=
 # ------------------------------------------------------------------------------------------------
 # causal switching Kalman filter, GPB2 (kvae_lgssm_switching_filter, csrc/lgssm_swf.h)
 # ------------------------------------------------------------------------------------------------
-_SWF_OUTPUTS = ("regime_filt", "regime_pred", "log_lik", "log_lik_seq", "a_pred", "S", "mus_filt", "Sigmas_filt", "levels", "state")
 SWF_SUPPORTED = dict(max_K=8, max_n=4, max_m=4, p=2)
 
 
@@ -1224,103 +959,6 @@ def switching_filter_supported(K, n, m, p, ref=None):
         return False
     s = SWF_SUPPORTED
     return 1 <= K <= s["max_K"] and 1 <= n <= s["max_n"] and 1 <= m <= s["max_m"] and p == s["p"]
-
-
-def _swf_want(want):
-    want = (want,) if isinstance(want, str) else tuple(want)
-    bad = [w for w in want if w not in _SWF_OUTPUTS]
-    if bad or not want:
-        raise ValueError(f"switching_filter: want must name some of {_SWF_OUTPUTS}, got {want}")
-    return want
-
-
-def _swf_state(state, Bsz, K, n):
-    if state is None:
-        return None
-    lw, mu, Sig = state["log_w"], state["mu"], state["Sigma"]
-    if lw.shape != (Bsz, K) or mu.shape != (Bsz, K, n) or Sig.shape != (Bsz, K, n, n):
-        raise ValueError(f"switching_filter: state must hold log_w [{Bsz},{K}], mu [{Bsz},{K},{n}], Sigma [{Bsz},{K},{n},{n}], got "
-                         f"{tuple(lw.shape)}, {tuple(mu.shape)}, {tuple(Sig.shape)}")
-    return lw, mu, Sig
-
-
-@torch.no_grad()
-def switching_filter_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, state=None, want=_SWF_OUTPUTS):
-    """The equations of kvae_lgssm_switching_filter (include/kvae_lgssm.h) in torch ops, vectorised over (B, i, j), in the dtype of
-    A: shapes outside the kernel's, non-fp32 and host tensors, and (in float64) the reference the kernel is tested against.
-    T steps of about thirty small launches.  Same arguments and returns as switching_filter."""
-    want = _swf_want(want)
-    dt, dev = A.dtype, Y.device
-    K, n = A.shape[0], A.shape[1]
-    Bsz, T, p = Y.shape
-    A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U = (t.detach().to(device=dev, dtype=dt) for t in (A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U))
-    mask = None if mask is None else mask.detach().to(device=dev, dtype=dt).reshape(Bsz, T)
-    st = _swf_state(state, Bsz, K, n)
-    if st is None:
-        lw = torch.full((Bsz, K), 1.0 / K, device=dev, dtype=dt).log()
-        mu, Sig = mu0.expand(Bsz, K, n), Sigma0.expand(Bsz, K, n, n)
-    else:
-        lw, mu, Sig = (t.detach().to(device=dev, dtype=dt) for t in st)
-    eye = torch.eye(n, device=dev, dtype=dt)
-    eyeK = torch.eye(K, device=dev, dtype=dt)
-    uniform = torch.full((K, K), 1.0 / K, device=dev, dtype=dt)
-    ninf = torch.full((), -float("inf"), device=dev, dtype=dt)
-    outs = {k: [] for k in ("regime_filt", "regime_pred", "log_lik", "a_pred", "S", "mus_filt", "Sigmas_filt", "levels")}
-    for t in range(T):
-        Pt = uniform if (t == 0 and st is None) else P
-        mk = torch.ones(Bsz, device=dev, dtype=dt) if mask is None else mask[:, t]
-        observed = mk != 0
-        # ---- the K^2 filter steps: [B, i, j, ...] ----
-        mp = torch.einsum("jrc,bic->bijr", A, mu) + torch.einsum("jrc,bc->bjr", Bm, U[:, t]).unsqueeze(1)
-        Sp = torch.einsum("jre,biec,jdc->bijrd", A, Sig, A) + Q
-        ap = mp @ Cm.mT
-        res = Y[:, t, None, None, :] - ap
-        S = Cm @ Sp @ Cm.mT + R
-        S = 0.5 * (S + S.mT)
-        L, lv = safe_cholesky_items(S)
-        wv = torch.linalg.solve_triangular(L, res.unsqueeze(-1), upper=False).squeeze(-1)
-        logdet = 2.0 * torch.log(torch.diagonal(L, dim1=-2, dim2=-1)).sum(-1)
-        lij = -0.5 * ((wv * wv).sum(-1) + logdet + p * _LOG_2PI)
-        lij = torch.where(observed[:, None, None], lij, torch.zeros_like(lij))
-        Kg = torch.linalg.solve(S, Cm @ Sp).mT * mk[:, None, None, None, None]      # S^-1 (Sigma_pred C^T)^T, transposed
-        muf = mp + (Kg @ res.unsqueeze(-1)).squeeze(-1)
-        IKC = eye - Kg @ Cm
-        Sf = IKC @ Sp @ IKC.mT + Kg @ R @ Kg.mT
-        Sf = 0.5 * (Sf + Sf.mT)
-        # ---- weights ----
-        logc = lw.unsqueeze(-1) + Pt.log() + lij                                     # [B, i, j]
-        pw = lw.exp().unsqueeze(-1) * Pt
-        cmx = logc.amax(1)                                                           # [B, j]
-        dead = cmx == ninf
-        ex = torch.where(dead.unsqueeze(1), eyeK.expand(Bsz, K, K), (logc - torch.where(dead, torch.zeros_like(cmx), cmx).unsqueeze(1)).exp())
-        se = ex.sum(1)
-        W = ex / se.unsqueeze(1)
-        mx = cmx.amax(-1, keepdim=True)
-        tot = mx.squeeze(-1) + (se * (cmx - mx).exp()).sum(-1).log()
-        lw = (cmx + se.log()) - tot.unsqueeze(-1)
-        rf = lw.exp()
-        # ---- collapse over i ----
-        mu = (W.unsqueeze(-1) * muf).sum(1)                                          # [B, j, n]
-        d = muf - mu.unsqueeze(1)
-        Sig = (W[..., None, None] * (Sf + d.unsqueeze(-1) * d.unsqueeze(-2))).sum(1)
-        Sig = 0.5 * (Sig + Sig.mT)
-        # ---- outputs of the step ----
-        outs["regime_pred"].append(pw.sum(1))
-        outs["regime_filt"].append(rf)
-        outs["log_lik"].append(torch.where(observed, tot, torch.zeros_like(tot)))
-        outs["levels"].append(torch.where(pw > 0, lv, torch.zeros_like(lv)).amax((1, 2)))
-        a = (pw.unsqueeze(-1) * ap).sum((1, 2))
-        e = ap - a[:, None, None, :]
-        outs["a_pred"].append(a)
-        outs["S"].append((pw[..., None, None] * (S + e.unsqueeze(-1) * e.unsqueeze(-2))).sum((1, 2)))
-        m_ = (rf.unsqueeze(-1) * mu).sum(1)
-        dd = mu - m_.unsqueeze(1)
-        outs["mus_filt"].append(m_)
-        outs["Sigmas_filt"].append((rf[..., None, None] * (Sig + dd.unsqueeze(-1) * dd.unsqueeze(-2))).sum(1))
-    full = {k: torch.stack(v, 1) for k, v in outs.items()}
-    full["log_lik_seq"] = full["log_lik"].sum(1)
-    full["state"] = {"log_w": lw, "mu": mu, "Sigma": Sig}
-    return {k: (full[k] if k in want else None) for k in _SWF_OUTPUTS}
 
 
 @torch.no_grad()
@@ -1334,7 +972,7 @@ def switching_filter(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, want=_SWF
     "state" (dict log_w [B,K], mu [B,K,n], Sigma [B,K,n,n] after the last step) to compute; entries not asked for are None.
     One launch for the sweep (one more for log_lik_seq), no host synchronisation, no gradients.
     impl: None = the HIP kernel where it is built (switching_filter_supported), else switching_filter_torch; "hip" / "torch" force one."""
-    want = _swf_want(want)
+    want = _want("switching_filter", _SWF_OUTPUTS, want)
     if impl not in (None, "hip", "torch"):
         raise ValueError(f"switching_filter: impl must be None, 'hip' or 'torch', got {impl!r}")
     K, n, m = A.shape[0], A.shape[1], Bm.shape[2]
@@ -1352,19 +990,12 @@ def switching_filter(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, want=_SWF
     st = _swf_state(state, Bsz, K, n)
     if st is not None:
         st = tuple(_f32c(t.detach().to(dev)) for t in st)
-    mk = lambda *s, dt=torch.float32: torch.empty(*s, device=dev, dtype=dt)
-    out = {k: None for k in _SWF_OUTPUTS}
-    ll = mk(Bsz, T) if ("log_lik" in want or "log_lik_seq" in want) else None   # the sequence sums read log_lik
+    out = _wanted(dev, _SWF_OUTPUTS, want, dict(regime_filt=(Bsz, T, K), regime_pred=(Bsz, T, K), log_lik_seq=(Bsz,), a_pred=(Bsz, T, p),
+                                                S=(Bsz, T, p, p), mus_filt=(Bsz, T, n), Sigmas_filt=(Bsz, T, n, n), levels=(Bsz, T)))
+    ll = _empty(dev, Bsz, T) if ("log_lik" in want or "log_lik_seq" in want) else None   # the sequence sums read log_lik
     out["log_lik"] = ll if "log_lik" in want else None
-    shapes = dict(regime_filt=(Bsz, T, K), regime_pred=(Bsz, T, K), log_lik_seq=(Bsz,), a_pred=(Bsz, T, p), S=(Bsz, T, p, p),
-                  mus_filt=(Bsz, T, n), Sigmas_filt=(Bsz, T, n, n))
-    for k, s in shapes.items():
-        if k in want:
-            out[k] = mk(*s)
-    if "levels" in want:
-        out["levels"] = mk(Bsz, T, dt=torch.int32)
     if "state" in want:
-        out["state"] = {"log_w": mk(Bsz, K), "mu": mk(Bsz, K, n), "Sigma": mk(Bsz, K, n, n)}
+        out["state"] = {"log_w": _empty(dev, Bsz, K), "mu": _empty(dev, Bsz, K, n), "Sigma": _empty(dev, Bsz, K, n, n)}
     pr = N.SwfProblem()
     pr.B, pr.T, pr.K, pr.n, pr.m, pr.p = Bsz, T, K, n, m, p
     pr.A, pr.Bm, pr.Q, pr.C, pr.R, pr.P = (t.data_ptr() for t in (A, Bm, Q, Cm, R, P))

@@ -1,0 +1,332 @@
+"""The LGSSM read-outs of lgssm_ops restated in plain torch ops: what the dispatchers there fall back to for dtypes, devices and
+shapes the HIP kernels are not built for, and (in float64) the references the kernels are tested against.  Nothing here touches
+the native library: the module imports without it.  lgssm_ops re-exports every name, which is where callers take them from.
+"""
+import torch
+
+_DECODE_OUTPUTS = ("marginals", "path", "kl")
+_PRED_OUTPUTS = ("ll", "nis", "a_pred", "S", "levels", "seq_ll")
+_LOG_2PI = 1.8378770664093453
+_SWF_OUTPUTS = ("regime_filt", "regime_pred", "log_lik", "log_lik_seq", "a_pred", "S", "mus_filt", "Sigmas_filt", "levels", "state")
+
+
+def _want(op, outputs, want):
+    """`want` (one name or several) of the read-out `op` as a tuple, checked against the `outputs` it can compute."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    bad = [w for w in want if w not in outputs]
+    if bad or not want:
+        raise ValueError(f"{op}: want must name some of {outputs}, got {want}")
+    return want
+
+
+def _jitter_ladder(max_tries=5, jitter_init=1e-6):
+    """The jitters 1e-6 * 10^level of the _safe_cholesky ladder as Python doubles, by the reference's repeated `*= 10.0`
+    (10 ** level gives other doubles)."""
+    jitter = jitter_init
+    for _ in range(max_tries):
+        yield jitter
+        jitter *= 10.0
+
+
+def safe_cholesky(Sigma, max_tries=5, jitter_init=1e-6):
+    """The reference's _safe_cholesky ladder (kalman_filter.py:282-303 there) over a batch [..., n, n]: symmetrise, add
+    jitter 1e-6 * 10^level until the WHOLE batch factorises (levels 0..4), else the clamped-diagonal fallback."""
+    Sigma = 0.5 * (Sigma + Sigma.mT)
+    eye = torch.eye(Sigma.shape[-1], device=Sigma.device, dtype=Sigma.dtype)
+    for jitter in _jitter_ladder(max_tries, jitter_init):
+        L, info = torch.linalg.cholesky_ex(Sigma + jitter * eye)
+        if not bool((info != 0).any()):
+            return L
+    return torch.diag_embed(torch.sqrt(torch.diagonal(Sigma, dim1=-2, dim2=-1).clamp(min=1e-6)))
+
+
+def safe_cholesky_items(Sigma, max_tries=5, jitter_init=1e-6):
+    """The _safe_cholesky ladder applied PER ITEM of a batch [..., n, n]: (L, levels) with levels[...] the first level 0..4
+    (jitter 1e-6 * 10^level) at which that item factorises, 5 = its clamped-diagonal fallback.  No host sync."""
+    Sigma = 0.5 * (Sigma + Sigma.mT)
+    eye = torch.eye(Sigma.shape[-1], device=Sigma.device, dtype=Sigma.dtype)
+    L = torch.diag_embed(torch.sqrt(torch.diagonal(Sigma, dim1=-2, dim2=-1).clamp(min=1e-6)))
+    levels = torch.full(Sigma.shape[:-2], max_tries, device=Sigma.device, dtype=torch.int32)
+    for lv, jitter in enumerate(_jitter_ladder(max_tries, jitter_init)):
+        Lv, info = torch.linalg.cholesky_ex(Sigma + jitter * eye)
+        take = (levels == max_tries) & (info == 0) & torch.isfinite(Lv).all(-1).all(-1)
+        L = torch.where(take[..., None, None], Lv, L)
+        levels = torch.where(take, torch.full_like(levels, lv), levels)
+    return L, levels
+
+
+def _bt(t, Bsz, T):
+    """[B,T,r,c] view of a per-step operand given as [r,c] or [B,T,r,c]."""
+    return t.expand(Bsz, T, *t.shape[-2:]) if t.dim() == 2 else t
+
+
+def _innovation(mus_pred, Sigmas_pred, Cm, R, Y, mask):
+    """What predictive_torch and log_marginal_torch share, in the dtype of Sigmas_pred: the forecast a_pred = C mu_pred [B,T,p], its
+    covariance S = C Sigma_pred C^T + R (symmetrised), the residual Y - a_pred and the observed steps [B,T] (bool, None = all)."""
+    mp = mus_pred.squeeze(-1) if mus_pred.dim() == 4 else mus_pred
+    dt = Sigmas_pred.dtype
+    Bsz, T, n = mp.shape
+    mp, Cm, R, Y = mp.to(dt), _bt(Cm.to(dt), Bsz, T), R.to(dt), Y.to(dt)
+    a_pred = (Cm @ mp.unsqueeze(-1)).squeeze(-1)
+    S = Cm @ Sigmas_pred @ Cm.mT + R
+    S = 0.5 * (S + S.mT)
+    observed = None if mask is None else mask.to(device=S.device).reshape(Bsz, T) != 0
+    return a_pred, S, Y - a_pred, observed
+
+
+def _gauss_ll(L, res):
+    """(ll, nis) of the residuals res [..., p] under N(0, L L^T): nis = |L^-1 res|^2, ll = -(nis + log det + p log 2 pi) / 2."""
+    w = torch.linalg.solve_triangular(L, res.unsqueeze(-1), upper=False).squeeze(-1)
+    nis = (w * w).sum(-1)
+    logdet = 2.0 * torch.log(torch.diagonal(L, dim1=-2, dim2=-1)).sum(-1)
+    return -0.5 * (nis + logdet + L.shape[-1] * _LOG_2PI), nis
+
+
+def _observed_only(v, observed):
+    """v with zeros where `observed` (bool, broadcast against v; None = everything observed) is False."""
+    return v if observed is None else torch.where(observed, v, torch.zeros_like(v))
+
+
+def regime_decode_torch(logits, init_logits, P, want=_DECODE_OUTPUTS):
+    """The equations of kvae_regime_decode in torch ops, in the dtype of the logits: K > 16 and non-fp32 tensors, and (in float64)
+    the reference the kernel is tested against.  Ties take the lowest index, in every backpointer and in the final argmax
+    (an argmax over (value == max), whose first hit torch returns).  T - 1 iterations of about ten small launches."""
+    want = _want("regime_decode", _DECODE_OUTPUTS, want)
+    Bsz, T, K, _ = logits.shape
+    dt = logits.dtype
+    init_logits, P = init_logits.to(dt), P.to(device=logits.device, dtype=dt)
+    first = lambda v: (v == v.max(-1, keepdim=True).values).to(torch.int8).argmax(-1)   # lowest index among the maxima
+    ls0 = torch.log_softmax(init_logits, -1)
+    m, d = torch.softmax(init_logits, -1), ls0
+    log_p = torch.log(P.clamp_min(1e-8))
+    ms, kls, bps = [m], [(m * (ls0 - torch.full_like(ls0, 1.0 / K).log())).sum(-1)], []
+    for t in range(1, T):
+        lq = torch.log_softmax(logits[:, t], -1)              # [B, i, j]
+        Q = torch.softmax(logits[:, t], -1)
+        if "marginals" in want or "kl" in want:
+            kls.append((m * (Q * (lq - log_p)).sum(-1)).sum(-1))
+            m = torch.einsum("bi,bij->bj", m, Q)
+            ms.append(m)
+        if "path" in want:
+            cand = (d.unsqueeze(-1) + lq).transpose(1, 2)      # [B, j, i]
+            bps.append(first(cand))
+            d = cand.max(-1).values
+    out = {"marginals": None, "path": None, "path_logq": None, "kl": None}
+    if "marginals" in want:
+        out["marginals"] = torch.stack(ms, 1)
+    if "kl" in want:
+        out["kl"] = torch.stack(kls, 1)
+    if "path" in want:
+        out["path_logq"] = d.max(-1).values
+        s = first(d)
+        path = [s]
+        for bp in reversed(bps):
+            s = bp.gather(1, s.unsqueeze(1)).squeeze(1)
+            path.append(s)
+        out["path"] = torch.stack(path[::-1], 1)
+    return out
+
+
+def rollout_torch(kind, A, Bm, Cm, mu, L0, U, LQ, LR, S, H, lstm=None, h0=None, c0=None, y0=None, P=None, s0=None,
+                  eps0=None, eps_z=None, eps_a=None, gumbel=None):
+    """The same recursion as csrc/lgssm_gen.h in torch ops, in the dtype of mu (fp32 on the product path): the shapes the
+    kernel is not built for (alpha-network hidden != 50 or a_dim != 2) - about fifteen launches per step."""
+    K = A.shape[0]
+    Bsz = mu.shape[0]
+    rep = lambda t: t.repeat_interleave(S, 0)
+    flat = lambda t: None if t is None else t.reshape(Bsz * S, *t.shape[2:]).to(mu.dtype)
+    eps0, eps_z, eps_a, gumbel = flat(eps0), flat(eps_z), flat(eps_a), flat(gumbel)
+    z = rep(mu)
+    if eps0 is not None:
+        z = z + (rep(L0) @ eps0.unsqueeze(-1)).squeeze(-1)
+    R = z.shape[0]
+    if kind == "switching":
+        s = rep(s0)
+    elif K == 1:
+        w = z.new_ones(R, 1)
+    else:
+        w_ih, w_hh, b_ih, b_hh, head_w, head_b = lstm
+        h, c, y = rep(h0), rep(c0), rep(y0)
+    a_out, z_out, w_out = [], [], []
+    for t in range(H):
+        if kind == "switching":
+            pi = s @ P
+            if gumbel is not None:
+                s = torch.nn.functional.one_hot((pi.log() + gumbel[:, t]).argmax(-1), K).to(pi.dtype)
+            else:
+                s = pi
+            w = s
+        elif K > 1:
+            gi, gf, gg, go = (y @ w_ih.T + h @ w_hh.T + b_ih + b_hh).chunk(4, -1)
+            c = torch.sigmoid(gf) * c + torch.sigmoid(gi) * torch.tanh(gg)
+            h = torch.sigmoid(go) * torch.tanh(c)
+            w = torch.softmax(h @ head_w.T + head_b, -1)
+        zn = torch.einsum("rk,kij,rj->ri", w, A, z)
+        if U is not None:
+            zn = zn + torch.einsum("rk,kij,rj->ri", w, Bm, rep(U[:, t]))
+        if eps_z is not None:
+            LQt = torch.einsum("rk,kij->rij", w, LQ) if kind == "switching" else LQ
+            zn = zn + (LQt @ eps_z[:, t].unsqueeze(-1)).squeeze(-1)
+        z = zn
+        a = Cm[0] @ z.unsqueeze(-1) if kind == "switching" else torch.einsum("rk,kij,rj->ri", w, Cm, z).unsqueeze(-1)
+        a = a.squeeze(-1)
+        if eps_a is not None:
+            a = a + (LR @ eps_a[:, t].unsqueeze(-1)).squeeze(-1)
+        y = a
+        a_out.append(a), z_out.append(z), w_out.append(w)
+    un = lambda lst: torch.stack(lst, 1).reshape(Bsz, S, H, -1)
+    return un(a_out), un(z_out), un(w_out)
+
+
+def posterior_paths_torch(mus_filt, Sigmas_filt, mus_pred, Sigmas_pred, A, Cm, Q, S, LR=None, eps=None, eta=None):
+    """The recursion of csrc/lgssm_post.h in torch ops, batched over B and S, in the dtype of mus_filt: for dtypes, devices and
+    shapes the kernels are not built for - several launches per time step.  Same arguments and returns as posterior_paths."""
+    mf = mus_filt.squeeze(-1) if mus_filt.dim() == 4 else mus_filt
+    mp = mus_pred.squeeze(-1) if mus_pred.dim() == 4 else mus_pred
+    dt = mf.dtype
+    Bsz, T, n = mf.shape
+    Sf, Sp = Sigmas_filt.to(dt), Sigmas_pred.to(dt)
+    A, Cm, Q = (_bt(t.to(dt), Bsz, T) for t in (A, Cm, Q))
+    eye = torch.eye(n, device=mf.device, dtype=dt)
+    J = torch.zeros(Bsz, T, n, n, device=mf.device, dtype=dt)
+    P = Sf.clone()
+    if T > 1:
+        An, Qn = A[:, 1:], Q[:, 1:]
+        Jt = torch.linalg.solve(Sp[:, 1:].mT, (Sf[:, :-1] @ An.mT).mT).mT
+        G = eye - Jt @ An
+        J[:, :-1] = Jt
+        P[:, :-1] = G @ Sf[:, :-1] @ G.mT + Jt @ Qn @ Jt.mT
+    L, levels = safe_cholesky_items(P)
+    c = mf.clone()
+    if T > 1:
+        c[:, :-1] = mf[:, :-1] - (J[:, :-1] @ mp[:, 1:].unsqueeze(-1)).squeeze(-1)
+    z = torch.zeros(Bsz, S, n, device=mf.device, dtype=dt)
+    zs = [None] * T
+    for t in range(T - 1, -1, -1):
+        z = c[:, t, None] + z @ J[:, t].mT
+        if eps is not None:
+            z = z + eps[:, :, t].to(dt) @ L[:, t].mT
+        zs[t] = z
+    z = torch.stack(zs, 2)
+    a = (Cm[:, None] @ z.unsqueeze(-1)).squeeze(-1)
+    if eta is not None:
+        a = a + eta.to(dt) @ LR.to(dt).mT
+    return z, a, levels
+
+
+def predictive_torch(mus_pred, Sigmas_pred, Cm, R, Y, mask=None, want=_PRED_OUTPUTS):
+    """The equations of kvae_lgssm_predictive in torch ops, batched over (b, t), in the dtype of Sigmas_pred: other a_dim than 2,
+    non-fp32 and host tensors, and (in float64) the reference the kernel is tested against.  The factor of S_t is found by the
+    per-item ladder (safe_cholesky_items).  Same arguments and returns as predictive (without packed / slots)."""
+    want = _want("predictive", _PRED_OUTPUTS, want)
+    a_pred, S, res, observed = _innovation(mus_pred, Sigmas_pred, Cm, R, Y, mask)
+    L, levels = safe_cholesky_items(S)
+    ll, nis = (_observed_only(v, observed) for v in _gauss_ll(L, res))
+    full = {"ll": ll, "nis": nis, "a_pred": a_pred, "S": S, "levels": levels, "seq_ll": ll.sum(1)}
+    return {k: (v if k in want else None) for k, v in full.items()}
+
+
+def log_marginal_torch(mus_pred, Sigmas_pred, Cm, R, Y, mask=None):
+    """log_marginal in torch ops, differentiable, in the dtype of Sigmas_pred: other a_dim than 2, non-fp32 and host tensors, and
+    (in float64) the reference the adjoint kernel is tested against.  The values are predictive_torch's.  Nothing is
+    differentiated through safe_cholesky_items (its torch.where over failed cholesky_ex attempts turns into NaN * 0 in the
+    backward): the levels are found without a tape, then S + jitter[level] I - for level-5 items the clamped diagonal matrix - is
+    factorised once."""
+    a_pred, S, res, observed = _innovation(mus_pred, Sigmas_pred, Cm, R, Y, mask)
+    with torch.no_grad():
+        _, levels = safe_cholesky_items(S)
+    jitter = torch.tensor([*_jitter_ladder(), 0.0], device=S.device, dtype=torch.float64)[levels.long()]
+    eye = torch.eye(S.shape[-1], device=S.device, dtype=S.dtype)
+    St = S + (jitter[..., None, None] * eye.double()).to(S.dtype)
+    clamped = torch.diag_embed(torch.diagonal(S, dim1=-2, dim2=-1).clamp(min=1e-6))
+    St = torch.where((levels == 5)[..., None, None], clamped, St)
+    ll = _observed_only(_gauss_ll(torch.linalg.cholesky(St), res)[0], observed)
+    return {"ll": ll, "seq_ll": ll.sum(1), "levels": levels}
+
+
+def _swf_state(state, Bsz, K, n):
+    if state is None:
+        return None
+    lw, mu, Sig = state["log_w"], state["mu"], state["Sigma"]
+    if lw.shape != (Bsz, K) or mu.shape != (Bsz, K, n) or Sig.shape != (Bsz, K, n, n):
+        raise ValueError(f"switching_filter: state must hold log_w [{Bsz},{K}], mu [{Bsz},{K},{n}], Sigma [{Bsz},{K},{n},{n}], got "
+                         f"{tuple(lw.shape)}, {tuple(mu.shape)}, {tuple(Sig.shape)}")
+    return lw, mu, Sig
+
+
+@torch.no_grad()
+def switching_filter_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, state=None, want=_SWF_OUTPUTS):
+    """The equations of kvae_lgssm_switching_filter (include/kvae_lgssm.h) in torch ops, vectorised over (B, i, j), in the dtype of
+    A: shapes outside the kernel's, non-fp32 and host tensors, and (in float64) the reference the kernel is tested against.
+    T steps of about thirty small launches.  Same arguments and returns as switching_filter."""
+    want = _want("switching_filter", _SWF_OUTPUTS, want)
+    dt, dev = A.dtype, Y.device
+    K, n = A.shape[0], A.shape[1]
+    Bsz, T, p = Y.shape
+    A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U = (t.detach().to(device=dev, dtype=dt) for t in (A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U))
+    mask = None if mask is None else mask.detach().to(device=dev, dtype=dt).reshape(Bsz, T)
+    st = _swf_state(state, Bsz, K, n)
+    if st is None:
+        lw = torch.full((Bsz, K), 1.0 / K, device=dev, dtype=dt).log()
+        mu, Sig = mu0.expand(Bsz, K, n), Sigma0.expand(Bsz, K, n, n)
+    else:
+        lw, mu, Sig = (t.detach().to(device=dev, dtype=dt) for t in st)
+    eye = torch.eye(n, device=dev, dtype=dt)
+    eyeK = torch.eye(K, device=dev, dtype=dt)
+    uniform = torch.full((K, K), 1.0 / K, device=dev, dtype=dt)
+    ninf = torch.full((), -float("inf"), device=dev, dtype=dt)
+    outs = {k: [] for k in ("regime_filt", "regime_pred", "log_lik", "a_pred", "S", "mus_filt", "Sigmas_filt", "levels")}
+    for t in range(T):
+        Pt = uniform if (t == 0 and st is None) else P
+        mk = torch.ones(Bsz, device=dev, dtype=dt) if mask is None else mask[:, t]
+        observed = mk != 0
+        # ---- the K^2 filter steps: [B, i, j, ...] ----
+        mp = torch.einsum("jrc,bic->bijr", A, mu) + torch.einsum("jrc,bc->bjr", Bm, U[:, t]).unsqueeze(1)
+        Sp = torch.einsum("jre,biec,jdc->bijrd", A, Sig, A) + Q
+        ap = mp @ Cm.mT
+        res = Y[:, t, None, None, :] - ap
+        S = Cm @ Sp @ Cm.mT + R
+        S = 0.5 * (S + S.mT)
+        L, lv = safe_cholesky_items(S)
+        lij = _observed_only(_gauss_ll(L, res)[0], observed[:, None, None])
+        Kg = torch.linalg.solve(S, Cm @ Sp).mT * mk[:, None, None, None, None]      # S^-1 (Sigma_pred C^T)^T, transposed
+        muf = mp + (Kg @ res.unsqueeze(-1)).squeeze(-1)
+        IKC = eye - Kg @ Cm
+        Sf = IKC @ Sp @ IKC.mT + Kg @ R @ Kg.mT
+        Sf = 0.5 * (Sf + Sf.mT)
+        # ---- weights ----
+        logc = lw.unsqueeze(-1) + Pt.log() + lij                                     # [B, i, j]
+        pw = lw.exp().unsqueeze(-1) * Pt
+        cmx = logc.amax(1)                                                           # [B, j]
+        dead = cmx == ninf
+        ex = torch.where(dead.unsqueeze(1), eyeK.expand(Bsz, K, K), (logc - torch.where(dead, torch.zeros_like(cmx), cmx).unsqueeze(1)).exp())
+        se = ex.sum(1)
+        W = ex / se.unsqueeze(1)
+        mx = cmx.amax(-1, keepdim=True)
+        tot = mx.squeeze(-1) + (se * (cmx - mx).exp()).sum(-1).log()
+        lw = (cmx + se.log()) - tot.unsqueeze(-1)
+        rf = lw.exp()
+        # ---- collapse over i ----
+        mu = (W.unsqueeze(-1) * muf).sum(1)                                          # [B, j, n]
+        d = muf - mu.unsqueeze(1)
+        Sig = (W[..., None, None] * (Sf + d.unsqueeze(-1) * d.unsqueeze(-2))).sum(1)
+        Sig = 0.5 * (Sig + Sig.mT)
+        # ---- outputs of the step ----
+        outs["regime_pred"].append(pw.sum(1))
+        outs["regime_filt"].append(rf)
+        outs["log_lik"].append(torch.where(observed, tot, torch.zeros_like(tot)))
+        outs["levels"].append(torch.where(pw > 0, lv, torch.zeros_like(lv)).amax((1, 2)))
+        a = (pw.unsqueeze(-1) * ap).sum((1, 2))
+        e = ap - a[:, None, None, :]
+        outs["a_pred"].append(a)
+        outs["S"].append((pw[..., None, None] * (S + e.unsqueeze(-1) * e.unsqueeze(-2))).sum((1, 2)))
+        m_ = (rf.unsqueeze(-1) * mu).sum(1)
+        dd = mu - m_.unsqueeze(1)
+        outs["mus_filt"].append(m_)
+        outs["Sigmas_filt"].append((rf[..., None, None] * (Sig + dd.unsqueeze(-1) * dd.unsqueeze(-2))).sum(1))
+    full = {k: torch.stack(v, 1) for k, v in outs.items()}
+    full["log_lik_seq"] = full["log_lik"].sum(1)
+    full["state"] = {"log_w": lw, "mu": mu, "Sigma": Sig}
+    return {k: (full[k] if k in want else None) for k in _SWF_OUTPUTS}
+
+
