@@ -53,19 +53,21 @@ def smooth_step(Sig_f, Sig_p_next, Sig_s_next, mu_f, mu_p_next, mu_s_next, A_nex
     return mu_s, Sig_s
 
 
-def safe_cholesky(Sigma, max_tries=5, jitter_init=1e-6):
-    """kalman_filter.py:282-302: jitter is added on the first try already; whole-batch retry."""
+def safe_cholesky(Sigma, max_tries=5, jitter_init=1e-6, return_level=False):
+    """kalman_filter.py:282-302: jitter is added on the first try already; whole-batch retry.
+    return_level: (L, level) with level = the number of failed tries (max_tries = the diagonal fallback)."""
     n = Sigma.size(-1)
     Sigma = 0.5 * (Sigma + Sigma.mT)
     eye = torch.eye(n, dtype=Sigma.dtype)
     jitter = jitter_init
-    for _ in range(max_tries):
+    for level in range(max_tries):
         L, info = torch.linalg.cholesky_ex(Sigma + jitter * eye)
         if not bool((info != 0).any()):
-            return L
+            return (L, level) if return_level else L
         jitter *= 10.0
     diag = torch.diagonal(Sigma, dim1=-2, dim2=-1).clamp(min=1e-6)
-    return torch.diag_embed(torch.sqrt(diag))
+    L = torch.diag_embed(torch.sqrt(diag))
+    return (L, max_tries) if return_level else L
 
 
 def mvn_logprob_tril(x, L):
@@ -245,9 +247,10 @@ def lgssm_smooth(Y, U, mask, dyn, kind, Qbuf, R, mu0, Sigma0, **kw):
     return out
 
 
-def lgssm_elbo_terms(mu_s, Sig_s, y, u, A_list, B_list, C_list, Q_list, R, mu0, Sigma0, mask, eps_z):
+def lgssm_elbo_terms(mu_s, Sig_s, y, u, A_list, B_list, C_list, Q_list, R, mu0, Sigma0, mask, eps_z, per_step=False):
     """The four LGSSM terms of KalmanFilter.elbo (kalman_filter.py:347-389), each summed over B,T:
-    (transition, emission, init, entropy). Q_list is [B,T,n,n] or [n,n]."""
+    (transition, emission, init, entropy). Q_list is [B,T,n,n] or [n,n].
+    per_step: the four terms un-summed, each [B,T] (transition 0 at t = 0, init 0 at t > 0)."""
     Bsz, T, p = y.shape
     n = A_list.shape[-1]
     if mu_s.dim() == 4:
@@ -266,6 +269,9 @@ def lgssm_elbo_terms(mu_s, Sig_s, y, u, A_list, B_list, C_list, Q_list, R, mu0, 
     L_0 = torch.linalg.cholesky(Sigma0)
     lp_init = mvn_logprob_tril(z[:, 0] - mu0, L_0)                                    # :380-381
     entropy = -mvn_logprob_tril(z - mu_s, L)                                          # :389
+    if per_step:
+        zero = lp_emiss.new_zeros(Bsz, 1)
+        return (torch.cat([zero, lp_trans], 1), lp_emiss, torch.cat([lp_init.unsqueeze(1), zero.expand(Bsz, T - 1)], 1), entropy)
     return lp_trans.sum(), lp_emiss.sum(), lp_init.sum(), entropy.sum()
 
 

@@ -55,7 +55,9 @@ class Barrier {
       cv_.notify_all();
       return;
     }
-    if (!cv_.wait_for(lk, std::chrono::seconds(kDeadlineSeconds), [&] { return gen_ != gen; })) {
+    // (a deadline on the system clock: the wait is then pthread_cond_timedwait, which thread sanitizers know releases the mutex;
+    // wait_for is pthread_cond_clockwait, which gcc 11's does not intercept - it reports the barrier itself as a double lock)
+    if (!cv_.wait_until(lk, std::chrono::system_clock::now() + std::chrono::seconds(kDeadlineSeconds), [&] { return gen_ != gen; })) {
       fprintf(stderr, "wave_emu: %s-scope rendezvous not reached by all %u lanes within %d s (lane %d, block %u waiting)\n",
               scope_, n_, kDeadlineSeconds, lane_id(), t_bid.x);
       fflush(stderr);

@@ -2360,3 +2360,401 @@ def lgssm_single_launch_cases(DEV):
             worst[k] = max(worst.get(k, 0.0), v)
     print(worst)
     return worst
+
+
+# ---- the ELBO bodies of csrc/lgssm_elbo.h (elbo_probe_body, elbo_body) one (b,t) at a time against float64 ----
+# Kernel families by key: "tpp" k_elbo_probe_tpp / k_elbo_tpp<SDims<4,4,2>> (one thread per step, levels[2] == 1), "n4w" / "n16w" /
+# "rt" k_elbo_probe<D> / k_elbo<D> (one wavefront per step, levels[2] == 0) for SDims<4,4,2> (KVAE_ELBO_TPP=0), SDims<16,16,2>
+# (misaligned operands or KVAE_N16=0) and RDims.  Bars = 4 x ELBO_YARDSTICK; the yardstick of "<family>.<quantity>" is the
+# largest per-slice ratio of the FLOAT32 run of the torch oracle (O.lgssm_elbo_terms) against its float64 run over the case lists
+# of both tiers (elbo_yardstick() reruns it); ".lv" keys: the cases with a raised _safe_cholesky level, where the yardstick differs
+# by more than 2 x from level 0 (a poisoned pivot amplifies rounding).  Kernel ratios against the same float64 runs: DESIGN section 2.
+# Less than a factor 2 under the bar, on the host bodies and on gfx950 alike: tpp.gC.sum / n4w.gC.sum (1.37 x), n16w.in (1.39 x),
+# tpp.gQ.lv (1.5 x), tpp.gB.lv (1.5 x), rt.gA.lv (1.6 x), tpp.gA.lv (1.9 x); n4w.ent.lv (1.9 x) on gfx950.
+ELBO_YARDSTICK = {   # float32 torch oracle against its float64 run, largest ratio over the case lists of both tiers
+    "n16w.em": 3.08e-07, "n16w.em.lv": 2.35e-06, "n16w.ent": 1.08e-07, "n16w.ent.lv": 1.85e-06, "n16w.gA": 2.90e-07,
+    "n16w.gB": 2.47e-07, "n16w.gC": 1.81e-07, "n16w.gC.lv": 4.60e-07, "n16w.gC.sum": 1.69e-07, "n16w.gC.sum.lv": 7.40e-08,
+    "n16w.gQ": 5.40e-07, "n16w.gU": 3.39e-07, "n16w.gY": 2.01e-07, "n16w.gY.lv": 4.81e-07, "n16w.g_Sigmas": 3.22e-07,
+    "n16w.g_mus": 1.97e-07, "n16w.g_mus.lv": 4.31e-06, "n16w.in": 3.79e-08, "n16w.in.lv": 1.33e-07, "n16w.tr": 3.22e-07,
+    "n4w.em": 9.39e-07, "n4w.ent": 2.26e-07, "n4w.ent.lv": 3.14e-06, "n4w.gA": 3.00e-07, "n4w.gA.lv": 9.24e-07, "n4w.gB": 2.71e-07,
+    "n4w.gB.lv": 9.62e-07, "n4w.gC": 1.02e-06, "n4w.gC.sum": 9.06e-08, "n4w.gC.sum.lv": 2.03e-07, "n4w.gQ": 8.52e-07,
+    "n4w.gQ.sum": 2.70e-07, "n4w.gU": 9.32e-07, "n4w.gY": 9.28e-07, "n4w.g_Sigmas": 1.25e-06, "n4w.g_mus": 8.13e-07,
+    "n4w.g_mus.lv": 1.34e-05, "n4w.in": 2.46e-07, "n4w.tr": 3.77e-07, "n4w.tr.lv": 1.04e-06, "rt.em": 2.53e-07,
+    "rt.em.lv": 7.90e-07, "rt.ent": 2.39e-07, "rt.ent.lv": 8.64e-07, "rt.gA": 3.08e-07, "rt.gA.lv": 7.59e-07, "rt.gB": 3.05e-07,
+    "rt.gB.lv": 8.35e-07, "rt.gC": 1.84e-07, "rt.gC.lv": 7.05e-07, "rt.gC.sum": 2.34e-07, "rt.gQ": 6.49e-07, "rt.gQ.lv": 1.69e-06,
+    "rt.gQ.sum": 2.51e-07, "rt.gU": 3.72e-07, "rt.gU.lv": 9.79e-07, "rt.gY": 1.54e-07, "rt.gY.lv": 7.02e-07,
+    "rt.g_Sigmas": 4.04e-07, "rt.g_Sigmas.lv": 2.13e-06, "rt.g_mus": 2.86e-07, "rt.g_mus.lv": 2.19e-06, "rt.in": 9.95e-08,
+    "rt.in.lv": 2.26e-07, "rt.tr": 6.40e-07, "rt.tr.lv": 1.58e-06, "tpp.em": 9.39e-07, "tpp.ent": 2.75e-07, "tpp.ent.lv": 7.47e-06,
+    "tpp.gA": 3.58e-07, "tpp.gA.lv": 1.48e-06, "tpp.gB": 2.71e-07, "tpp.gB.lv": 1.19e-06, "tpp.gC": 1.02e-06,
+    "tpp.gC.sum": 9.06e-08, "tpp.gC.sum.lv": 2.03e-07, "tpp.gQ": 6.53e-07, "tpp.gQ.lv": 2.31e-06, "tpp.gQ.sum": 2.74e-07,
+    "tpp.gU": 4.77e-07, "tpp.gU.lv": 1.59e-06, "tpp.gY": 9.28e-07, "tpp.g_Sigmas": 8.11e-07, "tpp.g_Sigmas.lv": 2.71e-06,
+    "tpp.g_mus": 8.13e-07, "tpp.g_mus.lv": 1.34e-05, "tpp.in": 2.46e-07, "tpp.tr": 5.48e-07, "tpp.tr.lv": 1.64e-06,
+}
+ELBO_STEP_TOL = {k: 4.0 * v for k, v in ELBO_YARDSTICK.items()}
+ELBO_TERMS = ("tr", "em", "in", "ent")
+ELBO_GRADS = ("g_mus", "g_Sigmas", "gY", "gU", "gA", "gB", "gC", "gQ")
+ELBO_GUARD = -7.25e33   # what the guard records and every output element hold before the call
+ELBO_SIG_BAD = {0: None, 2: -5e-5, 3: -4e-4, 5: -1.0}   # the first diagonal entry of the ONE poisoned Sigma_s, by level wanted
+ELBO_Q_BAD = {0: None, 1: -3e-6, 5: -1.0}              # ... and entry min(2, n-1) of the poisoned Q
+
+
+def _elbo_bar(name, raised, free):
+    if free:
+        return float("inf")
+    return ELBO_STEP_TOL[name + ".lv"] if raised and name + ".lv" in ELBO_STEP_TOL else ELBO_STEP_TOL[name]
+
+
+def _guarded(dev, B, T, rec):
+    """([B,T,rec] view, the flat buffer it lives in): one record in front and one behind, everything filled with ELBO_GUARD."""
+    flat = torch.full(((B * T + 2) * rec,), ELBO_GUARD, device=dev, dtype=torch.float32)
+    return flat[rec:(B * T + 1) * rec].view(B, T, rec), flat
+
+
+def elbo_raw(DEV, mus, Sig, eps, Y, U, mask, packed, A, Bm, Cm, Q, R, mu0, S0, slots, grads=True, need_q=True, use_ws=True,
+             sig_odd=False):
+    """kvae_lgssm_elbo through the loaded library, the problem built as LgssmElbo builds it (lgssm_ops._Call / _GradSink), the
+    outputs NOT summed.  terms, g_mus, g_Sigmas and ws_lz have one guard record in front and one behind; every output element
+    holds ELBO_GUARD before the call: afterwards both guards must be untouched and every (b,t) overwritten (ws_lz: when the
+    batch resolved Sigma_s at level 0 - a step whose own level is raised parks nothing).  use_ws=False: ws_lz = NULL, the
+    "always recompute" path of the C ABI.  sig_odd: Sigma_s 4 bytes off a 16-byte boundary.
+    Returns CPU tensors: terms [B,T,4], levels [3], ws [B,T,n] | None and, with grads, g_mus, g_Sigmas, gY, gU, gA, gB, gC,
+    gQ | None per step."""
+    import ctypes as C
+    from kvae import _native as N
+    from kvae.kalman.lgssm_ops import _Call, _GradSink
+    d = lambda t: None if t is None else t.detach().float().to(DEV).contiguous()
+    mus, eps, Y, U, mask, packed, A, Bm, Cm, Q, R, mu0, S0 = (d(t) for t in (mus, eps, Y, U, mask, packed, A, Bm, Cm, Q, R, mu0, S0))
+    Sig = _device_leaf(Sig, DEV, odd=sig_odd)[0].detach()
+    call = _Call(Y, U, mask, packed, A, Bm, Cm, Q, R, mu0, S0, slots)
+    B, T, n, m, p = call.dims
+    dev = call.Y.device
+    (terms, f_terms), (ws, f_ws) = _guarded(dev, B, T, 4), (_guarded(dev, B, T, n) if use_ws else (None, None))
+    levels = torch.full((3,), -1, device=dev, dtype=torch.int32)
+    g_mus = g_Sig = f_gm = f_gS = sink = None
+    filled = []
+    if grads:
+        (g_mus, f_gm), (g_Sig, f_gS) = _guarded(dev, B, T, n), _guarded(dev, B, T, n * n)
+        sink = _GradSink(call, packed, A, Bm, Cm, Q, slots, need_q)
+        filled = [sink.gY, sink.gU] + [b for b, _ in sink.out.values()] + ([sink.gpacked] if sink.gpacked is not None else [])
+        for t in filled:
+            t.fill_(ELBO_GUARD)
+    call.lib.check(call.lib.dll.kvae_lgssm_elbo(C.byref(call.prob), N.ptr(mus), N.ptr(Sig), N.ptr(eps), N.ptr(terms), N.ptr(levels),
+                                                N.ptr(ws), N.ptr(g_mus), N.ptr(g_Sig), C.byref(sink.g) if sink else None, call.stream),
+                   "kvae_lgssm_elbo")
+    lv = levels.cpu().tolist()
+    for name, view, flat, rec in (("terms", terms, f_terms, 4), ("ws_lz", ws, f_ws, n), ("g_mus", g_mus, f_gm, n), ("g_Sigmas", g_Sig, f_gS, n * n)):
+        if flat is None:
+            continue
+        flat = flat.cpu()
+        assert bool((flat[:rec] == ELBO_GUARD).all()), (name, "the guard record in front was written")
+        assert bool((flat[-rec:] == ELBO_GUARD).all()), (name, "the guard record behind was written")
+        if name != "ws_lz" or lv[0] == 0:
+            left = (view.cpu().reshape(B * T, -1) == ELBO_GUARD).any(-1).nonzero().flatten().tolist()
+            assert not left, (name, "not overwritten at (b,t)", [divmod(q, T) for q in left[:4]])
+    for t in filled:
+        assert not bool((t == ELBO_GUARD).any()), "an element of a gradient buffer was not overwritten"
+    c = lambda t: None if t is None else t.detach().cpu().clone()
+    out = dict(terms=c(terms), levels=lv, ws=c(ws))
+    if grads:
+        nn, nm = n * n, n * m
+
+        def stack(name, off, r, cc):
+            if off is not None:
+                return c(sink.gpacked[..., off:off + r * cc]).reshape(B, T, r, cc)
+            return c(sink.out[name][0]) if name in sink.out else None
+        out.update(g_mus=c(g_mus), g_Sigmas=c(g_Sig).reshape(B, T, n, n), gY=c(sink.gY), gU=c(sink.gU), gA=stack("gA", slots.A, n, n),
+                   gB=stack("gB", slots.B, n, m), gC=stack("gC", slots.C, p, n), gQ=stack("gQ", slots.Q, n, n))
+    return out
+
+
+def _elbo_oracle(ops, dtype, grads=True):
+    """O.lgssm_elbo_terms(per_step=True) in `dtype` on the CPU, every per-step operand expanded to a [B,T,r,c] leaf of its own (so a
+    broadcast operand has a per-step gradient too); gradients of the total by autograd.  The same dict as elbo_raw returns."""
+    from oracle import torch_oracle as O
+    c = lambda t: t.detach().cpu().to(dtype)
+    B, T = ops["Y"].shape[:2]
+    lv = {k: c(ops[k]).clone().requires_grad_(grads) for k in ("mus", "Sig", "Y", "U", "A", "B", "C", "Q")}
+    shared = {k: lv[k] for k in ("C", "Q") if lv[k].dim() == 2}   # autograd sums a broadcast operand's gradient in `dtype`
+    for k in ("A", "B", "C", "Q"):
+        if lv[k].dim() == 2:
+            lv[k] = lv[k].expand(B, T, *lv[k].shape).clone()
+            if grads:
+                lv[k].retain_grad()
+    mask = torch.ones(B, T, dtype=dtype) if ops["mask"] is None else c(ops["mask"])
+    with torch.set_grad_enabled(grads):
+        terms = torch.stack(O.lgssm_elbo_terms(lv["mus"], lv["Sig"], lv["Y"], lv["U"], lv["A"], lv["B"], lv["C"], lv["Q"], c(ops["R"]),
+                                               c(ops["mu0"]), c(ops["S0"]), mask, c(ops["eps"]), per_step=True), -1)
+    lvS = O.safe_cholesky(lv["Sig"].detach(), return_level=True)[1]
+    lvQ = O.safe_cholesky(lv["Q"].detach()[:, 1:], return_level=True)[1] if T > 1 else 0
+    out = dict(terms=terms.detach(), levels=[lvS, lvQ, None], ws=None)
+    if grads:
+        terms.sum().backward()
+        g = lambda k: lv[k].grad if lv[k].grad is not None else torch.zeros_like(lv[k])
+        out.update(g_mus=g("mus"), g_Sigmas=g("Sig"), gY=g("Y"), gU=g("U"), gA=g("A"), gB=g("B"), gC=g("C"), gQ=g("Q"))
+        out.update({"g%s.sum" % k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in shared.items()})
+    return out
+
+
+def _elbo_compare(fam, raised, got, ref, layout, free, out):
+    """Per (b,t): the four terms and every gradient stack `got` holds; the gradient of a broadcast operand as a whole tensor (the
+    per-step buffer summed in float32, as lgssm_ops._reduce_to does; the float32 oracle: autograd's own sum); the four sums within 1e-4 of float64.  Keys of `out`: "<fam>.<quantity>" (+ ".lv" for a case with a raised level)."""
+    sfx = ".lv" if raised else ""
+
+    def steps(name, a, b):
+        ratio, where = _per_step_ratio(a.detach().cpu(), b.detach())
+        out[name + sfx] = max(out.get(name + sfx, 0.0), ratio)
+        bar = _elbo_bar(name, raised, free)
+        assert ratio < bar, (name, "ratio %.3g at (b,t) = %s, bar %.3g" % (ratio, where, bar), fam, layout)
+    for i, k in enumerate(ELBO_TERMS):
+        steps(f"{fam}.{k}", got["terms"][..., i:i + 1], ref["terms"][..., i:i + 1])
+    for k in ELBO_GRADS:
+        if got.get(k) is not None:
+            steps(f"{fam}.{k}", got[k], ref[k])
+    for k, lay in (("gC", "abq"), ("gQ", "abc")):
+        if layout == lay and got.get(k) is not None:
+            name = f"{fam}.{k}.sum"
+            ratio = rel_err(got[name[len(fam) + 1:]] if name[len(fam) + 1:] in got else got[k].sum((0, 1)), ref[name[len(fam) + 1:]])   # (the product sums in float32)
+            out[name + sfx] = max(out.get(name + sfx, 0.0), ratio)
+            assert ratio < _elbo_bar(name, raised, free), (name, ratio, fam, layout)
+    for i, k in enumerate(ELBO_TERMS):
+        a, b = float(got["terms"][..., i].sum()), float(ref["terms"][..., i].sum())
+        assert abs(a - b) <= 1e-4 * abs(b) + 1e-3, ("sum of", k, a, b, fam, layout)
+
+
+def _elbo_poison_q(pos, B, T, for_q):
+    """The (b,t) of the ONE poisoned matrix: pos "first" (q = 0; Q: q = 1), an index q = b T + t, or "last"; a Q moves on to t = 1
+    of its sequence, since Q_0 is never factorised."""
+    q = {"first": 1 if for_q else 0, "last": B * T - 1}.get(pos, pos)
+    q = min(int(q), B * T - 1)
+    b, t = divmod(q, T)
+    if for_q and t == 0 and T > 1:
+        t = 1
+    return b, t
+
+
+def elbo_per_step(DEV, B, T, n, m, p, fam, layout="plain", mask_kind=None, prior="shared", levels=(0, 0), pos="first", q_grad=True,
+                  family=None, sig_odd=False, seed=0, yardstick=False, free=False):
+    """kvae_lgssm_elbo (elbo_raw: the un-summed terms and the sink's per-step gradients) against a FLOAT64 run of
+    O.lgssm_elbo_terms(per_step=True) on exactly the float32 operand values, one (b,t) slice at a time (_per_step_ratio).
+    fam: the key of the bars ("tpp", "n4w", "n16w", "rt"); family: what levels[2] must report (None: not 2 or 3).
+    layout: "abc" one packed record A|B|C and ONE Q for the batch (q_grad: with its gradient); "abq" one packed record A|B|Q and a
+    broadcast C; "plain" four [B,T,r,c] stacks.  Sigma_s, Q and Sigma0 dense SPD (asserted), R not diagonal; prior "shared" or
+    "per_seq" (mu0_sb, Sigma0_sb != 0); mask_kind: a kind of _step_mask.  levels = (level of Sigma_s, level of Q) of _safe_cholesky,
+    forced by ONE poisoned matrix at `pos` (_elbo_poison_q; layout "abc": the shared Q itself, which only (0,1) probes).  With T = 1
+    no Q is ever factorised: its level must be 0 whatever Q holds.  The levels of the float64 run, of the C oracle and of the
+    kernel must agree.
+    Exact, on what the kernel wrote: emission term, gY, gC zero at hidden steps; transition term, gA, gB, gU, gQ zero at t = 0; init
+    term zero at t > 0; g_Sigmas symmetric to the bit, and diagonal at level 5, where the clamped entry's gradient is exactly 0;
+    ws_lz = NULL gives the bits of the parked-sample path and meets the same bars; with mus, eps, Sigma_s of ONE sequence redrawn
+    (first, middle, last) every output of every other sequence keeps its bits.
+    yardstick: the float32 run of the torch oracle in the kernel's place; free: no bars (measuring).  Returns {key: largest ratio}."""
+    from kvae.kalman.lgssm_ops import Slots
+    from oracle import c_oracle
+    assert layout in ("abc", "abq", "plain") and prior in ("shared", "per_seq")
+    g = torch.Generator().manual_seed(7919 * seed + 1000 * B + 10 * T + n + 3 * len(layout))
+    rn = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
+    eye, eyep = torch.eye(n, dtype=torch.float64), torch.eye(p, dtype=torch.float64)
+    per_b = (B,) if prior == "per_seq" else ()
+
+    def draw_q(Bn):   # mus, eps, Sigma_s of Bn sequences
+        W = 0.1 * rn(Bn, T, n, n)
+        return 0.5 * rn(Bn, T, n), rn(Bn, T, n), W @ W.mT + 0.3 * eye
+    mus, eps, Sig = draw_q(B)
+    Y, U = rn(B, T, p), 0.3 * rn(B, T, m)
+    A, Bm = 0.9 * eye + 0.08 * rn(B, T, n, n), 0.1 * rn(B, T, n, m)
+    C = 0.3 * (rn(p, n) if layout == "abq" else rn(B, T, p, n))
+    Wq = rn(*(() if layout == "abc" else (B, T)), n, n)
+    Q = 0.02 * eye + 0.0005 * (Wq @ Wq.mT)
+    Wr = 0.1 * rn(p, p)
+    R = 0.03 * eyep + Wr @ Wr.T
+    mu0 = 0.1 * rn(*per_b, n)
+    W0 = 0.2 * rn(*per_b, n, n)
+    S0 = W0 @ W0.mT + 0.5 * eye
+    mask = _step_mask(mask_kind, B, T, g)
+    for M in (Sig, Q, S0, R):
+        assert float(torch.linalg.eigvalsh(M.float().double()).min()) > 0.0
+    lvS, lvQ = levels
+    sb, st = _elbo_poison_q(pos, B, T, False)
+    qb, qt = _elbo_poison_q(pos, B, T, True)
+    bad_S = None if ELBO_SIG_BAD[lvS] is None else torch.diag(torch.tensor([ELBO_SIG_BAD[lvS]] + [0.2] * (n - 1), dtype=torch.float64))
+    jq = min(2, n - 1)
+    bad_Q = None if ELBO_Q_BAD[lvQ] is None else torch.diag(torch.tensor([0.02] * jq + [ELBO_Q_BAD[lvQ]] + [0.02] * (n - 1 - jq), dtype=torch.float64))
+    if bad_S is not None:
+        Sig[sb, st] = bad_S
+    if bad_Q is not None:
+        if layout == "abc":
+            Q = bad_Q
+        else:
+            Q[qb, qt] = bad_Q
+    want = [lvS, lvQ if T > 1 else 0]
+    r32 = lambda t: None if t is None else t.float().double()   # the float32 values are the problem
+    ops = {k: r32(v) for k, v in dict(mus=mus, Sig=Sig, eps=eps, Y=Y, U=U, mask=mask, A=A, B=Bm, C=C, Q=Q, R=R, mu0=mu0, S0=S0).items()}
+    ref = _elbo_oracle(ops, torch.float64)
+    assert ref["levels"][:2] == want, ("levels of the float64 run", ref["levels"], want)
+    _, clv = c_oracle.elbo_terms(ops["mus"], ops["Sig"], ops["eps"], ops["Y"], ops["U"], ops["mask"], ops["A"], ops["B"], ops["C"], ops["Q"],
+                                 ops["R"], ops["mu0"][0] if per_b else ops["mu0"], ops["S0"][0] if per_b else ops["S0"])
+    assert list(clv) == want, ("levels of the C oracle", list(clv), want)
+    raised = max(want) > 0
+    out = {}
+    if yardstick:
+        got = _elbo_oracle(ops, torch.float32)
+        assert got["levels"][:2] == want, ("levels of the float32 run", got["levels"], want)
+        _elbo_compare(fam, raised, got, ref, layout, True, out)
+        return out
+    nn, nm = n * n, n * m
+    fl = lambda t: t.reshape(B, T, -1)
+    if layout == "plain":
+        stacks, slots = (None, ops["A"], ops["B"], ops["C"], ops["Q"]), Slots()
+    elif layout == "abc":
+        stacks, slots = (torch.cat([fl(ops["A"]), fl(ops["B"]), fl(ops["C"])], -1), None, None, None, ops["Q"]), Slots(A=0, B=nn, C=nn + nm)
+    else:
+        stacks, slots = (torch.cat([fl(ops["A"]), fl(ops["B"]), fl(ops["Q"])], -1), None, None, ops["C"], None), Slots(A=0, B=nn, Q=nn + nm)
+    need_q = layout != "abc" or q_grad
+
+    def run(mus_, eps_, Sig_, **kw):
+        r = elbo_raw(DEV, mus_, Sig_, eps_, ops["Y"], ops["U"], ops["mask"], *stacks, ops["R"], ops["mu0"], ops["S0"], slots, need_q=need_q,
+                     sig_odd=sig_odd, **kw)
+        assert r["levels"][:2] == want, ("levels of the kernel", r["levels"], want)
+        if family is None:
+            assert r["levels"][2] not in (2, 3), ("kernel family", r["levels"][2])
+        else:
+            assert r["levels"][2] == family, ("kernel family", r["levels"][2], family)
+        return r
+    got = run(ops["mus"], ops["eps"], ops["Sig"])
+    _elbo_compare(fam, raised, got, ref, layout, free, out)
+    # ---- exact, on what the kernel wrote ----
+    where = lambda cond: [tuple(x) for x in cond.nonzero()[:4].tolist()]
+    flat = lambda t: t.reshape(B, T, -1)
+    tm = got["terms"]
+    if mask is not None and bool((ops["mask"] == 0).any()):
+        hidden = ops["mask"] == 0
+        for k, v in (("em", tm[..., 1:2]), ("gY", got["gY"]), ("gC", got["gC"])):
+            bad = (flat(v) != 0).any(-1) & hidden
+            assert not bool(bad.any()), (k, "not exactly zero at hidden (b,t)", where(bad), fam, layout)
+    for k, v in (("tr", tm[..., 0:1]), ("gA", got["gA"]), ("gB", got["gB"]), ("gU", got["gU"]), ("gQ", got["gQ"])):
+        if v is not None:
+            bad = (flat(v)[:, 0] != 0).any(-1)
+            assert not bool(bad.any()), (k, "not exactly zero at t = 0 of sequences", where(bad), fam, layout)
+    bad = tm[:, 1:, 2] != 0
+    assert not bool(bad.any()), ("in", "not exactly zero at (b,t-1)", where(bad), fam, layout)
+    gS = got["g_Sigmas"]
+    bad = (gS != gS.mT).flatten(2).any(-1)
+    assert not bool(bad.any()), ("g_Sigmas", "not symmetric to the bit at (b,t)", where(bad), fam, layout)
+    offdiag = lambda M: (M - torch.diag_embed(torch.diagonal(M, dim1=-2, dim2=-1))).flatten(2).abs().amax(-1)
+    if want[0] == 5:
+        assert float(offdiag(gS).max()) == 0.0, ("g_Sigmas", "not diagonal at level 5", where(offdiag(gS) != 0), fam)
+        assert float(gS[sb, st, 0, 0]) == 0.0, ("g_Sigmas", "the clamped entry has a gradient", (sb, st), float(gS[sb, st, 0, 0]), fam)
+        assert float(gS[sb, st].diagonal()[1:].abs().min()) > 0.0 if n > 1 else True
+    if want[1] == 5 and got["gQ"] is not None:
+        gQ = got["gQ"]
+        assert float(offdiag(gQ).max()) == 0.0, ("gQ", "not diagonal at level 5", where(offdiag(gQ) != 0), fam)
+        clamped = gQ[:, 1:, jq, jq] if layout == "abc" else gQ[qb, qt, jq, jq]
+        assert float(clamped.abs().max()) == 0.0, ("gQ", "the clamped entry has a gradient", (qb, qt), fam, layout)
+    # ---- ws_lz = NULL: the "always recompute" path of the C ABI ----
+    same = lambda a, b_: all((a[k] is None and b_[k] is None) or torch.equal(a[k], b_[k]) for k in ("terms",) + ELBO_GRADS)
+    got_nows = run(ops["mus"], ops["eps"], ops["Sig"], use_ws=False)
+    _elbo_compare(fam, raised, got_nows, ref, layout, free, {})
+    out["ws_null_bits_equal"] = float(same(got, got_nows))
+    if not free:
+        assert out["ws_null_bits_equal"] == 1.0, ("ws_lz = NULL and the parked-sample path differ in bits", fam, layout, (B, T))
+    # ---- sequence isolation: the t = 0 / t = T-1 neighbour fetch ----
+    if B > 1:
+        for b2 in sorted({0, B // 2, B - 1}):
+            m2, e2, S2 = (t.clone() for t in (ops["mus"], ops["eps"], ops["Sig"]))
+            dm, de, dS = draw_q(1)
+            m2[b2], e2[b2], S2[b2] = r32(dm[0]), r32(de[0]), r32(dS[0])
+            if bad_S is not None and sb == b2:
+                S2[sb, st] = ops["Sig"][sb, st]
+            other = run(m2, e2, S2)
+            keep = torch.arange(B) != b2
+            for k in ("terms", "ws") + ELBO_GRADS:
+                if got[k] is None or (k == "ws" and want[0] != 0):
+                    continue
+                bad = (flat(got[k]) != flat(other[k])).any(-1) & keep[:, None]
+                assert not bool(bad.any()), (k, "changed at (b,t) when sequence %d was redrawn" % b2, where(bad), fam, layout)
+            changed = (flat(got["terms"])[b2] != flat(other["terms"])[b2]).any()
+            assert bool(changed), "the redrawn sequence kept its bits: the isolation check checks nothing"
+    return out
+
+
+def _el(B, T, layout, mask_kind, prior, levels=(0, 0), pos="first", **kw):
+    return dict(B=B, T=T, layout=layout, mask_kind=mask_kind, prior=prior, levels=levels, pos=pos, **kw)
+
+
+ELBO_LEVELS = [(0, 0), (0, 1), (2, 0), (3, 0), (5, 0), (0, 5), (2, 5)]
+_ELBO_LAYOUTS, _ELBO_MASKS, _ELBO_POS = ("abc", "abq", "plain"), (None, "ones", "t0_hidden", "last_hidden", "all_hidden", "random"), ("first", 63, 64, "last")
+
+
+def _elbo_rot(k, B, T, **kw):
+    """Entry k of the rotation over layouts, masks, priors, levels and positions (not their product)."""
+    return _el(B, T, _ELBO_LAYOUTS[k % 3], _ELBO_MASKS[(k + k // 3) % 6], ("shared", "per_seq")[(k // 2) % 2], ELBO_LEVELS[k % 7],
+               _ELBO_POS[(k + k // 7) % 4], **kw)
+
+
+# thread-per-step (4,4,2): B T = 1, 2, 63, 64, 65 (T = 1: every step is a whole sequence), 63, 64, 65, 128, 129 with T > 1 (a block
+# that ends mid-sequence, the ragged last block), 37 x 23 once.  The first eight shapes are also the wave-per-step (4,4,2) list.
+ELBO_TPP_SHAPES = [(1, 1), (1, 2), (63, 1), (64, 1), (65, 1), (9, 7), (1, 64), (13, 5), (32, 4), (43, 3)]
+ELBO_TPP_CASES = [_elbo_rot(3 * i + j, B, T) for i, (B, T) in enumerate(ELBO_TPP_SHAPES) for j in range(3)]
+ELBO_TPP_CASES.append(_el(37, 23, "abq", "random", "per_seq", (2, 5), 64))
+# the ONE poisoned matrix at q = 0 (Q: q = 1), 63, 64 and the last (b,t): the probe's level must arrive from every place of a block
+ELBO_TPP_CASES += [_el(B, T, lay, mk, pr, lv, pos) for pos in _ELBO_POS for B, T, lay, mk, pr, lv in (
+    (13, 5, "plain", "random", "shared", (2, 0)), (13, 5, "abq", None, "per_seq", (0, 1)),
+    (43, 3, "abq", "t0_hidden", "shared", (5, 0)), (43, 3, "plain", "last_hidden", "per_seq", (0, 5)))]
+# a shared poisoned Q, which only (b,t) = (0,1) probes; with T = 1 it is never probed and its level stays 0
+ELBO_TPP_CASES += [_el(13, 5, "abc", "random", "shared", (0, 1)), _el(43, 3, "abc", None, "per_seq", (0, 5)),
+                   _el(32, 4, "abc", "all_hidden", "shared", (2, 5), q_grad=False),
+                   _el(63, 1, "abc", "ones", "shared", (0, 5)), _el(64, 1, "abc", "random", "per_seq", (0, 1)), _el(65, 1, "abq", None, "shared", (0, 5))]
+ELBO_N4W_CASES = [c for c in ELBO_TPP_CASES if (c["B"], c["T"]) in ELBO_TPP_SHAPES[:8]]
+# run-time dimensions on k_elbo_probe<RDims> / k_elbo<RDims>, B = 3, T = 1, 2, 7
+ELBO_RT_DIMS = [(2, 1, 1), (5, 3, 2), (8, 8, 3), (12, 12, 2), (16, 8, 2), (16, 16, 16), (1, 1, 1)]
+ELBO_RT_CASES = [dict(n=n, m=m, p=p, **_elbo_rot(3 * i + j + 1, 3, T)) for i, (n, m, p) in enumerate(ELBO_RT_DIMS) for j, T in enumerate((1, 2, 7))]
+# wave-per-step (16,16,2): Sigma_s 4 bytes off a 16-byte boundary (the gate of kvae_lgssm_elbo), and the same under KVAE_N16=0
+ELBO_N16W_CASES = [dict(sig_odd=True, **_elbo_rot(2 * i + 3 * j + 2, B, T)) for i, B in enumerate((1, 3)) for j, T in enumerate((1, 2, 5))]
+ELBO_CASE_LISTS = {"tpp": ((4, 4, 2), ELBO_TPP_CASES), "n4w": ((4, 4, 2), ELBO_N4W_CASES), "n16w": ((16, 16, 2), ELBO_N16W_CASES),
+                   "rt": (None, ELBO_RT_CASES)}
+
+
+def elbo_case_id(c):
+    dims = "%d-%d-%d_" % (c["n"], c["m"], c["p"]) if "n" in c else ""
+    extra = "".join("_%s%s" % (k, "" if v is True else v) for k, v in c.items() if k in ("sig_odd", "q_grad", "seed"))
+    return "%sB%d_T%d_%s_%s_%s_S%dQ%d_%s%s" % (dims, c["B"], c["T"], c["layout"], c["mask_kind"], c["prior"], *c["levels"], c["pos"], extra)
+
+
+def run_elbo_case(DEV, fam, case, **kw):
+    """One entry of ELBO_CASE_LISTS[fam] through elbo_per_step."""
+    c = dict(case)
+    dims = tuple(c.pop(k) for k in ("n", "m", "p")) if "n" in c else ELBO_CASE_LISTS[fam][0]
+    return elbo_per_step(DEV, c.pop("B"), c.pop("T"), *dims, fam, **c, **kw)
+
+
+def run_elbo_list(DEV, fam, family, **kw):
+    """Every case of one list (what a child process started with KVAE_ELBO_TPP=0 or KVAE_N16=0 runs); prints and returns the
+    largest ratio per key."""
+    worst = {}
+    for c in ELBO_CASE_LISTS[fam][1]:
+        for k, v in run_elbo_case(DEV, fam, c, family=family, **kw).items():
+            worst[k] = min(worst.get(k, 1.0), v) if k == "ws_null_bits_equal" else max(worst.get(k, 0.0), v)
+    print("ELBO_WORST", fam, worst)
+    return worst
+
+
+def elbo_yardstick():
+    """The measured ELBO_YARDSTICK: float32 torch against float64 torch over every case list; a ".lv" key where the raised-level
+    cases differ by more than 2 x from level 0, else the larger of the two under the plain key."""
+    raw = {}
+    for fam in ELBO_CASE_LISTS:
+        for k, v in run_elbo_list("cpu", fam, None, yardstick=True).items():
+            raw[k] = max(raw.get(k, 0.0), v)
+    out = {}
+    for k, v in raw.items():
+        if k.endswith(".lv"):
+            base = raw.get(k[:-3])
+            if base is None or v > 2.0 * base or v < 0.5 * base:
+                out[k] = v
+                if base is None:
+                    out[k[:-3]] = v
+            else:
+                out[k[:-3]] = max(base, v)
+        else:
+            out.setdefault(k, v)
+    return dict(sorted(out.items()))

@@ -455,3 +455,19 @@ def test_alpha_lstm_per_step_hostsim(hostsim_backend, B, T, n, m, K, mask_kind, 
     checks the case function, the float64 reference O.lgssm_smooth(kind="lstm") with its masked feedback, and the yardstick
     before the card (tests/test_gpu_parity.py::test_alpha_lstm_per_step_gpu runs the same cases on the kernels)."""
     print(parity_cases.alpha_lstm_per_step("cpu", B, T, n, m, K, mask_kind, steps, with_rts))
+
+
+# ---- the ELBO bodies (csrc/lgssm_elbo.h) one (b,t) at a time against float64 ----
+@pytest.mark.parametrize("case", parity_cases.ELBO_TPP_CASES, ids=parity_cases.elbo_case_id)
+def test_elbo_per_step_hostsim(hostsim_backend, case):
+    """elbo_probe_body / elbo_body<SDims<4,4,2>> as the host simulation runs them - KV_PAR a serial loop, the thread-per-step form of
+    k_elbo_probe_tpp / k_elbo_tpp - at B T = 1 ... 129 and 37 x 23: the four terms and every gradient per (b,t) against float64, the
+    guard records, the exact zeros, ws_lz = NULL and the sequence isolation of parity_cases.elbo_per_step.  The family the host
+    simulation reports for the generic bodies must not be one of the matrix-core kernels (2, 3)."""
+    print(parity_cases.run_elbo_case("cpu", "tpp", case))
+
+
+@pytest.mark.parametrize("case", parity_cases.ELBO_RT_CASES, ids=parity_cases.elbo_case_id)
+def test_elbo_per_step_runtime_dims_hostsim(hostsim_backend, case):
+    """The same on elbo_probe_body / elbo_body<RDims>: (2,1,1) ... (16,16,16) and (1,1,1), B = 3, T = 1, 2, 7."""
+    print(parity_cases.run_elbo_case("cpu", "rt", case))

@@ -184,6 +184,7 @@ def test_jitter_ladder_torch_oracle(name, levels):
     elbo = O.lgssm_elbo(leaves["mu_s"], leaves["Sig_s"], leaves["a"], g["u"], leaves["A_list"], leaves["B_list"],
                         leaves["C_list"], leaves["Q_list"], g["R"], g["mu0"], g["Sigma0"], g["mask"], g["eps_z"])
     assert rel_err(elbo.detach(), g["elbo"]) < 1e-5
+    assert (lambda a: all(rel_err(s.sum(), w) < 1e-6 for s, w in zip(O.lgssm_elbo_terms(*a, per_step=True), O.lgssm_elbo_terms(*a))))([g[k] for k in ("mu_s", "Sig_s", "a", "u", "A_list", "B_list", "C_list", "Q_list", "R", "mu0", "Sigma0", "mask", "eps_z")])   # the un-summed [B,T] form sums to the existing return
     grads = torch.autograd.grad(-elbo, list(leaves.values()), allow_unused=True)
     for k, gr in zip(leaves, grads):
         ref = g["grad." + k]
