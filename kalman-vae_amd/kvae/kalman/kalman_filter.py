@@ -13,17 +13,17 @@ What differs is the execution: one launch (one wavefront per sequence, the whole
 RTS sweep inside the kernel) replaces ~580 aten calls per time step, and the backward is a
 hand-derived adjoint kernel instead of an autograd tape.  Inputs must live on a HIP device.
 Everything native is reached through lgssm_ops (the bridge; it also lays out the packed step record: Slots, alpha_lstm_slots,
-slot_view); the read-outs' torch restatements it falls back to are lgssm_torch's.
+slot_view); the read-outs' torch restatements it falls back to are lgssm_torch's.  Which operand form a pass used - a packed
+step record or plain stacks - is StepOperands' business (operands.py): every pass leaves its bundle in self._last, and the
+read-outs and the ELBO ask that bundle for their operands.
 """
 import torch
 import torch.nn as nn
 
-from .. import noise
-from ..noise import take as _take_noise
+from ..noise import normal as _normal
 from . import lgssm_ops
-from .lgssm_ops import LgssmElbo, LgssmSmooth, Slots
-
-_NO_SLOTS = Slots()
+from .lgssm_ops import LgssmElbo, LgssmSmooth
+from .operands import NO_PASS, StepOperands
 
 
 class KalmanFilter(nn.Module):
@@ -38,7 +38,7 @@ class KalmanFilter(nn.Module):
         self.register_buffer("I", torch.eye(n, dtype=dtp, device=dev))
         self.register_buffer("mu0", mu0.clone())
         self.register_buffer("Sigma0", Sigma0.clone())
-        self._last = None   # operand bundle of the most recent filter()/smooth() call
+        self._last = NO_PASS   # StepOperands of the most recent filter pass
 
     # ------------------------------------------------------------------------------------------
     # per-step operands
@@ -58,30 +58,26 @@ class KalmanFilter(nn.Module):
         return bool((mask != 0).all())
 
     def _operands(self, Y, mask):
-        """Build (record, slots, A, B, C, Q, views) for a whole sequence; None if the lstm alpha-net must be
-        stepped because some frames are missing."""
+        """StepOperands of a whole sequence; None if the lstm alpha-net must be stepped because some frames are missing."""
         dyn = self.dyn_params
         Bsz, T, _ = Y.shape
         if dyn.is_switching_dynamics:
             A_seq, B_seq, C_seq, Q_seq = dyn.compute_batch(Y, is_training=self.training)
-            rec, slots = getattr(dyn, "_record", None), getattr(dyn, "_slots", None)
-            if rec is not None:
-                return dict(rec=rec, slots=slots, A=None, B=None, C=dyn.C[0], Q=None,
-                            views=(A_seq, B_seq, C_seq), Q_view=Q_seq)
-            return dict(rec=None, slots=_NO_SLOTS, A=A_seq, B=B_seq, C=C_seq, Q=Q_seq,
-                        views=(A_seq, B_seq, C_seq), Q_view=Q_seq)
+            packed = dyn.packed_record()
+            if packed is None:
+                return StepOperands.plain(A_seq, B_seq, C_seq, Q_seq)
+            return StepOperands.packed(*packed, views=(A_seq, B_seq, C_seq), C=dyn.C[0], Q_view=Q_seq)
         if dyn.K == 1:
             A, Bm, C = dyn.A[0], dyn.B[0], dyn.C[0]
             ex = lambda M: M.expand(Bsz, T, -1, -1)
             dyn.state_seq = torch.ones(Bsz, T, 1, device=Y.device, dtype=Y.dtype)
-            return dict(rec=None, slots=_NO_SLOTS, A=A, B=Bm, C=C, Q=self.Q, views=(ex(A), ex(Bm), ex(C)),
-                        Q_view=None)
+            return StepOperands.plain(A, Bm, C, self.Q, views=(ex(A), ex(Bm), ex(C)))
         if not self._all_observed(mask):
             return None
         alpha = dyn.alpha_sequence(Y)
         rec, slots, views = dyn.step_record(alpha)
         dyn.state_seq = alpha
-        return dict(rec=rec, slots=slots, A=None, B=None, C=None, Q=self.Q, views=tuple(views), Q_view=None)
+        return StepOperands.packed(rec, slots, views, Q=self.Q)
 
     # ------------------------------------------------------------------------------------------
     # filter / smooth
@@ -96,9 +92,9 @@ class KalmanFilter(nn.Module):
         if mask_t is not None:
             mask_t = mask_t.to(device=y.device, dtype=y.dtype).expand(Bsz).reshape(Bsz, 1)
         st = lambda M, r, c: (M if M.dim() == 2 else M.reshape(Bsz, 1, r, c))
-        mf, Sf, mp, Sp = LgssmSmooth.apply(y, u, mask_t, None, st(A, self.n, self.n), st(B, self.n, self.m),
-                                           st(C, self.p, self.n), st(Q, self.n, self.n), self.R,
-                                           mu.contiguous(), Sigma_t_t.expand(Bsz, -1, -1).contiguous(), _NO_SLOTS, False)
+        ops = StepOperands.plain(st(A, self.n, self.n), st(B, self.n, self.m), st(C, self.p, self.n), st(Q, self.n, self.n))
+        mf, Sf, mp, Sp = LgssmSmooth.apply(y, u, mask_t, *ops.lgssm(self.R, mu.contiguous(),
+                                                                     Sigma_t_t.expand(Bsz, -1, -1).contiguous()), False)
         return mf[:, 0].unsqueeze(-1), Sf[:, 0], mp[:, 0].unsqueeze(-1), Sp[:, 0], A, B, C
 
     def _filter_stepwise(self, Y, U, mask):
@@ -126,62 +122,59 @@ class KalmanFilter(nn.Module):
             dyn.state_seq = torch.stack(dyn.state_seq, 1)
         return tuple(torch.stack(v, 1) for v in outs)
 
+    @staticmethod
+    def _six(outs, with_rts):
+        """(ms, Ss, mf, Sf, mp, Sp), the means as [B,T,n,1] columns, of a launch's (ms, Ss,) mf, Sf, mp, Sp; without the RTS sweep
+        ms and Ss are None."""
+        ms, Ss, mf, Sf, mp, Sp = outs if with_rts else (None, None) + tuple(outs)
+        return None if ms is None else ms.unsqueeze(-1), Ss, mf.unsqueeze(-1), Sf, mp.unsqueeze(-1), Sp
+
+    def _alpha_lstm(self, Y, U, mask, with_rts, keep_cell=False):
+        """The filter (+ RTS sweep) with the lstm alpha-network run inside the kernel, forward AND backward
+        (kvae_lgssm_filter_alpha_lstm / kvae_lgssm_alpha_lstm_bwd).  Leaves the pass's StepOperands in self._last and alpha in
+        dyn.state_seq; returns _six of the states and, with keep_cell, the cell's (h_seq, c_seq) [B,T,H]."""
+        dyn, n, m, p = self.dyn_params, self.n, self.m, self.p
+        outs = lgssm_ops.AlphaLstmSmooth.apply(Y, U, mask, dyn.lstm.weight_ih_l0, dyn.lstm.weight_hh_l0, dyn.lstm.bias_ih_l0,
+                                               dyn.lstm.bias_hh_l0, dyn.head_w.weight, dyn.head_w.bias, dyn.A, dyn.B, dyn.C,
+                                               self.Q, self.R, self.mu0, self.Sigma0, with_rts, keep_cell)
+        k = 6 if with_rts else 4
+        rec, dyn.state_seq = outs[k], outs[k + 1]
+        slots, _ = lgssm_ops.alpha_lstm_slots(n, m, p)
+        views = (lgssm_ops.slot_view(rec, slots.A, n, n), lgssm_ops.slot_view(rec, slots.B, n, m),
+                 lgssm_ops.slot_view(rec, slots.C, p, n))
+        self._last = StepOperands.packed(rec, slots, views, Q=self.Q)
+        return self._six(outs[:k], with_rts), outs[k + 2:]
+
     def _run(self, Y, U, mask, with_rts):
         if not Y.is_cuda:
             from .. import _native
             _native.lib_for(Y)  # raises: no CPU fallback (unless a test injected the host simulator)
         mask = self._mask(mask, Y)
         dyn = self.dyn_params
-        u1 = lambda v: v.unsqueeze(-1)
         if (mask is not None and not dyn.is_switching_dynamics and dyn.K > 1
                 and lgssm_ops.alpha_lstm_supported(Y, dyn.lstm, dyn.K)):
-            # lstm dynamics with an explicit mask: the alpha-network runs inside the filter kernel, forward AND backward
-            # (kvae_lgssm_filter_alpha_lstm / kvae_lgssm_alpha_lstm_bwd).  Whether the mask hides anything is never asked
-            # on the host: no sync, capturable, and a mask of ones (the reference's training loop) gives the same numbers
-            # as the precomputed-alpha path.
-            outs = lgssm_ops.AlphaLstmSmooth.apply(Y, U, mask, dyn.lstm.weight_ih_l0, dyn.lstm.weight_hh_l0, dyn.lstm.bias_ih_l0,
-                                                   dyn.lstm.bias_hh_l0, dyn.head_w.weight, dyn.head_w.bias, dyn.A, dyn.B, dyn.C,
-                                                   self.Q, self.R, self.mu0, self.Sigma0, with_rts)
-            rec, alpha = outs[-2], outs[-1]
-            n, m, p = self.n, self.m, self.p
-            slots, _ = lgssm_ops.alpha_lstm_slots(n, m, p)
-            views = (lgssm_ops.slot_view(rec, slots.A, n, n), lgssm_ops.slot_view(rec, slots.B, n, m),
-                     lgssm_ops.slot_view(rec, slots.C, p, n))
-            dyn.state_seq = alpha
-            self._last = dict(rec=rec, slots=slots, A=None, B=None, C=None, Q=self.Q, views=views, Q_view=None)
-            if with_rts:
-                ms, Ss, mf, Sf, mp, Sp = outs[:6]
-                return u1(ms), Ss, u1(mf), Sf, u1(mp), Sp
-            mf, Sf, mp, Sp = outs[:4]
-            return None, None, u1(mf), Sf, u1(mp), Sp
+            # lstm dynamics with an explicit mask: whether the mask hides anything is never asked on the host - no sync,
+            # capturable, and a mask of ones (the reference's training loop) gives the same numbers as the precomputed-alpha path.
+            return self._alpha_lstm(Y, U, mask, with_rts)[0]
         ops = self._operands(Y, mask)
-        if ops is None:  # lstm + missing frames on shapes outside the fused kernel (or host tensors in the test tier)
+        stepped = ops is None   # lstm + missing frames on shapes outside the fused kernel (or host tensors in the test tier)
+        if stepped:
             mf, Sf, mp, Sp, A_l, B_l, C_l = self._filter_stepwise(Y, U, mask)
-            self._last = dict(rec=None, slots=_NO_SLOTS, A=A_l, B=B_l, C=C_l, Q=self.Q, views=(A_l, B_l, C_l),
-                              Q_view=None)
-            if not with_rts:
-                return None, None, mf, Sf, mp, Sp
-            # smoother over the stepped filter results: RTS has no alpha dependence, reuse the fused op in
-            # "given operands" form by re-running filter+RTS in one launch on the per-step stacks
-            ms, Ss, mf, Sf, mp, Sp = LgssmSmooth.apply(Y, U, mask, None, A_l, B_l, C_l, self.Q, self.R, self.mu0,
-                                                       self.Sigma0, _NO_SLOTS, True)
-            return u1(ms), Ss, u1(mf), Sf, u1(mp), Sp
+            ops = StepOperands.plain(A_l, B_l, C_l, self.Q)
         self._last = ops
-        outs = LgssmSmooth.apply(Y, U, mask, ops["rec"], ops["A"], ops["B"], ops["C"], ops["Q"], self.R, self.mu0,
-                                 self.Sigma0, ops["slots"], with_rts)
-        if with_rts:
-            ms, Ss, mf, Sf, mp, Sp = outs
-            return u1(ms), Ss, u1(mf), Sf, u1(mp), Sp
-        mf, Sf, mp, Sp = outs
-        return None, None, u1(mf), Sf, u1(mp), Sp
+        if stepped and not with_rts:
+            return None, None, mf, Sf, mp, Sp
+        # the smoother over stepped filter results too: RTS has no alpha dependence, so the fused op re-runs filter+RTS in one
+        # launch on the per-step stacks
+        return self._six(LgssmSmooth.apply(Y, U, mask, *ops.lgssm(self.R, self.mu0, self.Sigma0), with_rts), with_rts)
 
     def filter(self, Y, U, mask=None):
         _, _, mf, Sf, mp, Sp = self._run(Y, U, mask, with_rts=False)
-        return (mf, Sf, mp, Sp) + tuple(self._last["views"])
+        return (mf, Sf, mp, Sp) + self._last.views
 
     def smooth(self, Y, U, mask=None):
         ms, Ss, mf, Sf, mp, Sp = self._run(Y, U, mask, with_rts=True)
-        return (ms, Ss, mf, Sf, mp, Sp) + tuple(self._last["views"])
+        return (ms, Ss, mf, Sf, mp, Sp) + self._last.views
 
     @torch.no_grad()
     def condition(self, Y, U, mask=None):
@@ -196,14 +189,9 @@ class KalmanFilter(nn.Module):
         out = {}
         if (not dyn.is_switching_dynamics and dyn.K > 1 and lgssm_ops.alpha_lstm_supported(Y, dyn.lstm, dyn.K)):
             m = mask if mask is not None else torch.ones(Bsz, T0, device=Y.device, dtype=Y.dtype)
-            mf, Sf, mp, Sp, rec, alpha, h_seq, c_seq = lgssm_ops.AlphaLstmSmooth.apply(
-                Y, U, m, dyn.lstm.weight_ih_l0, dyn.lstm.weight_hh_l0, dyn.lstm.bias_ih_l0, dyn.lstm.bias_hh_l0,
-                dyn.head_w.weight, dyn.head_w.bias, dyn.A, dyn.B, dyn.C, self.Q, self.R, self.mu0, self.Sigma0, False, True)
-            slots, _ = lgssm_ops.alpha_lstm_slots(self.n, self.m, self.p)
-            C_last = lgssm_ops.slot_view(rec[:, -1], slots.C, self.p, self.n)
-            dyn.state_seq = alpha
+            (_, _, mf, Sf, mp, Sp), (h_seq, c_seq) = self._alpha_lstm(Y, U, m, False, keep_cell=True)
+            C_last = self._last.views[2][:, -1]
             out.update(h=h_seq[:, -1], c=c_seq[:, -1])
-            mf, mp = mf.unsqueeze(-1), mp.unsqueeze(-1)
         else:
             mf, Sf, mp, Sp, _, _, C_list = self.filter(Y, U, mask)
             C_last = C_list[:, -1]
@@ -239,22 +227,12 @@ class KalmanFilter(nn.Module):
             raise ValueError(f"sample_posterior: num_samples must be >= 1, got {num_samples}")
         Bsz, T, _ = Y.shape
         _, _, mf, Sf, mp, Sp = self._run(Y, U, mask, with_rts=False)
-        last = self._last
-        A_l, B_l, C_l = last["views"]
-        dev, dt = Y.device, Y.dtype
-
-        def draw(slot, d):
-            v = _take_noise(slot)
-            return torch.randn(Bsz, S, T, d, device=dev, dtype=dt) if v is None else v.to(device=dev, dtype=dt).reshape(Bsz, S, T, d)
-
-        eps = draw("post_z", self.n) if noise else None
-        eta = draw("post_a", self.p) if emission_noise else None
+        eps = _normal("post_z", (Bsz, S, T, self.n), Y.device, Y.dtype) if noise else None
+        eta = _normal("post_a", (Bsz, S, T, self.p), Y.device, Y.dtype) if emission_noise else None
         LR = lgssm_ops.safe_cholesky(self.R) if emission_noise else None
-        Q = last["Q"] if last["Q"] is not None else last["Q_view"]
-        slots = last["slots"]
-        z, a, levels = lgssm_ops.posterior_paths(mf, Sf, mp, Sp, A_l, last["C"] if last["C"] is not None else C_l, Q, S, LR, eps, eta,
-                                                 packed=last["rec"], slots=Slots(A=slots.A, C=slots.C, Q=slots.Q))
-        return {"z": z, "a": a, "levels": levels, "filter": (mf, Sf, mp, Sp, A_l, B_l, C_l),
+        A, Cm, Q, packed, slots = self._last.posterior()
+        z, a, levels = lgssm_ops.posterior_paths(mf, Sf, mp, Sp, A, Cm, Q, S, LR, eps, eta, packed=packed, slots=slots)
+        return {"z": z, "a": a, "levels": levels, "filter": (mf, Sf, mp, Sp) + self._last.views,
                 "state_probs": self.dyn_params.state_seq}
 
     @torch.no_grad()
@@ -266,11 +244,9 @@ class KalmanFilter(nn.Module):
         Returns dict(ll [B,T], nis [B,T], a_pred [B,T,p], S [B,T,p,p], levels [B,T], seq_ll [B], filter = filter()'s 7-tuple,
         state_probs); ll and nis are 0 on hidden steps, a_pred and S are the forecast of every step."""
         _, _, mf, Sf, mp, Sp = self._run(Y, U, mask, with_rts=False)
-        last = self._last
-        A_l, B_l, C_l = last["views"]
-        out = lgssm_ops.predictive(mp, Sp, last["C"] if last["C"] is not None else C_l, self.R, Y, self._mask(mask, Y),
-                                   packed=last["rec"], slots=Slots(C=last["slots"].C), want=want)
-        out.update(filter=(mf, Sf, mp, Sp, A_l, B_l, C_l), state_probs=self.dyn_params.state_seq)
+        Cm, packed, slots = self._last.emission()
+        out = lgssm_ops.predictive(mp, Sp, Cm, self.R, Y, self._mask(mask, Y), packed=packed, slots=slots, want=want)
+        out.update(filter=(mf, Sf, mp, Sp) + self._last.views, state_probs=self.dyn_params.state_seq)
         return out
 
     @torch.no_grad()
@@ -299,18 +275,13 @@ class KalmanFilter(nn.Module):
         the C-slot gradient as the upstream of its record).  Returns dict(ll [B,T], seq_ll [B], levels [B,T], filter = filter()'s
         7-tuple, state_probs); ll is 0 on hidden steps."""
         _, _, mf, Sf, mp, Sp = self._run(Y, U, mask, with_rts=False)
-        A_l, B_l, C_l = self._last["views"]
-        out = self._log_marginal(mp, Sp, Y, C_l, mask)
-        out.update(filter=(mf, Sf, mp, Sp, A_l, B_l, C_l), state_probs=self.dyn_params.state_seq)
+        out = self._log_marginal(mp, Sp, Y, self._last.views[2], mask)
+        out.update(filter=(mf, Sf, mp, Sp) + self._last.views, state_probs=self.dyn_params.state_seq)
         return out
 
     def _log_marginal(self, mus_pred, Sigmas_pred, y_t, C_list, mask=None):
-        last = self._last
-        mask = self._mask(mask, y_t)
-        if last is not None and C_list is last["views"][2]:
-            return lgssm_ops.log_marginal(mus_pred, Sigmas_pred, last["C"] if last["C"] is not None else C_list, self.R, y_t, mask,
-                                          packed=last["rec"], slots=Slots(C=last["slots"].C))
-        return lgssm_ops.log_marginal(mus_pred, Sigmas_pred, C_list, self.R, y_t, mask)
+        Cm, packed, slots = self._last.emission(C_list)
+        return lgssm_ops.log_marginal(mus_pred, Sigmas_pred, Cm, self.R, y_t, self._mask(mask, y_t), packed=packed, slots=slots)
 
     def marginal(self, mus_pred, Sigmas_pred, y_t, C_list, mask=None):
         """The exact LGSSM objective, normalised as elbo(): (sum_b log p(a_b | u_b) [+ log_p - log_q of the regime chain]) / num_el,
@@ -328,10 +299,8 @@ class KalmanFilter(nn.Module):
 
     def emission_means(self, mus_smooth, mus_filt, C_list):
         """(C_t mu_t|T, C_t mu_t|t): the two latent read-outs KVAE.impute decodes (reference model.py:279-288), one launch."""
-        last = self._last
-        if last is not None and C_list is last["views"][2] and last["slots"].C is not None:
-            return lgssm_ops.emission_means(mus_smooth, mus_filt, C_list, last["rec"], last["slots"].C)
-        return lgssm_ops.emission_means(mus_smooth, mus_filt, C_list)
+        _, packed, slots = self._last.emission(C_list)
+        return lgssm_ops.emission_means(mus_smooth, mus_filt, C_list, packed, slots.C)
 
     # ------------------------------------------------------------------------------------------
     # ELBO
@@ -339,22 +308,16 @@ class KalmanFilter(nn.Module):
     def elbo(self, mu_t_T, Sigma_t_T, y_t, u_t, A_list, B_list, C_list, Q_list=None, mask=None, eps=None):
         Bsz, T = y_t.size(0), y_t.size(1)
         mask = self._mask(mask, y_t)
-        last = self._last
-        fast = (last is not None and Q_list is None and all(a is b for a, b in zip((A_list, B_list, C_list), last["views"])))
-        if fast:
-            rec, slots, A, Bm, Cm, Q = (last[k] for k in ("rec", "slots", "A", "B", "C", "Q"))
-        else:
-            rec, slots, A, Bm, Cm = None, _NO_SLOTS, A_list, B_list, C_list
+        ops = self._last
+        if Q_list is not None or not ops.owns(A_list, B_list, C_list):   # operands of the caller's own: plain stacks
             Q = Q_list if Q_list is not None else getattr(self.dyn_params, "Q_seq", None)
-            if Q is None:
-                Q = self.Q
+            ops = StepOperands.plain(A_list, B_list, C_list, self.Q if Q is None else Q)
         if eps is None:
-            eps = noise.take("eps_z")
-        if eps is None:
-            eps = torch.randn(Bsz, T, self.n, device=y_t.device, dtype=y_t.dtype)
-        eps = eps.to(device=y_t.device, dtype=y_t.dtype)
-        total, self.last_elbo_terms, self.last_chol_levels = LgssmElbo.apply(mu_t_T, Sigma_t_T, eps, y_t, u_t, mask, rec, A, Bm, Cm, Q,
-                                                      self.R, self.mu0, self.Sigma0, slots)
+            eps = _normal("eps_z", (Bsz, T, self.n), y_t.device, y_t.dtype)
+        else:
+            eps = eps.to(device=y_t.device, dtype=y_t.dtype)
+        total, self.last_elbo_terms, self.last_chol_levels = LgssmElbo.apply(
+            mu_t_T, Sigma_t_T, eps, y_t, u_t, mask, *ops.lgssm(self.R, self.mu0, self.Sigma0))
         if self.dyn_params.is_switching_dynamics:
             log_q, log_p = self.dyn_params.elbo_terms()
             total = total + log_p.sum() - log_q.sum()

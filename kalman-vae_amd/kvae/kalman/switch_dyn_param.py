@@ -46,7 +46,7 @@ class SwitchingDynamicsParameter(nn.Module):
             self.K, input_dim=self.p, hidden_size=hidden_lstm)
         self.hidden_size = hidden_lstm
         self.state_seq = None
-        self._record = self._slots = None
+        self._record = None
         self._pinned = None
 
     # The Gumbel-softmax temperature.  The reference's epoch loop assigns `dyn_params.tau = max(tau_min, tau * rate)`
@@ -70,7 +70,12 @@ class SwitchingDynamicsParameter(nn.Module):
 
     def reset_state(self):
         self.state_seq = None
-        self._record = self._slots = None
+        self._record = None
+
+    def packed_record(self):
+        """(record [B,T,E], Slots) of the A | B | Q step record the latest compute_batch mixed - what its A_seq, B_seq, Q_seq are
+        views of; None after reset_state() and for K = 1, whose stacks are plain."""
+        return self._record
 
     def _prior_matrix(self, dev, dt):
         """Device copy of the sticky prior, made once per device (a host->device copy is not allowed inside
@@ -146,17 +151,10 @@ class SwitchingDynamicsParameter(nn.Module):
             self.log_pseq = torch.zeros(Bsz, T, device=dev, dtype=dt)
             self.Q_seq = ex(self.Q)
             self.state_seq = torch.ones(Bsz, T, 1, device=dev, dtype=dt)
-            self._record = self._slots = None
+            self._record = None
             return ex(self.A), ex(self.B), ex(self.C), self.Q_seq
         logits, init_logits = self.markov_regime_posterior(a_seq)
-        if self._pinned is not None:
-            gumbel = None
-        else:
-            gumbel = noise.take("gumbel")
-            if gumbel is None:
-                gumbel = -torch.empty(Bsz, T, self.K, device=dev, dtype=dt).exponential_().log()
-            else:
-                gumbel = gumbel.to(device=dev, dtype=dt)
+        gumbel = noise.gumbel("gumbel", (Bsz, T, self.K), dev, dt) if self._pinned is None else None
         if self._pinned is not None:   # a given regime sequence (KVAE.decode_regimes: the most likely path)
             y_seq = self._pinned.to(device=dev, dtype=dt)
             if tuple(y_seq.shape) != (Bsz, T, self.K):
@@ -169,7 +167,7 @@ class SwitchingDynamicsParameter(nn.Module):
         else:
             y_seq, self.log_qseq, self.log_pseq = self.regime_chain(logits, init_logits, gumbel, hard=not is_training)
         rec, offs, (A_seq, B_seq, Q_seq) = mix_dynamics(y_seq, [self.A, self.B, self.Q])
-        self._record, self._slots = rec, Slots(A=offs[0], B=offs[1], Q=offs[2])
+        self._record = rec, Slots(A=offs[0], B=offs[1], Q=offs[2])
         C_seq = self.C[0].expand(Bsz, T, -1, -1)   # emission shared across regimes (switch_dyn_param.py:85-86)
         self.Q_seq = Q_seq
         self.state_seq = y_seq

@@ -6,17 +6,18 @@ signatures and output dictionaries.  For the reference's default shapes every la
 hand-written HIP kernels of csrc/vae_*.h (kvae/vae/fused.py; other shapes: MIOpen + fused epilogues), and everything
 between `a_samples` and the LGSSM ELBO runs in the HIP kernels behind `self.kalman_filter`.
 """
+import contextlib
 import math
 import os
 
 import torch
 from torch import nn
 
-from kvae import _native, noise
+from kvae import _native
 from kvae.kalman import dyn_param as base_dyn_param
 from kvae.kalman import lgssm_ops, switch_dyn_param
 from kvae.kalman.kalman_filter import KalmanFilter
-from kvae.noise import take as _take_noise
+from kvae.noise import gumbel as _gumbel, normal as _normal
 from kvae.vae.losses import LinearScheduler, count_active_units, log_gaussian, vae_loss
 from kvae.vae.vae import Decoder, Encoder
 
@@ -112,19 +113,15 @@ class KVAE(nn.Module):
     # -- VAE halves -----------------------------------------------------------------------------
     def reparameterize(self, mu, var):
         std = torch.sqrt(var + 1e-6)
-        eps = noise.take("eps_a")
-        eps = torch.randn_like(std) if eps is None else eps.to(device=std.device, dtype=std.dtype).reshape(std.shape)
-        return mu + eps * std
+        return mu + _normal("eps_a", std.shape, std.device, std.dtype) * std
 
     def encode_sequence(self, x, sample=True):
         """`sample=False`: a = a_mu (the heads kernel with eps = 0, no draw taken)."""
         lead = x.shape[:2]
         feat = self.encoder.features(x.flatten(0, 1))
-        eps = noise.take("eps_a") if sample else torch.zeros(feat.shape[0], self.config.a_dim, device=feat.device, dtype=feat.dtype)
-        if eps is None:
-            eps = torch.randn(feat.shape[0], self.config.a_dim, device=feat.device, dtype=feat.dtype)
-        else:
-            eps = eps.to(device=feat.device, dtype=feat.dtype).reshape(feat.shape[0], self.config.a_dim)
+        shape = (feat.shape[0], self.config.a_dim)
+        eps = (_normal("eps_a", shape, feat.device, feat.dtype) if sample
+               else torch.zeros(shape, device=feat.device, dtype=feat.dtype))
         a, mu, var = self.encoder.heads(feat, eps)   # both heads + reparameterisation: one kernel on the GPU path
         return a.unflatten(0, lead), mu.unflatten(0, lead), var.unflatten(0, lead)
 
@@ -140,6 +137,49 @@ class KVAE(nn.Module):
     def _to_pixels(self, logits):
         return torch.sigmoid(logits) if self.config.out_distr.lower() == "bernoulli" else logits
 
+    def _zero_u(self, like):
+        return torch.zeros(like.shape[0], like.shape[1], self.u_dim, device=like.device, dtype=like.dtype)
+
+    # -- what the eval-mode read-outs share ------------------------------------------------------
+    def _check_mask_u(self, who, x, mask, u, required=False, horizon=0):
+        """mask [B,T] (`required`: None is an error too) and u [B,T,m] - [B,T0+H,m] with a `horizon` - or None."""
+        Bsz, T = x.shape[:2]
+        if (required and mask is None) or (mask is not None and tuple(mask.shape) != (Bsz, T)):
+            raise ValueError(f"{who}: mask must be [B, T] = [{Bsz}, {T}], got {None if mask is None else list(mask.shape)}")
+        steps, name = (T + horizon, "T0+H") if horizon else (T, "T")
+        if u is not None and (u.dim() != 3 or u.shape[0] != Bsz or u.shape[1] != steps or u.shape[2] != self.u_dim):
+            raise ValueError(f"{who}: u must be [B, {name}, m] = [{Bsz}, {steps}, {self.u_dim}], got {list(u.shape)}")
+
+    def _readout(self, who, x, u, mask, sample=True, **check):
+        """Prelude of a read-out: `with self._readout(...) as (a_vae, a_mu, a_var, u, mask)`.  mask and u are checked HERE, at
+        the call (_check_mask_u); entering the block puts the model in eval mode - whatever way the block is left restores the
+        mode it was in - and encodes x (sample=False: a_vae = a_mu, no draw taken); u (zeros for None) and mask (None stays
+        None) come back on the encodings' device and dtype.  No host synchronisation."""
+        self._check_mask_u(who, x, mask, u, **check)
+
+        @contextlib.contextmanager
+        def block():
+            was_training = self.training
+            self.eval()
+            try:
+                a_vae, a_mu, a_var = self.encode_sequence(x, sample=sample)
+                dev, dt = a_vae.device, a_vae.dtype
+                yield (a_vae, a_mu, a_var, self._zero_u(a_vae) if u is None else u.to(device=dev, dtype=dt),
+                       None if mask is None else mask.to(device=dev, dtype=dt))
+            finally:
+                self.train(was_training)
+        return block()
+
+    @staticmethod
+    def _n_obs(mask, a):
+        """Observed steps per sequence [B] of latents a [B,T,p] under mask [B,T] or None, on the device."""
+        return torch.full((a.shape[0],), float(a.shape[1]), device=a.device, dtype=a.dtype) if mask is None else mask.sum(1)
+
+    def _decode_latents(self, a, dtype):
+        """Pixels [B, ..., C, h, w] of latents a [B, ..., p]: one decoder pass over all of them."""
+        x = self._to_pixels(self.decode_sequence(a.reshape(a.shape[0], -1, a.shape[-1]).to(dtype)))
+        return x.unflatten(1, a.shape[1:-1])
+
     # -- full pass ------------------------------------------------------------------------------
     def forward(self, x, u=None, mask=None, with_recon=True):
         """`with_recon=False` (addition over the reference) skips sigmoid(x_logits): the training loss only
@@ -148,7 +188,7 @@ class KVAE(nn.Module):
         probabilities: decode_regimes() gives the marginals and the most likely path."""
         a_samples, a_mu, a_var = self.encode_sequence(x)
         if u is None:
-            u = torch.zeros(x.shape[0], x.shape[1], self.u_dim, device=x.device, dtype=x.dtype)
+            u = self._zero_u(x)
         self.kalman_filter.dyn_params.reset_state()
         side = self.lgssm_stream if (self.training and a_samples.is_cuda) else None
         a_side = None
@@ -201,7 +241,7 @@ class KVAE(nn.Module):
         A_list, B_list, C_list = outputs["ABC"]
         u = outputs.get("u")
         if u is None:
-            u = torch.zeros(B, T, self.u_dim, device=x.device, dtype=x.dtype)
+            u = self._zero_u(x)
         x_mu = outputs["x_logits"] if outputs.get("x_logits") is not None else outputs["x_recon"]
         side = self.lgssm_stream if (self.training and a.is_cuda) else None
 
@@ -337,30 +377,11 @@ class KVAE(nn.Module):
         num_samples = int(num_samples)
         if num_samples < 1:
             raise ValueError(f"sample_imputations: num_samples must be >= 1, got {num_samples}")
-        Bsz, T = x.shape[:2]
-        if mask is None or tuple(mask.shape) != (Bsz, T):
-            raise ValueError(f"sample_imputations: mask must be [B, T] = [{Bsz}, {T}], got "
-                             f"{None if mask is None else list(mask.shape)}")
-        if u is not None and (u.dim() != 3 or u.shape[0] != Bsz or u.shape[1] != T or u.shape[2] != self.u_dim):
-            raise ValueError(f"sample_imputations: u must be [B, T, m] = [{Bsz}, {T}, {self.u_dim}], got {list(u.shape)}")
-        was_training = self.training
-        self.eval()
-        try:
-            a_vae, _, _ = self.encode_sequence(x)
-            dev, dt = a_vae.device, a_vae.dtype
-            u = torch.zeros(Bsz, T, self.u_dim, device=dev, dtype=dt) if u is None else u.to(device=dev, dtype=dt)
+        with self._readout("sample_imputations", x, u, mask, required=True) as (a_vae, _, _, u, mask):
             self.kalman_filter.dyn_params.reset_state()
-            post = self.kalman_filter.sample_posterior(a_vae, u, mask.to(device=dev, dtype=dt), num_samples, noise=noise,
-                                                       emission_noise=emission_noise)
-            a = post["a"]
-            x_s = None
-            if decode:
-                x_s = self._to_pixels(self.decode_sequence(a.reshape(Bsz, num_samples * T, self.a_dim).to(dt))).unflatten(
-                    1, (num_samples, T))
-            return {"x": x_s, "a": a, "z": post["z"], "a_vae": a_vae, "state_probs": post["state_probs"],
-                    "levels": post["levels"]}
-        finally:
-            self.train(was_training)
+            post = self.kalman_filter.sample_posterior(a_vae, u, mask, num_samples, noise=noise, emission_noise=emission_noise)
+            return {"x": self._decode_latents(post["a"], a_vae.dtype) if decode else None, "a": post["a"], "z": post["z"],
+                    "a_vae": a_vae, "state_probs": post["state_probs"], "levels": post["levels"]}
 
     @torch.no_grad()
     def decode_regimes(self, x, u=None, mask=None, sample_a=False, smooth=True, decode=False):
@@ -381,40 +402,22 @@ class KVAE(nn.Module):
         if not dyn.is_switching_dynamics:
             raise ValueError('decode_regimes needs a model with dynamics = "switching" (config.dynamics_model); this one has '
                              f'"{self.config.dynamics_model}"')
-        Bsz, T = x.shape[:2]
-        if mask is not None and tuple(mask.shape) != (Bsz, T):
-            raise ValueError(f"decode_regimes: mask must be [B, T] = [{Bsz}, {T}], got {list(mask.shape)}")
-        if u is not None and (u.dim() != 3 or u.shape[0] != Bsz or u.shape[1] != T or u.shape[2] != self.u_dim):
-            raise ValueError(f"decode_regimes: u must be [B, T, m] = [{Bsz}, {T}, {self.u_dim}], got {list(u.shape)}")
+        prelude = self._readout("decode_regimes", x, u, mask, sample=bool(sample_a))   # its shape checks come before this one
         if decode and not smooth:
             raise ValueError("decode_regimes: decode=True needs smooth=True (x_imputed is decoded from the smoothed latents)")
-        was_training = self.training
-        self.eval()
-        try:
-            a_vae, _, _ = self.encode_sequence(x, sample=bool(sample_a))
-            dev, dt = a_vae.device, a_vae.dtype
+        with prelude as (a_vae, _, _, u, mask):
             dyn.reset_state()
             out = dict(dyn.decode(a_vae), a_vae=a_vae)
             if smooth:
-                u = torch.zeros(Bsz, T, self.u_dim, device=dev, dtype=dt) if u is None else u.to(device=dev, dtype=dt)
-                y_map = torch.nn.functional.one_hot(out["regimes"], self.K).to(dt)
+                y_map = torch.nn.functional.one_hot(out["regimes"], self.K).to(a_vae.dtype)
                 with dyn.pinned(y_map):
-                    sm = self.kalman_filter.smooth(a_vae, u, mask=None if mask is None else mask.to(device=dev, dtype=dt))
+                    sm = self.kalman_filter.smooth(a_vae, u, mask=mask)
                 ms, Ss, mf, _, _, _, A_list, B_list, C_list = sm
                 a_imputed, _ = self.kalman_filter.emission_means(ms, mf, C_list)
                 out.update(mus_smooth=ms, Sigmas_smooth=Ss, mus_filt=mf, ABC=(A_list, B_list, C_list), a_imputed=a_imputed)
                 if decode:
                     out["x_imputed"] = self._to_pixels(self.decode_sequence(a_imputed))
             return out
-        finally:
-            self.train(was_training)
-
-    def _check_mask_u(self, who, x, mask, u):
-        Bsz, T = x.shape[:2]
-        if mask is not None and tuple(mask.shape) != (Bsz, T):
-            raise ValueError(f"{who}: mask must be [B, T] = [{Bsz}, {T}], got {list(mask.shape)}")
-        if u is not None and (u.dim() != 3 or u.shape[0] != Bsz or u.shape[1] != T or u.shape[2] != self.u_dim):
-            raise ValueError(f"{who}: u must be [B, T, m] = [{Bsz}, {T}, {self.u_dim}], got {list(u.shape)}")
 
     @torch.no_grad()
     def score(self, x, u=None, mask=None, sample_a=False, regimes="map", decode=False):
@@ -436,33 +439,22 @@ class KVAE(nn.Module):
         Training mode, tau and parameters are left as they were."""
         if regimes not in ("map", "draw"):
             raise ValueError(f'score: regimes must be "map" or "draw", got {regimes!r}')
-        self._check_mask_u("score", x, mask, u)
         dyn = self.kalman_filter.dyn_params
-        Bsz, T = x.shape[:2]
-        was_training = self.training
-        self.eval()
-        try:
-            a_vae, _, _ = self.encode_sequence(x, sample=bool(sample_a))
-            dev, dt = a_vae.device, a_vae.dtype
-            u = torch.zeros(Bsz, T, self.u_dim, device=dev, dtype=dt) if u is None else u.to(device=dev, dtype=dt)
-            mk = None if mask is None else mask.to(device=dev, dtype=dt)
+        with self._readout("score", x, u, mask, sample=bool(sample_a)) as (a_vae, _, _, u, mask):
             dyn.reset_state()
             out = {}
             if dyn.is_switching_dynamics and regimes == "map":
                 dec = dyn.decode(a_vae)
-                with dyn.pinned(torch.nn.functional.one_hot(dec["regimes"], self.K).to(dt)):
-                    pred = self.kalman_filter.predictive(a_vae, u, mk)
+                with dyn.pinned(torch.nn.functional.one_hot(dec["regimes"], self.K).to(a_vae.dtype)):
+                    pred = self.kalman_filter.predictive(a_vae, u, mask)
                 out.update(regimes=dec["regimes"], regimes_logq=dec["regimes_logq"])
             else:
-                pred = self.kalman_filter.predictive(a_vae, u, mk)
-            n_obs = torch.full((Bsz,), float(T), device=dev, dtype=dt) if mk is None else mk.sum(1)
+                pred = self.kalman_filter.predictive(a_vae, u, mask)
             out.update(log_lik=pred["ll"], log_lik_seq=pred["seq_ll"], nis=pred["nis"], a_pred=pred["a_pred"], S=pred["S"],
-                       levels=pred["levels"], a_vae=a_vae, state_probs=pred["state_probs"], n_obs=n_obs)
+                       levels=pred["levels"], a_vae=a_vae, state_probs=pred["state_probs"], n_obs=self._n_obs(mask, a_vae))
             if decode:
-                out["x_pred"] = self._to_pixels(self.decode_sequence(pred["a_pred"].to(dt)))
+                out["x_pred"] = self._decode_latents(pred["a_pred"], a_vae.dtype)
             return out
-        finally:
-            self.train(was_training)
 
     @torch.no_grad()
     def filter_regimes(self, x, u=None, mask=None, sample_a=False, state=None, decode=False):
@@ -488,25 +480,15 @@ class KVAE(nn.Module):
         if not dyn.is_switching_dynamics:
             raise ValueError('filter_regimes needs a model with dynamics = "switching" (config.dynamics_model); this one has '
                              f'"{self.config.dynamics_model}"')
-        self._check_mask_u("filter_regimes", x, mask, u)
-        Bsz, T = x.shape[:2]
-        was_training = self.training
-        self.eval()
-        try:
-            a_vae, _, _ = self.encode_sequence(x, sample=bool(sample_a))
-            dev, dt = a_vae.device, a_vae.dtype
-            u = torch.zeros(Bsz, T, self.u_dim, device=dev, dtype=dt) if u is None else u.to(device=dev, dtype=dt)
-            mk = None if mask is None else mask.to(device=dev, dtype=dt)
-            out = self.kalman_filter.filter_regimes(a_vae, u, mk, state=state)
+        with self._readout("filter_regimes", x, u, mask, sample=bool(sample_a)) as (a_vae, _, _, u, mask):
+            out = self.kalman_filter.filter_regimes(a_vae, u, mask, state=state)
             rf = out["regime_filt"]
             out["regimes"] = (rf == rf.max(-1, keepdim=True).values).to(torch.int8).argmax(-1)   # lowest index among the maxima
             out["a_vae"] = a_vae
-            out["n_obs"] = torch.full((Bsz,), float(T), device=dev, dtype=dt) if mk is None else mk.sum(1)
+            out["n_obs"] = self._n_obs(mask, a_vae)
             if decode:
-                out["x_pred"] = self._to_pixels(self.decode_sequence(out["a_pred"].to(dt)))
+                out["x_pred"] = self._decode_latents(out["a_pred"], a_vae.dtype)
             return out
-        finally:
-            self.train(was_training)
 
     @torch.no_grad()
     def log_likelihood(self, x, num_samples=1, u=None, mask=None):
@@ -526,21 +508,14 @@ class KVAE(nn.Module):
         S = int(num_samples)
         if S < 1:
             raise ValueError(f"log_likelihood: num_samples must be >= 1, got {num_samples}")
-        self._check_mask_u("log_likelihood", x, mask, u)
         dyn = self.kalman_filter.dyn_params
         Bsz, T = x.shape[:2]
-        was_training = self.training
-        self.eval()
-        try:
-            _, a_mu, a_var = self.encode_sequence(x, sample=False)
+        with self._readout("log_likelihood", x, u, mask, sample=False) as (_, a_mu, a_var, u, mask):
             dev, dt = a_mu.device, a_mu.dtype
-            eps = _take_noise("ll_a")
-            eps = (torch.randn(Bsz, S, T, self.a_dim, device=dev, dtype=dt) if eps is None
-                   else eps.to(device=dev, dtype=dt).reshape(Bsz, S, T, self.a_dim))
+            eps = _normal("ll_a", (Bsz, S, T, self.a_dim), dev, dt)
             a_s = a_mu.unsqueeze(1) + torch.sqrt(a_var).unsqueeze(1) * eps                      # [B,S,T,p]
             rows = a_s.reshape(Bsz * S, T, self.a_dim)
-            u = torch.zeros(Bsz, T, self.u_dim, device=dev, dtype=dt) if u is None else u.to(device=dev, dtype=dt)
-            mk = torch.ones(Bsz, T, device=dev, dtype=dt) if mask is None else mask.to(device=dev, dtype=dt)
+            mk = torch.ones(Bsz, T, device=dev, dtype=dt) if mask is None else mask
             rep = lambda t: t.repeat_interleave(S, 0)
             dyn.reset_state()
             pred = self.kalman_filter.predictive(rows, rep(u), None if mask is None else rep(mk), want=("seq_ll",))
@@ -568,8 +543,6 @@ class KVAE(nn.Module):
             return {"log_px": lse - math.log(S), "elbo": log_w.mean(1), "log_w": log_w, "log_px_a": log_px_a, "log_pa": log_pa,
                     "log_qa": log_qa, "log_ps_qs": log_ps_qs, "ess": torch.exp(2.0 * lse - torch.logsumexp(2.0 * log_w, 1)),
                     "n_obs": mk.sum(1)}
-        finally:
-            self.train(was_training)
 
     @torch.no_grad()
     def generate(self, x, horizon, num_samples=1, u=None, mask=None, noise=True, decode=True):
@@ -597,33 +570,21 @@ class KVAE(nn.Module):
             raise ValueError(f"generate: num_samples must be >= 1, got {num_samples}")
         Bsz, T0 = x.shape[:2]
         H, S = horizon, num_samples
-        if u is not None and (u.dim() != 3 or u.shape[0] != Bsz or u.shape[1] != T0 + H or u.shape[2] != self.u_dim):
-            raise ValueError(f"generate: u must be [B, T0+H, m] = [{Bsz}, {T0 + H}, {self.u_dim}], got {list(u.shape)}")
-        was_training = self.training
-        self.eval()
-        try:
+        # the conditioning mask goes to condition() as it came, which takes any shape of B*T0 elements
+        with self._readout("generate", x, u, None, horizon=H) as (a_vae, _, _, u_all, _):
             kf, dyn = self.kalman_filter, self.kalman_filter.dyn_params
-            a_vae, _, _ = self.encode_sequence(x)
             dev, dt = a_vae.device, a_vae.dtype
-            if u is None:
-                u_cond, u_fut = torch.zeros(Bsz, T0, self.u_dim, device=dev, dtype=dt), None
-            else:
-                u = u.to(device=dev, dtype=dt)
-                u_cond, u_fut = u[:, :T0], u[:, T0:]
+            u_cond, u_fut = (u_all, None) if u is None else (u_all[:, :T0], u_all[:, T0:])   # without u: zeros [B,T0,m]
             hand = kf.condition(a_vae, u_cond, mask)
             n, p, K = self.z_dim, self.a_dim, self.K
             switching = dyn.is_switching_dynamics
             draws = dict(eps0=None, eps_z=None, eps_a=None, gumbel=None)
             L0 = LQ = LR = None
             if noise:
-                def draw(slot, *shape):
-                    v = _take_noise(slot)
-                    return torch.randn(*shape, device=dev, dtype=dt) if v is None else v.to(device=dev, dtype=dt).reshape(shape)
-                draws.update(eps0=draw("gen_z0", Bsz, S, n), eps_z=draw("gen_z", Bsz, S, H, n), eps_a=draw("gen_a", Bsz, S, H, p))
+                draws.update(eps0=_normal("gen_z0", (Bsz, S, n), dev, dt), eps_z=_normal("gen_z", (Bsz, S, H, n), dev, dt),
+                             eps_a=_normal("gen_a", (Bsz, S, H, p), dev, dt))
                 if switching:
-                    g = _take_noise("gen_gumbel")
-                    draws["gumbel"] = (-torch.empty(Bsz, S, H, K, device=dev, dtype=dt).exponential_().log() if g is None
-                                       else g.to(device=dev, dtype=dt).reshape(Bsz, S, H, K))
+                    draws["gumbel"] = _gumbel("gen_gumbel", (Bsz, S, H, K), dev, dt)
                 L0 = lgssm_ops.safe_cholesky(hand["Sigma"])
                 LQ = lgssm_ops.safe_cholesky(dyn.Q.detach() if switching else kf.Q)
                 LR = lgssm_ops.safe_cholesky(kf.R)
@@ -638,9 +599,4 @@ class KVAE(nn.Module):
                 kind, extra = "lstm", {}
             a, z, w = lgssm_ops.rollout(kind, dyn.A.detach(), dyn.B.detach(), dyn.C.detach(), hand["mu"], L0, u_fut, LQ, LR, S, H,
                                         **extra, **draws)
-            x_gen = None
-            if decode:
-                x_gen = self._to_pixels(self.decode_sequence(a.reshape(Bsz, S * H, p).to(dt))).unflatten(1, (S, H))
-            return {"a": a, "z": z, "weights": w, "x": x_gen, "a_vae": a_vae}
-        finally:
-            self.train(was_training)
+            return {"a": a, "z": z, "weights": w, "x": self._decode_latents(a, dt) if decode else None, "a_vae": a_vae}

@@ -6,7 +6,7 @@ The reference draws its randomness from torch's global generator in three places
   * gumbel_softmax               gumbel ~ Gumbel  [B,T,K]           (switch_dyn_param.py:52,69)
 Results on a GPU can only be compared with the CPU oracle if both consume the same draws, so the
 drop-in classes look here first: inside `with inject(eps_a=..., eps_z=..., gumbel=...)` the given
-tensors are used instead of fresh device-side draws.
+tensors are used instead of fresh device-side draws.  Every draw site asks normal() / gumbel() below.
 
 KVAE.generate (no counterpart in the reference) draws four more, all before its one rollout launch:
   * gen_z0      ~ N(0,1)  [B,S,n]     start state z_{T0-1} = mu + L_Sigma gen_z0
@@ -24,6 +24,8 @@ KVAE.log_likelihood (no counterpart either) draws one, before the filter runs:
 """
 import contextlib
 
+import torch
+
 _slots = {"eps_a": None, "eps_z": None, "gumbel": None, "gen_z0": None, "gen_z": None, "gen_a": None, "gen_gumbel": None,
           "post_z": None, "post_a": None, "ll_a": None}
 
@@ -32,6 +34,20 @@ def take(name):
     v = _slots.get(name)
     _slots[name] = None if v is None else v  # values stay for the whole context (re-usable)
     return v
+
+
+def normal(slot, shape, device, dtype):
+    """The tensor injected into `slot`, moved, cast and reshaped to `shape`; without one a fresh N(0,1) draw of that shape."""
+    v = take(slot)
+    return torch.randn(shape, device=device, dtype=dtype) if v is None else v.to(device=device, dtype=dtype).reshape(shape)
+
+
+def gumbel(slot, shape, device, dtype):
+    """As normal(), the fresh draw being standard Gumbel: -log(Exp(1))."""
+    v = take(slot)
+    if v is None:
+        return -torch.empty(shape, device=device, dtype=dtype).exponential_().log()
+    return v.to(device=device, dtype=dtype).reshape(shape)
 
 
 @contextlib.contextmanager

@@ -57,7 +57,7 @@ def main():
             kf.dyn_params.reset_state()
             post = kf.sample_posterior(a_vae, torch.zeros(B, T, cfg.u_dim, device=DEV), mask, num_samples=1, noise=False)
         mf, Sf, mp, Sp, A_l, _, C_l = post["filter"]
-        Q = kf._last["Q"] if kf._last["Q"] is not None else kf._last["Q_view"]
+        Q = kf._last.transition_noise()
         eps = torch.randn(B, S, T, n, device=DEV)
         ops = dict(mus_filt=mf, Sigmas_filt=Sf, mus_pred=mp, Sigmas_pred=Sp, A=A_l, Cm=C_l, Q=Q, S=S, eps=eps)
         call = lgssm_ops.PosteriorCall(**ops)
