@@ -1,7 +1,7 @@
 """CPU tier of KVAE.generate: the host simulation injected (as tests/test_wave_emu.py does), so the rollout runs the kernel body
 of csrc/lgssm_gen.h on emulated wavefronts (tests/hostsim/wave_emu.h).  Noise-free generation against the reference's impute
 with the tail hidden (tests/golden/make_goldens_generate.py), the rollout with injected noise against an fp64 restatement
-(tests/gen_cases.py), the structure of sampled regimes, argument errors, and the kernel body under ASan + UBSan."""
+(tests/gen_cases.py: whole tensors, and per (rollout, step) up to 3073 rollouts), the structure of sampled regimes, argument errors, and the kernel body under ASan + UBSan."""
 import ctypes
 import os
 import subprocess
@@ -74,6 +74,43 @@ def test_switching_regimes(wave_emu_backend):
     _, _, w = gen_cases.rollout_vs_restatement("cpu", pr)
     start = pr["s0"][:, None, None, :].expand_as(w)
     assert torch.equal(w, start)
+
+
+def test_restate_vec_is_restate():
+    """The side-by-side float64 form of the restatement (the reference at thousands of rollouts) IS the scalar one: 1e-12."""
+    for c in gen_cases.GEN_CASES[:22]:
+        pr = gen_cases.gen_case_problem(c)
+        for x, y in zip(gen_cases.restate(pr, torch.float64), gen_cases.restate_vec(pr, torch.float64)):
+            assert x.shape == y.shape and float((x - y).abs().max()) <= 1e-12, gen_cases.gen_case_id(c)
+
+
+def test_per_step_case_lists_reach_every_edge():
+    """What the lists of rollout_per_step promise: every dispatch with K = 1, 2, 3, 16; every (B, S) of the quad; H = 1, 2, 3, 8;
+    p = 1, 2, 3, 16; controls present and absent; every noise subset; 3072 and 3073 rollouts on each of the four instantiations."""
+    cs = gen_cases.GEN_CASES
+    assert {(c["kind"], c["n"], c["m"], c["K"]) for c in cs} == {d + (K,) for d in gen_cases.GEN_DISPATCHES for K in (1, 2, 3, 16)}
+    assert {(c["B"], c["S"]) for c in cs} == set(gen_cases.GEN_BS) and {c["H"] for c in cs} == {1, 2, 3, 8}
+    assert {c["p"] for c in cs} == {1, 2, 3, 16} and {c["with_u"] for c in cs} == {True, False}
+    for kind, names in (("lstm", {"none", "eps0", "eps_z", "eps_a", "all"}), ("switching", {"none", "eps0", "gumbel", "eps_a", "all"})):
+        assert {c["noise"] for c in cs if c["kind"] == kind} == names
+        assert {c["with_u"] for c in cs if c["kind"] == kind} == {True, False}
+    assert {c["p"] for c in cs if c["kind"] == "switching"} == {1, 3, 16} == {c["p"] for c in cs if c["kind"] == "lstm" and c["K"] == 1}
+    fams = {(gen_cases.gen_family(c["kind"], c["n"], c["m"]), c["B"] * c["S"]) for c in gen_cases.GEN_LARGE_CASES}
+    assert fams >= {(f, R) for f in ("lstm4", "lstm16", "rt", "sw") for R in (3072, 3073)}
+    assert all(gen_cases.GEN_STEP_TOL[k] == 4.0 * v and v > 0 for k, v in gen_cases.GEN_YARDSTICK.items())
+
+
+@pytest.mark.parametrize("case", gen_cases.GEN_CASES, ids=gen_cases.gen_case_id)
+def test_rollout_per_step(wave_emu_backend, case):
+    """Every (rollout, step) of a, z, weights against the float64 restatement under GEN_STEP_TOL; guards, sentinels, exact
+    regimes, isolation of the sequences (gen_cases.rollout_per_step, which also asserts that the emulated kernel ran)."""
+    print(gen_cases.run_gen_case("cpu", case))
+
+
+@pytest.mark.parametrize("case", gen_cases.GEN_LARGE_CASES, ids=gen_cases.gen_case_id)
+def test_rollout_per_step_many_rollouts(wave_emu_backend, case):
+    """3072 rollouts (the last size at 4 per wavefront) and 3073 (8 per wavefront, the last one ragged) on every instantiation."""
+    print(gen_cases.run_gen_case("cpu", case))
 
 
 def small_model(kind="lstm", K=3, **kw):

@@ -1,4 +1,4 @@
-"""GPU tier of KVAE.generate on gfx950: the parity cases of tests/test_generate.py on the device, the statistics of sampled
+"""GPU tier of KVAE.generate on gfx950: the parity cases of tests/test_generate.py on the device (the per-step ones included), the statistics of sampled
 rollouts against their closed form, the torch fallback, training left bit-identical, determinism, and the rollout kernel's
 resource report (no scratch)."""
 import os
@@ -48,6 +48,16 @@ def test_kernel_many_rollouts_gpu():
                                   eps_a=a["eps_a"])
     for x, r in zip(got, ref):
         assert float((x - r).abs().max()) < 1e-4
+
+
+@pytest.mark.parametrize("case", gen_cases.GEN_CASES, ids=gen_cases.gen_case_id)
+def test_rollout_per_step_gpu(case):
+    print(gen_cases.run_gen_case(DEV, case))
+
+
+@pytest.mark.parametrize("case", gen_cases.GEN_LARGE_CASES, ids=gen_cases.gen_case_id)
+def test_rollout_per_step_many_rollouts_gpu(case):
+    print(gen_cases.run_gen_case(DEV, case))
 
 
 def test_sample_statistics_gpu():

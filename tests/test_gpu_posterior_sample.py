@@ -1,5 +1,5 @@
 """GPU tier of KalmanFilter.sample_posterior / KVAE.sample_imputations on gfx950: the cases of tests/test_posterior_sample.py on
-the device (reference fixtures, moments at S = 8192, restatement, ladder, model level), a large case against the torch path,
+the device (reference fixtures, moments at S = 8192, restatement, per-item and per-step cases, ladder, model level), a large case against the torch path,
 determinism, and training left bit-identical."""
 import pytest
 import torch
@@ -67,6 +67,25 @@ def test_misaligned_operands_take_the_fallback_gpu(n):
 def test_ladder_levels_per_item_gpu():
     post_cases.check_ladder(DEV)
     post_cases.check_ladder(DEV, impl="torch")
+
+
+@pytest.mark.parametrize("case", post_cases.POST_GAIN_CASES, ids=post_cases.post_case_id)
+def test_gains_per_item_gpu(case):
+    print(post_cases.run_gain_case(DEV, case))
+
+
+@pytest.mark.parametrize("name", list(post_cases.LADDER_CASES))
+def test_ladder_per_item_gpu(name):
+    print(post_cases.ladder_per_item(DEV, name))
+
+
+@pytest.mark.parametrize("case", post_cases.POST_RING_CASES + post_cases.POST_SHAPE_CASES, ids=post_cases.post_case_id)
+def test_paths_per_step_gpu(case):
+    print(post_cases.run_path_case(DEV, case))
+
+
+def test_paths_per_step_emission_grid_stride_gpu():
+    print(post_cases.run_path_case(DEV, post_cases.POST_EMIT_CASE))
 
 
 @pytest.mark.parametrize("kind", ["lstm", "switching"])

@@ -1,7 +1,7 @@
 """CPU tier of KalmanFilter.sample_posterior / KVAE.sample_imputations: the host simulation injected (as tests/test_generate.py
 does), so the gains and the paths run the kernel bodies of csrc/lgssm_post.h on emulated wavefronts (tests/hostsim/wave_emu.h).
 Pinned to the reference's masked fixtures (noise-free paths, moments of sampled paths), against an fp64 restatement
-(tests/post_cases.py), the per-item Cholesky ladder, the model level against KVAE.impute, argument errors, the resource report
+(tests/post_cases.py: whole tensors, and per gains item / per (path, step)), the per-item Cholesky ladder, the model level against KVAE.impute, argument errors, the resource report
 of the gfx950 kernels, and both kernel bodies under ASan + UBSan."""
 import ctypes
 import os
@@ -166,6 +166,61 @@ def test_ladder_levels_per_item(wave_emu_backend):
     post_cases.check_ladder("cpu")
     assert launches(wave_emu_backend) > before
     post_cases.check_ladder("cpu", impl="torch")
+
+
+def test_restate_paths_vec_is_restate():
+    """The side-by-side float64 form of the path recursion (the reference of paths_per_step) IS the scalar restatement: 1e-12."""
+    for c in post_cases.POST_RING_CASES[20:30] + post_cases.POST_SHAPE_CASES[-6:]:
+        pr = post_cases.post_case_problem(c)
+        ref = post_cases.restate(pr, torch.float64)
+        for x, y in zip(post_cases.restate_paths_vec(pr, torch.float64), ref[:2]):
+            assert x.shape == y.shape and float((x - y).abs().max()) <= 1e-12, post_cases.post_case_id(c)
+
+
+def test_per_step_case_lists_reach_every_edge():
+    """What the lists of gains_per_item / paths_per_step promise, and the bars: 4 x the tabled yardsticks."""
+    ring = post_cases.POST_RING_CASES
+    assert {(c["n"], c["misalign"], c["T"]) for c in ring} == {(n, mis, T) for n, mis in ((4, None), (16, None), (5, None), (4, "eps"), (16, "ws"))
+                                                            for T in range(1, 10)}
+    sh = post_cases.POST_SHAPE_CASES
+    assert {c["B"] * c["S"] for c in sh if c["n"] == 4} >= {63, 64, 65} <= {c["B"] * c["S"] for c in sh if c["n"] == 5}
+    assert {(c["B"], c["S"]) for c in sh if c["n"] == 16} >= {(1, 3), (2, 2), (5, 1), (3, 3), (2, 70)} and any((c["B"], c["S"]) == (5, 13) for c in sh)
+    every = ring + sh
+    for n in (4, 16, 5):
+        mine = [c for c in every if c["n"] == n]
+        assert {c["S"] for c in mine} >= {1, 70} and {c["per_step_Q"] for c in mine} == {True, False} == {c["shared_ac"] for c in mine}
+        assert {c["with_noise"] for c in mine} == {True, False} == {c["rescaled"] for c in mine}
+    assert {(c["p"], c["emission_noise"]) for c in every} >= {(p, e) for p in (1, 2, 3, 16) for e in (True, False)}
+    c = post_cases.POST_EMIT_CASE
+    assert c["B"] * c["S"] * c["T"] > 64 * 1024 and c["n"] == 4
+    assert post_cases.POST_YARDSTICK and all(post_cases.POST_STEP_TOL[k] == 4.0 * v and v > 0 for k, v in post_cases.POST_YARDSTICK.items())
+
+
+@pytest.mark.parametrize("case", post_cases.POST_GAIN_CASES, ids=post_cases.post_case_id)
+def test_gains_per_item(wave_emu_backend, case):
+    """The record J | L | c of every (b, t) against the float64 restatement under POST_STEP_TOL; levels, the triangle of L, J of
+    the last item, guards and sentinels; the rescaled problems exchange rows at every item (post_cases.gains_per_item, which
+    also asserts that the emulated kernels ran)."""
+    print(post_cases.run_gain_case("cpu", case))
+
+
+@pytest.mark.parametrize("name", list(post_cases.LADDER_CASES))
+def test_ladder_per_item(wave_emu_backend, name):
+    """Raised ladder levels at n = 4, 16 and 5, four different ones in one wavefront of the n = 4 gains, and one on the last
+    item of a ragged last wavefront: levels as the float64 run's, L, z, a per slice under the .lv bars."""
+    print(post_cases.ladder_per_item("cpu", name))
+
+
+@pytest.mark.parametrize("case", post_cases.POST_RING_CASES + post_cases.POST_SHAPE_CASES, ids=post_cases.post_case_id)
+def test_paths_per_step(wave_emu_backend, case):
+    """z and a of every (path, step) against the float64 restatement under POST_STEP_TOL, a against the emission of the kernel's
+    own z, guards and sentinels, isolation of paths and sequences (post_cases.paths_per_step)."""
+    print(post_cases.run_path_case("cpu", case))
+
+
+def test_paths_per_step_emission_grid_stride(wave_emu_backend):
+    """65585 rows: more than the emission's 1024 wavefronts hold, so its grid-stride loop takes a second turn."""
+    print(post_cases.run_path_case("cpu", post_cases.POST_EMIT_CASE))
 
 
 @pytest.mark.parametrize("kind", ["lstm", "switching"])
