@@ -254,11 +254,10 @@ __global__ __launch_bounds__(256) void k_grad_sumsq(const float *__restrict__ g,
                                                     float *__restrict__ ws) {
   __shared__ float red[256];
   const float inv = div_dev ? 1.0f / fmaxf(*div_dev, 1.0f) : 1.0f;
-  const bool gated = seg_of && seg_active;
   float s = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     float v = g[i] * inv;
-    if (gated && seg_active[seg_of[i]] == 0.f) v = 0.f;
+    if (seg_active && seg_active[seg_of ? seg_of[i] : 0] == 0.f) v = 0.f;   // the same predicate as k_clip_adam's freeze
     s = fmaf(v, v, s);
   }
   red[threadIdx.x] = s;

@@ -350,6 +350,8 @@ int kvae_clip_adam(float *p, const float *g, float *m, float *v, int64_t n, cons
 }
 int kvae_colsum2(const float *pa, float *oa, int64_t rows_a, int64_t cols_a, const float *pb, float *ob, int64_t rows_b,
                  int64_t cols_b, void *s) {
+  if (!pa || !oa || !pb || !ob) return KVAE_ERR_NULL;   // refused before either job runs, as the entry point of kvae_vae.hip
+  if (rows_a < 1 || cols_a < 1 || rows_b < 1 || cols_b < 1) return KVAE_ERR_ARG;
   const int rc = kvae_colsum(pa, oa, rows_a, cols_a, s);
   return rc ? rc : kvae_colsum(pb, ob, rows_b, cols_b, s);
 }

@@ -225,7 +225,9 @@ def test_flat_clip_adam_equals_torch_adam(monkeypatch):
     assert sf == st == 3.0
     assert max(abs(a - b) / b for a, b in zip(nf, nt)) < 1e-5 and nt[0] > 0.5          # the clip was active
     assert float((pf - pt).abs().max()) < 2e-6
-    assert rel_err(mf, mt) < 1e-5 and rel_err(vf, vt) < 5e-5   # (the second moment squares the clip scale: twice its rounding)
+    # v: torch multiplies by float32(0.001), the kernel by 1 - float32(0.999) = 9.99987e-4 - a difference of CONSTANTS, 1.30e-5
+    # relative after one step, not rounding (tests/step_cases.py holds the kernel per element against the rounded beta2)
+    assert rel_err(mf, mt) < 1e-5 and rel_err(vf, vt) < 5e-5
 
 
 @pytest.mark.parametrize("kind", ["lstm", "switching"])

@@ -277,7 +277,9 @@ def test_clip_adam_c_abi_vs_torch(hostsim_backend, clip, wd, div):
     assert float(step) == 3.0
     assert float((p - ref.detach()).abs().max()) < 2e-6
     st = opt.state[ref]
-    assert rel_err(m, st["exp_avg"]) < 1e-5 and rel_err(v, st["exp_avg_sq"]) < 5e-5   # (v squares the clip scale: twice its rounding)
+    # v: torch multiplies by float32(0.001), the kernel by 1 - float32(0.999) = 9.99987e-4 - a difference of CONSTANTS, 1.30e-5 relative
+    # after one step (the kernel's bias correction uses the same rounded beta2, so it is self-consistent); tests/step_cases.py
+    assert rel_err(m, st["exp_avg"]) < 1e-5 and rel_err(v, st["exp_avg_sq"]) < 5e-5
 
 
 def test_clip_adam_frozen_segments_vs_torch(hostsim_backend):
