@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 #define KVAE_MAX_DIM 16
-#define KVAE_ABI_VERSION 16
+#define KVAE_ABI_VERSION 17
 
 typedef enum {
   KVAE_OK = 0,
@@ -611,6 +611,43 @@ typedef struct {
  * what is built (K outside [1,8], n or m outside [1,4], p != 2), a partly given carried state, or more sequences than one grid
  * holds.  Nothing is written on error. */
 int kvae_lgssm_switching_filter(const kvae_swf_problem *prob, void *stream);
+
+/* ---- switching Kalman smoother, GPB2 (kvae/model/model.py KVAE.smooth_regimes) ------------------------------------------------
+ * The offline half of kvae_lgssm_switching_filter: p(s_t | a_{0:T-1}), p(s_t, s_{t+1} | a_{0:T-1}) and the smoothed z_t with the
+ * regimes summed out, under the same model.  The forward pass is kvae_lgssm_switching_filter unchanged (`filt`: the same fields,
+ * the same NULL rules, outputs bit-identical to that call's); it also keeps, per step t, the collapsed per-regime beliefs
+ * (mu^j_t, Sigma^j_t) it hands to step t + 1 (hist_mu, hist_Sigma), its pair weights W_t[i,j] = W_{i|j} (hist_W, the dead-column
+ * rule included) and the final weights w_{T-1} = regime_filt_{T-1} (hist_w).  The backward pass (Murphy 1998, GPB2 smoothing, with
+ * the filter's own W_{t+1} as backward weights) starts at t = T-1 with M_{T-1}(k) = w_{T-1}(k), (mu_s^k, Sigma_s^k) =
+ * (mu^k_{T-1}, Sigma^k_{T-1}) and runs t = T-2 .. 0, for every pair (j at t, k at t+1):
+ *   mu_p = A_k mu^j_t + B_k u_{t+1}              Sigma_p = A_k Sigma^j_t A_k^T + Q_k   (the filter's predict of that pair: same bits)
+ *   J = Sigma^j_t A_k^T Sigma_p^-1               (elimination without pivoting: every Sigma_p, hence every Q_k, must be positive definite)
+ *   mu_s_jk = mu^j_t + J (mu_s^k_{t+1} - mu_p)   Sigma_s_jk = sym(Sigma^j_t + J (Sigma_s^k_{t+1} - Sigma_p) J^T)
+ *   regime_pairs_t(j,k) = W_{t+1}[j,k] M_{t+1}(k)      = p(s_t = j, s_{t+1} = k | a_{0:T-1}) under p(s_t | s_{t+1}, a_{0:T-1}) ~= p(s_t | s_{t+1}, a_{0:t+1})
+ *   regime_smooth_t(j) = M_t(j) = sum_k regime_pairs_t(j,k)            V_{k|j} = regime_pairs_t(j,k) / M_t(j)   (one-hot at k = j where M_t(j) = 0)
+ *   mu_s^j_t = sum_k V_{k|j} mu_s_jk             Sigma_s^j_t = sum_k V_{k|j} (Sigma_s_jk + (mu_s_jk - mu_s^j_t)(mu_s_jk - mu_s^j_t)^T)
+ * (the kernel divides M_{t+1}(k) by sum_j W_{t+1}[j,k], which is 1 in exact arithmetic: the column sums of a rounded W would
+ * otherwise let the total mass of M drift linearly in T).
+ * mus_smooth_t / Sigmas_smooth_t: the moment match of the K Gaussians (mu_s^j_t, Sigma_s^j_t) under M_t.  The mask enters through
+ * the filter only; the uniform first step of a stream without carried state is the step INTO t = 0, which the backward pass never
+ * crosses; with a carried state the smoothing is conditional on this window alone.  Built for the filter's shapes (fp32, K <= 8,
+ * n <= 4, m <= 4, p == 2), one wavefront per sequence on the same grid (csrc/lgssm_sws.h).  At most three launches: forward,
+ * backward (skipped when none of its outputs is asked for), seq_ll.  No atomics, every output element written once, two calls give
+ * the same bits; any output may be NULL and the bits of the others do not depend on it. */
+typedef struct {
+  kvae_swf_problem filt;      /* the forward pass: inputs and filter outputs, as kvae_lgssm_switching_filter                 */
+  float *hist_mu;             /* [B,T,K,n]    workspace, required: written by the forward, read by the backward              */
+  float *hist_Sigma;          /* [B,T,K,n,n]                                                                                 */
+  float *hist_W;              /* [B,T,K,K]    indexed (i, j)                                                                 */
+  float *hist_w;              /* [B,K]        regime_filt of step T-1                                                        */
+  float *regime_smooth;       /* [B,T,K]      outputs: each may be NULL                                                      */
+  float *regime_pairs;        /* [B,max(T-1,1),K,K]  indexed (s_t, s_{t+1}); nothing written at T = 1                        */
+  float *mus_smooth;          /* [B,T,n]                                                                                     */
+  float *Sigmas_smooth;       /* [B,T,n,n]                                                                                   */
+} kvae_sws_problem;
+/* The error codes of kvae_lgssm_switching_filter over `filt`; in addition KVAE_ERR_NULL: prob or a history buffer NULL.  Nothing is
+ * written on error. */
+int kvae_lgssm_switching_smoother(const kvae_sws_problem *prob, void *stream);
 
 /* ---- misc --------------------------------------------------------------------------------- */
 int kvae_abi_version(void);

@@ -47,7 +47,18 @@ __device__ __forceinline__ float padded(const float *M, int rows, int cols, int 
   return in ? v : 0.0f;
 }
 
-__device__ inline void sweep_wave(const kvae_swf_problem &P) {
+// What the smoother's forward (csrc/lgssm_sws.h, k_sws_fwd) keeps of every step: the collapsed per-regime beliefs - the values the
+// sweep hands to step t + 1 - the pair weights W of that step, and the weights after the last step.  The filter's own sweep
+// (HIST = false) holds none of it and compiles to what it was.
+struct History {
+  float *mu;      // [B,T,K,n]
+  float *Sigma;   // [B,T,K,n,n]
+  float *W;       // [B,T,K,K], indexed (i, j)
+  float *w;       // [B,K]: regime_filt of step T - 1
+};
+
+template <bool HIST = false>
+__device__ inline void sweep_wave(const kvae_swf_problem &P, const History H = History{}) {
   const int lane = (int)(threadIdx.x & 63), k = lane & 7, g = lane >> 3;
   const int T = P.T, K = P.K, n = P.n, m = P.m;
   const int64_t b = blockIdx.x;
@@ -274,6 +285,19 @@ __device__ inline void sweep_wave(const kvae_swf_problem &P) {
         }
       }
     }
+    if constexpr (HIST) {   // the step's history: every live lane its own W, one lane per group the belief of regime j = g
+      if (ve) H.W[(q * K + k) * K + g] = W;
+      const bool w = vg && k == 0;
+      const int64_t s = q * K + g;
+      if (t == T - 1 && w) H.w[b * K + g] = rf;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if (w && r < n) H.mu[s * n + r] = mc[r];
+#pragma unroll
+        for (int c = r; c < 4; ++c)
+          if (w && c < n) H.Sigma[(s * n + r) * n + c] = Sc[r][c], H.Sigma[(s * n + c) * n + r] = Sc[r][c];
+      }
+    }
     if (t == T - 1) {   // the carried state out: regime j = g, one lane per group
       const bool w = vg && k == 0;
       const int64_t s = b * K + g;
@@ -355,7 +379,7 @@ extern "C" int kvae_lgssm_switching_filter(const kvae_swf_problem *prob, void *)
   const kvae_swf_problem &P = *prob;
   if (swf_wants_sweep(P)) {
     emu_launches()[0] += 1;
-    wemu::launch((unsigned)P.B, [&] { sweep_wave(P); });
+    wemu::launch((unsigned)P.B, [&] { sweep_wave<false>(P); });
   }
   if (P.seq_ll) {
     emu_launches()[1] += 1;
@@ -364,4 +388,8 @@ extern "C" int kvae_lgssm_switching_filter(const kvae_swf_problem *prob, void *)
   return KVAE_OK;
 }
 extern "C" int kvae_wemu_switching_filter_launches(int which) { return which == 0 || which == 1 ? kvae_swf::emu_launches()[which] : -1; }
+#endif
+
+#if defined(KVAE_WAVE_EMU)
+#include "lgssm_sws.h"    // likewise kvae_lgssm_switching_smoother
 #endif

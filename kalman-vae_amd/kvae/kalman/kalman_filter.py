@@ -267,6 +267,23 @@ class KalmanFilter(nn.Module):
                                           dyn._prior_matrix(dev, dt), self.mu0, self.Sigma0, Y, U, self._mask(mask, Y), want=want,
                                           state=state)
 
+    @torch.no_grad()
+    def smooth_regimes(self, Y, U, mask=None, state=None, want=lgssm_ops._SWS_OUTPUTS):
+        """The generative switching model smoothed on its own (switching dynamics only): filter_regimes forwards, then the GPB2
+        backward pass over the beliefs and pair weights the filter kept - lgssm_ops.switching_smoother; include/kvae_lgssm.h
+        kvae_lgssm_switching_smoother.  The regime posterior network plays no part.  Every Q_k must be positive definite.
+        state: as filter_regimes; the smoothing is then conditional on this window alone.  Returns filter_regimes' dict (the
+        same bits) plus regime_smooth [B,T,K] = p(s_t | a_{0:T-1}), regime_pairs [B,T-1,K,K] = p(s_t, s_{t+1} | a_{0:T-1}),
+        mus_smooth [B,T,n], Sigmas_smooth [B,T,n,n]; entries not named in `want` are None."""
+        dyn = self.dyn_params
+        if not dyn.is_switching_dynamics:
+            raise ValueError("smooth_regimes needs switching dynamics (SwitchingDynamicsParameter): the alpha-network of the lstm "
+                             "dynamics has no regime chain to smooth")
+        dev, dt = Y.device, Y.dtype
+        return lgssm_ops.switching_smoother(dyn.A.detach(), dyn.B.detach(), dyn.Q.detach(), dyn.C[0].detach(), self.R,
+                                            dyn._prior_matrix(dev, dt), self.mu0, self.Sigma0, Y, U, self._mask(mask, Y), want=want,
+                                            state=state)
+
     def log_marginal(self, Y, U, mask=None):
         """log p(a | u), exactly and DIFFERENTIABLY: the filter (training or eval dynamics as self.training says; no RTS sweep),
         then lgssm_ops.log_marginal over its one-step-ahead beliefs - C_t out of the packed step record where there is one.

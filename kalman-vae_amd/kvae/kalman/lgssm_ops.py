@@ -20,9 +20,9 @@ from typing import NamedTuple, Optional
 import torch
 
 from .. import _native as N
-from .lgssm_torch import (_DECODE_OUTPUTS, _LOG_2PI, _PRED_OUTPUTS, _SWF_OUTPUTS, _bt, _swf_state, _want,  # noqa: F401 (re-exported)
+from .lgssm_torch import (_DECODE_OUTPUTS, _LOG_2PI, _PRED_OUTPUTS, _SWF_OUTPUTS, _SWS_OUTPUTS, _SWS_SMOOTH, _bt, _swf_state, _want,  # noqa: F401 (re-exported)
                           log_marginal_torch, posterior_paths_torch, predictive_torch, regime_decode_torch, rollout_torch,
-                          safe_cholesky, safe_cholesky_items, switching_filter_torch)
+                          safe_cholesky, safe_cholesky_items, switching_filter_torch, switching_smoother_torch)
 
 
 class Slots(NamedTuple):
@@ -984,6 +984,18 @@ def switching_filter(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, want=_SWF
                          f"n = {n}, m = {m}, p = {p}, {Y.dtype} on {Y.device}")
     if impl == "torch" or not supported:
         return switching_filter_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, state, want)
+    out, pr, keep = _swf_problem(N.SwfProblem(), A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, state, want)
+    lib = N.lib_for(Y)
+    lib.check(N.timed("switching_filter", Y, lambda: lib.dll.kvae_lgssm_switching_filter(C.byref(pr), N.stream_for(Y))),
+              "kvae_lgssm_switching_filter")
+    return out
+
+
+def _swf_problem(pr, A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, state, want):
+    """Fill the kvae_swf_problem `pr` for the outputs of _SWF_OUTPUTS named in `want`: (the dict of outputs, pr, the tensors pr
+    points to, which must outlive the call)."""
+    K, n, m = A.shape[0], A.shape[1], Bm.shape[2]
+    Bsz, T, p = Y.shape
     dev = Y.device
     A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U = (_f32c(t.detach().to(dev)) for t in (A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U))
     mask = None if mask is None else _f32c(mask.detach().to(dev).reshape(Bsz, T))
@@ -996,7 +1008,6 @@ def switching_filter(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, want=_SWF
     out["log_lik"] = ll if "log_lik" in want else None
     if "state" in want:
         out["state"] = {"log_w": _empty(dev, Bsz, K), "mu": _empty(dev, Bsz, K, n), "Sigma": _empty(dev, Bsz, K, n, n)}
-    pr = N.SwfProblem()
     pr.B, pr.T, pr.K, pr.n, pr.m, pr.p = Bsz, T, K, n, m, p
     pr.A, pr.Bm, pr.Q, pr.C, pr.R, pr.P = (t.data_ptr() for t in (A, Bm, Q, Cm, R, P))
     pr.mu0, pr.Sigma0, pr.y, pr.u, pr.mask = mu0.data_ptr(), Sigma0.data_ptr(), Y.data_ptr(), U.data_ptr(), N.ptr(mask)
@@ -1007,7 +1018,54 @@ def switching_filter(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, want=_SWF
     pr.levels = N.ptr(out["levels"])
     if out["state"] is not None:
         pr.out_log_w, pr.out_mu, pr.out_Sigma = (out["state"][k].data_ptr() for k in ("log_w", "mu", "Sigma"))
+    return out, pr, (A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, st, ll)
+
+
+# ------------------------------------------------------------------------------------------------
+# switching Kalman smoother, GPB2 (kvae_lgssm_switching_smoother, csrc/lgssm_sws.h)
+# ------------------------------------------------------------------------------------------------
+def switching_smoother_supported(K, n, m, p, ref=None):
+    """Shapes / tensors kvae_lgssm_switching_smoother is built for: the filter's (switching_filter_supported); the rest takes
+    switching_smoother_torch."""
+    return switching_filter_supported(K, n, m, p, ref)
+
+
+@torch.no_grad()
+def switching_smoother(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, want=_SWS_OUTPUTS, state=None, impl=None):
+    """The switching Kalman smoother with GPB2 collapse over the generative switching model (semantics: include/kvae_lgssm.h,
+    kvae_lgssm_switching_smoother): switching_filter forwards, with the same arguments, then a backward pass
+    over the beliefs and pair weights the filter kept.  Every Q_k must be positive definite (the backward pass solves with
+    Sigma_pred without pivoting).  want: any of switching_filter's outputs - the bits of that call's - and "regime_smooth" [B,T,K]
+    = p(s_t | a_{0:T-1}), "regime_pairs" [B,T-1,K,K] = p(s_t = j, s_{t+1} = k | a_{0:T-1}) indexed (j, k), "mus_smooth" [B,T,n],
+    "Sigmas_smooth" [B,T,n,n] the moment-matched smoothed belief; entries not asked for are None.  state: as switching_filter;
+    the smoothing is then conditional on this window alone (nothing flows back into the earlier chunk).  At most three launches
+    (forward, backward, log_lik_seq), no host synchronisation, no gradients.
+    impl: None = the HIP kernel where it is built (switching_smoother_supported), else switching_smoother_torch; "hip" / "torch"
+    force one."""
+    want = _want("switching_smoother", _SWS_OUTPUTS, want)
+    if impl not in (None, "hip", "torch"):
+        raise ValueError(f"switching_smoother: impl must be None, 'hip' or 'torch', got {impl!r}")
+    K, n, m = A.shape[0], A.shape[1], Bm.shape[2]
+    Bsz, T, p = Y.shape
+    supported = switching_smoother_supported(K, n, m, p, Y)
+    if impl == "hip" and not supported:
+        raise ValueError(f"switching_smoother: impl='hip' needs fp32 tensors on a HIP device and K <= {SWF_SUPPORTED['max_K']}, "
+                         f"n <= {SWF_SUPPORTED['max_n']}, m <= {SWF_SUPPORTED['max_m']}, p == {SWF_SUPPORTED['p']}; got K = {K}, "
+                         f"n = {n}, m = {m}, p = {p}, {Y.dtype} on {Y.device}")
+    if impl == "torch" or not supported:
+        return switching_smoother_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, state, want)
+    dev = Y.device
+    sp = N.SwsProblem()
+    out, _, keep = _swf_problem(sp.filt, A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, state, tuple(w for w in want if w in _SWF_OUTPUTS))
+    hist = (_empty(dev, Bsz, T, K, n), _empty(dev, Bsz, T, K, n, n), _empty(dev, Bsz, T, K, K), _empty(dev, Bsz, K))
+    sp.hist_mu, sp.hist_Sigma, sp.hist_W, sp.hist_w = (t.data_ptr() for t in hist)
+    out.update(_wanted(dev, _SWS_SMOOTH, want, dict(regime_smooth=(Bsz, T, K), regime_pairs=(Bsz, max(T - 1, 1), K, K),
+                                                    mus_smooth=(Bsz, T, n), Sigmas_smooth=(Bsz, T, n, n))))
+    sp.regime_smooth, sp.regime_pairs = N.ptr(out["regime_smooth"]), N.ptr(out["regime_pairs"])
+    sp.mus_smooth, sp.Sigmas_smooth = N.ptr(out["mus_smooth"]), N.ptr(out["Sigmas_smooth"])
     lib = N.lib_for(Y)
-    lib.check(N.timed("switching_filter", Y, lambda: lib.dll.kvae_lgssm_switching_filter(C.byref(pr), N.stream_for(Y))),
-              "kvae_lgssm_switching_filter")
+    lib.check(N.timed("switching_smoother", Y, lambda: lib.dll.kvae_lgssm_switching_smoother(C.byref(sp), N.stream_for(Y))),
+              "kvae_lgssm_switching_smoother")
+    if out["regime_pairs"] is not None:
+        out["regime_pairs"] = out["regime_pairs"][:, :T - 1]   # nothing is written at T = 1
     return out

@@ -8,6 +8,8 @@ _DECODE_OUTPUTS = ("marginals", "path", "kl")
 _PRED_OUTPUTS = ("ll", "nis", "a_pred", "S", "levels", "seq_ll")
 _LOG_2PI = 1.8378770664093453
 _SWF_OUTPUTS = ("regime_filt", "regime_pred", "log_lik", "log_lik_seq", "a_pred", "S", "mus_filt", "Sigmas_filt", "levels", "state")
+_SWS_SMOOTH = ("regime_smooth", "regime_pairs", "mus_smooth", "Sigmas_smooth")
+_SWS_OUTPUTS = _SWF_OUTPUTS + _SWS_SMOOTH
 
 
 def _want(op, outputs, want):
@@ -254,12 +256,10 @@ def _swf_state(state, Bsz, K, n):
     return lw, mu, Sig
 
 
-@torch.no_grad()
-def switching_filter_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, state=None, want=_SWF_OUTPUTS):
-    """The equations of kvae_lgssm_switching_filter (include/kvae_lgssm.h) in torch ops, vectorised over (B, i, j), in the dtype of
-    A: shapes outside the kernel's, non-fp32 and host tensors, and (in float64) the reference the kernel is tested against.
-    T steps of about thirty small launches.  Same arguments and returns as switching_filter."""
-    want = _want("switching_filter", _SWF_OUTPUTS, want)
+def _swf_forward(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, state, history=False):
+    """The sweep of switching_filter_torch: (every output of _SWF_OUTPUTS, the history, the cast (A, Bm, Q, Cm, U)).  history: the
+    collapsed per-regime beliefs mu [B,T,K,n], Sigma [B,T,K,n,n] and the pair weights W [B,T,K,K] (indexed (i, j)) of every step,
+    which switching_smoother_torch runs backwards over; None unless asked for."""
     dt, dev = A.dtype, Y.device
     K, n = A.shape[0], A.shape[1]
     Bsz, T, p = Y.shape
@@ -276,6 +276,7 @@ def switching_filter_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, sta
     uniform = torch.full((K, K), 1.0 / K, device=dev, dtype=dt)
     ninf = torch.full((), -float("inf"), device=dev, dtype=dt)
     outs = {k: [] for k in ("regime_filt", "regime_pred", "log_lik", "a_pred", "S", "mus_filt", "Sigmas_filt", "levels")}
+    hist = {k: [] for k in ("mu", "Sigma", "W")} if history else None
     for t in range(T):
         Pt = uniform if (t == 0 and st is None) else P
         mk = torch.ones(Bsz, device=dev, dtype=dt) if mask is None else mask[:, t]
@@ -311,6 +312,8 @@ def switching_filter_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, sta
         d = muf - mu.unsqueeze(1)
         Sig = (W[..., None, None] * (Sf + d.unsqueeze(-1) * d.unsqueeze(-2))).sum(1)
         Sig = 0.5 * (Sig + Sig.mT)
+        if history:
+            hist["mu"].append(mu), hist["Sigma"].append(Sig), hist["W"].append(W)
         # ---- outputs of the step ----
         outs["regime_pred"].append(pw.sum(1))
         outs["regime_filt"].append(rf)
@@ -327,6 +330,68 @@ def switching_filter_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, sta
     full = {k: torch.stack(v, 1) for k, v in outs.items()}
     full["log_lik_seq"] = full["log_lik"].sum(1)
     full["state"] = {"log_w": lw, "mu": mu, "Sigma": Sig}
+    return full, ({k: torch.stack(v, 1) for k, v in hist.items()} if history else None), (A, Bm, Q, Cm, U)
+
+
+@torch.no_grad()
+def switching_filter_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, state=None, want=_SWF_OUTPUTS):
+    """The equations of kvae_lgssm_switching_filter (include/kvae_lgssm.h) in torch ops, vectorised over (B, i, j), in the dtype of
+    A: shapes outside the kernel's, non-fp32 and host tensors, and (in float64) the reference the kernel is tested against.
+    T steps of about thirty small launches.  Same arguments and returns as switching_filter."""
+    want = _want("switching_filter", _SWF_OUTPUTS, want)
+    full, _, _ = _swf_forward(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, state)
     return {k: (full[k] if k in want else None) for k in _SWF_OUTPUTS}
+
+
+def _moment_match(w, mu, Sig):
+    """(mean [B,n], covariance [B,n,n]) of the mixture of the K Gaussians (mu [B,K,n], Sig [B,K,n,n]) under the weights w [B,K]."""
+    m_ = (w.unsqueeze(-1) * mu).sum(1)
+    dd = mu - m_.unsqueeze(1)
+    return m_, (w[..., None, None] * (Sig + dd.unsqueeze(-1) * dd.unsqueeze(-2))).sum(1)
+
+
+@torch.no_grad()
+def switching_smoother_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, state=None, want=_SWS_OUTPUTS):
+    """The equations of kvae_lgssm_switching_smoother (include/kvae_lgssm.h) in torch ops, in the dtype of A: the sweep of
+    switching_filter_torch with its history kept, then the backward pass vectorised over (B, j, k) = (regime at t, regime at
+    t + 1).  The fallback of switching_smoother and (in float64) the reference its kernel is tested against.  Every Q_k must be
+    positive definite.  Same arguments and returns as switching_smoother."""
+    want = _want("switching_smoother", _SWS_OUTPUTS, want)
+    full, hist, (A, Bm, Q, Cm, U) = _swf_forward(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, state, history=True)
+    full.update(_sws_backward(A, Bm, Q, U, hist, full["regime_filt"][:, -1]))
+    return {k: (full[k] if k in want else None) for k in _SWS_OUTPUTS}
+
+
+def _sws_backward(A, Bm, Q, U, hist, w_last):
+    """The backward pass of switching_smoother_torch over the history of _swf_forward and the final weights w_last [B,K]: the
+    four outputs of _SWS_SMOOTH."""
+    K, T = A.shape[0], U.shape[1]
+    eyeK = torch.eye(K, device=A.device, dtype=A.dtype)
+    M, ms, Ss = w_last, hist["mu"][:, -1], hist["Sigma"][:, -1]
+    outs = {"regime_smooth": [M], "regime_pairs": [], "mus_smooth": [], "Sigmas_smooth": []}
+    m_, S_ = _moment_match(M, ms, Ss)
+    outs["mus_smooth"].append(m_), outs["Sigmas_smooth"].append(S_)
+    for t in range(T - 2, -1, -1):
+        mu, Sig = hist["mu"][:, t], hist["Sigma"][:, t]                              # regime j at t: [B, j, ...]
+        # ---- the filter's predict of pair (j, k) at step t + 1: [B, j, k, ...] ----
+        mp = torch.einsum("jrc,bic->bijr", A, mu) + torch.einsum("jrc,bc->bjr", Bm, U[:, t + 1]).unsqueeze(1)
+        Sp = torch.einsum("jre,biec,jdc->bijrd", A, Sig, A) + Q
+        J = torch.linalg.solve(Sp.mT, (Sig.unsqueeze(2) @ A.mT).mT).mT               # Sigma A_k^T Sigma_p^-1
+        mj = mu.unsqueeze(2) + (J @ (ms.unsqueeze(1) - mp).unsqueeze(-1)).squeeze(-1)
+        Sj = Sig.unsqueeze(2) + J @ (Ss.unsqueeze(1) - Sp) @ J.mT
+        Sj = 0.5 * (Sj + Sj.mT)
+        # ---- weights: the pair marginal, M_t, V_{k|j} ----
+        pair = hist["W"][:, t + 1] * M.unsqueeze(1)                                  # [B, j, k]
+        M = pair.sum(2)
+        dead = ~(M > 0)
+        V = torch.where(dead.unsqueeze(2), eyeK.expand_as(pair), pair / torch.where(dead, torch.ones_like(M), M).unsqueeze(2))
+        # ---- collapse over k ----
+        ms = (V.unsqueeze(-1) * mj).sum(2)
+        d = mj - ms.unsqueeze(2)
+        Ss = (V[..., None, None] * (Sj + d.unsqueeze(-1) * d.unsqueeze(-2))).sum(2)
+        Ss = 0.5 * (Ss + Ss.mT)
+        m_, S_ = _moment_match(M, ms, Ss)
+        outs["regime_smooth"].append(M), outs["regime_pairs"].append(pair), outs["mus_smooth"].append(m_), outs["Sigmas_smooth"].append(S_)
+    return {k: (torch.stack(v[::-1], 1) if v else w_last.new_zeros(w_last.shape[0], 0, K, K)) for k, v in outs.items()}
 
 

@@ -491,6 +491,38 @@ class KVAE(nn.Module):
             return out
 
     @torch.no_grad()
+    def smooth_regimes(self, x, u=None, mask=None, sample_a=False, state=None, decode=False):
+        """What the generative switching model believes on its own, given the WHOLE sequence (switching dynamics only; no
+        counterpart in the reference): filter_regimes forwards, then the GPB2 smoothing pass backwards over the beliefs and pair
+        weights the filter kept - kvae_lgssm_switching_smoother.  The bidirectional regime posterior network plays no part.
+
+        1. Encode x, as filter_regimes does.  Every output of filter_regimes but x_pred is returned, with the bits of that call.
+        2. regime_smooth [B,T,K] = p(s_t | a_{0:T-1}); regimes [B,T] (int64) = its argmax (lowest index on ties);
+           regime_pairs [B,T-1,K,K] = p(s_t = j, s_{t+1} = k | a_{0:T-1}), whose sums over k and j are regime_smooth_t and
+           regime_smooth_{t+1}: the expected transition counts of an EM step for P.
+        3. mus_smooth [B,T,n], Sigmas_smooth [B,T,n,n]: the smoothed z_t with the regimes summed out (moment-matched);
+           a_smooth [B,T,p] = C mus_smooth - on hidden steps (mask [B,T], 1 = observed) it uses the frames after the gap.
+        4. decode=True: x_smooth = decoder(a_smooth).
+        Also returns a_vae and n_obs [B].  state=prev["state"] starts from an earlier chunk's filter state; the smoothing is then
+        conditional on this window alone.  Every Q_k must be positive definite.  Exact when P is the identity or when all
+        regimes share A, B, Q; regime_smooth and regime_pairs are exact at T = 2; otherwise the GPB2 approximation (DESIGN.md
+        section 15).  No host synchronisation.  Training mode, tau and parameters are left as they were."""
+        dyn = self.kalman_filter.dyn_params
+        if not dyn.is_switching_dynamics:
+            raise ValueError('smooth_regimes needs a model with dynamics = "switching" (config.dynamics_model); this one has '
+                             f'"{self.config.dynamics_model}"')
+        with self._readout("smooth_regimes", x, u, mask, sample=bool(sample_a)) as (a_vae, _, _, u, mask):
+            out = self.kalman_filter.smooth_regimes(a_vae, u, mask, state=state)
+            rs = out["regime_smooth"]
+            out["regimes"] = (rs == rs.max(-1, keepdim=True).values).to(torch.int8).argmax(-1)   # lowest index among the maxima
+            out["a_smooth"] = out["mus_smooth"] @ dyn.C[0].detach().to(rs.dtype).mT
+            out["a_vae"] = a_vae
+            out["n_obs"] = self._n_obs(mask, a_vae)
+            if decode:
+                out["x_smooth"] = self._decode_latents(out["a_smooth"], a_vae.dtype)
+            return out
+
+    @torch.no_grad()
     def log_likelihood(self, x, num_samples=1, u=None, mask=None):
         """Importance-weighted bound on log p(x_observed) per sequence under the generative model p(x | a) p_LGSSM(a), with the
         encoder as proposal (no counterpart in the reference).  B sequences of T frames, S = num_samples.

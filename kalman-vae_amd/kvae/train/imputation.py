@@ -2,7 +2,8 @@
 pattern of BASELINE configs[3] ("observe, hide a block, observe again") and of masked training.  Same function
 names, arguments and results; everything else in that module (imputation plots, MSE reports) is evaluation tooling
 outside the hot path and is not shipped.  `config_block_mask` wires KVAEConfig.t_init_mask / t_steps_mask in.
-`sample_imputation_scores` (no counterpart there) scores the sampled completions of KVAE.sample_imputations.
+`sample_imputation_scores` (no counterpart there) scores the sampled completions of KVAE.sample_imputations,
+`regime_smoother_scores` the switching smoother of KVAE.smooth_regimes on the hidden frames.
 """
 import torch
 
@@ -56,3 +57,30 @@ def sample_imputation_scores(x, x_samples, mask):
     best = ((per.min(1).values / per_count) * has).sum() / has.sum().clamp(min=1.0)
     std = x_samples.std(1, unbiased=False) if x_samples.shape[1] > 1 else torch.zeros_like(x)
     return {"mse_mean": err_mean, "mse_best": best, "std": (std * w).sum() / count}
+
+
+@torch.no_grad()
+def regime_smoother_scores(model, x, mask, u=None):
+    """The generative switching model's own smoother (KVAE.smooth_regimes) next to the read-outs that go through the regime
+    posterior network, on the HIDDEN frames of x [B,T,...] (mask [B,T], 1 = observed).  Switching dynamics only.  Python floats:
+      mse_smooth         MSE of x_smooth: the decoded smoothed latent, which has seen the frames after the gap
+      mse_impute         MSE of impute()'s x_imputed (the reference's imputation, one drawn regime sequence)
+      mse_pred           MSE of filter_regimes' one-step-ahead forecast x_pred, which has not
+      regime_agreement   share of steps whose smoothed argmax regime equals decode_regimes' most likely path
+    0 for the errors where nothing is hidden.  The model's training mode is left as it was."""
+    dev = next(model.parameters()).device
+    x, mask = x.to(dev), mask.to(dev)
+    was_training = model.training
+    try:
+        sm = model.smooth_regimes(x, u=u, mask=mask, decode=True)
+        fr = model.filter_regimes(x, u=u, mask=mask, decode=True)
+        dec = model.decode_regimes(x, u=u, mask=mask, smooth=False)
+        imp = model.impute(x, mask, u=u)
+    finally:
+        model.train(was_training)
+    hid = 1.0 - mask.to(x.dtype)
+    w = hid.reshape(*hid.shape, *([1] * (x.dim() - 2)))
+    count = (hid.sum() * x[0, 0].numel()).clamp(min=1.0)
+    mse = lambda y: float((((y.to(x.dtype) - x) ** 2) * w).sum() / count)
+    return {"mse_smooth": mse(sm["x_smooth"]), "mse_impute": mse(imp["x_imputed"]), "mse_pred": mse(fr["x_pred"]),
+            "regime_agreement": float((sm["regimes"] == dec["regimes"]).double().mean())}
