@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 #define KVAE_MAX_DIM 16
-#define KVAE_ABI_VERSION 17
+#define KVAE_ABI_VERSION 18
 
 typedef enum {
   KVAE_OK = 0,
@@ -648,6 +648,52 @@ typedef struct {
 /* The error codes of kvae_lgssm_switching_filter over `filt`; in addition KVAE_ERR_NULL: prob or a history buffer NULL.  Nothing is
  * written on error. */
 int kvae_lgssm_switching_smoother(const kvae_sws_problem *prob, void *stream);
+
+/* ---- log p(a | u) of the switching model with the regimes summed out (GPB2), differentiable ------------------------------------
+ * (kvae/kalman/kalman_filter.py KalmanFilter.regime_log_marginal; the "regime_marginal" training objective)
+ * Forward: kvae_lgssm_switching_filter over `filt` (the same fields and NULL rules, every output the bits of that call's) which also
+ * keeps, per step t, what it hands to step t + 1: the collapsed per-regime beliefs (hist_mu, hist_Sigma: the smoother's layout) and
+ * the log weights log w'(j) (hist_lw).  A carried state is not accepted (truncated back-propagation through streams is not built).
+ * Backward: the hand-derived adjoint of that sweep, t = T-1 .. 0, for the loss sum_bt g_ll[b,t] ll[b,t] + sum_b g_seq[b] seq_ll[b]:
+ * the weight of step t is g_ll[b,t] + g_seq[b] on observed steps and 0 on hidden ones (either upstream may be NULL, not both).
+ * It is the gradient of the GPB2 VALUE: where the filter is exact (P = I, shared A/B/Q, t <= 1) the exact gradient of log p(a | u),
+ * elsewhere the gradient of the approximation.  One wavefront per sequence on the filter's grid recomputes every pair step from the
+ * history with the forward's own statements (the same level, S and W bits), accumulates its pair's parameter gradients in
+ * registers over t and writes ONE partial per sequence into ws [B, G], G = K (2 n^2 + n m) + 2 n + K^2 + n + n^2, laid out
+ *   gA [K,n,n] | gB [K,n,m] | gQ [K,n,n] | gC [2,n] | g_logP [K,K] | g_mu0 [n] | g_Sigma0 [n,n]
+ * (kvae_lgssm_switching_marginal_ws_floats); a second launch sums ws over b in ascending order, one thread per element, into the
+ * requested outputs.  No atomics: two calls give the same bits, and the bits of an output do not depend on which others are asked
+ * for.  g_logP is the adjoint of log c_ij summed over the steps that use P (not the uniform first step), exactly 0 where
+ * P[i,j] = 0: gP = g_logP / P where P > 0.  gQ, g_Sigma0 are symmetric (the gradient over symmetric matrices).  gY is exactly 0 on
+ * hidden steps.  R gets no gradient.  ll_recomputed is what the adjoint's recomputed pair steps give for ll[b,t]: it must equal the
+ * forward's ll bit for bit, which is how the tests pin that the two copies of the step's statements have not drifted apart. */
+typedef struct {
+  kvae_swf_problem filt;      /* inputs and filter outputs, as kvae_lgssm_switching_filter; state_* must be NULL                */
+  float *hist_lw;             /* [B,T,K]      required: written by the forward, read by the backward                            */
+  float *hist_mu;             /* [B,T,K,n]                                                                                       */
+  float *hist_Sigma;          /* [B,T,K,n,n]                                                                                     */
+} kvae_swm_problem;
+typedef struct {
+  const float *g_ll;          /* [B,T]  upstream of ll, or NULL                                                                  */
+  const float *g_seq;         /* [B]    upstream of seq_ll, or NULL (not both)                                                   */
+  float *ws;                  /* [B,G]  required workspace: the per-sequence partials, every element written                     */
+  float *gA;                  /* [K,n,n]   outputs: each may be NULL                                                             */
+  float *gB;                  /* [K,n,m]                                                                                         */
+  float *gQ;                  /* [K,n,n]                                                                                         */
+  float *gC;                  /* [2,n]                                                                                           */
+  float *g_logP;              /* [K,K]                                                                                           */
+  float *g_mu0;               /* [n]                                                                                             */
+  float *g_Sigma0;            /* [n,n]                                                                                           */
+  float *gY;                  /* [B,T,2]                                                                                         */
+  float *gU;                  /* [B,T,m]                                                                                         */
+  float *ll_recomputed;       /* [B,T]     the adjoint's own recomputation of ll: the forward's bits (a check, not a gradient)   */
+} kvae_swm_grads;
+/* The error codes of kvae_lgssm_switching_filter over `filt`; in addition KVAE_ERR_ARG: a carried state; KVAE_ERR_NULL: prob or a
+ * history buffer NULL, and for the adjoint g NULL, g_ll and g_seq both NULL, or ws NULL.  Nothing is written on error.  The
+ * adjoint launches nothing when no output is asked for, and skips the reduction when only gY / gU / ll_recomputed are. */
+int kvae_lgssm_switching_marginal(const kvae_swm_problem *prob, void *stream);
+int kvae_lgssm_switching_marginal_bwd(const kvae_swm_problem *prob, const kvae_swm_grads *g, void *stream);
+int64_t kvae_lgssm_switching_marginal_ws_floats(int32_t B, int32_t K, int32_t n, int32_t m);
 
 /* ---- misc --------------------------------------------------------------------------------- */
 int kvae_abi_version(void);

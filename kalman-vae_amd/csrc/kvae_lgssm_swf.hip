@@ -14,7 +14,7 @@ extern "C" int kvae_launch_status(const char *what);   // kvae_lgssm.hip: hipGet
 
 using namespace kvae_swf;
 
-__global__ __launch_bounds__(64) void k_swf_sweep(kvae_swf_problem P) { sweep_wave<false>(P); }
+__global__ __launch_bounds__(64) void k_swf_sweep(kvae_swf_problem P) { sweep_wave<0>(P); }
 __global__ __launch_bounds__(64) void k_swf_seq(kvae_swf_problem P) { seq_wave(P); }
 
 extern "C" int kvae_lgssm_switching_filter(const kvae_swf_problem *prob, void *stream) {

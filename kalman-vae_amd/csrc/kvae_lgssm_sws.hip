@@ -14,7 +14,7 @@ extern "C" int kvae_launch_status(const char *what);   // kvae_lgssm.hip: hipGet
 
 using namespace kvae_sws;
 
-__global__ __launch_bounds__(64) void k_sws_fwd(kvae_swf_problem P, kvae_swf::History H) { kvae_swf::sweep_wave<true>(P, H); }
+__global__ __launch_bounds__(64) void k_sws_fwd(kvae_swf_problem P, kvae_swf::History H) { kvae_swf::sweep_wave<1>(P, H); }
 __global__ __launch_bounds__(64) void k_sws_back(kvae_sws_problem S) { back_wave(S); }
 __global__ __launch_bounds__(64) void k_sws_seq(kvae_swf_problem P) { kvae_swf::seq_wave(P); }
 

@@ -48,16 +48,19 @@ __device__ __forceinline__ float padded(const float *M, int rows, int cols, int 
 }
 
 // What the smoother's forward (csrc/lgssm_sws.h, k_sws_fwd) keeps of every step: the collapsed per-regime beliefs - the values the
-// sweep hands to step t + 1 - the pair weights W of that step, and the weights after the last step.  The filter's own sweep
-// (HIST = false) holds none of it and compiles to what it was.
+// sweep hands to step t + 1 - the pair weights W of that step, and the weights after the last step.  The forward of the
+// differentiable log-likelihood (csrc/lgssm_swm.h, k_swm_fwd: HIST = 2) keeps the beliefs and, in place of W and w, the log weights
+// log w' handed to step t + 1; its adjoint recomputes W.  The filter's own sweep (HIST = 0) holds none of it and compiles to what
+// it was.
 struct History {
   float *mu;      // [B,T,K,n]
   float *Sigma;   // [B,T,K,n,n]
-  float *W;       // [B,T,K,K], indexed (i, j)
-  float *w;       // [B,K]: regime_filt of step T - 1
+  float *W;       // [B,T,K,K], indexed (i, j)          (HIST = 1)
+  float *w;       // [B,K]: regime_filt of step T - 1   (HIST = 1)
+  float *lw;      // [B,T,K]: log w' of every step      (HIST = 2)
 };
 
-template <bool HIST = false>
+template <int HIST = 0>
 __device__ inline void sweep_wave(const kvae_swf_problem &P, const History H = History{}) {
   const int lane = (int)(threadIdx.x & 63), k = lane & 7, g = lane >> 3;
   const int T = P.T, K = P.K, n = P.n, m = P.m;
@@ -285,11 +288,15 @@ __device__ inline void sweep_wave(const kvae_swf_problem &P, const History H = H
         }
       }
     }
-    if constexpr (HIST) {   // the step's history: every live lane its own W, one lane per group the belief of regime j = g
-      if (ve) H.W[(q * K + k) * K + g] = W;
+    if constexpr (HIST != 0) {   // the step's history: every live lane its own W, one lane per group the belief of regime j = g
       const bool w = vg && k == 0;
       const int64_t s = q * K + g;
-      if (t == T - 1 && w) H.w[b * K + g] = rf;
+      if constexpr (HIST == 1) {
+        if (ve) H.W[(q * K + k) * K + g] = W;
+        if (t == T - 1 && w) H.w[b * K + g] = rf;
+      } else {
+        if (w) H.lw[s] = lwn;
+      }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         if (w && r < n) H.mu[s * n + r] = mc[r];
@@ -379,7 +386,7 @@ extern "C" int kvae_lgssm_switching_filter(const kvae_swf_problem *prob, void *)
   const kvae_swf_problem &P = *prob;
   if (swf_wants_sweep(P)) {
     emu_launches()[0] += 1;
-    wemu::launch((unsigned)P.B, [&] { sweep_wave<false>(P); });
+    wemu::launch((unsigned)P.B, [&] { sweep_wave<0>(P); });
   }
   if (P.seq_ll) {
     emu_launches()[1] += 1;

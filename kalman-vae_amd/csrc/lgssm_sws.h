@@ -1,7 +1,7 @@
 // lgssm_sws.h — the switching Kalman smoother with GPB2 collapse (Murphy 1998) over the generative switching model
 // (include/kvae_lgssm.h kvae_lgssm_switching_smoother, lgssm_ops.switching_smoother, KalmanFilter.smooth_regimes,
 // KVAE.smooth_regimes).  The equations are in the header of the C ABI; this file is the backward pass on a wavefront.  The forward
-// pass is the filter's sweep (csrc/lgssm_swf.h, sweep_wave<true>), which keeps the collapsed beliefs (mu^j_t, Sigma^j_t), the pair
+// pass is the filter's sweep (csrc/lgssm_swf.h, sweep_wave<1>), which keeps the collapsed beliefs (mu^j_t, Sigma^j_t), the pair
 // weights W_t and the final weights w_{T-1}.
 //
 // One wavefront per sequence on the filter's 8 x 8 grid: lane = 8 g + k owns the pair (regime j = k at step t, regime g at step
@@ -281,7 +281,7 @@ inline int sws_check(const kvae_sws_problem *S) {
   return KVAE_OK;
 }
 inline bool sws_wants_back(const kvae_sws_problem &S) { return S.regime_smooth || S.regime_pairs || S.mus_smooth || S.Sigmas_smooth; }
-inline kvae_swf::History sws_history(const kvae_sws_problem &S) { return kvae_swf::History{S.hist_mu, S.hist_Sigma, S.hist_W, S.hist_w}; }
+inline kvae_swf::History sws_history(const kvae_sws_problem &S) { return kvae_swf::History{S.hist_mu, S.hist_Sigma, S.hist_W, S.hist_w, nullptr}; }
 
 }  // namespace kvae_sws
 
@@ -304,7 +304,7 @@ extern "C" int kvae_lgssm_switching_smoother(const kvae_sws_problem *prob, void 
   if (back || kvae_swf::swf_wants_sweep(S.filt)) {
     emu_launches()[0] += 1;
     const kvae_swf::History H = sws_history(S);
-    wemu::launch((unsigned)S.filt.B, [&] { kvae_swf::sweep_wave<true>(S.filt, H); });
+    wemu::launch((unsigned)S.filt.B, [&] { kvae_swf::sweep_wave<1>(S.filt, H); });
   }
   if (back) {
     emu_launches()[1] += 1;
@@ -317,4 +317,6 @@ extern "C" int kvae_lgssm_switching_smoother(const kvae_sws_problem *prob, void 
   return KVAE_OK;
 }
 extern "C" int kvae_wemu_switching_smoother_launches(int which) { return which >= 0 && which <= 2 ? kvae_sws::emu_launches()[which] : -1; }
+
+#include "lgssm_swm.h"    // likewise kvae_lgssm_switching_marginal and its adjoint
 #endif

@@ -284,6 +284,30 @@ class KalmanFilter(nn.Module):
                                             dyn._prior_matrix(dev, dt), self.mu0, self.Sigma0, Y, U, self._mask(mask, Y), want=want,
                                             state=state)
 
+    def regime_log_marginal(self, Y, U, mask=None):
+        """log p(a | u) of the generative switching model with the regimes summed out under GPB2 collapse, DIFFERENTIABLY (switching
+        dynamics only): filter_regimes' log_lik / log_lik_seq / levels - the same bits - with a tape through A_k, B_k, Q_k, the
+        shared C, (mu0, Sigma0), Y and U - lgssm_ops.switching_log_marginal; include/kvae_lgssm.h kvae_lgssm_switching_marginal and
+        its adjoint.  The regime posterior network plays no part and no regime is drawn: zero variance, no tau.  It is the gradient
+        of the GPB2 value: exact where the filter is exact (P = I, shared A / B / Q, t <= 1), elsewhere the gradient of the
+        approximation.  R and the prior's P are constants.  Returns dict(ll [B,T], seq_ll [B], levels [B,T]); ll is 0 on hidden steps."""
+        dyn = self.dyn_params
+        if not dyn.is_switching_dynamics:
+            raise ValueError("regime_log_marginal needs switching dynamics (SwitchingDynamicsParameter): the alpha-network of the "
+                             "lstm dynamics has no regime chain to sum out")
+        return lgssm_ops.switching_log_marginal(dyn.A, dyn.B, dyn.Q, dyn.C[0], self.R, dyn._prior_matrix(Y.device, Y.dtype), self.mu0,
+                                                self.Sigma0, Y, U, self._mask(mask, Y))
+
+    def regime_marginal(self, y_t, u_t, mask=None):
+        """The regime-marginal objective, normalised as elbo(): sum_b log p(a_b | u_b) / num_el with the regimes summed out
+        (regime_log_marginal) - no log_p - log_q term, no draw of any kind."""
+        Bsz, T = y_t.size(0), y_t.size(1)
+        mask = self._mask(mask, y_t)
+        out = self.regime_log_marginal(y_t, u_t, mask)
+        self.last_marginal_levels = out["levels"]
+        num_el = mask.sum().clamp(min=1.0) if mask is not None else float(Bsz * T)
+        return out["seq_ll"].sum() / num_el
+
     def log_marginal(self, Y, U, mask=None):
         """log p(a | u), exactly and DIFFERENTIABLY: the filter (training or eval dynamics as self.training says; no RTS sweep),
         then lgssm_ops.log_marginal over its one-step-ahead beliefs - C_t out of the packed step record where there is one.

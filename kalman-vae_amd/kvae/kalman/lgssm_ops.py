@@ -11,8 +11,9 @@ a whole step record, a single tensor carries its gradient) or a plain tensor tha
 ([r,c]) or per-step ([B,T,r,c]).
 
 This module is the bridge only.  The read-outs (regime_decode, rollout, posterior_paths, predictive, log_marginal,
-switching_filter) dispatch between their kernel and its restatement in torch ops; the restatements - also the float64 references
-of the tests - and safe_cholesky / safe_cholesky_items live in lgssm_torch (no native library behind it) and are re-exported here.
+switching_filter, switching_smoother, switching_log_marginal) dispatch between their kernel and its restatement in torch ops;
+the restatements - also the float64 references of the tests - and safe_cholesky / safe_cholesky_items live in lgssm_torch (no
+native library behind it) and are re-exported here.
 """
 import ctypes as C
 from typing import NamedTuple, Optional
@@ -22,7 +23,8 @@ import torch
 from .. import _native as N
 from .lgssm_torch import (_DECODE_OUTPUTS, _LOG_2PI, _PRED_OUTPUTS, _SWF_OUTPUTS, _SWS_OUTPUTS, _SWS_SMOOTH, _bt, _swf_state, _want,  # noqa: F401 (re-exported)
                           log_marginal_torch, posterior_paths_torch, predictive_torch, regime_decode_torch, rollout_torch,
-                          safe_cholesky, safe_cholesky_items, switching_filter_torch, switching_smoother_torch)
+                          safe_cholesky, safe_cholesky_items, switching_filter_torch, switching_log_marginal_torch,
+                          switching_smoother_torch)
 
 
 class Slots(NamedTuple):
@@ -1069,3 +1071,99 @@ def switching_smoother(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, want=_S
     if out["regime_pairs"] is not None:
         out["regime_pairs"] = out["regime_pairs"][:, :T - 1]   # nothing is written at T = 1
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# log p(a | u) with the regimes summed out, differentiable (kvae_lgssm_switching_marginal[_bwd], csrc/lgssm_swm.h)
+# ------------------------------------------------------------------------------------------------
+def _swm_problem(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, hist):
+    """(kvae_swm_problem, tensors to keep alive) over the inputs and the history (lw, mu, Sigma); the output pointers are NULL."""
+    sp = N.SwmProblem()
+    _, _, keep = _swf_problem(sp.filt, A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, None, ())
+    sp.hist_lw, sp.hist_mu, sp.hist_Sigma = (t.data_ptr() for t in hist)
+    return sp, keep[:-1] + (hist,)
+
+
+class SwitchingLogLik(torch.autograd.Function):
+    """(ll [B,T], seq_ll [B], levels [B,T]) of kvae_lgssm_switching_marginal with the adjoint kvae_lgssm_switching_marginal_bwd: one
+    call each way (the backward: the sweep and the sum of its per-sequence partials).  Gradients for A, Bm, Q, Cm, P (g_logP / P
+    where P > 0, else 0), mu0, Sigma0, Y and U.  R is a buffer of the model: no gradient."""
+
+    @staticmethod
+    def forward(ctx, A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask):
+        K, n = A.shape[0], A.shape[1]
+        Bsz, T, _ = Y.shape
+        dev = Y.device
+        hist = (_empty(dev, Bsz, T, K), _empty(dev, Bsz, T, K, n), _empty(dev, Bsz, T, K, n, n))
+        sp, keep = _swm_problem(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, hist)
+        ll, seq, levels = _empty(dev, Bsz, T), _empty(dev, Bsz), _empty(dev, Bsz, T, dt=torch.int32)
+        sp.filt.ll, sp.filt.seq_ll, sp.filt.levels = ll.data_ptr(), seq.data_ptr(), levels.data_ptr()
+        lib = N.lib_for(Y)
+        lib.check(N.timed("switching_marginal", Y, lambda: lib.dll.kvae_lgssm_switching_marginal(C.byref(sp), N.stream_for(Y))),
+                  "kvae_lgssm_switching_marginal")
+        del keep
+        ctx.mark_non_differentiable(levels)
+        ctx.set_materialize_grads(False)   # an output nobody differentiates arrives as None: a NULL upstream
+        ctx.has_mask = mask is not None
+        ctx.save_for_backward(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, *hist, *(() if mask is None else (mask,)))
+        return ll, seq, levels
+
+    @staticmethod
+    def backward(ctx, g_ll, g_seq, _g_levels):
+        need = ctx.needs_input_grad
+        if (g_ll is None and g_seq is None) or not any(need):
+            return (None,) * 11
+        A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, *rest = ctx.saved_tensors
+        hist, mask = tuple(rest[:3]), (rest[3] if ctx.has_mask else None)
+        K, n, m = A.shape[0], A.shape[1], Bm.shape[2]
+        Bsz, T, p = Y.shape
+        dev = Y.device
+        sp, keep = _swm_problem(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, hist)
+        g_ll, g_seq = _f32c(g_ll), _f32c(g_seq)
+        lib = N.lib_for(Y)
+        ws = _empty(dev, lib.dll.kvae_lgssm_switching_marginal_ws_floats(Bsz, K, n, m))
+        shapes = ((K, n, n), (K, n, m), (K, n, n), None, None, (K, K), (n,), (n, n), (Bsz, T, p), (Bsz, T, m))
+        outs = [None if s is None or not need[i] else _empty(dev, *s) for i, s in enumerate(shapes)]
+        if need[3]:
+            outs[3] = _empty(dev, p, n)
+        g = N.SwmGrads()
+        g.g_ll, g.g_seq, g.ws = N.ptr(g_ll), N.ptr(g_seq), ws.data_ptr()
+        g.gA, g.gB, g.gQ, g.gC, _, g.g_logP, g.g_mu0, g.g_Sigma0, g.gY, g.gU = (N.ptr(o) for o in outs)
+        lib.check(N.timed("switching_marginal_bwd", Y, lambda: lib.dll.kvae_lgssm_switching_marginal_bwd(C.byref(sp), C.byref(g),
+                                                                                                        N.stream_for(Y))),
+                  "kvae_lgssm_switching_marginal_bwd")
+        del keep
+        if outs[5] is not None:   # gP from the adjoint of log P: exactly 0 at the zeros of P
+            Pd = P.detach().to(dev, torch.float32)
+            outs[5] = torch.where(Pd > 0, outs[5] / torch.where(Pd > 0, Pd, torch.ones_like(Pd)), torch.zeros_like(Pd))
+        cast = lambda o, ref: None if o is None else o.to(ref.dtype).reshape(ref.shape)
+        return tuple(cast(o, ref) for o, ref in zip(outs, (A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U))) + (None,)
+
+
+def switching_log_marginal(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, state=None, impl=None):
+    """log p(a_t | a_{0:t-1}, u) of every step with the regimes summed out under GPB2 collapse, and its per-sequence sum,
+    DIFFERENTIABLE w.r.t. A, Bm, Q, Cm, P, mu0, Sigma0, Y and U (switching_filter is the no-grad read-out with more outputs; its
+    log_lik, log_lik_seq and levels are these bits).  Arguments as switching_filter; R is a buffer (no gradient); a carried
+    `state` is not accepted (no truncated back-propagation through streams): ValueError.  It is the gradient of the GPB2 value:
+    exact where the filter is exact (P = I, shared A / B / Q, t <= 1), elsewhere the gradient of the approximation.
+    Returns dict(ll [B,T], seq_ll [B], levels [B,T] int32).  Forward two launches, backward two (the adjoint sweep, the sum of its
+    per-sequence partials), no atomics, no host synchronisation.
+    impl: None = the HIP kernels where built (switching_filter_supported), else switching_log_marginal_torch; "hip" / "torch" force one."""
+    if state is not None:
+        raise ValueError("switching_log_marginal: a carried state is not differentiable here (state must be None)")
+    if impl not in (None, "hip", "torch"):
+        raise ValueError(f"switching_log_marginal: impl must be None, 'hip' or 'torch', got {impl!r}")
+    K, n, m = A.shape[0], A.shape[1], Bm.shape[2]
+    Bsz, T, p = Y.shape
+    supported = switching_filter_supported(K, n, m, p, Y) and A.dtype == torch.float32
+    if impl == "hip" and not supported:
+        raise ValueError(f"switching_log_marginal: impl='hip' needs fp32 tensors on a HIP device and K <= {SWF_SUPPORTED['max_K']}, "
+                         f"n <= {SWF_SUPPORTED['max_n']}, m <= {SWF_SUPPORTED['max_m']}, p == {SWF_SUPPORTED['p']}; got K = {K}, "
+                         f"n = {n}, m = {m}, p = {p}, {Y.dtype} on {Y.device}")
+    if impl == "torch" or not supported:
+        return switching_log_marginal_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask)
+    dev = Y.device
+    mask = None if mask is None else mask.detach().to(dev).reshape(Bsz, T)
+    ll, seq, levels = SwitchingLogLik.apply(*(t.to(dev) for t in (A, Bm, Q, Cm)), R.detach().to(dev), *(t.to(dev) for t in (P, mu0, Sigma0)), Y, U, mask)
+    return {"ll": ll, "seq_ll": seq, "levels": levels}
+

@@ -395,3 +395,76 @@ def _sws_backward(A, Bm, Q, U, hist, w_last):
     return {k: (torch.stack(v[::-1], 1) if v else w_last.new_zeros(w_last.shape[0], 0, K, K)) for k, v in outs.items()}
 
 
+def switching_log_marginal_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None):
+    """switching_log_marginal in torch ops, DIFFERENTIABLE, in the dtype of A: dict(ll [B,T], seq_ll [B], levels [B,T]) - the log_lik,
+    log_lik_seq and levels of switching_filter_torch without a carried state - with a tape through A, Bm, Q, Cm, P, mu0, Sigma0, Y
+    and U (R is a buffer of the model).  The fallback of switching_log_marginal and (in float64) the reference its adjoint kernel is
+    tested against.  It is the gradient of the GPB2 VALUE: where the filter is exact (P = I, shared A / B / Q, t <= 1) the exact
+    gradient of log p(a | u), elsewhere the gradient of the approximation.
+    The sweep of _swf_forward without the detaches, restated where autograd would otherwise give NaN: the ladder levels are found
+    without a tape and S + jitter[level] I is factorised once (as log_marginal_torch); every -inf (a zero of P, a dead column) is
+    kept out of the taped arithmetic by selects, so that its gradient is 0.  Q and Sigma0 enter through their symmetric part (the
+    same numbers for symmetric matrices): their gradients are the gradients over symmetric matrices, hence symmetric."""
+    dt, dev = A.dtype, Y.device
+    K, n = A.shape[0], A.shape[1]
+    Bsz, T, p = Y.shape
+    A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U = (t.to(device=dev, dtype=dt) for t in (A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U))
+    R = R.detach()
+    Q, Sigma0 = 0.5 * (Q + Q.mT), 0.5 * (Sigma0 + Sigma0.mT)
+    mask = None if mask is None else mask.detach().to(device=dev, dtype=dt).reshape(Bsz, T)
+    lw = torch.full((Bsz, K), 1.0 / K, device=dev, dtype=dt).log()
+    mu, Sig = mu0.expand(Bsz, K, n), Sigma0.expand(Bsz, K, n, n)
+    eye, eyeP, eyeK = torch.eye(n, device=dev, dtype=dt), torch.eye(p, device=dev, dtype=dt), torch.eye(K, device=dev, dtype=dt)
+    uniform = torch.full((K, K), 1.0 / K, device=dev, dtype=dt)
+    jitters = torch.tensor([*_jitter_ladder(), 0.0], device=dev, dtype=torch.float64)
+    zero = torch.zeros((), device=dev, dtype=dt)
+    lls, levels = [], []
+    for t in range(T):
+        Pt = uniform if t == 0 else P
+        mk = torch.ones(Bsz, device=dev, dtype=dt) if mask is None else mask[:, t]
+        observed = mk != 0
+        # ---- the K^2 filter steps: [B, i, j, ...] ----
+        mp = torch.einsum("jrc,bic->bijr", A, mu) + torch.einsum("jrc,bc->bjr", Bm, U[:, t]).unsqueeze(1)
+        Sp = torch.einsum("jre,biec,jdc->bijrd", A, Sig, A) + Q
+        ap = mp @ Cm.mT
+        res = Y[:, t, None, None, :] - ap
+        S = Cm @ Sp @ Cm.mT + R
+        S = 0.5 * (S + S.mT)
+        with torch.no_grad():
+            _, lv = safe_cholesky_items(S)
+        St = S + (jitters[lv.long()][..., None, None] * eyeP.double()).to(dt)
+        clamped = torch.diag_embed(torch.diagonal(S, dim1=-2, dim2=-1).clamp(min=1e-6))
+        St = torch.where((lv == 5)[..., None, None], clamped, St)
+        lij = _observed_only(_gauss_ll(torch.linalg.cholesky(St), res)[0], observed[:, None, None])
+        Kg = torch.linalg.solve(S, Cm @ Sp).mT * mk[:, None, None, None, None]
+        muf = mp + (Kg @ res.unsqueeze(-1)).squeeze(-1)
+        IKC = eye - Kg @ Cm
+        Sf = IKC @ Sp @ IKC.mT + Kg @ R @ Kg.mT
+        Sf = 0.5 * (Sf + Sf.mT)
+        # ---- weights: an impossible pair (P[i,j] = 0, or regime i dead) is masked out, never added as -inf ----
+        possible = (Pt > 0) & torch.isfinite(lw.detach()).unsqueeze(-1)               # [B, i, j]
+        logc = torch.where(possible, torch.where(possible, lw.unsqueeze(-1), zero) + torch.where(Pt > 0, Pt, torch.ones_like(Pt)).log() + lij, zero)
+        with torch.no_grad():
+            pw = lw.exp().unsqueeze(-1) * Pt
+            cmx = torch.where(possible, logc, torch.full_like(logc, -float("inf"))).amax(1)   # [B, j]
+            dead = ~possible.any(1)
+            shift = torch.where(dead, torch.zeros_like(cmx), cmx)
+        ex = torch.where(possible, (logc - shift.unsqueeze(1)).exp(), zero)
+        ex = torch.where(dead.unsqueeze(1), eyeK.expand(Bsz, K, K), ex)
+        se = ex.sum(1)
+        W = ex / se.unsqueeze(1)
+        with torch.no_grad():
+            mx = torch.where(dead, torch.full_like(cmx, -float("inf")), cmx).amax(-1, keepdim=True)
+        col = torch.where(dead, zero, se * (shift - mx).exp())                       # a dead column adds nothing
+        tot = mx.squeeze(-1) + col.sum(-1).log()
+        lw = torch.where(dead, torch.full_like(cmx, -float("inf")), (shift + torch.where(dead, torch.ones_like(se), se).log()) - tot.unsqueeze(-1))
+        # ---- collapse over i ----
+        mu = (W.unsqueeze(-1) * muf).sum(1)
+        d = muf - mu.unsqueeze(1)
+        Sig = (W[..., None, None] * (Sf + d.unsqueeze(-1) * d.unsqueeze(-2))).sum(1)
+        Sig = 0.5 * (Sig + Sig.mT)
+        lls.append(torch.where(observed, tot, torch.zeros_like(tot)))
+        levels.append(torch.where(pw > 0, lv, torch.zeros_like(lv)).amax((1, 2)))
+    ll = torch.stack(lls, 1)
+    return {"ll": ll, "seq_ll": ll.sum(1), "levels": torch.stack(levels, 1)}
+

@@ -69,6 +69,8 @@ class KVAE(nn.Module):
     # The LGSSM term of the objective: "elbo" = the reference's one-sample ELBO (z_t drawn from the smoothing marginals), "marginal"
     # = the exact log p(a | u) of the prediction-error decomposition (KalmanFilter.marginal: zero variance, no RTS sweep, no eps_z).
     # With "marginal" a TRAINING-mode forward runs the filter only: outputs["mus_smooth"] / ["Sigmas_smooth"] are None.
+    # "regime_marginal" (switching dynamics) = log p(a | u) with the regimes summed out under GPB2 (KalmanFilter.regime_marginal): the
+    # regime posterior network plays no part; a TRAINING-mode forward runs neither it nor the filter, every LGSSM output is None.
     kf_objective = "elbo"
     kf_value_only = False   # "vae" phase (reference train.py:246-250: kf_weight = 0, every LGSSM parameter frozen): the chain runs
     #                         forward only, without a tape, for the logged elbo_kf; nothing of it is differentiated
@@ -130,8 +132,10 @@ class KVAE(nn.Module):
 
     def _kf_objective(self, value=None):
         value = self.kf_objective if value is None else value
-        if value not in ("elbo", "marginal"):
-            raise ValueError(f"kf_objective must be 'elbo' or 'marginal', got {value!r}")
+        if value not in ("elbo", "marginal", "regime_marginal"):
+            raise ValueError(f"kf_objective must be 'elbo', 'marginal' or 'regime_marginal', got {value!r}")
+        if value == "regime_marginal" and not self.kalman_filter.dyn_params.is_switching_dynamics:
+            raise ValueError("kf_objective 'regime_marginal' needs switching dynamics: the lstm dynamics have no regimes to sum out")
         return value
 
     def _to_pixels(self, logits):
@@ -194,7 +198,10 @@ class KVAE(nn.Module):
         a_side = None
         value_only = self.kf_value_only and self.training
         kf = self.kalman_filter
-        if self._kf_objective() == "marginal" and self.training:   # the exact objective reads the one-step-ahead beliefs only
+        objective = self._kf_objective()
+        if objective == "regime_marginal" and self.training:   # compute_loss sums the regimes out over a_samples: nothing to run here
+            run = lambda y, uu, mask=None: (None,) * 9
+        elif objective == "marginal" and self.training:   # the exact objective reads the one-step-ahead beliefs only
             run = lambda y, uu, mask=None: (None, None) + kf.filter(y, uu, mask=mask)
         else:
             run = kf.smooth
@@ -232,7 +239,8 @@ class KVAE(nn.Module):
         at run time, so a step captured into a hipGraph follows the reference's phase weights (train.py:246-260).
         `kf_objective` (addition): None = self.kf_objective; "elbo" = the reference's one-sample ELBO; "marginal" = elbo_kf is the
         exact (seq_ll.sum() [+ switching: log_p.sum() - log_q.sum()]) / num_el over outputs["mus_pred"], ["Sigmas_pred"], ["ABC"] and
-        a_samples (KalmanFilter.marginal), num_el as in KalmanFilter.elbo."""
+        a_samples (KalmanFilter.marginal), num_el as in KalmanFilter.elbo; "regime_marginal" (switching dynamics) = elbo_kf is
+        seq_ll.sum() / num_el of KalmanFilter.regime_log_marginal over a_samples and u: the regimes summed out, no regime-chain term."""
         objective = self._kf_objective(kf_objective)
         if weights_dev is not None:
             vae_weight, kf_weight = weights_dev[0], weights_dev[1]
@@ -252,6 +260,8 @@ class KVAE(nn.Module):
             stats = ((variances > 1e-2).sum(), variances)
 
         def kf_term(a_in):
+            if objective == "regime_marginal":
+                return self.kalman_filter.regime_marginal(a_in, u, mask=mask)
             if objective == "marginal":
                 return self.kalman_filter.marginal(outputs["mus_pred"], outputs["Sigmas_pred"], a_in, C_list, mask=mask)
             return self.kalman_filter.elbo(outputs["mus_smooth"], outputs["Sigmas_smooth"], a_in, u, A_list, B_list, C_list, mask=mask)

@@ -98,10 +98,10 @@ class Trainer:
         graph_allreduce: with world_size > 1, capture the RCCL all-reduce into the step's hipGraph (one replay per step)
         instead of cutting the graph around an eager call.
         kf_objective: the LGSSM term of this trainer's steps - "elbo" (the reference's one-sample ELBO) or "marginal" (the exact
-        log p(a | u): KVAE.kf_objective); carried by the model only inside the trainer's own forward+backward (_schedule)."""
-        if kf_objective not in ("elbo", "marginal"):
-            raise ValueError(f"kf_objective must be 'elbo' or 'marginal', got {kf_objective!r}")
-        self.kf_objective = kf_objective
+        log p(a | u): KVAE.kf_objective) or "regime_marginal" (switching dynamics: log p(a | u) with the regimes summed out; the
+        regime posterior network then takes no gradient - inactive slots of the fused clip + Adam); carried by the model only
+        inside the trainer's own forward+backward (_schedule)."""
+        self.kf_objective = model._kf_objective(kf_objective)   # raises for an unknown name, or one the dynamics cannot serve
         self.model, self.clip = model, grad_clip_norm
         self.world = world_size
         self.reference_logging = bool(reference_logging)
