@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 #define KVAE_MAX_DIM 16
-#define KVAE_ABI_VERSION 18
+#define KVAE_ABI_VERSION 19
 
 typedef enum {
   KVAE_OK = 0,
@@ -694,6 +694,51 @@ typedef struct {
 int kvae_lgssm_switching_marginal(const kvae_swm_problem *prob, void *stream);
 int kvae_lgssm_switching_marginal_bwd(const kvae_swm_problem *prob, const kvae_swm_grads *g, void *stream);
 int64_t kvae_lgssm_switching_marginal_ws_floats(int32_t B, int32_t K, int32_t n, int32_t m);
+
+/* ---- EM for the switching dynamics: the expected sufficient statistics (GPB2 E-step) -------------------------------------------
+ * (kvae/kalman/kalman_filter.py KalmanFilter.em_statistics / em_step; kvae/train/em.py fit_dynamics_em)
+ * kvae_lgssm_switching_smoother over `prob` (the same fields and NULL rules, every output the bits of that call's; a carried state
+ * is not accepted) whose backward pass also crosses the transition INTO t = 0 - source belief (mu0, Sigma0) for every i, weights
+ * hist_W[:, 0] (the uniform-matrix step), input u_0, destination the smoothed belief of step 0 - and accumulates, over every
+ * transition into step t = 0 .. T-1 and every pair (j = source regime, k = regime at t), with
+ *   xi = W_t[j,k] M_t(k)   (after the column-sum division)      x = (z_{t-1}, u_t)
+ *   destination moments mu_s^k_t, Sigma_s^k_t    source moments mu_s_jk, Sigma_s_jk    Cov(z_t, z_{t-1}) = Sigma_s^k_t J_jk^T
+ * the sums
+ *   N[k] += xi                                      S11[k] += xi (Sigma_s^k + mu_s^k mu_s^k^T)
+ *   S10[k] += xi [ Sigma_s^k J^T + mu_s^k mu_s_jk^T | mu_s^k u_t^T ]
+ *   S00[k] += xi [[Sigma_s_jk + mu_s_jk mu_s_jk^T, mu_s_jk u^T], [., u u^T]]
+ *   counts[j,k] += xi   (t >= 1 only)
+ *   z0 = sum_ik xi mu_s_ik,  z0z0 = sum_ik xi (Sigma_s_ik + mu_s_ik mu_s_ik^T)        (the step into t = 0)
+ * and at every observed step, with (m_t, V_t) the moment match that gives mus_smooth / Sigmas_smooth,
+ *   Syz += a_t m_t^T     Szz += V_t + m_t m_t^T     Syy += a_t a_t^T     Nobs += 1.
+ * Under GPB2 mu_s^k_t stands in for the pair-conditional mean of the destination: exact wherever the smoother is exact.  One
+ * wavefront per sequence accumulates its pair's share in registers over t, reduces over the source regime after the step into
+ * t = 0 and writes ONE row per sequence into ws [B, G], every element once (symmetric blocks mirrored from the upper triangle),
+ * G = K (1 + n^2 + n (n+m) + (n+m)^2) + K^2 + 2 n + n^2 + 4 + 1 + n + n^2, laid out
+ *   N [K] | S11 [K,n,n] | S10 [K,n,n+m] | S00 [K,n+m,n+m] | counts [K,K] | Syz [2,n] | Szz [n,n] | Syy [2,2] | Nobs [1] | z0 [n] | z0z0 [n,n]
+ * (kvae_lgssm_switching_em_ws_floats); a second launch sums ws over b in ascending order, one thread per element, into the
+ * requested outputs.  No atomics: two calls give the same bits, the bits of an output do not depend on which others are asked for,
+ * and a sequence's row of ws does not depend on B. */
+typedef struct {
+  float *ws;                  /* [B,G]  required workspace: the per-sequence rows, every element written                        */
+  float *N;                   /* [K]         outputs, each the sum over b; each may be NULL                                      */
+  float *S11;                 /* [K,n,n]                                                                                         */
+  float *S10;                 /* [K,n,n+m]                                                                                       */
+  float *S00;                 /* [K,n+m,n+m]                                                                                     */
+  float *counts;              /* [K,K]       indexed (s_{t-1}, s_t)                                                              */
+  float *Syz;                 /* [2,n]                                                                                           */
+  float *Szz;                 /* [n,n]                                                                                           */
+  float *Syy;                 /* [2,2]                                                                                           */
+  float *Nobs;                /* [1]         observed steps                                                                      */
+  float *z0;                  /* [n]                                                                                             */
+  float *z0z0;                /* [n,n]                                                                                           */
+  float *nseq;                /* [1]         = B                                                                                 */
+} kvae_em_stats;
+/* The error codes of kvae_lgssm_switching_smoother over `prob`; in addition KVAE_ERR_ARG: a carried state; KVAE_ERR_NULL: st or
+ * st->ws NULL.  Nothing is written on error.  At most four launches: forward, backward (skipped when neither a smoother output
+ * nor a statistic is asked for), the reduction (skipped when no statistic is asked for), seq_ll. */
+int kvae_lgssm_switching_em(const kvae_sws_problem *prob, const kvae_em_stats *st, void *stream);
+int64_t kvae_lgssm_switching_em_ws_floats(int32_t B, int32_t K, int32_t n, int32_t m);
 
 /* ---- misc --------------------------------------------------------------------------------- */
 int kvae_abi_version(void);

@@ -569,4 +569,6 @@ extern "C" int64_t kvae_lgssm_switching_marginal_ws_floats(int32_t B, int32_t K,
   return B < 1 || K < 1 || n < 1 || m < 1 ? 0 : (int64_t)B * kvae_swm::layout(K, n, m).G;
 }
 extern "C" int kvae_wemu_switching_marginal_launches(int which) { return which >= 0 && which <= 3 ? kvae_swm::emu_launches()[which] : -1; }
+
+#include "lgssm_em.h"     // likewise kvae_lgssm_switching_em
 #endif

@@ -40,6 +40,8 @@ __device__ __forceinline__ void load_sym(const float *S, int n, bool live, float
   }
 }
 
+// kvae_em::back_wave (csrc/lgssm_em.h, the E-step of EM) is a sibling of this body that repeats its statements in its order and
+// must give the bits of its outputs (tests/em_cases.py per_sequence compares them): a change here is made there too.
 __device__ inline void back_wave(const kvae_sws_problem &S) {
   const kvae_swf_problem &P = S.filt;
   const int lane = (int)(threadIdx.x & 63), k = lane & 7, g = lane >> 3;

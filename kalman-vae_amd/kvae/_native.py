@@ -17,7 +17,7 @@ LIB_PATH = _HERE / "lib" / "libkvae_lgssm.so"
 KVAE_MAX_DIM = 16
 KVAE_MAX_K = 16
 LSTM_MAX_H, LSTM_MAX_I = 52, 16
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 _STATUS = {1: "KVAE_ERR_DIMS (n, m, p must be in [1,16]; B, T >= 1)", 2: "KVAE_ERR_NULL", 3: "KVAE_ERR_LAUNCH",
            4: "KVAE_ERR_ARG"}
@@ -91,6 +91,10 @@ class SwmGrads(C.Structure):  # kvae_swm_grads
                                          "ll_recomputed")]
 
 
+class EmStats(C.Structure):  # kvae_em_stats
+    _fields_ = [(k, C.c_void_p) for k in ("ws", "N", "S11", "S10", "S00", "counts", "Syz", "Szz", "Syy", "Nobs", "z0", "z0z0", "nseq")]
+
+
 class InputGrads(C.Structure):  # kvae_lgssm_input_grads
     _fields_ = [("gA", Stack), ("gB", Stack), ("gC", Stack), ("gQ", Stack),
                 ("gY", C.c_void_p), ("gU", C.c_void_p), ("g_mu0", C.c_void_p), ("g_Sigma0", C.c_void_p)]
@@ -110,7 +114,8 @@ SYMBOLS = (
     "kvae_loss_head_bwd", "kvae_lgssm_emission_means", "kvae_lgssm_generate", "kvae_lgssm_posterior_sample",
     "kvae_lgssm_posterior_sample_ws_floats", "kvae_lgssm_predictive", "kvae_lgssm_predictive_bwd",
     "kvae_lgssm_switching_filter", "kvae_lgssm_switching_smoother", "kvae_lgssm_switching_marginal",
-    "kvae_lgssm_switching_marginal_bwd", "kvae_lgssm_switching_marginal_ws_floats", "kvae_rnn_wgrad", "kvae_rnn_wgrad_ws_floats", "kvae_linear_fwd",
+    "kvae_lgssm_switching_marginal_bwd", "kvae_lgssm_switching_marginal_ws_floats", "kvae_lgssm_switching_em",
+    "kvae_lgssm_switching_em_ws_floats", "kvae_rnn_wgrad", "kvae_rnn_wgrad_ws_floats", "kvae_linear_fwd",
     "kvae_linear_bwd_input", "kvae_abi_version", "kvae_last_error", "kvae_build_info",
 )
 
@@ -153,6 +158,10 @@ class LgssmLib:
         d.kvae_lgssm_switching_marginal_bwd.restype = C.c_int
         d.kvae_lgssm_switching_marginal_ws_floats.argtypes = [C.c_int32] * 4
         d.kvae_lgssm_switching_marginal_ws_floats.restype = C.c_int64
+        d.kvae_lgssm_switching_em.argtypes = [C.POINTER(SwsProblem), C.POINTER(EmStats), vp]
+        d.kvae_lgssm_switching_em.restype = C.c_int
+        d.kvae_lgssm_switching_em_ws_floats.argtypes = [C.c_int32] * 4
+        d.kvae_lgssm_switching_em_ws_floats.restype = C.c_int64
         d.kvae_lgssm_smooth_bwd.argtypes = [P, S, S, G, vp, C.c_int, vp]
         d.kvae_lgssm_smooth_bwd.restype = C.c_int
         d.kvae_lgssm_elbo.argtypes = [P, vp, vp, vp, vp, vp, vp, vp, vp, G, vp]

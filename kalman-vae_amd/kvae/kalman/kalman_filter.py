@@ -298,6 +298,58 @@ class KalmanFilter(nn.Module):
         return lgssm_ops.switching_log_marginal(dyn.A, dyn.B, dyn.Q, dyn.C[0], self.R, dyn._prior_matrix(Y.device, Y.dtype), self.mu0,
                                                 self.Sigma0, Y, U, self._mask(mask, Y))
 
+    def _em_operands(self, method, Y):
+        dyn = self.dyn_params
+        if not dyn.is_switching_dynamics:
+            raise ValueError(f"{method} needs switching dynamics (SwitchingDynamicsParameter): EM is built for the generative "
+                             "switching model, not for the alpha-network of the lstm dynamics")
+        return (dyn.A.detach(), dyn.B.detach(), dyn.Q.detach(), dyn.C[0].detach(), self.R, dyn._prior_matrix(Y.device, Y.dtype),
+                self.mu0, self.Sigma0)
+
+    @torch.no_grad()
+    def em_statistics(self, Y, U, mask=None, want=lgssm_ops._EM_OUTPUTS):
+        """The E-step of EM for the generative switching model (switching dynamics only; K = 1 is allowed): smooth_regimes, whose
+        backward pass also crosses the transition into t = 0 and accumulates the expected sufficient statistics of (A_k, B_k,
+        Q_k), (C, R), P and (mu0, Sigma0) - lgssm_ops.switching_em_statistics; include/kvae_lgssm.h kvae_lgssm_switching_em.  The
+        regime posterior network plays no part.  Returns the sums over the batch (additive over batches: lgssm_ops.em_add),
+        log_lik_seq [B] and smooth_regimes' four outputs; entries not named in `want` are None.  No host synchronisation: the call
+        can be captured into a hipGraph."""
+        ops = self._em_operands("em_statistics", Y)
+        return lgssm_ops.switching_em_statistics(*ops, Y, U, self._mask(mask, Y), want=want)
+
+    @torch.no_grad()
+    def em_step(self, Y, U, mask=None, update=("A", "B", "Q", "C", "P"), stats=None, min_count=None):
+        """One EM iteration of the generative switching model in closed form (switching dynamics only): em_statistics over
+        (Y, U, mask) - or the `stats` given, e.g. added over several batches with lgssm_ops.em_add - then
+        lgssm_ops.switching_em_mstep.  update: which of "A", "B", "Q", "C", "R", "P", "mu0", "Sigma0" to re-estimate.  The new values
+        are copied into dyn_params.A / B / Q / C (the one shared C into every slice), a new prior.transition_matrix is assigned (so
+        that its cached device copy is rebuilt), and the buffers R, mu0, Sigma0 are written only when they are named.  A regime
+        with fewer than min_count (default n + m + 1) expected visits, or whose new Q_k is not positive definite, keeps its
+        parameters; a row of P without counts keeps its values; without a control input (u identically 0) B_k is held and A_k
+        is fitted given it.  Returns dict(log_lik = sum_b log p(a_b | u_b) BEFORE the step - None if `stats` holds no log_lik_seq -
+        stats, skipped = switching_em_mstep's {"regimes": [...], "rows": [...], "B_held": [...], "emission": bool}).  The M-step
+        reads the skipped lists back: it synchronises with the host and cannot be captured into a hipGraph (em_statistics can)."""
+        update = lgssm_ops._want("em_step", lgssm_ops._EM_PARAMS, update)
+        ops = self._em_operands("em_step", self.mu0 if Y is None else Y)   # Y, U may be None when `stats` is given
+        if stats is None:
+            stats = self.em_statistics(Y, U, mask, want=lgssm_ops._EM_STATS + ("log_lik_seq",))
+        dyn = self.dyn_params
+        old = dict(zip(("A", "B", "Q", "C", "R", "P", "mu0", "Sigma0"), ops))
+        new, skipped = lgssm_ops.switching_em_mstep(stats, old, update, min_count)
+        for k in ("A", "B", "Q"):
+            if k in update:
+                getattr(dyn, k).copy_(new[k].to(getattr(dyn, k)))
+        if "C" in update:
+            dyn.C.copy_(new["C"].to(dyn.C).expand_as(dyn.C))
+        if "P" in update:
+            P_old = dyn.prior.transition_matrix
+            dyn.prior.transition_matrix = new["P"].to(device=P_old.device, dtype=P_old.dtype)
+        for k in ("R", "mu0", "Sigma0"):
+            if k in update:
+                getattr(self, k).copy_(new[k].to(getattr(self, k)))
+        lls = stats.get("log_lik_seq")   # None when the caller's statistics were made without it
+        return {"log_lik": None if lls is None else lls.double().sum(), "stats": stats, "skipped": skipped}
+
     def regime_marginal(self, y_t, u_t, mask=None):
         """The regime-marginal objective, normalised as elbo(): sum_b log p(a_b | u_b) / num_el with the regimes summed out
         (regime_log_marginal) - no log_p - log_q term, no draw of any kind."""

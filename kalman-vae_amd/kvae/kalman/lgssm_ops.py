@@ -11,7 +11,7 @@ a whole step record, a single tensor carries its gradient) or a plain tensor tha
 ([r,c]) or per-step ([B,T,r,c]).
 
 This module is the bridge only.  The read-outs (regime_decode, rollout, posterior_paths, predictive, log_marginal,
-switching_filter, switching_smoother, switching_log_marginal) dispatch between their kernel and its restatement in torch ops;
+switching_filter, switching_smoother, switching_log_marginal, switching_em_statistics) dispatch between their kernel and its restatement in torch ops;
 the restatements - also the float64 references of the tests - and safe_cholesky / safe_cholesky_items live in lgssm_torch (no
 native library behind it) and are re-exported here.
 """
@@ -21,10 +21,10 @@ from typing import NamedTuple, Optional
 import torch
 
 from .. import _native as N
-from .lgssm_torch import (_DECODE_OUTPUTS, _LOG_2PI, _PRED_OUTPUTS, _SWF_OUTPUTS, _SWS_OUTPUTS, _SWS_SMOOTH, _bt, _swf_state, _want,  # noqa: F401 (re-exported)
-                          log_marginal_torch, posterior_paths_torch, predictive_torch, regime_decode_torch, rollout_torch,
-                          safe_cholesky, safe_cholesky_items, switching_filter_torch, switching_log_marginal_torch,
-                          switching_smoother_torch)
+from .lgssm_torch import (_DECODE_OUTPUTS, _EM_OUTPUTS, _EM_PARAMS, _EM_STATS, _LOG_2PI, _PRED_OUTPUTS, _SWF_OUTPUTS, _SWS_OUTPUTS, _SWS_SMOOTH, _bt,  # noqa: F401 (re-exported)
+                          _swf_state, _want, log_marginal_torch, posterior_paths_torch, predictive_torch, regime_decode_torch,
+                          rollout_torch, safe_cholesky, safe_cholesky_items, switching_em_mstep, switching_em_statistics_torch,
+                          switching_filter_torch, switching_log_marginal_torch, switching_smoother_torch)
 
 
 class Slots(NamedTuple):
@@ -1167,3 +1167,98 @@ def switching_log_marginal(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, sta
     ll, seq, levels = SwitchingLogLik.apply(*(t.to(dev) for t in (A, Bm, Q, Cm)), R.detach().to(dev), *(t.to(dev) for t in (P, mu0, Sigma0)), Y, U, mask)
     return {"ll": ll, "seq_ll": seq, "levels": levels}
 
+
+
+# ------------------------------------------------------------------------------------------------
+# EM for the switching dynamics: the expected sufficient statistics (kvae_lgssm_switching_em, csrc/lgssm_em.h)
+# ------------------------------------------------------------------------------------------------
+def switching_em_supported(K, n, m, p, ref=None):
+    """Shapes / tensors kvae_lgssm_switching_em is built for: the filter's (switching_filter_supported); the rest takes
+    switching_em_statistics_torch."""
+    return switching_filter_supported(K, n, m, p, ref)
+
+
+def _em_shapes(K, n, m):
+    x = n + m
+    return dict(N=(K,), S11=(K, n, n), S10=(K, n, x), S00=(K, x, x), counts=(K, K), Syz=(2, n), Szz=(n, n), Syy=(2, 2), Nobs=(1,),
+                z0=(n,), z0z0=(n, n), nseq=(1,))
+
+
+@torch.no_grad()
+def switching_em_statistics(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, want=_EM_OUTPUTS, state=None, impl=None, ws_out=None):
+    """The E-step of EM for the generative switching model (semantics: include/kvae_lgssm.h, kvae_lgssm_switching_em; DESIGN.md
+    section 17): switching_smoother, whose backward pass also crosses the transition into t = 0 and accumulates the expected
+    sufficient statistics.  Arguments as switching_smoother; a carried `state` is not accepted: ValueError.  want: which of the
+    sums over the sequences "N" [K], "S11" [K,n,n], "S10" [K,n,n+m], "S00" [K,n+m,n+m], "counts" [K,K], "Syz" [2,n], "Szz" [n,n],
+    "Syy" [2,2], "Nobs" [1], "z0" [n], "z0z0" [n,n], "nseq" [1], of "log_lik_seq" [B] and of the four smoother outputs to compute;
+    entries not asked for are None.  The statistics are additive over batches (em_add) and feed switching_em_mstep.  At most four
+    launches (forward, backward, the sum over the sequences, log_lik_seq), no atomics, no host synchronisation, no gradients.
+    ws_out: a list that receives the per-sequence rows [B, G] the kernel wrote (tests).
+    impl: None = the HIP kernel where it is built (switching_em_supported), else switching_em_statistics_torch; "hip" / "torch"
+    force one."""
+    want = _want("switching_em_statistics", _EM_OUTPUTS, want)
+    if state is not None:
+        raise ValueError("switching_em_statistics: a carried state is not accepted (the step into t = 0 needs the prior; state must be None)")
+    if impl not in (None, "hip", "torch"):
+        raise ValueError(f"switching_em_statistics: impl must be None, 'hip' or 'torch', got {impl!r}")
+    K, n, m = A.shape[0], A.shape[1], Bm.shape[2]
+    Bsz, T, p = Y.shape
+    supported = switching_em_supported(K, n, m, p, Y) and A.dtype == torch.float32
+    if impl == "hip" and not supported:
+        raise ValueError(f"switching_em_statistics: impl='hip' needs fp32 tensors on a HIP device and K <= {SWF_SUPPORTED['max_K']}, "
+                         f"n <= {SWF_SUPPORTED['max_n']}, m <= {SWF_SUPPORTED['max_m']}, p == {SWF_SUPPORTED['p']}; got K = {K}, "
+                         f"n = {n}, m = {m}, p = {p}, {A.dtype} on {Y.device}")
+    if impl == "torch" or not supported:
+        return switching_em_statistics_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, want)
+    dev = Y.device
+    sp, es = N.SwsProblem(), N.EmStats()
+    out, _, keep = _swf_problem(sp.filt, A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, None, tuple(w for w in want if w == "log_lik_seq"))
+    out = {"log_lik_seq": out["log_lik_seq"]}
+    hist = (_empty(dev, Bsz, T, K, n), _empty(dev, Bsz, T, K, n, n), _empty(dev, Bsz, T, K, K), _empty(dev, Bsz, K))
+    sp.hist_mu, sp.hist_Sigma, sp.hist_W, sp.hist_w = (t.data_ptr() for t in hist)
+    out.update(_wanted(dev, _SWS_SMOOTH, want, dict(regime_smooth=(Bsz, T, K), regime_pairs=(Bsz, max(T - 1, 1), K, K),
+                                                    mus_smooth=(Bsz, T, n), Sigmas_smooth=(Bsz, T, n, n))))
+    sp.regime_smooth, sp.regime_pairs = N.ptr(out["regime_smooth"]), N.ptr(out["regime_pairs"])
+    sp.mus_smooth, sp.Sigmas_smooth = N.ptr(out["mus_smooth"]), N.ptr(out["Sigmas_smooth"])
+    out.update(_wanted(dev, _EM_STATS, want, _em_shapes(K, n, m)))
+    lib = N.lib_for(Y)
+    ws = _empty(dev, Bsz, lib.dll.kvae_lgssm_switching_em_ws_floats(Bsz, K, n, m) // Bsz)
+    es.ws = ws.data_ptr()
+    for k in _EM_STATS:
+        setattr(es, k, N.ptr(out[k]))
+    lib.check(N.timed("switching_em", Y, lambda: lib.dll.kvae_lgssm_switching_em(C.byref(sp), C.byref(es), N.stream_for(Y))),
+              "kvae_lgssm_switching_em")
+    del keep
+    if out["regime_pairs"] is not None:
+        out["regime_pairs"] = out["regime_pairs"][:, :T - 1]   # nothing is written at T = 1
+    if ws_out is not None:
+        ws_out.append(ws)
+    return {k: out[k] for k in _EM_OUTPUTS}
+
+
+def em_ws_blocks(ws, K, n, m):
+    """The per-sequence rows [B, G] of kvae_lgssm_switching_em's workspace as a dict of [B, ...] views, in the layout of
+    include/kvae_lgssm.h."""
+    out, off = {}, 0
+    for k, shp in _em_shapes(K, n, m).items():
+        if k == "nseq":
+            continue
+        size = 1
+        for d in shp:
+            size *= d
+        out[k] = ws[:, off:off + size].reshape(ws.shape[0], *shp)
+        off += size
+    assert off == ws.shape[1], (off, ws.shape)
+    return out
+
+
+def em_add(a, b):
+    """The sum of two statistics dicts of switching_em_statistics (the statistics are additive over batches); "log_lik_seq" is
+    concatenated; the smoother outputs, which belong to one batch, are dropped."""
+    out = {}
+    for k in _EM_STATS:
+        x, y = a.get(k), b.get(k)
+        out[k] = None if x is None or y is None else x.double() + y.double().to(x.device)
+    x, y = a.get("log_lik_seq"), b.get("log_lik_seq")
+    out["log_lik_seq"] = None if x is None or y is None else torch.cat([x, y.to(x.device)])
+    return out

@@ -362,26 +362,42 @@ def switching_smoother_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, s
     return {k: (full[k] if k in want else None) for k in _SWS_OUTPUTS}
 
 
-def _sws_backward(A, Bm, Q, U, hist, w_last):
+def _sws_pair_step(A, Bm, Q, u, mu, Sig, ms, Ss, W, M):
+    """One transition of the backward pass, over every pair (j = source regime, k = destination regime): [B, j, k, ...].  (mu, Sig)
+    [B, j, ...]: the source beliefs; u [B, m]: the input of the destination step; (ms, Ss, M) [B, k, ...]: the destination's smoothed
+    beliefs and weights; W [B, j, k]: the filter's pair weights of the destination step.  Returns (J, the smoothed pair mean and
+    covariance, the pair marginal)."""
+    # ---- the filter's predict of pair (j, k) ----
+    mp = torch.einsum("jrc,bic->bijr", A, mu) + torch.einsum("jrc,bc->bjr", Bm, u).unsqueeze(1)
+    Sp = torch.einsum("jre,biec,jdc->bijrd", A, Sig, A) + Q
+    J = torch.linalg.solve(Sp.mT, (Sig.unsqueeze(2) @ A.mT).mT).mT                   # Sigma A_k^T Sigma_p^-1
+    mj = mu.unsqueeze(2) + (J @ (ms.unsqueeze(1) - mp).unsqueeze(-1)).squeeze(-1)
+    Sj = Sig.unsqueeze(2) + J @ (Ss.unsqueeze(1) - Sp) @ J.mT
+    Sj = 0.5 * (Sj + Sj.mT)
+    return J, mj, Sj, W * M.unsqueeze(1)
+
+
+def _sws_backward(A, Bm, Q, U, hist, w_last, em=None):
     """The backward pass of switching_smoother_torch over the history of _swf_forward and the final weights w_last [B,K]: the
-    four outputs of _SWS_SMOOTH."""
+    four outputs of _SWS_SMOOTH.  em: None, or dict(mu0, Sigma0, Y, mask) - then the pass also crosses the transition into t = 0
+    and the second return value holds the expected sufficient statistics PER SEQUENCE (switching_em_statistics_torch)."""
     K, T = A.shape[0], U.shape[1]
     eyeK = torch.eye(K, device=A.device, dtype=A.dtype)
     M, ms, Ss = w_last, hist["mu"][:, -1], hist["Sigma"][:, -1]
     outs = {"regime_smooth": [M], "regime_pairs": [], "mus_smooth": [], "Sigmas_smooth": []}
     m_, S_ = _moment_match(M, ms, Ss)
     outs["mus_smooth"].append(m_), outs["Sigmas_smooth"].append(S_)
-    for t in range(T - 2, -1, -1):
-        mu, Sig = hist["mu"][:, t], hist["Sigma"][:, t]                              # regime j at t: [B, j, ...]
-        # ---- the filter's predict of pair (j, k) at step t + 1: [B, j, k, ...] ----
-        mp = torch.einsum("jrc,bic->bijr", A, mu) + torch.einsum("jrc,bc->bjr", Bm, U[:, t + 1]).unsqueeze(1)
-        Sp = torch.einsum("jre,biec,jdc->bijrd", A, Sig, A) + Q
-        J = torch.linalg.solve(Sp.mT, (Sig.unsqueeze(2) @ A.mT).mT).mT               # Sigma A_k^T Sigma_p^-1
-        mj = mu.unsqueeze(2) + (J @ (ms.unsqueeze(1) - mp).unsqueeze(-1)).squeeze(-1)
-        Sj = Sig.unsqueeze(2) + J @ (Ss.unsqueeze(1) - Sp) @ J.mT
-        Sj = 0.5 * (Sj + Sj.mT)
-        # ---- weights: the pair marginal, M_t, V_{k|j} ----
-        pair = hist["W"][:, t + 1] * M.unsqueeze(1)                                  # [B, j, k]
+    acc = None if em is None else _EmSums(em, A.shape[1], U.shape[2], K, w_last)
+    for t in range(T - 1, -1, -1):
+        if acc is not None:
+            acc.emission(t, m_, S_)
+        if t == 0:
+            break
+        mu, Sig = hist["mu"][:, t - 1], hist["Sigma"][:, t - 1]                      # regime j at t - 1: [B, j, ...]
+        J, mj, Sj, pair = _sws_pair_step(A, Bm, Q, U[:, t], mu, Sig, ms, Ss, hist["W"][:, t], M)
+        if acc is not None:
+            acc.transition(pair, ms, Ss, J, mj, Sj, U[:, t], first=False)
+        # ---- weights: M_{t-1}, V_{k|j} ----
         M = pair.sum(2)
         dead = ~(M > 0)
         V = torch.where(dead.unsqueeze(2), eyeK.expand_as(pair), pair / torch.where(dead, torch.ones_like(M), M).unsqueeze(2))
@@ -392,7 +408,191 @@ def _sws_backward(A, Bm, Q, U, hist, w_last):
         Ss = 0.5 * (Ss + Ss.mT)
         m_, S_ = _moment_match(M, ms, Ss)
         outs["regime_smooth"].append(M), outs["regime_pairs"].append(pair), outs["mus_smooth"].append(m_), outs["Sigmas_smooth"].append(S_)
-    return {k: (torch.stack(v[::-1], 1) if v else w_last.new_zeros(w_last.shape[0], 0, K, K)) for k, v in outs.items()}
+    smooth = {k: (torch.stack(v[::-1], 1) if v else w_last.new_zeros(w_last.shape[0], 0, K, K)) for k, v in outs.items()}
+    if acc is None:
+        return smooth
+    # ---- the transition into t = 0: every source regime starts at (mu0, Sigma0); W of the uniform-matrix step ----
+    Bsz, n = w_last.shape[0], A.shape[1]
+    mu, Sig = em["mu0"].expand(Bsz, K, n), em["Sigma0"].expand(Bsz, K, n, n)
+    J, mj, Sj, pair = _sws_pair_step(A, Bm, Q, U[:, 0], mu, Sig, ms, Ss, hist["W"][:, 0], M)
+    acc.transition(pair, ms, Ss, J, mj, Sj, U[:, 0], first=True)
+    return smooth, acc.s
+
+
+_EM_STATS = ("N", "S11", "S10", "S00", "counts", "Syz", "Szz", "Syy", "Nobs", "z0", "z0z0", "nseq")
+_EM_OUTPUTS = _EM_STATS + ("log_lik_seq",) + _SWS_SMOOTH
+
+
+class _EmSums:
+    """The expected sufficient statistics of include/kvae_lgssm.h kvae_lgssm_switching_em, per sequence ([B, ...]), accumulated by
+    _sws_backward step by step."""
+
+    def __init__(self, em, n, m, K, ref):
+        Bsz, x = ref.shape[0], n + m
+        z = lambda *s: ref.new_zeros(Bsz, *s)
+        self.Y, self.mask, self.n = em["Y"], em["mask"], n
+        self.s = dict(N=z(K), S11=z(K, n, n), S10=z(K, n, x), S00=z(K, x, x), counts=z(K, K), Syz=z(self.Y.shape[-1], n), Szz=z(n, n),
+                      Syy=z(self.Y.shape[-1], self.Y.shape[-1]), Nobs=z(1), z0=z(n), z0z0=z(n, n), nseq=z(1) + 1.0)
+
+    def emission(self, t, m_, V_):
+        y = self.Y[:, t]
+        ob = torch.ones_like(y[:, 0]) if self.mask is None else (self.mask[:, t] != 0).to(y.dtype)
+        y = torch.where(ob[:, None] != 0, y, torch.zeros_like(y))   # selected, as the kernel does: a hidden y adds exactly 0
+        s = self.s
+        s["Syz"] += y.unsqueeze(-1) * m_.unsqueeze(-2)
+        s["Szz"] += ob[:, None, None] * (V_ + m_.unsqueeze(-1) * m_.unsqueeze(-2))
+        s["Syy"] += y.unsqueeze(-1) * y.unsqueeze(-2)
+        s["Nobs"] += ob[:, None]
+
+    def transition(self, xi, ms, Ss, J, mj, Sj, u, first):
+        """xi [B,j,k]; (ms, Ss) [B,k,...] the destination; J, (mj, Sj) [B,j,k,...] the gain and the smoothed source; u [B,m]."""
+        s, n = self.s, self.n
+        w = xi[..., None, None]
+        out = lambda a, b: a.unsqueeze(-1) * b.unsqueeze(-2)
+        msx, ux = ms.unsqueeze(1).expand_as(mj), u[:, None, None, :].expand(*mj.shape[:3], u.shape[-1])
+        s["N"] += xi.sum(1)
+        s["S11"] += xi.sum(1)[..., None, None] * (Ss + out(ms, ms))
+        s["S10"][..., :n] += (w * (Ss.unsqueeze(1) @ J.mT + out(msx, mj))).sum(1)
+        s["S10"][..., n:] += (w * out(msx, ux)).sum(1)
+        zz = w * (Sj + out(mj, mj))
+        zu = (w * out(mj, ux)).sum(1)
+        s["S00"][..., :n, :n] += zz.sum(1)
+        s["S00"][..., :n, n:] += zu
+        s["S00"][..., n:, :n] += zu.mT
+        s["S00"][..., n:, n:] += (w * out(ux, ux)).sum(1)
+        if first:
+            s["z0"] += (xi.unsqueeze(-1) * mj).sum((1, 2))
+            s["z0z0"] += zz.sum((1, 2))
+        else:
+            s["counts"] += xi
+
+
+@torch.no_grad()
+def switching_em_statistics_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, want=_EM_OUTPUTS, per_sequence=False):
+    """The equations of kvae_lgssm_switching_em (include/kvae_lgssm.h) in torch ops, in the dtype of A: the
+    sweep of switching_filter_torch with its history kept, then the smoother's backward pass carried one transition further, into
+    t = 0, with the expected sufficient statistics of the switching model accumulated on the way.  The fallback of
+    switching_em_statistics and (in float64) the reference its kernel is tested against.  Returns the statistics summed over the
+    sequences (per_sequence: with their leading [B]), "log_lik_seq" [B] and the four smoother outputs; entries not asked for are None."""
+    want = _want("switching_em_statistics", _EM_OUTPUTS, want)
+    full, hist, (A, Bm, Q, Cm, U) = _swf_forward(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, None, history=True)
+    dt, dev = A.dtype, A.device
+    em = dict(mu0=mu0.detach().to(dev, dt), Sigma0=Sigma0.detach().to(dev, dt), Y=Y.detach().to(dev, dt),
+              mask=None if mask is None else mask.detach().to(dev, dt).reshape(Y.shape[0], Y.shape[1]))
+    smooth, stats = _sws_backward(A, Bm, Q, U, hist, full["regime_filt"][:, -1], em)
+    if not per_sequence:
+        stats = {k: v.sum(0) for k, v in stats.items()}
+    stats.update(smooth, log_lik_seq=full["log_lik_seq"])
+    return {k: (stats[k] if k in want else None) for k in _EM_OUTPUTS}
+
+
+_EM_PARAMS = ("A", "B", "Q", "C", "R", "P", "mu0", "Sigma0")
+
+
+@torch.no_grad()
+def switching_em_mstep(stats, old, update=("A", "B", "Q", "C", "P"), min_count=None):
+    """The closed-form M-step of EM for the switching model, in float64 on the statistics' device.  stats: the sums of
+    switching_em_statistics (added over batches with em_add); old: dict of the current A [K,n,n], B [K,n,m], Q, C [p,n], R, P [K,K],
+    mu0, Sigma0; update: which of them to re-estimate.  Returns (params, skipped): the float64 parameters - the old value where a name
+    is not in `update` - and {"regimes": [k, ...], "rows": [j, ...], "B_held": [k, ...], "emission": bool}.
+      [A_k B_k] = S10_k S00_k^-1                 Q_k = sym((S11_k - [A_k B_k] S10_k^T) / N_k)
+      C = Syz Szz^-1                             R = sym((Syy - C Syz^T) / Nobs)
+      P[j, :] = counts[j, :] / sum_k counts[j, k]
+      mu0 = z0 / nseq                            Sigma0 = z0z0 / nseq - mu0 mu0^T
+    (with only one of A / B, or Q without both, or R without C, named in `update`: the maximiser given the ones held, and the
+    general quadratic form for the covariance).  Regime k keeps its old A_k, B_k, Q_k where N_k < min_count (default n + m + 1) or
+    the new Q_k fails cholesky_ex (or S00_k cannot be inverted at all); a row of P keeps its old values where its counts sum to 0.
+    Without a control input - u = None is zeros, as in forward() - the u-block of S00_k is singular (smallest eigenvalue <= 1e-10 of
+    S00_k's largest): B_k is held, A_k is the maximiser given it, Q_k takes the general form, and k is listed under "B_held", not
+    under "regimes".  The 1e-10 is a choice, not a measurement: far above float64 rounding of an exactly zero block (the case
+    of u = None), far below any u that carries information; a u between the two is fitted jointly and may give a poorly determined B_k.
+    A regime whose statistics are not finite is skipped like one below min_count.  C and R keep their old values ("emission": True) where no step is observed, Szz cannot be inverted or the new
+    R is not positive definite.  Everything held is listed in `skipped`, which takes a host synchronisation: the M-step cannot be
+    captured into a graph."""
+    update = _want("switching_em_mstep", _EM_PARAMS, update)
+    dev = stats["N"].device
+    s = {k: v.detach().to(dev, torch.float64) for k, v in stats.items() if v is not None and k in _EM_STATS}
+    o = {k: old[k].detach().to(dev, torch.float64) for k in _EM_PARAMS}
+    new = dict(o)
+    skipped = {"regimes": [], "rows": [], "B_held": [], "emission": False}
+    sym = lambda M: 0.5 * (M + M.mT)
+    if any(k in update for k in ("A", "B", "Q")):
+        K, n, m = o["A"].shape[0], o["A"].shape[1], o["B"].shape[2]
+        min_count = n + m + 1 if min_count is None else min_count
+        S11, S10, S00, Nk = s["S11"], s["S10"], s["S00"], s["N"]
+        finite = torch.isfinite(S00).all(-1).all(-1) & torch.isfinite(S10).all(-1).all(-1) & torch.isfinite(S11).all(-1).all(-1) & torch.isfinite(Nk)
+        low = ~(Nk >= min_count) | ~finite   # a regime with non-finite statistics is skipped like one never visited
+        eye = torch.eye(n + m, device=dev, dtype=torch.float64)
+        safe00 = torch.where(low[:, None, None], eye.expand_as(S00), S00)
+        S10, S11 = torch.where(low[:, None, None], torch.zeros_like(S10), S10), torch.where(low[:, None, None], torch.zeros_like(S11), S11)
+        # without a control input (u = 0, or the same u at every step up to rounding) the u-block of S00_k is singular and B_k
+        # cannot be told from the data: it is held, and A_k is the maximiser given it
+        flat = torch.linalg.eigvalsh(sym(safe00[:, n:, n:]))[:, 0] <= 1e-10 * torch.linalg.eigvalsh(sym(safe00))[:, -1].clamp_min(1e-300)
+        Fo = torch.cat([o["A"], o["B"]], -1)
+
+        def solved(S, X):   # X S^-1 per regime, and where it could not be had
+            sol, info = torch.linalg.solve_ex(S, X, left=False)
+            return sol, (info != 0) | ~torch.isfinite(sol).all(-1).all(-1)
+
+        uu_safe = torch.where(flat[:, None, None], eye[:m, :m].expand(K, m, m), safe00[:, n:, n:])
+        Fa, bad_a = solved(safe00[:, :n, :n], S10[..., :n] - o["B"] @ safe00[:, n:, :n])
+        Fa = torch.cat([Fa, o["B"]], -1)
+        if "A" in update and "B" in update:
+            Fj, bad_j = solved(torch.where(flat[:, None, None], eye.expand_as(S00), safe00), S10)
+            F, unsolved = torch.where(flat[:, None, None], Fa, Fj), torch.where(flat, bad_a, bad_j)
+        elif "A" in update:
+            F, unsolved = Fa, bad_a
+        elif "B" in update:
+            Fb, bad_b = solved(uu_safe, S10[..., n:] - o["A"] @ safe00[:, :n, n:])
+            F, unsolved = torch.where(flat[:, None, None], Fo, torch.cat([o["A"], Fb], -1)), bad_b & ~flat
+        else:
+            F, unsolved = Fo, torch.zeros_like(low)
+        F = torch.where(unsolved[:, None, None], Fo, F)
+        joint = ~flat if ("A" in update and "B" in update) else torch.zeros_like(flat)   # where F is the joint maximiser
+        Nsafe = torch.where(low, torch.ones_like(Nk), Nk)[:, None, None]
+        Qn = torch.where(joint[:, None, None], sym((S11 - F @ S10.mT) / Nsafe),
+                         sym((S11 - F @ S10.mT - S10 @ F.mT + F @ S00 @ F.mT) / Nsafe))
+        info = torch.linalg.cholesky_ex(Qn).info
+        bad = low | unsolved | (info != 0) | ~torch.isfinite(Qn).all(-1).all(-1)
+        keep = bad[:, None, None]
+        if "A" in update:
+            new["A"] = torch.where(keep, o["A"], F[..., :n])
+        if "B" in update:
+            new["B"] = torch.where(keep, o["B"], F[..., n:])
+        if "Q" in update:
+            new["Q"] = torch.where(keep, o["Q"], Qn)
+        skipped["regimes"] = [int(k) for k in torch.nonzero(bad).flatten().tolist()]
+        if "B" in update:
+            skipped["B_held"] = [int(k) for k in torch.nonzero(flat & ~bad).flatten().tolist()]
+    if "C" in update or "R" in update:
+        Cn, Syz, nobs = o["C"], s["Syz"], s["Nobs"].sum()
+        lost = ~(nobs > 0)
+        if "C" in update:   # C = Syz Szz^-1; held, with R, where Szz cannot be inverted (too few observed steps)
+            Cs, info = torch.linalg.solve_ex(s["Szz"], Syz, left=False)
+            lost = lost | (info != 0) | ~torch.isfinite(Cs).all()
+            Cn = torch.where(lost, o["C"], Cs)
+            new["C"] = Cn
+        if "R" in update:
+            quad = s["Syy"] - Cn @ Syz.mT if "C" in update else s["Syy"] - Cn @ Syz.mT - Syz @ Cn.mT + Cn @ s["Szz"] @ Cn.mT
+            Rn = sym(quad / torch.where(lost, torch.ones_like(nobs), nobs))
+            lost = lost | (torch.linalg.cholesky_ex(Rn).info != 0) | ~torch.isfinite(Rn).all()
+            new["R"] = torch.where(lost, o["R"], Rn)
+            if "C" in update:
+                new["C"] = torch.where(lost, o["C"], Cn)
+        skipped["emission"] = bool(lost)
+    if "P" in update:
+        rows = s["counts"].sum(1)
+        empty = ~(rows > 0)
+        new["P"] = torch.where(empty[:, None], o["P"], s["counts"] / torch.where(empty, torch.ones_like(rows), rows)[:, None])
+        skipped["rows"] = [int(j) for j in torch.nonzero(empty).flatten().tolist()]
+    if "mu0" in update or "Sigma0" in update:
+        mean = s["z0"] / s["nseq"]
+        if "Sigma0" in update:
+            ref = mean if "mu0" in update else o["mu0"]   # around the mean kept: E (z - mu0)(z - mu0)^T
+            new["Sigma0"] = sym(s["z0z0"] / s["nseq"] - torch.outer(mean, ref) - torch.outer(ref, mean) + torch.outer(ref, ref))
+        if "mu0" in update:
+            new["mu0"] = mean
+    return new, skipped
 
 
 def switching_log_marginal_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None):

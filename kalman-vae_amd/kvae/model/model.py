@@ -532,6 +532,13 @@ class KVAE(nn.Module):
                 out["x_smooth"] = self._decode_latents(out["a_smooth"], a_vae.dtype)
             return out
 
+    def fit_dynamics_em(self, batches, iters, update=("A", "B", "Q", "C", "P"), sample_a=False, min_count=None):
+        """Closed-form EM for the generative switching model on the encoded sequences (switching dynamics only):
+        kvae.train.em.fit_dynamics_em.  The encoder, the decoder and the regime posterior network are not touched.  Returns the
+        log-likelihood history, one value per iteration."""
+        from kvae.train.em import fit_dynamics_em
+        return fit_dynamics_em(self, batches, iters, update=update, sample_a=sample_a, min_count=min_count)
+
     @torch.no_grad()
     def log_likelihood(self, x, num_samples=1, u=None, mask=None):
         """Importance-weighted bound on log p(x_observed) per sequence under the generative model p(x | a) p_LGSSM(a), with the
