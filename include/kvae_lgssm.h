@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 #define KVAE_MAX_DIM 16
-#define KVAE_ABI_VERSION 19
+#define KVAE_ABI_VERSION 20
 
 typedef enum {
   KVAE_OK = 0,
@@ -339,6 +339,16 @@ int kvae_dec_head_fwd(const float *in, const float *W, const float *bias, float 
  * b_partials [rows, 4]: the weight / bias gradients are their column sums. */
 int kvae_dec_head_bwd(const float *in, const float *W, const float *g_logits, float *g_in, float *w_partials,
                       float *b_partials, float *w_scratch, int64_t N, int32_t Cin, int32_t side, void *stream);
+/* The head with the Bernoulli term of its own frames folded in (kvae/vae/vae.py:103-104, kvae/vae/losses.py:85-87): logits as
+ * kvae_dec_head_fwd writes them (the same bits), x_recon[N,1,2s,2s] = sigmoid(logits) (may be NULL to skip) and
+ * frame_ll[n] = -sum_{pixels} BCEWithLogits(logits[n], x[n]), x [N,1,2s,2s] the target frames. */
+int kvae_dec_head_loss_fwd(const float *in, const float *W, const float *bias, const float *x, float *logits, float *x_recon,
+                           float *frame_ll, float *w_scratch, int64_t N, int32_t Cin, int32_t side, void *stream);
+/* kvae_dec_head_bwd for g_logits[n] = -g_frame[n] * (sigmoid(logits[n]) - x[n]), the gradient kvae_bce_frames_bwd would write:
+ * it is formed inside the kernel and never stored.  g_in may be NULL to skip the data gradient. */
+int kvae_dec_head_loss_bwd(const float *in, const float *W, const float *logits, const float *x, const float *g_frame, float *g_in,
+                           float *w_partials, float *b_partials, float *w_scratch, int64_t N, int32_t Cin, int32_t side,
+                           void *stream);
 /* Encoder stem (kvae/vae/vae.py:20-31): out[N,Cout,s/2,s/2] = relu(conv3x3_stride2_pad1(x[N,1,s,s], W[Cout,1,3,3]) + b).
  * Built for Cout = 32, s = 32.  relu_bits (may be NULL): [N, (s/2)^2] words, bit co of word (n, pixel) = out[n,co,pixel] > 0 -
  * the ReLU mask in 1/32 of the bytes of out, for kvae_enc_stem_bwd. */

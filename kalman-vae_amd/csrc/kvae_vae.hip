@@ -400,23 +400,51 @@ int kvae_dec_head_fwd(const float *in, const float *W, const float *bias, float 
   if (N < 1) return KVAE_ERR_ARG;
   if (Cin != DH_CI || side != DH_S) return KVAE_ERR_DIMS;
   k_dec_head_prep<<<dim3(1), dim3(256), 0, (hipStream_t)stream>>>(W, w_scratch);
-  k_dec_head_fwd<<<dim3((unsigned)N), dim3(256), 0, (hipStream_t)stream>>>(in, w_scratch, bias, logits);
+  k_dec_head_fwd<false><<<dim3((unsigned)N), dim3(256), 0, (hipStream_t)stream>>>(in, w_scratch, bias, logits, nullptr, nullptr, nullptr);
   return launch_status("k_dec_head_fwd");
 }
+int kvae_dec_head_loss_fwd(const float *in, const float *W, const float *bias, const float *x, float *logits, float *x_recon,
+                           float *frame_ll, float *w_scratch, int64_t N, int32_t Cin, int32_t side, void *stream) {
+  if (!in || !W || !bias || !x || !logits || !frame_ll || !w_scratch) return KVAE_ERR_NULL;
+  if (N < 1) return KVAE_ERR_ARG;
+  if (Cin != DH_CI || side != DH_S) return KVAE_ERR_DIMS;
+  k_dec_head_prep<<<dim3(1), dim3(256), 0, (hipStream_t)stream>>>(W, w_scratch);
+  k_dec_head_fwd<true><<<dim3((unsigned)N), dim3(256), 0, (hipStream_t)stream>>>(in, w_scratch, bias, logits, x, x_recon, frame_ll);
+  return launch_status("k_dec_head_loss_fwd");
+}
+}  // extern "C"
+// one persistent launch for both gradients of the head; the gradient of the logits is read (LOSS = false) or formed from the
+// Bernoulli term (LOSS = true)
+template <bool LOSS>
+static int dec_head_bwd_launch(const float *in, const float *W, const float *g_logits, const float *logits, const float *x,
+                               const float *g_frame, float *g_in, float *w_partials, float *b_partials, float *w_scratch,
+                               int64_t N, hipStream_t st) {
+  const dim3 grid((unsigned)kvae_conv_edge_partial_rows(N));
+  if (g_in) {
+    k_dec_head_prep<<<dim3(1), dim3(256), 0, st>>>(W, w_scratch);
+    k_dec_head_bwd<LOSS, true><<<grid, dim3(256), 0, st>>>(in, g_logits, logits, x, g_frame, w_scratch, g_in, w_partials, b_partials, N);
+  } else {
+    k_dec_head_bwd<LOSS, false><<<grid, dim3(256), 0, st>>>(in, g_logits, logits, x, g_frame, w_scratch, g_in, w_partials, b_partials, N);
+  }
+  return launch_status("k_dec_head_bwd");
+}
+extern "C" {
 int kvae_dec_head_bwd(const float *in, const float *W, const float *g_logits, float *g_in, float *w_partials,
                       float *b_partials, float *w_scratch, int64_t N, int32_t Cin, int32_t side, void *stream) {
   if (!in || !W || !g_logits || !w_partials || !b_partials || !w_scratch) return KVAE_ERR_NULL;
   if (N < 1) return KVAE_ERR_ARG;
   if (Cin != DH_CI || side != DH_S) return KVAE_ERR_DIMS;
-  if (g_in) {
-    k_dec_head_prep<<<dim3(1), dim3(256), 0, (hipStream_t)stream>>>(W, w_scratch);
-    k_dec_head_bwd_data<<<dim3((unsigned)N), dim3(256), 0, (hipStream_t)stream>>>(g_logits, w_scratch, g_in);
-    const int rc = launch_status("k_dec_head_bwd_data");
-    if (rc) return rc;
-  }
-  k_dec_head_wrw<<<dim3((unsigned)kvae_conv_edge_partial_rows(N)), dim3(256), 0, (hipStream_t)stream>>>(in, g_logits, w_partials,
-                                                                                                     b_partials, N);
-  return launch_status("k_dec_head_wrw");
+  return dec_head_bwd_launch<false>(in, W, g_logits, nullptr, nullptr, nullptr, g_in, w_partials, b_partials, w_scratch, N,
+                                    (hipStream_t)stream);
+}
+int kvae_dec_head_loss_bwd(const float *in, const float *W, const float *logits, const float *x, const float *g_frame, float *g_in,
+                           float *w_partials, float *b_partials, float *w_scratch, int64_t N, int32_t Cin, int32_t side,
+                           void *stream) {
+  if (!in || !W || !logits || !x || !g_frame || !w_partials || !b_partials || !w_scratch) return KVAE_ERR_NULL;
+  if (N < 1) return KVAE_ERR_ARG;
+  if (Cin != DH_CI || side != DH_S) return KVAE_ERR_DIMS;
+  return dec_head_bwd_launch<true>(in, W, nullptr, logits, x, g_frame, g_in, w_partials, b_partials, w_scratch, N,
+                                   (hipStream_t)stream);
 }
 int kvae_enc_stem_fwd(const float *x, const float *W, const float *bias, float *out, uint32_t *relu_bits, int64_t N, int32_t Cout,
                       int32_t side, void *stream) {

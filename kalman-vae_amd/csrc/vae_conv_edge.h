@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vae_loss.h"
+
 namespace kvae {
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -54,18 +56,30 @@ __device__ __forceinline__ void dh_store_interior(float *tile, int i, const floa
 // The frame sits in LDS as a plain 32 x 16 x 16 copy (32 KiB: five workgroups per CU instead of three with a halo, and
 // the staging is eight ds_write_b128 per thread).  The zero padding comes from the out-of-range trick of vae_conv_mid.h:
 // border lanes take a base far outside the LDS allocation for the taps that fall off the frame, where DS reads return 0.
+// LOSS: the Bernoulli term of the frame is folded in while the four logits of the thread are in registers (vae_loss.h):
+// x_recon = sigmoid(logits) (optional) and frame_ll[n] = -sum BCEWithLogits(logits, x).  The convolution is the same code
+// in both instantiations, so the logits are the same bits.
+template <bool LOSS>
 __global__ __launch_bounds__(256) void k_dec_head_fwd(const float *__restrict__ in, const float *__restrict__ scratch,
-                                                      const float *__restrict__ bias, float *__restrict__ logits) {
-  __shared__ float tile[DH_CI * 256];
+                                                      const float *__restrict__ bias, float *__restrict__ logits,
+                                                      const float *__restrict__ x, float *__restrict__ x_recon,
+                                                      float *__restrict__ frame_ll) {
+  __shared__ float tile[DH_CI * 256];                 // exactly 32 KiB: one more word of LDS and a CU holds four workgroups, not five
   const int64_t n = blockIdx.x;
   const float4 *src = reinterpret_cast<const float4 *>(in + n * DH_CI * 256);
   float4 pre[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) pre[j] = src[threadIdx.x + 256 * j];
+  const int h = threadIdx.x >> 4, w = threadIdx.x & 15;
+  const int64_t po = n * 1024 + (2 * h) * 32 + 2 * w;            // co = 2*dy + dx -> pixel (2h+dy, 2w+dx)
+  float2 x01 = make_float2(0.f, 0.f), x23 = x01;
+  if constexpr (LOSS) {
+    x01 = *reinterpret_cast<const float2 *>(x + po);
+    x23 = *reinterpret_cast<const float2 *>(x + po + 32);
+  }
 #pragma unroll
   for (int j = 0; j < 8; ++j) reinterpret_cast<float4 *>(tile)[threadIdx.x + 256 * j] = pre[j];
   __syncthreads();
-  const int h = threadIdx.x >> 4, w = threadIdx.x & 15;
   constexpr int OOB = 1 << 24;                       // float index 64 MiB past the start of LDS
   const int tb = (h - 1) * 16 + (w - 1);
   int base[9];
@@ -87,60 +101,47 @@ __global__ __launch_bounds__(256) void k_dec_head_fwd(const float *__restrict__ 
       a23 += wv.zw * v;
     }
   }
-  float *o = logits + n * 1024 + (2 * h) * 32 + 2 * w;          // co = 2*dy + dx -> pixel (2h+dy, 2w+dx)
+  float *o = logits + po;
   *reinterpret_cast<float2 *>(o) = make_float2(a01.x, a01.y);
   *reinterpret_cast<float2 *>(o + 32) = make_float2(a23.x, a23.y);
-}
-
-// g_in[n,ci,h,w] = sum_{co,ky,kx} W[co,ci,ky,kx] g_conv[n,co,h-ky+1,w-kx+1],  g_conv = pixel_unshuffle(g_logits)
-__global__ __launch_bounds__(256) void k_dec_head_bwd_data(const float *__restrict__ g_logits,
-                                                           const float *__restrict__ scratch, float *__restrict__ g_in) {
-  __shared__ float gt[DH_CO * DH_CS];
-  const int64_t n = blockIdx.x;
-  float gp[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) gp[j] = g_logits[n * 1024 + threadIdx.x + 256 * j];
-  dh_zero_halo(gt, DH_CO);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int i = threadIdx.x + 256 * j, oh = i >> 5, ow = i & 31, co = (oh & 1) * 2 + (ow & 1);
-    gt[co * DH_CS + ((oh >> 1) + 1) * DH_TS + (ow >> 1) + 1] = gp[j];
-  }
-  __syncthreads();
-  const int h = threadIdx.x >> 4, w = threadIdx.x & 15;
-  kv_f2 acc[DH_CI / 2];
-#pragma unroll
-  for (int j = 0; j < DH_CI / 2; ++j) acc[j] = kv_f2{0.f, 0.f};
-  const kv_f2 *Wb = reinterpret_cast<const kv_f2 *>(scratch + DH_W);
-#pragma unroll
-  for (int co = 0; co < DH_CO; ++co)
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-      for (int kx = 0; kx < 3; ++kx) {
-        const float v = gt[co * DH_CS + (h + 2 - ky) * DH_TS + (w + 2 - kx)];
-        const kv_f2 *wr = Wb + (co * 9 + ky * 3 + kx) * (DH_CI / 2);
-#pragma unroll
-        for (int j = 0; j < DH_CI / 2; ++j) acc[j] += wr[j] * v;
-      }
-  float *o = g_in + n * DH_CI * 256 + threadIdx.x;
-#pragma unroll
-  for (int j = 0; j < DH_CI / 2; ++j) {
-    o[(2 * j) * 256] = acc[j].x;
-    o[(2 * j + 1) * 256] = acc[j].y;
+  if constexpr (LOSS) {
+    if (x_recon) {
+      *reinterpret_cast<float2 *>(x_recon + po) = make_float2(sigmoid_stable(a01.x), sigmoid_stable(a01.y));
+      *reinterpret_cast<float2 *>(x_recon + po + 32) = make_float2(sigmoid_stable(a23.x), sigmoid_stable(a23.y));
+    }
+    // 256 per-thread sums -> four wave sums (shuffle tree) -> one fixed-order fold: no atomics, the same bits every run
+    float s = (bce_logit(a01.x, x01.x) + bce_logit(a01.y, x01.y)) + (bce_logit(a23.x, x23.x) + bce_logit(a23.y, x23.y));
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    __syncthreads();                                  // every wave is done with the frame: its first words carry the wave sums
+    if ((threadIdx.x & 63) == 0) tile[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) frame_ll[n] = -((tile[0] + tile[1]) + (tile[2] + tile[3]));
   }
 }
 
-// partial[blk, co, ci, k] = sum over this block's frames of sum_{h,w} g_conv[n,co,h,w] in[n,ci,h+ky-1,w+kx-1];
-// partial_b[blk, co] = sum g_conv.  Thread = (ci = tid & 31, pixel group = tid >> 5: 32 pixels each).  The next
-// frame is fetched into registers while the current one is being reduced out of LDS.
-__global__ __launch_bounds__(256) void k_dec_head_wrw(const float *__restrict__ in, const float *__restrict__ g_logits,
-                                                      float *__restrict__ partial, float *__restrict__ partial_b, int64_t N) {
+// Backward of the head, one persistent kernel: per frame the activation h and the un-shuffled gradient tile
+// g_conv = pixel_unshuffle(g_logits) are staged in LDS once (the next frame is fetched into registers meanwhile) and feed
+//   * the weight / bias gradient:  partial[blk, co, ci, k] = sum over this block's frames of
+//       sum_{h,w} g_conv[n,co,h,w] in[n,ci,h+ky-1,w+kx-1],  partial_b[blk, co] = sum g_conv
+//     (thread = (ci = tid & 31, pixel group = tid >> 5: 32 pixels each), folded through LDS after the last frame;
+//   * DATA: the data gradient  g_in[n,ci,h,w] = sum_{co,ky,kx} W[co,ci,ky,kx] g_conv[n,co,h-ky+1,w-kx+1]
+//     (thread = pixel, 32 accumulators, coalesced plane stores that overlap the loads of the next frame).
+// As two launches these took the same time (227 against 141 + 90 us at 12800 frames: both phases are VALU work of the one
+// workgroup); what the one kernel saves is the second read of the gradient and, with LOSS, the gradient itself.
+// LOSS: the gradient tile is not read but formed from the Bernoulli term, g_logits = -g_frame[n] (sigmoid(logits) - x), the
+// expression of k_vae_bce_bwd: the 52 MB gradient never exists in memory.
+template <bool LOSS, bool DATA>
+__global__ __launch_bounds__(256, 2) void k_dec_head_bwd(const float *__restrict__ in, const float *__restrict__ g_logits,
+                                                         const float *__restrict__ logits, const float *__restrict__ x,
+                                                         const float *__restrict__ g_frame, const float *__restrict__ scratch,
+                                                         float *__restrict__ g_in, float *__restrict__ partial,
+                                                         float *__restrict__ partial_b, int64_t N) {
   // frame copy with the channel planes padded by one float (32 lanes on 32 channels -> 32 banks), no halo: the rows
   // above / below the frame are read from outside the LDS allocation (-> 0), the columns left / right of it are
-  // compile-time zeros of the sliding window.  9248 floats = 37 KiB: four workgroups per CU.
+  // compile-time zeros of the sliding window.  The four gradient planes carry a zero halo (the data gradient reads it).
+  // 9524 floats = 38 KiB: four workgroups per CU.
   constexpr int CS = 257, OOB = 1 << 24;
-  __shared__ float lds[DH_CI * CS + DH_CO * 256];
+  __shared__ float lds[DH_CI * CS + DH_CO * DH_CS];
   __shared__ float redb[8 * DH_CO];
   float *tile = lds, *gt = lds + DH_CI * CS;
   const int ci = threadIdx.x & 31, grp = threadIdx.x >> 5;
@@ -156,17 +157,27 @@ __global__ __launch_bounds__(256) void k_dec_head_wrw(const float *__restrict__ 
 #pragma unroll
   for (int co = 0; co < DH_CO; ++co) accb[co] = 0.f;
   float4 pre[8];
-  float gp[4];
-  int64_t n = blockIdx.x;
-  if (n < N) {
-    const float4 *src = reinterpret_cast<const float4 *>(in + n * DH_CI * 256);
+  float gp[4], xp[4], gf = 0.f;                       // LOSS: gp holds the logits until the tile is staged
+  auto fetch = [&](int64_t f) {
+    const float4 *src = reinterpret_cast<const float4 *>(in + f * DH_CI * 256);
 #pragma unroll
     for (int j = 0; j < 8; ++j) pre[j] = src[tin + 256 * j];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) gp[j] = g_logits[n * 1024 + threadIdx.x + 256 * j];
-  }
+    for (int j = 0; j < 4; ++j) {
+      if constexpr (LOSS) {
+        gp[j] = logits[f * 1024 + threadIdx.x + 256 * j];
+        xp[j] = x[f * 1024 + threadIdx.x + 256 * j];
+      } else {
+        gp[j] = g_logits[f * 1024 + threadIdx.x + 256 * j];
+      }
+    }
+    if constexpr (LOSS) gf = -g_frame[f];
+  };
+  int64_t n = blockIdx.x;
+  if (n < N) fetch(n);
+  dh_zero_halo(gt, DH_CO);                            // the interior writes below never touch it
   for (; n < N; n += gridDim.x) {
-    __syncthreads();                                  // previous frame's tile fully consumed
+    __syncthreads();                                  // previous frame's tiles fully consumed
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int e = (tin + 256 * j) * 4;
@@ -176,22 +187,18 @@ __global__ __launch_bounds__(256) void k_dec_head_wrw(const float *__restrict__ 
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int i = threadIdx.x + 256 * j, oh = i >> 5, ow = i & 31, co = (oh & 1) * 2 + (ow & 1);
-      gt[co * 256 + (oh >> 1) * 16 + (ow >> 1)] = gp[j];
+      float g = gp[j];
+      if constexpr (LOSS) g = gf * (sigmoid_stable(gp[j]) - xp[j]);
+      gt[co * DH_CS + ((oh >> 1) + 1) * DH_TS + (ow >> 1) + 1] = g;
     }
     __syncthreads();
     const int64_t nn = n + gridDim.x;
-    if (nn < N) {
-      const float4 *src = reinterpret_cast<const float4 *>(in + nn * DH_CI * 256);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) pre[j] = src[tin + 256 * j];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) gp[j] = g_logits[nn * 1024 + threadIdx.x + 256 * j];
-    }
+    if (nn < N) fetch(nn);
     // this thread's 32 pixels are rows 2*grp and 2*grp+1; a 3x3 window slides along each row, so a pixel costs three
     // new input reads (its right-hand column) instead of nine
 #pragma unroll
-    for (int rr = 0; rr < 2; ++rr) {                  // fully unrolled on purpose: 234 VGPRs / 2 workgroups per CU beat
-      const int h = 2 * grp + rr;                     // the 128-VGPR / 4-per-CU build (148 vs 175 us)
+    for (int rr = 0; rr < 2; ++rr) {                  // fully unrolled on purpose: two workgroups per CU at ~230 VGPRs beat
+      const int h = 2 * grp + rr;                     // the 128-VGPR / 4-per-CU build (148 vs 175 us as a kernel of its own)
       int rb[3];
 #pragma unroll
       for (int ky = 0; ky < 3; ++ky) {
@@ -201,12 +208,12 @@ __global__ __launch_bounds__(256) void k_dec_head_wrw(const float *__restrict__ 
       float c0[3] = {0.f, 0.f, 0.f}, c1[3], c2[3];
 #pragma unroll
       for (int ky = 0; ky < 3; ++ky) c1[ky] = tile[rb[ky]];
+      const float *gr = gt + (h + 1) * DH_TS + 1;
 #pragma unroll
       for (int w = 0; w < 16; ++w) {
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) c2[ky] = w + 1 < 16 ? tile[rb[ky] + w + 1] : 0.f;
-        const int hw = h * 16 + w;
-        const kv_f2 g01 = {gt[hw], gt[256 + hw]}, g23 = {gt[512 + hw], gt[768 + hw]};
+        const kv_f2 g01 = {gr[w], gr[DH_CS + w]}, g23 = {gr[2 * DH_CS + w], gr[3 * DH_CS + w]};
         accb[0] += g01.x; accb[1] += g01.y; accb[2] += g23.x; accb[3] += g23.y;
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
@@ -218,9 +225,38 @@ __global__ __launch_bounds__(256) void k_dec_head_wrw(const float *__restrict__ 
         }
       }
     }
+    if constexpr (DATA) {
+      __builtin_amdgcn_sched_barrier(0);              // the 32 accumulators below take the registers the window above has left
+      const int h = threadIdx.x >> 4, w = threadIdx.x & 15;
+      kv_f2 dacc[DH_CI / 2];
+#pragma unroll
+      for (int j = 0; j < DH_CI / 2; ++j) dacc[j] = kv_f2{0.f, 0.f};
+      // the 1152 weights are scalar loads issued tap by tap, every frame: hoisted out of the frame loop as loop invariants
+      // they would need ten times the scalar registers there are, hence an offset the compiler cannot see through
+      int wofs = DH_W;
+      asm volatile("" : "+s"(wofs));
+      const kv_f2 *Wb = reinterpret_cast<const kv_f2 *>(scratch + wofs);
+#pragma unroll
+      for (int co = 0; co < DH_CO; ++co)
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+          for (int kx = 0; kx < 3; ++kx) {
+            const float v = gt[co * DH_CS + (h + 2 - ky) * DH_TS + (w + 2 - kx)];
+            const kv_f2 *wr = Wb + (co * 9 + ky * 3 + kx) * (DH_CI / 2);
+#pragma unroll
+            for (int j = 0; j < DH_CI / 2; ++j) dacc[j] += wr[j] * v;
+          }
+      float *o = g_in + n * DH_CI * 256 + threadIdx.x;
+#pragma unroll
+      for (int j = 0; j < DH_CI / 2; ++j) {
+        o[(2 * j) * 256] = dacc[j].x;
+        o[(2 * j + 1) * 256] = dacc[j].y;
+      }
+    }
   }
   __syncthreads();
-  // reduce the 8 pixel groups through LDS (reuse the frame buffers: 8 * 32 * 36 floats = 9216 <= 9248)
+  // reduce the 8 pixel groups through LDS (reuse the frame buffers: 8 * 32 * 36 floats = 9216 <= 9524)
   float *red = lds;
 #pragma unroll
   for (int k = 0; k < 9; ++k) {

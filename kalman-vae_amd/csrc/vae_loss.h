@@ -17,3 +17,52 @@ KV_DEV float sigmoid_stable(float l) {
 }
 
 }  // namespace kvae
+
+#ifdef KVAE_HOSTSIM
+// Host twins of the decoder head with the Bernoulli term folded in (vae_conv_edge.h: k_dec_head_fwd<true>, k_dec_head_bwd<true, .>)
+// for the CPU test tier: plain loops over the host twins of the unfused entry points, which the public header declares.
+#include <stdlib.h>
+extern "C" {
+int kvae_dec_head_loss_fwd(const float *in, const float *W, const float *bias, const float *x, float *logits, float *x_recon,
+                           float *frame_ll, float *w_scratch, int64_t N, int32_t Cin, int32_t side, void *) {
+  if (!in || !W || !bias || !x || !logits || !frame_ll || !w_scratch) return KVAE_ERR_NULL;
+  if (N < 1) return KVAE_ERR_ARG;
+  if (Cin != 32 || side != 16) return KVAE_ERR_DIMS;
+  const int rc = kvae_dec_head_fwd(in, W, bias, logits, w_scratch, N, Cin, side, nullptr);
+  if (rc) return rc;
+  for (int64_t n = 0; n < N; ++n) {
+    const float *l = logits + n * 1024, *t = x + n * 1024;
+    // the kernel's order: thread (h, w) sums its 2 x 2 pixels, 64 threads fold in a shuffle tree, the four waves in a fixed order
+    float wave[4];
+    for (int wv = 0; wv < 4; ++wv) {
+      float lane[64];
+      for (int j = 0; j < 64; ++j) {
+        const int tid = wv * 64 + j, p = (2 * (tid >> 4)) * 32 + 2 * (tid & 15);
+        lane[j] = (kvae::bce_logit(l[p], t[p]) + kvae::bce_logit(l[p + 1], t[p + 1])) +
+                  (kvae::bce_logit(l[p + 32], t[p + 32]) + kvae::bce_logit(l[p + 33], t[p + 33]));
+      }
+      for (int off = 32; off > 0; off >>= 1)
+        for (int j = 0; j < off; ++j) lane[j] += lane[j + off];
+      wave[wv] = lane[0];
+    }
+    frame_ll[n] = -((wave[0] + wave[1]) + (wave[2] + wave[3]));
+    if (x_recon)
+      for (int p = 0; p < 1024; ++p) x_recon[n * 1024 + p] = kvae::sigmoid_stable(l[p]);
+  }
+  return KVAE_OK;
+}
+int kvae_dec_head_loss_bwd(const float *in, const float *W, const float *logits, const float *x, const float *g_frame,
+                           float *g_in, float *w_partials, float *b_partials, float *w_scratch, int64_t N, int32_t Cin,
+                           int32_t side, void *) {
+  if (!in || !W || !logits || !x || !g_frame || !w_partials || !b_partials || !w_scratch) return KVAE_ERR_NULL;
+  if (N < 1) return KVAE_ERR_ARG;
+  if (Cin != 32 || side != 16) return KVAE_ERR_DIMS;
+  float *g = static_cast<float *>(malloc(sizeof(float) * N * 1024));   // the gradient the kernel never stores
+  if (!g) return KVAE_ERR_ARG;
+  int rc = kvae_bce_frames_bwd(logits, x, g_frame, g, N, 1024, nullptr);
+  if (!rc) rc = kvae_dec_head_bwd(in, W, g, g_in, w_partials, b_partials, w_scratch, N, Cin, side, nullptr);
+  free(g);
+  return rc;
+}
+}  // extern "C"
+#endif

@@ -219,9 +219,18 @@ class KVAE(nn.Module):
         else:
             smoothed = run(a_samples, u, mask=mask)
         (mus_smooth, Sigmas_smooth, mus_filt, Sigmas_filt, mus_pred, Sigmas_pred, A_list, B_list, C_list) = smoothed
-        x_logits = self.decode_sequence(a_samples)
+        # the decoder sees its own target frames: the head's kernels also give sigmoid(x_logits) and the per-frame Bernoulli term
+        # (fused.DecoderHeadBernoulli), or None for both where they do not apply
+        lead = a_samples.shape[:2]
+        x_logits, x_recon, frame_ll = self.decoder.forward_with_frames(a_samples.flatten(0, 1), x.flatten(0, 1), with_recon)
+        x_logits = x_logits.unflatten(0, lead)
+        if frame_ll is not None:
+            frame_ll = frame_ll.unflatten(0, lead)
+            x_recon = x_recon.unflatten(0, lead) if with_recon else None
+        else:
+            x_recon = self._to_pixels(x_logits) if with_recon else None
         return {
-            "x_recon": self._to_pixels(x_logits) if with_recon else None, "x_logits": x_logits,
+            "x_recon": x_recon, "x_logits": x_logits, "frame_ll": frame_ll, "frame_ll_x": x if frame_ll is not None else None,
             "a_samples": a_samples, "a_mu": a_mu, "a_var": a_var, "a_side": a_side,
             "mus_smooth": mus_smooth, "Sigmas_smooth": Sigmas_smooth,
             "mus_filt": mus_filt, "Sigmas_filt": Sigmas_filt,
@@ -304,7 +313,9 @@ class KVAE(nn.Module):
             # second kernel on their CUs): the fused head made the replayed graph slower.  With
             # early_kf_backward the side chain no longer needs that head start and the frame terms take the fused head ("2").
             from kvae.vae.fused import BernoulliFrameLogLik, LatentReg, LossHead
-            lpx = BernoulliFrameLogLik.apply(x_mu, x)
+            # log p(x_t | a_t) came with the decoder's forward if these are the very frames it decoded against
+            lpx = outputs["frame_ll"] if outputs.get("frame_ll") is not None and outputs.get("frame_ll_x") is x \
+                else BernoulliFrameLogLik.apply(x_mu, x)
             regf = LatentReg.apply(a, a_mu, a_var)
             mk = None if mask is None else mask.to(device=x.device, dtype=torch.float32).reshape(B, T)
             if head == "2":

@@ -62,7 +62,8 @@ def conv_block(x, conv, r=1, relu=True):
 class DecoderHead(torch.autograd.Function):
     """logits[N,1,2s,2s] = pixel_shuffle_2(conv3x3(h[N,32,s,s], W[4,32,3,3]) + b) as ONE direct-convolution kernel
     (csrc/vae_conv_edge.h; reference kvae/vae/vae.py:103-104).  A 4-output-channel implicit GEMM has nothing to
-    tile over; the direct form is bound by reading h once."""
+    tile over.  The direct form reads h once but is bound by its 576 packed FMAs per thread, not by that read (DESIGN 4b);
+    both gradients come from one persistent kernel that stages h once per frame."""
 
     SCRATCH = 2304   # KVAE_DEC_HEAD_SCRATCH_FLOATS
 
@@ -100,6 +101,63 @@ class DecoderHead(torch.autograd.Function):
                   "kvae_dec_head_bwd")
         gw, gb = colsum_pair(wp, bp)
         return g_h, gw.view_as(weight), gb
+
+
+class DecoderHeadBernoulli(torch.autograd.Function):
+    """(logits, x_recon, frame_ll) of the head against its own target frames x[N,1,2s,2s]: DecoderHead's logits (the same bits),
+    x_recon = sigmoid(logits) (None unless `with_recon`) and frame_ll[N] = -sum_pixels BCEWithLogits(logits, x) (reference
+    kvae/vae/losses.py:85-87) from the one forward kernel.  The backward of frame_ll alone - the training step - is one
+    persistent kernel that forms the gradient of the logits in registers; a gradient handed to `logits` as well takes
+    kvae_bce_frames_bwd + kvae_dec_head_bwd.  x takes no gradient."""
+
+    @staticmethod
+    def forward(ctx, h, weight, bias, x, *with_recon):
+        ctx.n_opt = len(with_recon)
+        with_recon = with_recon[0] if with_recon else True
+        h, weight, bias, x = h.contiguous(), weight.contiguous(), bias.contiguous(), x.contiguous()
+        Nb, Cin, s, _ = h.shape
+        logits = torch.empty(Nb, 1, 2 * s, 2 * s, device=h.device, dtype=torch.float32)
+        x_recon = torch.empty_like(logits) if with_recon else None
+        frame_ll = torch.empty(Nb, device=h.device, dtype=torch.float32)
+        scratch = torch.empty(DecoderHead.SCRATCH, device=h.device, dtype=torch.float32)
+        lib = N.lib_for(h)
+        lib.check(lib.dll.kvae_dec_head_loss_fwd(N.ptr(h), N.ptr(weight), N.ptr(bias), N.ptr(x), N.ptr(logits), _optr(x_recon),
+                                                 N.ptr(frame_ll), N.ptr(scratch), Nb, Cin, s, N.stream_for(h)),
+                  "kvae_dec_head_loss_fwd")
+        ctx.save_for_backward(h, weight, logits, x)
+        ctx.set_materialize_grads(False)
+        if x_recon is not None:
+            ctx.mark_non_differentiable(x_recon)
+        return logits, x_recon, frame_ll
+
+    @staticmethod
+    def backward(ctx, g_logits, _g_recon, g_ll):
+        if g_logits is None and g_ll is None:
+            return (None,) * (4 + ctx.n_opt)
+        h, weight, logits, x = ctx.saved_tensors
+        Nb, Cin, s, _ = h.shape
+        lib = N.lib_for(h)
+        rows = lib.dll.kvae_conv_edge_partial_rows(Nb)
+        g_h = torch.empty_like(h) if ctx.needs_input_grad[0] else None
+        wp = torch.empty(rows, weight.numel(), device=h.device, dtype=torch.float32)
+        bp = torch.empty(rows, 4, device=h.device, dtype=torch.float32)
+        scratch = torch.empty(DecoderHead.SCRATCH, device=h.device, dtype=torch.float32)
+        if g_logits is None:
+            g_ll = g_ll.contiguous()
+            lib.check(lib.dll.kvae_dec_head_loss_bwd(N.ptr(h), N.ptr(weight), N.ptr(logits), N.ptr(x), N.ptr(g_ll), _optr(g_h),
+                                                     N.ptr(wp), N.ptr(bp), N.ptr(scratch), Nb, Cin, s, N.stream_for(h)),
+                      "kvae_dec_head_loss_bwd")
+        else:
+            g = g_logits.contiguous()
+            if g_ll is not None:
+                gl = torch.empty_like(logits)
+                lib.check(lib.dll.kvae_bce_frames_bwd(N.ptr(logits), N.ptr(x), N.ptr(g_ll.contiguous()), N.ptr(gl), Nb,
+                                                      logits.numel() // Nb, N.stream_for(h)), "kvae_bce_frames_bwd")
+                g = gl + g
+            lib.check(lib.dll.kvae_dec_head_bwd(N.ptr(h), N.ptr(weight), N.ptr(g), _optr(g_h), N.ptr(wp), N.ptr(bp),
+                                                N.ptr(scratch), Nb, Cin, s, N.stream_for(h)), "kvae_dec_head_bwd")
+        gw, gb = colsum_pair(wp, bp)
+        return (g_h, gw.view_as(weight), gb, None) + (None,) * ctx.n_opt
 
 
 class EncoderStem(torch.autograd.Function):

@@ -12,7 +12,7 @@ import torch.nn as nn
 
 from kvae import _native
 from kvae.utils.config import KVAEConfig
-from kvae.vae.fused import DecoderFc, DecoderHead, DecoderUp, EncoderHead, EncoderMid, EncoderStem, conv_block
+from kvae.vae.fused import DecoderFc, DecoderHead, DecoderHeadBernoulli, DecoderUp, EncoderHead, EncoderMid, EncoderStem, conv_block
 
 
 def _conv_out(size, k, s, p):
@@ -81,23 +81,41 @@ class Decoder(nn.Module):
         up += [nn.Conv2d(chans[-1], 4 * config.img_channels, kernel_size=3, padding=1), nn.PixelShuffle(2)]
         self.deconv_layers = nn.Sequential(*up)
 
-    def forward(self, a: torch.Tensor) -> torch.Tensor:
+    def head_loss_supported(self, h: torch.Tensor, conv: nn.Conv2d, x: torch.Tensor) -> bool:
+        """The head's kernels can fold the Bernoulli term of the target frames x in (fused.DecoderHeadBernoulli)."""
+        return (DecoderHead.supported(h, conv) and self.config.out_distr.lower() == "bernoulli" and h.dtype == torch.float32
+                and x.dtype == torch.float32 and not x.requires_grad and x.device == h.device
+                and tuple(x.shape) == (h.shape[0], 1, 2 * h.shape[2], 2 * h.shape[3]))
+
+    def _decode(self, a: torch.Tensor, x=None, with_recon=True):
+        """(logits, x_recon, frame_ll); the last two are None unless target frames x are given and the head takes them."""
         fused = _native.fused_ok(a) and a.dtype == torch.float32
         h = DecoderFc.apply(a, self.fc.weight, self.fc.bias) if fused and DecoderFc.supported(a, self.fc) else self.fc(a)
         h = h.unflatten(1, (self.init_channels, self.init_size, self.init_size))
         if not fused:
-            return self.deconv_layers(h)
+            return self.deconv_layers(h), None, None
         layers = list(self.deconv_layers)   # conv -> PixelShuffle(2) [-> ReLU] triples, fused per conv
         for i, layer in enumerate(layers):
             if isinstance(layer, nn.Conv2d):
                 relu = i + 2 < len(layers) and isinstance(layers[i + 2], nn.ReLU)
+                if not relu and x is not None and i + 2 == len(layers) and self.head_loss_supported(h, layer, x):
+                    return DecoderHeadBernoulli.apply(h, layer.weight, layer.bias, x, with_recon)
                 if not relu and DecoderHead.supported(h, layer):     # 4 output channels: direct kernel
                     h = DecoderHead.apply(h, layer.weight, layer.bias)
                 elif relu and DecoderUp.supported(h, layer):         # 32 -> 128 + shuffle + ReLU on the f32 matrix cores
                     h = DecoderUp.apply(h, layer.weight, layer.bias)
                 else:
                     h = conv_block(h, layer, r=2, relu=relu)
-        return h
+        return h, None, None
+
+    def forward(self, a: torch.Tensor) -> torch.Tensor:
+        return self._decode(a)[0]
+
+    def forward_with_frames(self, a: torch.Tensor, x: torch.Tensor, with_recon=True):
+        """The decoder against its own target frames x [N,C,H,W]: (logits, x_recon, frame_ll) with x_recon = sigmoid(logits) (None
+        without `with_recon`) and frame_ll [N] = log p(x | a) from the head's own kernels (fused.DecoderHeadBernoulli), or
+        (logits, None, None) where the head does not take them (other shapes, Gaussian output, host tensors)."""
+        return self._decode(a, x, with_recon)
 
 
 class VAE(nn.Module):

@@ -3,7 +3,7 @@
 
 MIOpen's first-call solver search launches >1e6 throw-away kernels during warm-up, which swamps
 `--stats`.  This tool keeps the dispatches of the last K training steps (delimited by the last K+1
-launches of an anchor kernel, default k_smooth_bwd) and prints per-kernel totals per step.
+launches of an anchor kernel launched ONCE per step, default k_clip_adam) and prints per-kernel totals per step.
 usage: prof_summary.py <kernel_trace.csv> [--steps K] [--anchor NAME] [--top N]"""
 import argparse
 import csv
@@ -13,7 +13,7 @@ import sys
 ap = argparse.ArgumentParser()
 ap.add_argument("trace")
 ap.add_argument("--steps", type=int, default=10)
-ap.add_argument("--anchor", default="k_smooth_bwd")
+ap.add_argument("--anchor", default="k_clip_adam")
 ap.add_argument("--top", type=int, default=40)
 a = ap.parse_args()
 rows = []
