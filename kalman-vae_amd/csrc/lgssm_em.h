@@ -3,9 +3,9 @@
 // smoother's backward pass (csrc/lgssm_sws.h) with the expected sufficient statistics accumulated on the fly.  The equations are
 // in the header of the C ABI.  The forward pass is the filter's sweep with its history kept (csrc/lgssm_swf.h, sweep_wave<1>).
 //
-// back_wave below is a SIBLING of kvae_sws::back_wave: it repeats that body's statements in that body's order (so every smoother
-// output carries that kernel's bits; the tests compare them) on the same 8 x 8 grid - lane = 8 g + k owns the pair (source regime
-// k, destination regime g) - and differs in three places:
+// back_wave below is composed of the steps kvae_sws::back_wave is composed of (csrc/lgssm_sw_pair.h: so every smoother output
+// carries that kernel's bits) on the same 8 x 8 grid - lane = 8 g + k owns the pair (source regime k, destination regime g) - and
+// differs in three places:
 //   the loop runs one transition further, INTO t = 0: the source belief is (mu0, Sigma0) on every lane, the weights are
 //     hist_W[:, 0] (the uniform-matrix step), the input is u_0; nothing is collapsed after it.
 //   every transition adds the pair's share xi (.) to the lane's accumulators (N, S11, S10, S00, counts: 80 registers at
@@ -21,11 +21,8 @@
 
 namespace kvae_em {
 
-using kvae::rdec::xg8;
 using kvae::rgrid::oct_sum;
-using kvae_swf::padded;
-using kvae_swf::wave_sum;
-using kvae_sws::load_sym;
+using kvae_sw::wave_sum;
 
 // offsets of the blocks in a row of ws (floats), in the order of kvae_em_stats; G = the row
 struct Layout {
@@ -41,48 +38,19 @@ constexpr Layout layout(int K, int n, int m) {   // constexpr: callable from the
 }
 
 __device__ inline void back_wave(const kvae_sws_problem &S, const kvae_em_stats &E) {
+  using namespace kvae_sw;
   const kvae_swf_problem &P = S.filt;
-  const int lane = (int)(threadIdx.x & 63), k = lane & 7, g = lane >> 3;
+  const Lane ln = lane_of(P.K);
+  const auto [lane, k, g, kc, gc, vk, vg, ve] = ln;
   const int T = P.T, K = P.K, n = P.n, m = P.m;
-  const int64_t b = blockIdx.x;
-  const bool vk = k < K, vg = g < K, ve = vk && vg;
-  const int kc = vk ? k : 0, gc = vg ? g : 0;
-  // ---- regime g's dynamics, in the filter's orientation ----
-  float A[4][4], Bm[4][4], Q[4][4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      A[r][c] = padded(P.A + gc * n * n, n, n, r, c, vg);
-      Bm[r][c] = padded(P.Bm + gc * n * m, n, m, r, c, vg);
-      Q[r][c] = padded(P.Q + gc * n * n, n, n, r, c, vg);
-    }
-  }
-  const int64_t q0 = b * T;
+  const int64_t b = blockIdx.x, q0 = b * T;
   const int64_t p0 = b * (T > 1 ? T - 1 : 1);   // regime_pairs holds T - 1 steps
-  // ---- t = T - 1: regime k's filtered belief is its smoothed one, M = the final weights ("along the lanes") ----
-  float Mk, ms[4], Ss[4][4];
-  {
-    const int64_t s = (q0 + T - 1) * K + kc;
-    const float w = S.hist_w[b * K + kc];
-    Mk = vk ? w : 0.0f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) ms[r] = padded(S.hist_mu + s * n, 1, n, 0, r, vk);
-    load_sym(S.hist_Sigma + s * n * n, n, vk, Ss);
-  }
-  // ---- the operands of the transition into T - 1, in flight: the source belief (step T - 2; the prior at T = 1), W and u of T - 1 ----
-  float mun[4], Sgn[4][4], Wn, un[4];
-  {
-    const bool pri = T == 1;
-    const int64_t s = (q0 + (pri ? 0 : T - 2)) * K + kc;
-    const float *pm = pri ? P.mu0 : S.hist_mu + s * n, *pS = pri ? P.Sigma0 : S.hist_Sigma + s * n * n;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) mun[r] = padded(pm, 1, n, 0, r, vk);
-    load_sym(pS, n, vk, Sgn);
-    Wn = S.hist_W[ve ? ((q0 + T - 1) * K + k) * K + g : 0];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) un[c] = padded(P.u + (q0 + T - 1) * m, 1, m, 0, c, true);
-  }
+  float A[4][4], Bm[4][4], Q[4][4];   // regime g's dynamics, in the filter's orientation
+  load_dynamics(P, gc, vg, A, Bm, Q);
+  Smoothed Z;      // regime k's smoothed belief of step t, along the lanes
+  Transition N;    // the operands of the transition into step t, in flight: the source is the prior at t = 0
+  last_belief(S, ln, Z);
+  fetch(S, ln, T - 1, true, N);
   // ---- the lane's accumulators: the share of pair (k, g) over t; the emission sums (the same on every lane) ----
   float aN = 0.f, aP = 0.f;
   float a11[4][4], a10z[4][4], a10u[4][4], a00z[4][4], a00zu[4][4], a00u[4][4];   // a11, a00z, a00u: the upper triangle only
@@ -97,31 +65,21 @@ __device__ inline void back_wave(const kvae_sws_problem &S, const kvae_em_stats 
 
   for (int t = T - 1;; --t) {
     const int64_t q = q0 + t;
-    // ---- the outputs of step t: M_t, and the moment match of the K smoothed Gaussians under it (inside a group) ----
-    if (S.regime_smooth && lane < K) S.regime_smooth[q * K + lane] = Mk;
+    // ---- the outputs of step t, and the emission sums from the moment match (m_t, V_t) ----
+    float mm[4], V[4][4];
+    step_outputs(S, ln, q, Z, true, mm, V);
     {
       const float mk = P.mask ? P.mask[q] : 1.0f;
       const bool seen = mk != 0.0f;
       const float ob = seen ? 1.0f : 0.0f;   // the weight of the step in the emission sums
       const float y0r = P.y[q * 2], y1r = P.y[q * 2 + 1];
       const float y0 = seen ? y0r : 0.0f, y1 = seen ? y1r : 0.0f;   // selected, not multiplied: whatever a hidden y holds adds 0
-      float mm[4], dd[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        mm[r] = oct_sum(Mk * ms[r]);
-        dd[r] = ms[r] - mm[r];
-        if (S.mus_smooth && lane == 0 && r < n) S.mus_smooth[q * n + r] = mm[r];
         eyz[0][r] = fmaf(y0, mm[r], eyz[0][r]);
         eyz[1][r] = fmaf(y1, mm[r], eyz[1][r]);
-      }
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-#pragma unroll
-        for (int c = r; c < 4; ++c) {
-          const float v = oct_sum(Mk * fmaf(dd[r], dd[c], Ss[r][c]));
-          if (S.Sigmas_smooth && lane == 0 && c < n) S.Sigmas_smooth[q * n * n + r * n + c] = v, S.Sigmas_smooth[q * n * n + c * n + r] = v;
-          ezz[r][c] = fmaf(ob, fmaf(mm[r], mm[c], v), ezz[r][c]);
-        }
+        for (int c = r; c < 4; ++c) ezz[r][c] = fmaf(ob, fmaf(mm[r], mm[c], V[r][c]), ezz[r][c]);
       }
       eyy[0] = fmaf(y0, y0, eyy[0]);
       eyy[1] = fmaf(y0, y1, eyy[1]);
@@ -130,145 +88,15 @@ __device__ inline void back_wave(const kvae_sws_problem &S, const kvae_em_stats 
     }
     // ---- hand-over: lane (k, g) takes regime g's smoothed belief of step t from lane g ("on the groups") ----
     float Mg, mg[4], Sgs[4][4];
-    {
-      const float v = __shfl(Mk, g, 64);
-      Mg = vg ? v : 0.0f;
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float v = __shfl(ms[r], g, 64);
-      mg[r] = vg ? v : 0.0f;
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int c = r; c < 4; ++c) {
-        const float v = __shfl(Ss[r][c], g, 64);
-        Sgs[r][c] = vg ? v : 0.0f;
-        Sgs[c][r] = Sgs[r][c];
-      }
-    }
+    hand_over(g, vg, 0.0f, Z.M, Z.mu, Z.Sigma, Mg, mg, Sgs);
     // ---- the transition into t: its operands, and the next one's in flight ----
-    const float W = ve ? Wn : 0.0f;
-    const float u[4] = {un[0], un[1], un[2], un[3]};
-    float mu[4], Sg[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      mu[r] = mun[r];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) Sg[r][c] = Sgn[r][c];
-    }
-    {
-      const int tn = t >= 1 ? t - 1 : 0;   // the transition into tn: source step tn - 1, the prior at tn = 0
-      const bool pri = tn == 0;
-      const int64_t s = (q0 + (pri ? 0 : tn - 1)) * K + kc;
-      const float *pm = pri ? P.mu0 : S.hist_mu + s * n, *pS = pri ? P.Sigma0 : S.hist_Sigma + s * n * n;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) mun[r] = padded(pm, 1, n, 0, r, vk);
-      load_sym(pS, n, vk, Sgn);
-      Wn = S.hist_W[ve ? ((q0 + tn) * K + k) * K + g : 0];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) un[c] = padded(P.u + (q0 + tn) * m, 1, m, 0, c, true);
-    }
-    // ---- predict of the pair: the filter's statements (csrc/lgssm_swf.h) ----
-    float mp[4], AS[4][4], Sp[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float acc = 0.f;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) acc = fmaf(A[r][c], mu[c], acc);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) acc = fmaf(Bm[r][c], u[c], acc);
-      mp[r] = acc;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s = fmaf(A[r][e], Sg[e][c], s);
-        AS[r][c] = s;
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s = fmaf(AS[r][e], A[c][e], s);
-        Sp[r][c] = s + Q[r][c];
-      }
-    }
-    // ---- X = J^T = Sigma_p^-T (A Sigma): elimination in natural order, no pivoting; padding gets a unit diagonal ----
-    float L[4][4], X[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        L[r][c] = (r == c && (r >= n || !vg)) ? 1.0f : Sp[c][r];
-        X[r][c] = AS[r][c];
-      }
-    }
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-#pragma unroll
-      for (int r = p + 1; r < 4; ++r) {
-        const float f = L[r][p] / L[p][p];
-#pragma unroll
-        for (int c = p + 1; c < 4; ++c) L[r][c] = fmaf(-f, L[p][c], L[r][c]);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) X[r][c] = fmaf(-f, X[p][c], X[r][c]);
-      }
-    }
-#pragma unroll
-    for (int r = 3; r >= 0; --r) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float s = X[r][c];
-#pragma unroll
-        for (int e = r + 1; e < 4; ++e) s = fmaf(-L[r][e], X[e][c], s);
-        X[r][c] = s / L[r][r];
-      }
-    }
-    // ---- the smoothed pair: mu_s = mu + J (mu_s^g - mu_p), Sigma_s = sym(Sigma + J (Sigma_s^g - Sigma_p) J^T) ----
-    float dm[4], D[4][4], JD[4][4], mj[4], F[4][4], Sj[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      dm[r] = mg[r] - mp[r];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) D[r][c] = Sgs[r][c] - Sp[r][c];
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float acc = mu[r];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) acc = fmaf(X[c][r], dm[c], acc);
-      mj[r] = acc;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s = fmaf(X[e][r], D[e][c], s);
-        JD[r][c] = s;
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s = fmaf(JD[r][e], X[e][c], s);
-        F[r][c] = Sg[r][c] + s;
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int c = r; c < 4; ++c) Sj[r][c] = 0.5f * (F[r][c] + F[c][r]);   // the upper triangle: the lower has the same bits
-    }
-    // ---- weights: the pair marginal xi (the column-sum division: the note in csrc/lgssm_sws.h) ----
-    const float cs = oct_sum(W);
-    const float pr = W * (Mg / (vg ? cs : 1.0f));
+    const Transition X = N;
+    const float (&u)[4] = X.u;
+    fetch(S, ln, t >= 1 ? t - 1 : 0, true, N);
+    float mp[4], AS[4][4], Sp[4][4], Jt[4][4], mj[4], Sj[4][4];
+    predict(A, Bm, Q, X.mu, X.Sigma, u, mp, AS, Sp);
+    smoothed_pair(n, vg, X.mu, X.Sigma, mp, AS, Sp, mg, Sgs, Jt, mj, Sj);
+    const float pr = pair_marginal(ve ? X.W : 0.0f, Mg, vg);
     // ---- the pair's share of the statistics of this transition: xi = pr, 0 on the padding lanes ----
     aN += pr;
 #pragma unroll
@@ -277,7 +105,7 @@ __device__ inline void back_wave(const kvae_sws_problem &S, const kvae_em_stats 
       for (int c = 0; c < 4; ++c) {
         float cr = 0.f;   // (Sigma_s^g J^T)[r][c]: Cov(z_t, z_{t-1}) of the pair
 #pragma unroll
-        for (int e = 0; e < 4; ++e) cr = fmaf(Sgs[r][e], X[e][c], cr);
+        for (int e = 0; e < 4; ++e) cr = fmaf(Sgs[r][e], Jt[e][c], cr);
         a10z[r][c] = fmaf(pr, fmaf(mg[r], mj[c], cr), a10z[r][c]);
         a10u[r][c] = fmaf(pr, mg[r] * u[c], a10u[r][c]);
         a00zu[r][c] = fmaf(pr, mj[r] * u[c], a00zu[r][c]);
@@ -299,27 +127,7 @@ __device__ inline void back_wave(const kvae_sws_problem &S, const kvae_em_stats 
       break;
     }
     aP += pr;
-    // ---- M_{t-1}(k) over the groups, V_{g|k} (one-hot at g = k where M_{t-1}(k) = 0) ----
-    const float Mn = xg8<0>(pr);
-    const bool dead = !(Mn > 0.0f);
-    const float V = dead ? (k == g ? 1.0f : 0.0f) : pr / Mn;
-    if (S.regime_pairs && ve) S.regime_pairs[((p0 + t - 1) * K + k) * K + g] = pr;
-    // ---- collapse over g: regime k's smoothed belief of step t - 1, along the lanes ----
-    float d[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      ms[r] = xg8<0>(V * mj[r]);
-      d[r] = mj[r] - ms[r];
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int c = r; c < 4; ++c) {
-        Ss[r][c] = xg8<0>(V * fmaf(d[r], d[c], Sj[r][c]));
-        Ss[c][r] = Ss[r][c];
-      }
-    }
-    Mk = Mn;
+    collapse(S, ln, p0 + t - 1, pr, mj, Sj, Z);
   }
   // ---- the sequence's row: the shares reduced over the source regime, every element of ws[b, :] written once ----
   const Layout Lw = layout(K, n, m);
@@ -370,16 +178,12 @@ __device__ inline void reduce_thread(const kvae_sws_problem &S, const kvae_em_st
   const kvae_swf_problem &P = S.filt;
   const Layout L = layout(P.K, P.n, P.m);
   const int e = (int)blockIdx.x * 64 + (int)(threadIdx.x & 63);
-  if (e >= L.G) return;
   if (e == 0 && E.nseq) E.nseq[0] = (float)P.B;
-  float *out = e < L.S11 ? E.N : e < L.S10 ? E.S11 : e < L.S00 ? E.S10 : e < L.counts ? E.S00 : e < L.Syz ? E.counts : e < L.Szz ? E.Syz
-             : e < L.Syy ? E.Szz : e < L.Nobs ? E.Syy : e < L.z0 ? E.Nobs : e < L.z0z0 ? E.z0 : E.z0z0;
-  const int base = e < L.S11 ? L.N : e < L.S10 ? L.S11 : e < L.S00 ? L.S10 : e < L.counts ? L.S00 : e < L.Syz ? L.counts : e < L.Szz ? L.Syz
-                 : e < L.Syy ? L.Szz : e < L.Nobs ? L.Syy : e < L.z0 ? L.Nobs : e < L.z0z0 ? L.z0 : L.z0z0;
-  if (!out) return;   // a block nobody asked for is not read
-  float acc = 0.f;
-  for (int b = 0; b < P.B; ++b) acc += E.ws[(int64_t)b * L.G + e];
-  out[e - base] = acc;
+  kvae_sw::Block k{E.N, L.N};
+  offer(k, e, E.S11, L.S11), offer(k, e, E.S10, L.S10), offer(k, e, E.S00, L.S00), offer(k, e, E.counts, L.counts);
+  offer(k, e, E.Syz, L.Syz), offer(k, e, E.Szz, L.Szz), offer(k, e, E.Syy, L.Syy), offer(k, e, E.Nobs, L.Nobs);
+  offer(k, e, E.z0, L.z0), offer(k, e, E.z0z0, L.z0z0);
+  kvae_sw::reduce_rows(E.ws, P.B, L.G, e, k);
 }
 
 // ---- what both entry points (kvae_lgssm_em.hip, the host simulation below) share ---------------------------------------------

@@ -6,9 +6,8 @@
 // (previous regime i = k, current regime j = g).  A_j, B_j, Q_j, C, R and log P[i,j] are loaded once, padded with zeros to
 // 4 x 4 (run-time n, m <= 4), and stay in registers for the whole sweep; only y_t, u_t, mask_t are streamed, one step ahead of
 // the step that uses them, from a clamped address (the last step fetches itself again).
-//   per step, on every lane: the filter step of pair (i, j) from (mu^i, Sigma^i) - the statements of filter_gain /
-//     filter_step_core (csrc/lgssm_fwd.h), the 2 x 2 solve by elimination without pivoting (S is positive definite) - and the
-//     pair density by pred_tail (csrc/lgssm_pred.h).
+//   per step, on every lane: the filter step of pair (i, j) from (mu^i, Sigma^i) and the pair density - kvae_sw::predict and
+//     kvae_sw::update (csrc/lgssm_sw_pair.h, where the per-pair statements of the four GPB2 kernels are written once).
 //   reductions over i inside a column j: the eight lanes of group g, three DPP moves each (rgrid::oct_sum / oct_max): the column
 //     maximum, the softmax weights W_{i|j}, log w'(j) and the fourteen sums of the collapse.  Every lane of the group ends with
 //     the same bits ("on the groups").
@@ -21,31 +20,17 @@
 // run time (every loop below is unrolled over constants), no LDS, no scratch.  Every multiply-add is an explicit fmaf and the
 // unit is compiled with contraction off, so the bits of an output do not depend on which others are requested.
 #pragma once
-#include <math.h>
-#include <stdint.h>
-
-#include "../../include/kvae_lgssm.h"
-#include "lgssm_pred.h"
-#include "regime_decode.h"
+#include "lgssm_sw_pair.h"
 
 namespace kvae_swf {
 
 using kvae::rdec::xg8;
-using kvae::rgrid::oct_max;
 using kvae::rgrid::oct_sum;
+using kvae_sw::padded;
+using kvae_sw::wave_max;
+using kvae_sw::wave_sum;
 
 constexpr int MAX_K = 8, MAX_N = 4, MAX_M = 4;
-
-// all 64 lanes: the eight lanes of a group, then the eight groups
-__device__ __forceinline__ float wave_sum(float x) { return xg8<0>(oct_sum(x)); }
-__device__ __forceinline__ float wave_max(float x) { return xg8<1>(oct_max(x)); }
-
-// element (r, c) of a row-major [rows, cols] matrix padded to 4 x 4: loaded from a valid address, selected afterwards
-__device__ __forceinline__ float padded(const float *M, int rows, int cols, int r, int c, bool live) {
-  const bool in = live && r < rows && c < cols;
-  const float v = M[in ? r * cols + c : 0];
-  return in ? v : 0.0f;
-}
 
 // What the smoother's forward (csrc/lgssm_sws.h, k_sws_fwd) keeps of every step: the collapsed per-regime beliefs - the values the
 // sweep hands to step t + 1 - the pair weights W of that step, and the weights after the last step.  The forward of the
@@ -62,31 +47,15 @@ struct History {
 
 template <int HIST = 0>
 __device__ inline void sweep_wave(const kvae_swf_problem &P, const History H = History{}) {
-  const int lane = (int)(threadIdx.x & 63), k = lane & 7, g = lane >> 3;
+  const kvae_sw::Lane ln = kvae_sw::lane_of(P.K);
+  const auto [lane, k, g, kc, gc, vk, vg, ve] = ln;
   const int T = P.T, K = P.K, n = P.n, m = P.m;
   const int64_t b = blockIdx.x;
-  const bool vk = k < K, vg = g < K, ve = vk && vg;
-  const int kc = vk ? k : 0, gc = vg ? g : 0;
   // ---- operands of the sweep: regime j = g's dynamics, the shared emission, log P[i = k, j = g] ----
-  float A[4][4], Bm[4][4], Q[4][4], C[2][4], R[2][2];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      A[r][c] = padded(P.A + gc * n * n, n, n, r, c, vg);
-      Bm[r][c] = padded(P.Bm + gc * n * m, n, m, r, c, vg);
-      Q[r][c] = padded(P.Q + gc * n * n, n, n, r, c, vg);
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) C[q][c] = padded(P.C, 2, n, q, c, true);
-    R[q][0] = P.R[2 * q], R[q][1] = P.R[2 * q + 1];
-  }
-  const float Pr = P.P[ve ? k * K + g : 0];
-  const float Pij = ve ? Pr : 0.0f, lPij = ve ? logf(Pr) : -INFINITY;
-  const float Puni = 1.0f / (float)K, lPuni = logf(Puni);
+  float A[4][4], Bm[4][4], Q[4][4];
+  kvae_sw::Emission E;
+  kvae_sw::load_dynamics(P, gc, vg, A, Bm, Q);
+  kvae_sw::load_emission(P, ln, E);
   // ---- the carried belief of regime i = k ("along the lanes") ----
   const bool carried = P.state_log_w != nullptr;
   float mu[4], Sg[4][4], lw;
@@ -95,7 +64,7 @@ __device__ inline void sweep_wave(const kvae_swf_problem &P, const History H = H
     const float *S0 = carried ? P.state_Sigma + (b * K + kc) * n * n : P.Sigma0;
     const float *w0 = carried ? P.state_log_w + b * K + kc : P.R;   // a valid address either way
     const float lw0 = *w0;
-    lw = vk ? (carried ? lw0 : lPuni) : -INFINITY;
+    lw = vk ? (carried ? lw0 : E.lPuni) : -INFINITY;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       mu[r] = padded(m0, 1, n, 0, r, vk);
@@ -123,145 +92,47 @@ __device__ inline void sweep_wave(const kvae_swf_problem &P, const History H = H
       for (int c = 0; c < 4; ++c) un[c] = padded(P.u + qn * m, 1, m, 0, c, true);
     }
     const bool observed = mk != 0.0f, first = t == 0 && !carried;
-    // ---- the Kalman step of pair (i, j): predict ----
+    // ---- the Kalman step of pair (i, j): predict, forecast, S, the pair density, gain, Joseph update ----
     float mp[4], AS[4][4], Sp[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float acc = 0.f;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) acc = fmaf(A[r][c], mu[c], acc);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) acc = fmaf(Bm[r][c], u[c], acc);
-      mp[r] = acc;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s = fmaf(A[r][e], Sg[e][c], s);
-        AS[r][c] = s;
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s = fmaf(AS[r][e], A[c][e], s);
-        Sp[r][c] = s + Q[r][c];
-      }
-    }
-    // ---- forecast of the pair, S, the pair density ----
-    float ap[2], res[2], CP[2][4], PCT[4][2];
-#pragma unroll
-    for (int qq = 0; qq < 2; ++qq) {
-      float acc = 0.f;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc = fmaf(C[qq][e], mp[e], acc);
-      ap[qq] = acc;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s1 = fmaf(C[qq][e], Sp[e][c], s1), s2 = fmaf(Sp[c][e], C[qq][e], s2);
-        CP[qq][c] = s1, PCT[c][qq] = s2;
-      }
-    }
-    res[0] = y0 - ap[0], res[1] = y1 - ap[1];
-    float s00 = 0.f, s01a = 0.f, s01b = 0.f, s11 = 0.f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      s00 = fmaf(CP[0][e], C[0][e], s00), s01a = fmaf(CP[0][e], C[1][e], s01a);
-      s01b = fmaf(CP[1][e], C[0][e], s01b), s11 = fmaf(CP[1][e], C[1][e], s11);
-    }
-    const float S00 = s00 + R[0][0], S11 = s11 + R[1][1];   // 0.5 (x + x) = x
-    const float S01 = 0.5f * ((s01a + R[0][1]) + (s01b + R[1][0]));
-    const kvae_pred::Tail tl = kvae_pred::pred_tail(S00, S01, S11, res[0], res[1]);
-    // ---- gain (S^-1 PCT^T by elimination), update, Joseph form ----
-    const float el = S01 / S00, ed = fmaf(-el, S01, S11);
-    float Kg[4][2];   // K = mask * Kt^T
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float x1 = fmaf(-el, PCT[r][0], PCT[r][1]) / ed;
-      const float x0 = fmaf(-S01, x1, PCT[r][0]) / S00;
-      Kg[r][0] = mk * x0, Kg[r][1] = mk * x1;
-    }
-    float IKC[4][4], KR[4][2], muf[4], T1[4][4], Sf[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) IKC[r][c] = (r == c ? 1.0f : 0.0f) - fmaf(Kg[r][1], C[1][c], Kg[r][0] * C[0][c]);
-      KR[r][0] = fmaf(Kg[r][1], R[1][0], Kg[r][0] * R[0][0]), KR[r][1] = fmaf(Kg[r][1], R[1][1], Kg[r][0] * R[0][1]);
-      muf[r] = fmaf(Kg[r][1], res[1], fmaf(Kg[r][0], res[0], mp[r]));
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s = fmaf(IKC[r][e], Sp[e][c], s);
-        T1[r][c] = s;
-      }
-    }
-    float F0[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s = fmaf(T1[r][e], IKC[c][e], s);
-        F0[r][c] = s + fmaf(KR[r][1], Kg[c][1], KR[r][0] * Kg[c][0]);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int c = r; c < 4; ++c) Sf[r][c] = 0.5f * (F0[r][c] + F0[c][r]);   // the upper triangle: the lower has the same bits
-    }
+    kvae_sw::Update U;   // of Sf, the upper triangle is read
+    kvae_sw::predict(A, Bm, Q, mu, Sg, u, mp, AS, Sp);
+    kvae_sw::update(E.C, E.R, mp, Sp, y0, y1, mk, U);
     // ---- weights: log c_ij, the prior weight w(i) P[i,j], the column softmax ----
-    const float lPt = first ? (ve ? lPuni : -INFINITY) : lPij, Pt = first ? (ve ? Puni : 0.0f) : Pij;
-    const float lij = observed ? tl.ll : 0.0f;
-    const float logc = ve ? (lw + lPt) + lij : -INFINITY;
+    const float lPt = first ? (ve ? E.lPuni : -INFINITY) : E.lPij, Pt = first ? (ve ? E.Puni : 0.0f) : E.Pij;
+    const float lij = observed ? U.tl.ll : 0.0f;
     const float pw = ve ? expf(lw) * Pt : 0.0f;
     const float rp = oct_sum(pw);                                   // regime_pred(j), on the groups
-    const float cmx = oct_max(logc);
-    const bool dead = !(cmx > -INFINITY);                           // an impossible regime: W one-hot at i = j
-    const float ex = dead ? (k == g ? 1.0f : 0.0f) : expf(logc - cmx);
-    const float se = oct_sum(ex);
-    const float W = ex / se;
-    const float mx = xg8<1>(cmx);
-    const float tot = mx + logf(xg8<0>(vg ? se * expf(cmx - mx) : 0.0f));   // logsumexp_ij; a dead column adds 1 * exp(-inf) = 0
-    const float lwn = (cmx + logf(se)) - tot;                       // log w'(j), on the groups
+    const kvae_sw::Weights wt = kvae_sw::weights(ln, lw, lPt, lij);
+    const float W = wt.W, tot = wt.tot;
+    const float lwn = (wt.cmx + logf(wt.se)) - tot;                 // log w'(j), on the groups
     const float rf = vg ? expf(lwn) : 0.0f;
     // ---- collapse over i ----
     float mc[4], Sc[4][4], d[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      mc[r] = oct_sum(W * muf[r]);
-      d[r] = muf[r] - mc[r];
+      mc[r] = oct_sum(W * U.muf[r]);
+      d[r] = U.muf[r] - mc[r];
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
 #pragma unroll
-      for (int c = r; c < 4; ++c) Sc[r][c] = oct_sum(W * fmaf(d[r], d[c], Sf[r][c]));
+      for (int c = r; c < 4; ++c) Sc[r][c] = oct_sum(W * fmaf(d[r], d[c], U.Sf[r][c]));
     }
     // ---- the step's outputs ----
     if (P.regime_pred && vg && k == 0) P.regime_pred[q * K + g] = rp;
     if (P.regime_filt && vg && k == 0) P.regime_filt[q * K + g] = rf;
     if (P.ll && lane == 0) P.ll[q] = observed ? tot : 0.0f;
     if (P.levels) {
-      const float lv = wave_max(pw > 0.0f ? (float)tl.level : 0.0f);
+      const float lv = wave_max(pw > 0.0f ? (float)U.tl.level : 0.0f);
       if (lane == 0) P.levels[q] = (int32_t)lv;
     }
     if (P.a_pred || P.S_out) {   // moment match of the K^2 pair forecasts under the prior weights
-      const float a0 = wave_sum(pw * ap[0]), a1 = wave_sum(pw * ap[1]);
+      const float a0 = wave_sum(pw * U.ap[0]), a1 = wave_sum(pw * U.ap[1]);
       if (P.a_pred && lane == 0) P.a_pred[q * 2] = a0, P.a_pred[q * 2 + 1] = a1;
       if (P.S_out) {
-        const float e0 = ap[0] - a0, e1 = ap[1] - a1;
-        const float o00 = wave_sum(pw * fmaf(e0, e0, S00)), o01 = wave_sum(pw * fmaf(e0, e1, S01));
-        const float o11 = wave_sum(pw * fmaf(e1, e1, S11));
+        const float e0 = U.ap[0] - a0, e1 = U.ap[1] - a1;
+        const float o00 = wave_sum(pw * fmaf(e0, e0, U.S00)), o01 = wave_sum(pw * fmaf(e0, e1, U.S01));
+        const float o11 = wave_sum(pw * fmaf(e1, e1, U.S11));
         if (lane == 0) {
           float *o = P.S_out + q * 4;
           o[0] = o00, o[1] = o01, o[2] = o01, o[3] = o11;
@@ -318,23 +189,7 @@ __device__ inline void sweep_wave(const kvae_swf_problem &P, const History H = H
       }
     }
     // ---- hand-over: lane (i = k, j = g) takes regime k's belief from group k ----
-    const int src = k << 3;
-    const float lwA = __shfl(lwn, src, 64);
-    lw = vk ? lwA : -INFINITY;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float v = __shfl(mc[r], src, 64);
-      mu[r] = vk ? v : 0.0f;
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int c = r; c < 4; ++c) {
-        const float v = __shfl(Sc[r][c], src, 64);
-        Sg[r][c] = vk ? v : 0.0f;
-        Sg[c][r] = Sg[r][c];
-      }
-    }
+    kvae_sw::hand_over(k << 3, vk, -INFINITY, lwn, mc, Sc, lw, mu, Sg);
   }
 }
 

@@ -8,8 +8,8 @@
 // i = k, current regime j = g).  A_j, B_j, Q_j, C, R and log P[i,j] stay in registers for the whole sweep; step t = T-1 .. 0 streams,
 // one step ahead from clamped addresses, the belief and log weight that ENTERED it (history slot t - 1; (mu0, Sigma0, log 1/K) at
 // t = 0) and y_t, u_t, mask_t, g_ll[b,t].
-//   per step, on every lane: the pair step recomputed by the forward's own statements (repeated here, as the smoother repeats the
-//     predict: the level, S and W are the forward's bits), then its adjoint - the equations of DESIGN.md section 16.
+//   per step, on every lane: the pair step recomputed by the forward's own functions (kvae_sw::predict, update and weights of
+//     csrc/lgssm_sw_pair.h: the level, S and W are the forward's bits), then its adjoint - the equations of DESIGN.md section 16.
 //   the adjoints that arrive from step t + 1 - of log w'(j), mu'^j, Sigma'^j - sit "on the groups" (regime j = g); the adjoints
 //     this step hands on - of log w(i), mu^i, Sigma^i, summed over j by rdec::xg8 - come out "along the lanes" (regime i = k);
 //     the hand-over is the transpose of the grid, fifteen __shfl from lane g, as the smoother's backward.
@@ -28,10 +28,10 @@
 namespace kvae_swm {
 
 using kvae::rdec::xg8;
-using kvae::rgrid::oct_max;
 using kvae::rgrid::oct_sum;
-using kvae_swf::padded;
-using kvae_swf::wave_sum;
+using kvae_sw::padded;
+using kvae_sw::wave_sum;
+
 
 // ---- the layout of one sequence's partial, ws[b, :], in floats ----
 struct Layout {
@@ -66,31 +66,17 @@ __device__ __forceinline__ void entering(const kvae_swm_problem &M, int64_t q0, 
 
 __device__ inline void back_wave(const kvae_swm_problem &M, const kvae_swm_grads &G) {
   const kvae_swf_problem &P = M.filt;
-  const int lane = (int)(threadIdx.x & 63), k = lane & 7, g = lane >> 3;
+  const kvae_sw::Lane ln = kvae_sw::lane_of(P.K);
+  const auto [lane, k, g, kc, gc, vk, vg, ve] = ln;
   const int T = P.T, K = P.K, n = P.n, m = P.m;
   const int64_t b = blockIdx.x;
-  const bool vk = k < K, vg = g < K, ve = vk && vg;
-  const int kc = vk ? k : 0, gc = vg ? g : 0;
   // ---- operands of the sweep, as the forward's ----
-  float A[4][4], Bm[4][4], Q[4][4], C[2][4], R[2][2];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      A[r][c] = padded(P.A + gc * n * n, n, n, r, c, vg);
-      Bm[r][c] = padded(P.Bm + gc * n * m, n, m, r, c, vg);
-      Q[r][c] = padded(P.Q + gc * n * n, n, n, r, c, vg);
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) C[q][c] = padded(P.C, 2, n, q, c, true);
-    R[q][0] = P.R[2 * q], R[q][1] = P.R[2 * q + 1];
-  }
-  const float Pr = P.P[ve ? k * K + g : 0];
-  const float lPij = ve ? logf(Pr) : -INFINITY;
-  const float Puni = 1.0f / (float)K, lPuni = logf(Puni);
+  float A[4][4], Bm[4][4], Q[4][4];
+  kvae_sw::Emission E;
+  kvae_sw::load_dynamics(P, gc, vg, A, Bm, Q);
+  kvae_sw::load_emission(P, ln, E);
+  const float (&C)[2][4] = E.C;
+  const float lPuni = E.lPuni;
   const int64_t q0 = b * T;
   const float *maskp = P.mask ? P.mask + q0 : P.R;   // always a valid address
   const int mstep = P.mask ? 1 : 0;
@@ -148,119 +134,19 @@ __device__ inline void back_wave(const kvae_swm_problem &M, const kvae_swm_grads
     }
     const bool observed = mk != 0.0f, first = t == 0;
     const float om = observed ? gll + gseq : 0.0f;
-    // ======== the pair step, recomputed: the statements of kvae_swf::sweep_wave ========
+    // ======== the pair step, recomputed: the functions of kvae_swf::sweep_wave ========
     float mp[4], AS[4][4], Sp[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float acc = 0.f;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) acc = fmaf(A[r][c], mu[c], acc);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) acc = fmaf(Bm[r][c], u[c], acc);
-      mp[r] = acc;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s = fmaf(A[r][e], Sg[e][c], s);
-        AS[r][c] = s;
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s = fmaf(AS[r][e], A[c][e], s);
-        Sp[r][c] = s + Q[r][c];
-      }
-    }
-    float ap[2], res[2], CP[2][4], PCT[4][2];
-#pragma unroll
-    for (int qq = 0; qq < 2; ++qq) {
-      float acc = 0.f;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc = fmaf(C[qq][e], mp[e], acc);
-      ap[qq] = acc;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s1 = fmaf(C[qq][e], Sp[e][c], s1), s2 = fmaf(Sp[c][e], C[qq][e], s2);
-        CP[qq][c] = s1, PCT[c][qq] = s2;
-      }
-    }
-    res[0] = y0 - ap[0], res[1] = y1 - ap[1];
-    float s00 = 0.f, s01a = 0.f, s01b = 0.f, s11 = 0.f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      s00 = fmaf(CP[0][e], C[0][e], s00), s01a = fmaf(CP[0][e], C[1][e], s01a);
-      s01b = fmaf(CP[1][e], C[0][e], s01b), s11 = fmaf(CP[1][e], C[1][e], s11);
-    }
-    const float S00 = s00 + R[0][0], S11 = s11 + R[1][1];
-    const float S01 = 0.5f * ((s01a + R[0][1]) + (s01b + R[1][0]));
-    const kvae_pred::Tail tl = kvae_pred::pred_tail(S00, S01, S11, res[0], res[1]);
-    const float el = S01 / S00, ed = fmaf(-el, S01, S11);
-    float Kt[4][2], Kg[4][2];   // Kt = Sigma_p C^T S^-1, K = mask * Kt
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float x1 = fmaf(-el, PCT[r][0], PCT[r][1]) / ed;
-      const float x0 = fmaf(-S01, x1, PCT[r][0]) / S00;
-      Kt[r][0] = x0, Kt[r][1] = x1;
-      Kg[r][0] = mk * x0, Kg[r][1] = mk * x1;
-    }
-    float IKC[4][4], KR[4][2], muf[4], T1[4][4], Sf[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) IKC[r][c] = (r == c ? 1.0f : 0.0f) - fmaf(Kg[r][1], C[1][c], Kg[r][0] * C[0][c]);
-      KR[r][0] = fmaf(Kg[r][1], R[1][0], Kg[r][0] * R[0][0]), KR[r][1] = fmaf(Kg[r][1], R[1][1], Kg[r][0] * R[0][1]);
-      muf[r] = fmaf(Kg[r][1], res[1], fmaf(Kg[r][0], res[0], mp[r]));
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s = fmaf(IKC[r][e], Sp[e][c], s);
-        T1[r][c] = s;
-      }
-    }
-    float F0[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s = fmaf(T1[r][e], IKC[c][e], s);
-        F0[r][c] = s + fmaf(KR[r][1], Kg[c][1], KR[r][0] * Kg[c][0]);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int c = r; c < 4; ++c) {
-        Sf[r][c] = 0.5f * (F0[r][c] + F0[c][r]);
-        Sf[c][r] = Sf[r][c];
-      }
-    }
-    const float lPt = first ? (ve ? lPuni : -INFINITY) : lPij;
-    const float lij = observed ? tl.ll : 0.0f;
-    const float logc = ve ? (lw + lPt) + lij : -INFINITY;
-    const float cmx = oct_max(logc);
-    const bool dead = !(cmx > -INFINITY);
-    const float ex = dead ? (k == g ? 1.0f : 0.0f) : expf(logc - cmx);
-    const float se = oct_sum(ex);
-    const float W = ex / se;
-    const float mx = xg8<1>(cmx);
-    const float tot = mx + logf(xg8<0>(vg ? se * expf(cmx - mx) : 0.0f));
+    kvae_sw::Update U;
+    kvae_sw::predict(A, Bm, Q, mu, Sg, u, mp, AS, Sp);
+    kvae_sw::update(C, E.R, mp, Sp, y0, y1, mk, U);
+    const float lPt = first ? (ve ? lPuni : -INFINITY) : E.lPij;
+    const float lij = observed ? U.tl.ll : 0.0f;
+    const kvae_sw::Weights wt = kvae_sw::weights(ln, lw, lPt, lij);
+    const float logc = wt.logc, W = wt.W, tot = wt.tot;
     if (G.ll_recomputed && lane == 0) G.ll_recomputed[q] = observed ? tot : 0.0f;   // the forward's P.ll[q], bit for bit
     float d[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) d[r] = muf[r] - oct_sum(W * muf[r]);
+    for (int r = 0; r < 4; ++r) d[r] = U.muf[r] - oct_sum(W * U.muf[r]);
     // ======== the adjoint of the collapse: Sigma'^j = sum_i W (Sigma_ij + d d^T), mu'^j = sum_i W mu_ij ========
     float GSd[4], gmuf[4], Gm[4][4];
 #pragma unroll
@@ -279,7 +165,7 @@ __device__ inline void back_wave(const kvae_swm_problem &M, const kvae_swm_grads
       gW = fmaf(gm[r], d[r], gW);
 #pragma unroll
       for (int c = r; c < 4; ++c) {
-        const float e = fmaf(d[r], d[c], Sf[r][c]);
+        const float e = fmaf(d[r], d[c], U.Sf[r][c]);
         const float dev = e - oct_sum(W * e);
         gW = fmaf(r == c ? GS[r][c] : 2.0f * GS[r][c], dev, gW);
       }
@@ -297,18 +183,18 @@ __device__ inline void back_wave(const kvae_swm_problem &M, const kvae_swm_grads
     aP += first ? 0.0f : glc;                    // the uniform-matrix step does not read P
     const float gli = observed ? glc : 0.0f;     // the adjoint of l_ij
     // ======== the pair's Kalman step ========
-    const kvae_pred::Adj ad = kvae_pred::pred_adjoint(tl, S00, S11, res[0], res[1]);
-    const float Si11 = 1.0f / ed, Si01 = -el / ed, Si00 = S11 / (S00 * ed);   // S^-1, by the gain's elimination
+    const kvae_pred::Adj ad = kvae_pred::pred_adjoint(U.tl, U.S00, U.S11, U.res[0], U.res[1]);
+    const float Si11 = 1.0f / U.ed, Si01 = -U.el / U.ed, Si00 = U.S11 / (U.S00 * U.ed);   // S^-1, by the gain's elimination
     float Kb[4][2], KbSi[4][2];   // Kb: the adjoint of Kt;  KbSi = Kb S^-1
 #pragma unroll
-    for (int r = 0; r < 4; ++r) Kb[r][0] = gmuf[r] * res[0], Kb[r][1] = gmuf[r] * res[1];
+    for (int r = 0; r < 4; ++r) Kb[r][0] = gmuf[r] * U.res[0], Kb[r][1] = gmuf[r] * U.res[1];
     // K R - M Sigma_p C^T = (mask - 1) Sigma_p C^T, because Kt S = Sigma_p C^T: 0 on an observed step (the gain is the stationary
     // point of the Joseph form).  Formed as written it is the difference of two equal matrices - rounding noise that 2 G amplifies
     // where Sigma_p >> R (the model's Sigma0 = 20 I against R = 0.03^2 I: gA off by 1.4e-5).
     const float mk1 = mk - 1.0f;
     float H[4][2];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) H[r][0] = mk1 * PCT[r][0], H[r][1] = mk1 * PCT[r][1];
+    for (int r = 0; r < 4; ++r) H[r][0] = mk1 * U.PCT[r][0], H[r][1] = mk1 * U.PCT[r][1];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       float s0 = 0.f, s1 = 0.f;
@@ -320,15 +206,15 @@ __device__ inline void back_wave(const kvae_swm_problem &M, const kvae_swm_grads
     float k00 = 0.f, k01 = 0.f, k10 = 0.f, k11 = 0.f;   // Kt^T Kb S^-1
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      k00 = fmaf(Kt[r][0], KbSi[r][0], k00), k01 = fmaf(Kt[r][0], KbSi[r][1], k01);
-      k10 = fmaf(Kt[r][1], KbSi[r][0], k10), k11 = fmaf(Kt[r][1], KbSi[r][1], k11);
+      k00 = fmaf(U.Kt[r][0], KbSi[r][0], k00), k01 = fmaf(U.Kt[r][0], KbSi[r][1], k01);
+      k10 = fmaf(U.Kt[r][1], KbSi[r][0], k10), k11 = fmaf(U.Kt[r][1], KbSi[r][1], k11);
     }
     const float gS00 = fmaf(gli, ad.g00, -k00), gS11 = fmaf(gli, ad.g11, -k11), gS01 = fmaf(gli, ad.g01, -0.5f * (k01 + k10));
     float gr[2];
     {
       float s0 = 0.f, s1 = 0.f;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) s0 = fmaf(Kg[r][0], gmuf[r], s0), s1 = fmaf(Kg[r][1], gmuf[r], s1);
+      for (int r = 0; r < 4; ++r) s0 = fmaf(U.Kg[r][0], gmuf[r], s0), s1 = fmaf(U.Kg[r][1], gmuf[r], s1);
       gr[0] = fmaf(-gli, ad.v0, s0), gr[1] = fmaf(-gli, ad.v1, s1);
     }
     float GM[4][4], gSp[4][4], gmp[4];
@@ -338,7 +224,7 @@ __device__ inline void back_wave(const kvae_swm_problem &M, const kvae_swm_grads
       for (int c = 0; c < 4; ++c) {
         float s = 0.f;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) s = fmaf(Gm[r][e], IKC[e][c], s);
+        for (int e = 0; e < 4; ++e) s = fmaf(Gm[r][e], U.IKC[e][c], s);
         GM[r][c] = s;
       }
       gmp[r] = gmuf[r] - fmaf(C[1][r], gr[1], C[0][r] * gr[0]);
@@ -352,7 +238,7 @@ __device__ inline void back_wave(const kvae_swm_problem &M, const kvae_swm_grads
       for (int c = r; c < 4; ++c) {
         float s = 0.f;   // M^T G M
 #pragma unroll
-        for (int e = 0; e < 4; ++e) s = fmaf(IKC[e][r], GM[e][c], s);
+        for (int e = 0; e < 4; ++e) s = fmaf(U.IKC[e][r], GM[e][c], s);
         const float ksc = fmaf(KbSi[r][1], C[1][c], KbSi[r][0] * C[0][c]), kcs = fmaf(KbSi[c][1], C[1][r], KbSi[c][0] * C[0][r]);
         s = fmaf(0.5f, ksc + kcs, s);
         s += fmaf(C[1][r], Hc[1][c], C[0][r] * Hc[0][c]);
@@ -369,10 +255,10 @@ __device__ inline void back_wave(const kvae_swm_problem &M, const kvae_swm_grads
         float gms = 0.f;
 #pragma unroll
         for (int e = 0; e < 4; ++e) gms = fmaf(GM[r][e], Sp[e][c], gms);
-        g0 = fmaf(-2.0f * Kg[r][0], gms, g0), g1 = fmaf(-2.0f * Kg[r][1], gms, g1);
+        g0 = fmaf(-2.0f * U.Kg[r][0], gms, g0), g1 = fmaf(-2.0f * U.Kg[r][1], gms, g1);
         g0 = fmaf(KbSi[r][0], Sp[r][c], g0), g1 = fmaf(KbSi[r][1], Sp[r][c], g1);
       }
-      g0 = fmaf(2.0f, fmaf(gS01, CP[1][c], gS00 * CP[0][c]), g0), g1 = fmaf(2.0f, fmaf(gS11, CP[1][c], gS01 * CP[0][c]), g1);
+      g0 = fmaf(2.0f, fmaf(gS01, U.CP[1][c], gS00 * U.CP[0][c]), g0), g1 = fmaf(2.0f, fmaf(gS11, U.CP[1][c], gS01 * U.CP[0][c]), g1);
       aC[0][c] += fmaf(-gr[0], mp[c], g0), aC[1][c] += fmaf(-gr[1], mp[c], g1);
     }
 #pragma unroll
@@ -438,24 +324,7 @@ __device__ inline void back_wave(const kvae_swm_problem &M, const kvae_swm_grads
       }
     }
     // ---- hand-over: lane (i = k, j = g) of step t - 1 takes regime g's adjoints from lane g (the transpose of the grid) ----
-    {
-      const float v = __shfl(glw, g, 64);
-      gl = vg ? v : 0.0f;
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float v = __shfl(gmu_out[r], g, 64);
-      gm[r] = vg ? v : 0.0f;
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int c = r; c < 4; ++c) {
-        const float v = __shfl(gSg_out[r][c], g, 64);
-        GS[r][c] = vg ? v : 0.0f;
-        GS[c][r] = GS[r][c];
-      }
-    }
+    kvae_sw::hand_over(g, vg, 0.0f, glw, gmu_out, gSg_out, gl, gm, GS);
   }
   // ---- the sequence's partial: the pairs reduced, every element of ws[b, :] written once ----
   const Layout L = layout(K, n, m);
@@ -496,12 +365,10 @@ __device__ inline void reduce_thread(const kvae_swm_problem &M, const kvae_swm_g
   const kvae_swf_problem &P = M.filt;
   const Layout L = layout(P.K, P.n, P.m);
   const int e = (int)blockIdx.x * 64 + (int)(threadIdx.x & 63);
-  if (e >= L.G) return;
-  float acc = 0.f;
-  for (int b = 0; b < P.B; ++b) acc += G.ws[(int64_t)b * L.G + e];
-  float *out = e < L.B ? G.gA : e < L.Q ? G.gB : e < L.C ? G.gQ : e < L.P ? G.gC : e < L.mu0 ? G.g_logP : e < L.Sigma0 ? G.g_mu0 : G.g_Sigma0;
-  const int base = e < L.B ? L.A : e < L.Q ? L.B : e < L.C ? L.Q : e < L.P ? L.C : e < L.mu0 ? L.P : e < L.Sigma0 ? L.mu0 : L.Sigma0;
-  if (out) out[e - base] = acc;
+  kvae_sw::Block k{G.gA, L.A};
+  offer(k, e, G.gB, L.B), offer(k, e, G.gQ, L.Q), offer(k, e, G.gC, L.C), offer(k, e, G.g_logP, L.P);
+  offer(k, e, G.g_mu0, L.mu0), offer(k, e, G.g_Sigma0, L.Sigma0);
+  kvae_sw::reduce_rows(G.ws, P.B, L.G, e, k);
 }
 
 // ---- what both entry points (kvae_lgssm_swm.hip, the host simulation below) share --------------------------------------------

@@ -198,7 +198,7 @@ def gradients(DEV, case):
                   ("regime_filt", "regime_filt")):
         assert torch.equal(got[k], filt[fk]), k
     assert torch.equal(got["levels"].cpu(), ref["levels"])
-    # the adjoint repeats the statements of the forward's pair step: what they give for ll must be the forward's bits
+    # the adjoint recomputes the pair step by the forward's own functions (csrc/lgssm_sw_pair.h): their ll must be the forward's bits
     assert torch.equal(got["ll_recomputed"], got["ll"])
     return check(got, ref, mask, what=str(case))
 
