@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 #define KVAE_MAX_DIM 16
-#define KVAE_ABI_VERSION 20
+#define KVAE_ABI_VERSION 21
 
 typedef enum {
   KVAE_OK = 0,
@@ -349,6 +349,15 @@ int kvae_dec_head_loss_fwd(const float *in, const float *W, const float *bias, c
 int kvae_dec_head_loss_bwd(const float *in, const float *W, const float *logits, const float *x, const float *g_frame, float *g_in,
                            float *w_partials, float *b_partials, float *w_scratch, int64_t N, int32_t Cin, int32_t side,
                            void *stream);
+/* kvae_dec_head_bwd / kvae_dec_head_loss_bwd with the ReLU mask of the layer that PRODUCED `in` applied to the data gradient
+ * where it is made: g_in = in > 0 ? g_in : 0, every other output the same bits.  For a caller whose `in` is a ReLU output with
+ * no other consumer (the decoder: the 8x8 up-sampling block), which then hands g_in to kvae_dec_up_bwd_flags with
+ * KVAE_UP_G_PREMASKED.  It is NOT the gradient of `in`.  No reference counterpart. */
+int kvae_dec_head_bwd_masked(const float *in, const float *W, const float *g_logits, float *g_in, float *w_partials,
+                             float *b_partials, float *w_scratch, int64_t N, int32_t Cin, int32_t side, void *stream);
+int kvae_dec_head_loss_bwd_masked(const float *in, const float *W, const float *logits, const float *x, const float *g_frame,
+                                  float *g_in, float *w_partials, float *b_partials, float *w_scratch, int64_t N, int32_t Cin,
+                                  int32_t side, void *stream);
 /* Encoder stem (kvae/vae/vae.py:20-31): out[N,Cout,s/2,s/2] = relu(conv3x3_stride2_pad1(x[N,1,s,s], W[Cout,1,3,3]) + b).
  * Built for Cout = 32, s = 32.  relu_bits (may be NULL): [N, (s/2)^2] words, bit co of word (n, pixel) = out[n,co,pixel] > 0 -
  * the ReLU mask in 1/32 of the bytes of out, for kvae_enc_stem_bwd. */
@@ -379,6 +388,16 @@ int kvae_dec_up_fwd(const float *x, const float *W, const float *bias, float *ou
  * w_partials [rows, 128*32*9], b_partials [rows, 128], rows = kvae_dec_up_partial_rows(N, side): column sums. */
 int kvae_dec_up_bwd(const float *x, const float *W, const float *out, const float *g_out, float *g_x, float *w_partials,
                     float *b_partials, int64_t N, int32_t Cin, int32_t side, void *stream);
+/* kvae_dec_up_bwd with the ReLU masks moved to where each gradient is made (flags = 0: kvae_dec_up_bwd).
+ *   KVAE_UP_G_PREMASKED: the caller guarantees g_out == (out > 0 ? g_out : 0) already (kvae_dec_head_*_bwd_masked, or this entry
+ *     with KVAE_UP_MASK_GX one level up).  The results are the same bits; the Winograd kernels then never read `out` (it must
+ *     still be a valid pointer: the direct kernels of KVAE_WINO=0 go on reading it).
+ *   KVAE_UP_MASK_GX: g_x = x > 0 ? g_x : 0, the mask of the layer that produced x (x a ReLU output with no other consumer).
+ * Any other bit returns KVAE_ERR_ARG. */
+#define KVAE_UP_G_PREMASKED 1
+#define KVAE_UP_MASK_GX 2
+int kvae_dec_up_bwd_flags(const float *x, const float *W, const float *out, const float *g_out, float *g_x, float *w_partials,
+                          float *b_partials, int64_t N, int32_t Cin, int32_t side, int32_t flags, void *stream);
 int64_t kvae_dec_up_partial_rows(int64_t N, int32_t side);
 /* The decoder blocks run as persistent workgroups, one per CU (256).  A caller that overlaps them with a second stream whose
  * kernels cannot share a CU with them (kvae/train/train.py: the LGSSM chain of the switching model) may ask for fewer, which

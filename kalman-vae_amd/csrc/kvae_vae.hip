@@ -418,11 +418,14 @@ int kvae_dec_head_loss_fwd(const float *in, const float *W, const float *bias, c
 template <bool LOSS>
 static int dec_head_bwd_launch(const float *in, const float *W, const float *g_logits, const float *logits, const float *x,
                                const float *g_frame, float *g_in, float *w_partials, float *b_partials, float *w_scratch,
-                               int64_t N, hipStream_t st) {
+                               int64_t N, bool mask, hipStream_t st) {
   const dim3 grid((unsigned)kvae_conv_edge_partial_rows(N));
   if (g_in) {
     k_dec_head_prep<<<dim3(1), dim3(256), 0, st>>>(W, w_scratch);
-    k_dec_head_bwd<LOSS, true><<<grid, dim3(256), 0, st>>>(in, g_logits, logits, x, g_frame, w_scratch, g_in, w_partials, b_partials, N);
+    if (mask)
+      k_dec_head_bwd<LOSS, true, true><<<grid, dim3(256), 0, st>>>(in, g_logits, logits, x, g_frame, w_scratch, g_in, w_partials, b_partials, N);
+    else
+      k_dec_head_bwd<LOSS, true><<<grid, dim3(256), 0, st>>>(in, g_logits, logits, x, g_frame, w_scratch, g_in, w_partials, b_partials, N);
   } else {
     k_dec_head_bwd<LOSS, false><<<grid, dim3(256), 0, st>>>(in, g_logits, logits, x, g_frame, w_scratch, g_in, w_partials, b_partials, N);
   }
@@ -434,7 +437,7 @@ int kvae_dec_head_bwd(const float *in, const float *W, const float *g_logits, fl
   if (!in || !W || !g_logits || !w_partials || !b_partials || !w_scratch) return KVAE_ERR_NULL;
   if (N < 1) return KVAE_ERR_ARG;
   if (Cin != DH_CI || side != DH_S) return KVAE_ERR_DIMS;
-  return dec_head_bwd_launch<false>(in, W, g_logits, nullptr, nullptr, nullptr, g_in, w_partials, b_partials, w_scratch, N,
+  return dec_head_bwd_launch<false>(in, W, g_logits, nullptr, nullptr, nullptr, g_in, w_partials, b_partials, w_scratch, N, false,
                                     (hipStream_t)stream);
 }
 int kvae_dec_head_loss_bwd(const float *in, const float *W, const float *logits, const float *x, const float *g_frame, float *g_in,
@@ -443,7 +446,25 @@ int kvae_dec_head_loss_bwd(const float *in, const float *W, const float *logits,
   if (!in || !W || !logits || !x || !g_frame || !w_partials || !b_partials || !w_scratch) return KVAE_ERR_NULL;
   if (N < 1) return KVAE_ERR_ARG;
   if (Cin != DH_CI || side != DH_S) return KVAE_ERR_DIMS;
-  return dec_head_bwd_launch<true>(in, W, nullptr, logits, x, g_frame, g_in, w_partials, b_partials, w_scratch, N,
+  return dec_head_bwd_launch<true>(in, W, nullptr, logits, x, g_frame, g_in, w_partials, b_partials, w_scratch, N, false,
+                                   (hipStream_t)stream);
+}
+// the same two with g_in = in > 0 ? g_in : 0 (k_dec_head_bwd<., true, true>)
+int kvae_dec_head_bwd_masked(const float *in, const float *W, const float *g_logits, float *g_in, float *w_partials,
+                             float *b_partials, float *w_scratch, int64_t N, int32_t Cin, int32_t side, void *stream) {
+  if (!in || !W || !g_logits || !w_partials || !b_partials || !w_scratch) return KVAE_ERR_NULL;
+  if (N < 1) return KVAE_ERR_ARG;
+  if (Cin != DH_CI || side != DH_S) return KVAE_ERR_DIMS;
+  return dec_head_bwd_launch<false>(in, W, g_logits, nullptr, nullptr, nullptr, g_in, w_partials, b_partials, w_scratch, N, true,
+                                    (hipStream_t)stream);
+}
+int kvae_dec_head_loss_bwd_masked(const float *in, const float *W, const float *logits, const float *x, const float *g_frame,
+                                  float *g_in, float *w_partials, float *b_partials, float *w_scratch, int64_t N, int32_t Cin,
+                                  int32_t side, void *stream) {
+  if (!in || !W || !logits || !x || !g_frame || !w_partials || !b_partials || !w_scratch) return KVAE_ERR_NULL;
+  if (N < 1) return KVAE_ERR_ARG;
+  if (Cin != DH_CI || side != DH_S) return KVAE_ERR_DIMS;
+  return dec_head_bwd_launch<true>(in, W, nullptr, logits, x, g_frame, g_in, w_partials, b_partials, w_scratch, N, true,
                                    (hipStream_t)stream);
 }
 int kvae_enc_stem_fwd(const float *x, const float *W, const float *bias, float *out, uint32_t *relu_bits, int64_t N, int32_t Cout,
@@ -547,30 +568,69 @@ int kvae_dec_up_fwd(const float *x, const float *W, const float *bias, float *ou
   else k_dec_up_fwd<4><<<grid, dim3(256), 0, (hipStream_t)stream>>>(x, W, bias, out, N);
   return launch_status("k_dec_up_fwd");
 }
+}  // extern "C"
+// g[i] = act[i] > 0 ? g[i] : 0 in place, 16 bytes per thread: KVAE_UP_MASK_GX wherever the Winograd 8x8 data gradient does not
+// apply it itself (the direct kernels of KVAE_WINO=0, the 4x4 block, a gradient that is not pre-masked) - A/B and test routes
+__global__ __launch_bounds__(256) void k_relu_mask_inplace(float *__restrict__ g, const float *__restrict__ act, int64_t quads) {
+  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < quads; q += (int64_t)gridDim.x * 256) {
+    const float4 a = reinterpret_cast<const float4 *>(act)[q];
+    float4 v = reinterpret_cast<float4 *>(g)[q];
+    v = make_float4(a.x > 0.f ? v.x : 0.f, a.y > 0.f ? v.y : 0.f, a.z > 0.f ? v.z : 0.f, a.w > 0.f ? v.w : 0.f);
+    reinterpret_cast<float4 *>(g)[q] = v;
+  }
+}
+static int dec_up_bwd_launch(const float *x, const float *W, const float *out, const float *g_out, float *g_x, float *w_partials,
+                             float *b_partials, int64_t N, int32_t side, int32_t flags, hipStream_t st) {
+  const dim3 grid((unsigned)dec_up_grid(N, side));
+  const bool pre = (flags & KVAE_UP_G_PREMASKED) != 0, wino = dec_up_wino();
+  if (g_x) {
+    const int64_t sets = side == 8 ? N : (N + 3) / 4;
+    const dim3 wgrid((unsigned)(sets < dec_up_cap() ? sets : dec_up_cap()));
+    bool mask_gx = (flags & KVAE_UP_MASK_GX) != 0;
+    if (wino && side == 8 && pre && mask_gx) {
+      k_dec_up_bwd_data_wino<8, true, true><<<wgrid, dim3(512), 0, st>>>(W, x, out, g_out, g_x, N);
+      mask_gx = false;                                // done by the kernel
+    } else if (wino && side == 8 && pre) k_dec_up_bwd_data_wino<8, true><<<wgrid, dim3(512), 0, st>>>(W, x, out, g_out, g_x, N);
+    else if (wino && side == 8) k_dec_up_bwd_data_wino<8><<<wgrid, dim3(512), 0, st>>>(W, x, out, g_out, g_x, N);
+    else if (wino && pre) k_dec_up_bwd_data_wino<4, true><<<wgrid, dim3(512), 0, st>>>(W, x, out, g_out, g_x, N);
+    else if (wino) k_dec_up_bwd_data_wino<4><<<wgrid, dim3(512), 0, st>>>(W, x, out, g_out, g_x, N);
+    else if (side == 8) k_dec_up_bwd_data<8><<<grid, dim3(256), 0, st>>>(W, out, g_out, g_x, N);   // the direct kernels mask again:
+    else k_dec_up_bwd_data<4><<<grid, dim3(256), 0, st>>>(W, out, g_out, g_x, N);                   // the select is idempotent
+    int rc = launch_status("k_dec_up_bwd_data");
+    if (rc) return rc;
+    if (mask_gx) {
+      const int64_t quads = N * UP_CI * side * side / 4;
+      k_relu_mask_inplace<<<dim3(epi_grid(quads)), dim3(256), 0, st>>>(g_x, x, quads);
+      rc = launch_status("k_relu_mask_inplace");
+      if (rc) return rc;
+    }
+  }
+  if (wino) {
+    if (side == 8 && pre) k_dec_up_wrw_wino<8, true><<<grid, dim3(512), 0, st>>>(x, out, g_out, w_partials, b_partials, N);
+    else if (side == 8) k_dec_up_wrw_wino<8><<<grid, dim3(512), 0, st>>>(x, out, g_out, w_partials, b_partials, N);
+    else if (pre) k_dec_up_wrw_wino<4, true><<<grid, dim3(512), 0, st>>>(x, out, g_out, w_partials, b_partials, N);
+    else k_dec_up_wrw_wino<4><<<grid, dim3(512), 0, st>>>(x, out, g_out, w_partials, b_partials, N);
+    return launch_status("k_dec_up_wrw_wino");
+  }
+  if (side == 8) k_dec_up_wrw<8><<<grid, dim3(256), 0, st>>>(x, out, g_out, w_partials, b_partials, N);
+  else k_dec_up_wrw<4><<<grid, dim3(256), 0, st>>>(x, out, g_out, w_partials, b_partials, N);
+  return launch_status("k_dec_up_wrw");
+}
+extern "C" {
 int kvae_dec_up_bwd(const float *x, const float *W, const float *out, const float *g_out, float *g_x, float *w_partials,
                     float *b_partials, int64_t N, int32_t Cin, int32_t side, void *stream) {
   if (!x || !W || !out || !g_out || !w_partials || !b_partials) return KVAE_ERR_NULL;
   if (N < 1 || (N + 256 * 8) * UP_CO * side * side * 4 >= EM_MAX_BYTES) return KVAE_ERR_ARG;
   if (Cin != UP_CI || (side != 8 && side != 4)) return KVAE_ERR_DIMS;
-  const dim3 grid((unsigned)dec_up_grid(N, side));
-  if (g_x) {
-    const int64_t sets = side == 8 ? N : (N + 3) / 4;
-    const dim3 wgrid((unsigned)(sets < dec_up_cap() ? sets : dec_up_cap()));
-    if (dec_up_wino() && side == 8) k_dec_up_bwd_data_wino<8><<<wgrid, dim3(512), 0, (hipStream_t)stream>>>(W, out, g_out, g_x, N);
-    else if (dec_up_wino()) k_dec_up_bwd_data_wino<4><<<wgrid, dim3(512), 0, (hipStream_t)stream>>>(W, out, g_out, g_x, N);
-    else if (side == 8) k_dec_up_bwd_data<8><<<grid, dim3(256), 0, (hipStream_t)stream>>>(W, out, g_out, g_x, N);
-    else k_dec_up_bwd_data<4><<<grid, dim3(256), 0, (hipStream_t)stream>>>(W, out, g_out, g_x, N);
-    const int rc = launch_status("k_dec_up_bwd_data");
-    if (rc) return rc;
-  }
-  if (dec_up_wino()) {
-    if (side == 8) k_dec_up_wrw_wino<8><<<grid, dim3(512), 0, (hipStream_t)stream>>>(x, out, g_out, w_partials, b_partials, N);
-    else k_dec_up_wrw_wino<4><<<grid, dim3(512), 0, (hipStream_t)stream>>>(x, out, g_out, w_partials, b_partials, N);
-    return launch_status("k_dec_up_wrw_wino");
-  }
-  if (side == 8) k_dec_up_wrw<8><<<grid, dim3(256), 0, (hipStream_t)stream>>>(x, out, g_out, w_partials, b_partials, N);
-  else k_dec_up_wrw<4><<<grid, dim3(256), 0, (hipStream_t)stream>>>(x, out, g_out, w_partials, b_partials, N);
-  return launch_status("k_dec_up_wrw");
+  return dec_up_bwd_launch(x, W, out, g_out, g_x, w_partials, b_partials, N, side, 0, (hipStream_t)stream);
+}
+int kvae_dec_up_bwd_flags(const float *x, const float *W, const float *out, const float *g_out, float *g_x, float *w_partials,
+                          float *b_partials, int64_t N, int32_t Cin, int32_t side, int32_t flags, void *stream) {
+  if (!x || !W || !out || !g_out || !w_partials || !b_partials) return KVAE_ERR_NULL;
+  if (N < 1 || (N + 256 * 8) * UP_CO * side * side * 4 >= EM_MAX_BYTES) return KVAE_ERR_ARG;
+  if (flags & ~(KVAE_UP_G_PREMASKED | KVAE_UP_MASK_GX)) return KVAE_ERR_ARG;
+  if (Cin != UP_CI || (side != 8 && side != 4)) return KVAE_ERR_DIMS;
+  return dec_up_bwd_launch(x, W, out, g_out, g_x, w_partials, b_partials, N, side, flags, (hipStream_t)stream);
 }
 }  // extern "C"
 

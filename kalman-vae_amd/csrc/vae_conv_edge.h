@@ -130,7 +130,11 @@ __global__ __launch_bounds__(256) void k_dec_head_fwd(const float *__restrict__ 
 // workgroup); what the one kernel saves is the second read of the gradient and, with LOSS, the gradient itself.
 // LOSS: the gradient tile is not read but formed from the Bernoulli term, g_logits = -g_frame[n] (sigmoid(logits) - x), the
 // expression of k_vae_bce_bwd: the 52 MB gradient never exists in memory.
-template <bool LOSS, bool DATA>
+// MASK (with DATA): `in` is a ReLU output whose producer is the only other reader of g_in (the decoder's 8x8 up-sampling block,
+// vae_conv_up_wino.h), so the producer's ReLU mask is applied HERE, where the gradient is made: g_in = in > 0 ? g_in : 0, the
+// activation read back from the frame tile that is still in LDS (one conflict-free ds_read_b32 and one select per stored float).
+// The producer's gradient kernels then take g_in as it is and never read their 419 MB activation (PREMASKED there).
+template <bool LOSS, bool DATA, bool MASK = false>
 __global__ __launch_bounds__(256, 2) void k_dec_head_bwd(const float *__restrict__ in, const float *__restrict__ g_logits,
                                                          const float *__restrict__ logits, const float *__restrict__ x,
                                                          const float *__restrict__ g_frame, const float *__restrict__ scratch,
@@ -250,8 +254,13 @@ __global__ __launch_bounds__(256, 2) void k_dec_head_bwd(const float *__restrict
       float *o = g_in + n * DH_CI * 256 + threadIdx.x;
 #pragma unroll
       for (int j = 0; j < DH_CI / 2; ++j) {
-        o[(2 * j) * 256] = dacc[j].x;
-        o[(2 * j + 1) * 256] = dacc[j].y;
+        if constexpr (MASK) {                         // the tile is untouched until the barrier at the top of the next frame
+          o[(2 * j) * 256] = tile[(2 * j) * CS + threadIdx.x] > 0.f ? dacc[j].x : 0.f;
+          o[(2 * j + 1) * 256] = tile[(2 * j + 1) * CS + threadIdx.x] > 0.f ? dacc[j].y : 0.f;
+        } else {
+          o[(2 * j) * 256] = dacc[j].x;
+          o[(2 * j + 1) * 256] = dacc[j].y;
+        }
       }
     }
   }

@@ -304,6 +304,12 @@ __global__ __launch_bounds__(512) void k_dec_up_fwd_wino(const float *__restrict
 // each other).  g_out and out reach LDS by DMA (buffer_load ... lds, no registers: there are none to spare) one column set
 // ahead, in their own [32][16][16] layout; a short phase between two barriers turns them into masked, un-shuffled,
 // zero-bordered planes, and folds the four K-quarters of the previous set (red[]) into one coalesced 16-byte store per thread.
+// PREMASKED: g_out arrives with the mask already applied by the kernel that made it (k_dec_head_bwd<., true, true> for the 8x8
+// block, this kernel with MASK_GX for the 4x4 block): `out` is never read - half of the DMA pieces, the 32 KB rawo buffer and half
+// of the LDS reads of the convert phase are gone, and the remaining four pieces go out one per k-step.
+// MASK_GX (8x8 block only, with PREMASKED): x is itself a ReLU output whose only other reader of g_x is the 4x4 block, so that
+// block's mask is applied in fold(): g_x = x > 0 ? sum : 0.  The set's 8 KB of x are one more DMA piece (k-step 4, into the
+// space rawo vacated), issued while the set is computed and read one iteration later, when its partial sums are folded.
 // ---------------------------------------------------------------------------------------------------------------
 // 4x4 layer: a column set is four frames; their planes keep the left / right border columns but NOT the top / bottom border
 // rows (4 x 6 floats instead of 6 x 6: 128 channels x 4 frames must fit beside the DMA buffers) - those two patch rows are read
@@ -318,21 +324,23 @@ struct WinoBwd {
   static constexpr int RED = 2048;                   // one K-quarter's partial g_x of a column set
 };
 
-template <int S>
-__global__ __launch_bounds__(512) void k_dec_up_bwd_data_wino(const float *__restrict__ W, const float *__restrict__ out,
-                                                              const float *__restrict__ g_out, float *__restrict__ g_x, int64_t N) {
+template <int S, bool PREMASKED = false, bool MASK_GX = false>
+__global__ __launch_bounds__(512) void k_dec_up_bwd_data_wino(const float *__restrict__ W, const float *__restrict__ x,
+                                                              const float *__restrict__ out, const float *__restrict__ g_out,
+                                                              float *__restrict__ g_x, int64_t N) {
   using D = UpDims<S>;
   using Wd = WinoDims<S>;
   using K = WinoBwd<S>;
+  static_assert(!MASK_GX || (PREMASKED && S == 8), "MASK_GX: one frame of x per column set, in the space of rawo");
   // two objects on purpose: the DMA target must be provably distinct from the arrays the MFMA phase reads, or hipcc drains
   // the DMA (s_waitcnt vmcnt(0)) in front of the first ds_read after it
-  __shared__ __attribute__((aligned(16))) float raw[2 * K::RAW];
+  __shared__ __attribute__((aligned(16))) float raw[(PREMASKED ? 1 : 2) * K::RAW + (MASK_GX ? K::RED : 0)];
   __shared__ __attribute__((aligned(16))) float work[K::GY + 4 * K::RED];
-  float *rawg = raw, *rawo = raw + K::RAW, *gy = work, *red = work + K::GY;
+  float *rawg = raw, *rawo = raw + K::RAW, *gy = work, *red = work + K::GY;   // rawo: !PREMASKED only; MASK_GX: x of a set
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, j = lane & 15, g = lane >> 4, hh = wv & 1, kq = wv >> 1;
   const int64_t stride = gridDim.x, nsets = (N + Wd::FPC - 1) / Wd::FPC;
-  const __amdgpu_buffer_rsrc_t rg = em_rsrc(g_out, N * D::YFRAME * 4), ro = em_rsrc(out, N * D::YFRAME * 4),
-                               rgx = em_rsrc(g_x, N * D::XFRAME * 4);
+  const __amdgpu_buffer_rsrc_t rg = em_rsrc(g_out, N * D::YFRAME * 4), ro = em_rsrc(PREMASKED ? g_out : out, N * D::YFRAME * 4),
+                               rxm = em_rsrc(MASK_GX ? x : g_out, N * D::XFRAME * 4), rgx = em_rsrc(g_x, N * D::XFRAME * 4);
   for (int i = tid; i < K::GY; i += 512) gy[i] = 0.f;             // the borders stay zero for the whole kernel
 
   float U[16][8];                                                 // A operands: flip(W)[co = 32 kq + 4 s + g][ci = 16 hh + j]
@@ -358,15 +366,23 @@ __global__ __launch_bounds__(512) void k_dec_up_bwd_data_wino(const float *__res
 
   // (the staging phases recompute their addresses from an opaque copy of tid: hoisted out of the loop they would sit in
   //  registers through the MFMA phase, which has none to spare)
-  // eight 8 KB pieces per column set (g_out and out, four each).  Issued back to back they hold the later waves of the workgroup
-  // for ~3000 cycles (the memory queue is full: stamps, tools/wino_stamp_bwd.hip) before their first MFMA; dealt out one pair
-  // per k-step over the first four k-steps they queue behind the partner wave's MFMAs instead.
+  // eight 8 KB pieces per column set (g_out and out, four each; PREMASKED: the four of g_out).  Issued back to back they hold the
+  // later waves of the workgroup for ~3000 cycles (the memory queue is full: stamps, tools/wino_stamp_bwd.hip) before their
+  // first MFMA; dealt out one pair (PREMASKED: one piece) per k-step over the first four k-steps they queue behind the partner
+  // wave's MFMAs instead.
   auto dma_piece = [&](int64_t k, int q) {
     int t2 = tid;
     asm volatile("" : "+v"(t2));
     const uint32_t off = (uint32_t)(k * K::RAW + (t2 + 512 * q) * 4) * 4u;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rg, (__attribute__((address_space(3))) void *)(rawg + (wv * 64 + 512 * q) * 4), 16, off, 0, 0, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(ro, (__attribute__((address_space(3))) void *)(rawo + (wv * 64 + 512 * q) * 4), 16, off, 0, 0, 0);
+    if constexpr (!PREMASKED)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(ro, (__attribute__((address_space(3))) void *)(rawo + (wv * 64 + 512 * q) * 4), 16, off, 0, 0, 0);
+  };
+  auto dma_x = [&](int64_t k) {                       // MASK_GX: x of set k, as g_x is laid out (frames >= N read zeros)
+    int t2 = tid;
+    asm volatile("" : "+v"(t2));
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rxm, (__attribute__((address_space(3))) void *)(rawo + wv * 64 * 4), 16,
+                                             (uint32_t)(k * K::RED + t2 * 4) * 4u, 0, 0, 0);
   };
   auto dma = [&](int64_t k) {
 #pragma unroll
@@ -378,7 +394,11 @@ __global__ __launch_bounds__(512) void k_dec_up_bwd_data_wino(const float *__res
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int e = (t2 + 512 * q) * 4;
-      const float4 gv = *reinterpret_cast<const float4 *>(rawg + e), ov = *reinterpret_cast<const float4 *>(rawo + e);
+      float4 gv = *reinterpret_cast<const float4 *>(rawg + e);
+      if constexpr (!PREMASKED) {
+        const float4 ov = *reinterpret_cast<const float4 *>(rawo + e);
+        gv = make_float4(ov.x > 0.f ? gv.x : 0.f, ov.y > 0.f ? gv.y : 0.f, ov.z > 0.f ? gv.z : 0.f, ov.w > 0.f ? gv.w : 0.f);
+      }
       float *d;
       if constexpr (S == 8) {
         const int c = e >> 8, y = (e >> 4) & 15, xx = e & 15;
@@ -387,10 +407,10 @@ __global__ __launch_bounds__(512) void k_dec_up_bwd_data_wino(const float *__res
         const int f = e >> 11, c = (e >> 6) & 31, y = (e >> 3) & 7, xx = e & 7;
         d = gy + f * K::FSB + (4 * c + 2 * (y & 1)) * K::PLANE + (y >> 1) * K::RS + (xx >> 1) + 1;
       }
-      d[0] = ov.x > 0.f ? gv.x : 0.f;
-      d[K::PLANE] = ov.y > 0.f ? gv.y : 0.f;
-      d[1] = ov.z > 0.f ? gv.z : 0.f;
-      d[K::PLANE + 1] = ov.w > 0.f ? gv.w : 0.f;
+      d[0] = gv.x;
+      d[K::PLANE] = gv.y;
+      d[1] = gv.z;
+      d[K::PLANE + 1] = gv.w;
     }
   };
   uint32_t done = 0x80000000u;                        // byte offset of the set whose partials sit in red[] (none yet)
@@ -399,8 +419,12 @@ __global__ __launch_bounds__(512) void k_dec_up_bwd_data_wino(const float *__res
     asm volatile("" : "+v"(t2));
     const float4 a = *reinterpret_cast<const float4 *>(red + 4 * t2), b = *reinterpret_cast<const float4 *>(red + K::RED + 4 * t2),
                  c = *reinterpret_cast<const float4 *>(red + 2 * K::RED + 4 * t2), d = *reinterpret_cast<const float4 *>(red + 3 * K::RED + 4 * t2);
-    em_st4(rgx, done + (uint32_t)t2 * 16u, make_float4((a.x + b.x) + (c.x + d.x), (a.y + b.y) + (c.y + d.y), (a.z + b.z) + (c.z + d.z),
-                                                        (a.w + b.w) + (c.w + d.w)));
+    float4 s = make_float4((a.x + b.x) + (c.x + d.x), (a.y + b.y) + (c.y + d.y), (a.z + b.z) + (c.z + d.z), (a.w + b.w) + (c.w + d.w));
+    if constexpr (MASK_GX) {                          // x of the set in red[] (nothing yet: the store is dropped)
+      const float4 xv = *reinterpret_cast<const float4 *>(rawo + 4 * t2);
+      s = make_float4(xv.x > 0.f ? s.x : 0.f, xv.y > 0.f ? s.y : 0.f, xv.z > 0.f ? s.z : 0.f, xv.w > 0.f ? s.w : 0.f);
+    }
+    em_st4(rgx, done + (uint32_t)t2 * 16u, s);
   };
   auto patch = [&](int s, float2 (&d)[4][2]) {
 #pragma unroll
@@ -410,7 +434,7 @@ __global__ __launch_bounds__(512) void k_dec_up_bwd_data_wino(const float *__res
       d[r][1] = *reinterpret_cast<const float2 *>(p + 2);
     }
   };
-  auto compute = [&](int64_t knext) {
+  auto compute = [&](int64_t kcur, int64_t knext) {
     wn_f4 acc[16];
 #pragma unroll
     for (int p = 0; p < 16; ++p) acc[p] = wn_f4{0.f, 0.f, 0.f, 0.f};
@@ -426,6 +450,8 @@ __global__ __launch_bounds__(512) void k_dec_up_bwd_data_wino(const float *__res
       for (int p = 0; p < 16; ++p) acc[p] = WN_MFMA(U[p][s], v[p], acc[p]);
       __builtin_amdgcn_sched_barrier(0);
       if (s < 4) dma_piece(knext, s);                 // the raw buffers are free since the convert phase
+      if constexpr (MASK_GX)
+        if (s == 4) dma_x(kcur);                      // ... and x of THIS set, for the fold of the next iteration
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int r = 0; r < 4; ++r) d[r][0] = dn[r][0], d[r][1] = dn[r][1];
@@ -452,7 +478,7 @@ __global__ __launch_bounds__(512) void k_dec_up_bwd_data_wino(const float *__res
     __syncthreads();
     WN_STAMP(slot, 2);
     WN_STAMP(slot, 3);
-    compute(k + stride);                              // ... and the next set's DMA, dealt out between its k-steps
+    compute(k, k + stride);                           // ... and the next set's DMA, dealt out between its k-steps
     done = (uint32_t)(k * 2048) * 4u;
     WN_STAMP(slot, 4);
     __syncthreads();
@@ -469,6 +495,7 @@ __global__ __launch_bounds__(512) void k_dec_up_bwd_data_wino(const float *__res
 // transformed once for the whole workgroup (one patch per thread, through LDS, as in the forward); every wave expands its own
 // 2x2 tiles of gy = unshuffle(g_out * (out > 0)), which a short phase between two barriers lays out so that a lane's tile is
 // one ds_read_b128 (g_out / out arrive by DMA, x through 4 registers, one frame ahead).
+// PREMASKED: g_out carries the mask already (see the data gradient): `out` is not read, no rawo, four DMA pieces instead of eight.
 // ---------------------------------------------------------------------------------------------------------------
 template <int S>
 struct WinoWrw {
@@ -480,20 +507,20 @@ struct WinoWrw {
   static constexpr int VROW = 20, VSET = 8 * 64 * VROW;
 };
 
-template <int S>
+template <int S, bool PREMASKED = false>
 __global__ __launch_bounds__(512) void k_dec_up_wrw_wino(const float *__restrict__ x, const float *__restrict__ out,
                                                          const float *__restrict__ g_out, float *__restrict__ w_partials,
                                                          float *__restrict__ b_partials, int64_t N) {
   using D = UpDims<S>;
   using Wd = WinoDims<S>;
   using K = WinoWrw<S>;
-  __shared__ __attribute__((aligned(16))) float raw[2 * K::RAW];                        // DMA targets (own object: see bwd_data)
+  __shared__ __attribute__((aligned(16))) float raw[(PREMASKED ? 1 : 2) * K::RAW];      // DMA targets (own object: see bwd_data)
   __shared__ __attribute__((aligned(16))) float work[K::GY4 + K::XPL + K::VSET];
-  float *rawg = raw, *rawo = raw + K::RAW, *gy4 = work, *xp = work + K::GY4, *vt = xp + K::XPL;
+  float *rawg = raw, *rawo = raw + K::RAW, *gy4 = work, *xp = work + K::GY4, *vt = xp + K::XPL;   // rawo: !PREMASKED only
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, j = lane & 15, g = lane >> 4;
   const int64_t stride = gridDim.x, nsets = (N + Wd::FPC - 1) / Wd::FPC;
   const __amdgpu_buffer_rsrc_t rx = em_rsrc(x, N * D::XFRAME * 4), rg = em_rsrc(g_out, N * D::YFRAME * 4),
-                               ro = em_rsrc(out, N * D::YFRAME * 4);
+                               ro = em_rsrc(PREMASKED ? g_out : out, N * D::YFRAME * 4);
   for (int i = tid; i < K::XPL; i += 512) xp[i] = 0.f;            // the borders stay zero for the whole kernel
 
   wn_f4 acc[16][2];                                               // Z_p[co = 16 wv + 4 g + r][ci = 16 nh + j]
@@ -501,12 +528,13 @@ __global__ __launch_bounds__(512) void k_dec_up_wrw_wino(const float *__restrict
   for (int p = 0; p < 16; ++p) acc[p][0] = acc[p][1] = wn_f4{0.f, 0.f, 0.f, 0.f};
   float bsum = 0.f;
 
-  auto dma_piece = [&](int64_t k, int q) {            // dealt out one pair per k-step (see the data gradient)
+  auto dma_piece = [&](int64_t k, int q) {            // dealt out over the k-steps (see the data gradient)
     int t2 = tid;
     asm volatile("" : "+v"(t2));
     const uint32_t off = (uint32_t)(k * K::RAW + (t2 + 512 * q) * 4) * 4u;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rg, (__attribute__((address_space(3))) void *)(rawg + (wv * 64 + 512 * q) * 4), 16, off, 0, 0, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(ro, (__attribute__((address_space(3))) void *)(rawo + (wv * 64 + 512 * q) * 4), 16, off, 0, 0, 0);
+    if constexpr (!PREMASKED)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(ro, (__attribute__((address_space(3))) void *)(rawo + (wv * 64 + 512 * q) * 4), 16, off, 0, 0, 0);
   };
   auto dma = [&](int64_t k) {
 #pragma unroll
@@ -533,7 +561,11 @@ __global__ __launch_bounds__(512) void k_dec_up_wrw_wino(const float *__restrict
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int e = (t2 + 512 * q) * 4;
-      const float4 gv = *reinterpret_cast<const float4 *>(rawg + e), ov = *reinterpret_cast<const float4 *>(rawo + e);
+      float4 gv = *reinterpret_cast<const float4 *>(rawg + e);
+      if constexpr (!PREMASKED) {
+        const float4 ov = *reinterpret_cast<const float4 *>(rawo + e);
+        gv = make_float4(ov.x > 0.f ? gv.x : 0.f, ov.y > 0.f ? gv.y : 0.f, ov.z > 0.f ? gv.z : 0.f, ov.w > 0.f ? gv.w : 0.f);
+      }
       int ks, co, tg, a;
       if constexpr (S == 8) {
         const int c = e >> 8, y = (e >> 4) & 15, xx = e & 15;
@@ -543,8 +575,8 @@ __global__ __launch_bounds__(512) void k_dec_up_wrw_wino(const float *__restrict
         ks = f, co = 4 * c + 2 * (y & 1), tg = 2 * (y >> 2) + (xx >> 2), a = (y >> 1) & 1;
       }
       float *d = gy4 + ((ks * 128 + co) * 4 + tg) * 4 + 2 * a;
-      *reinterpret_cast<float2 *>(d) = make_float2(ov.x > 0.f ? gv.x : 0.f, ov.z > 0.f ? gv.z : 0.f);          // dx = 0: b = 0, 1
-      *reinterpret_cast<float2 *>(d + 16) = make_float2(ov.y > 0.f ? gv.y : 0.f, ov.w > 0.f ? gv.w : 0.f);     // dx = 1 (next co)
+      *reinterpret_cast<float2 *>(d) = make_float2(gv.x, gv.z);          // dx = 0: b = 0, 1
+      *reinterpret_cast<float2 *>(d + 16) = make_float2(gv.y, gv.w);     // dx = 1 (next co)
     }
   };
   // operand row of this thread in vt: (ks = wv >> 1, nh = wv & 1, lane): channel 16 nh + j, tile g of k-step ks

@@ -64,5 +64,32 @@ int kvae_dec_head_loss_bwd(const float *in, const float *W, const float *logits,
   free(g);
   return rc;
 }
+// Host twins of the entries that apply a ReLU mask where the gradient is made (k_dec_head_bwd<., true, true>, vae_conv_up_wino.h
+// PREMASKED / MASK_GX): the existing twins plus the select.  A pre-masked gradient needs nothing here: the twin of
+// kvae_dec_up_bwd masks by `out` again, which changes no bit of it.
+static void kv_relu_mask_host(float *g, const float *act, int64_t n) {
+  for (int64_t i = 0; i < n; ++i) g[i] = act[i] > 0.f ? g[i] : 0.f;
+}
+int kvae_dec_head_bwd_masked(const float *in, const float *W, const float *g_logits, float *g_in, float *w_partials,
+                             float *b_partials, float *w_scratch, int64_t N, int32_t Cin, int32_t side, void *) {
+  const int rc = kvae_dec_head_bwd(in, W, g_logits, g_in, w_partials, b_partials, w_scratch, N, Cin, side, nullptr);
+  if (!rc && g_in) kv_relu_mask_host(g_in, in, N * Cin * side * side);
+  return rc;
+}
+int kvae_dec_head_loss_bwd_masked(const float *in, const float *W, const float *logits, const float *x, const float *g_frame,
+                                  float *g_in, float *w_partials, float *b_partials, float *w_scratch, int64_t N, int32_t Cin,
+                                  int32_t side, void *) {
+  const int rc = kvae_dec_head_loss_bwd(in, W, logits, x, g_frame, g_in, w_partials, b_partials, w_scratch, N, Cin, side, nullptr);
+  if (!rc && g_in) kv_relu_mask_host(g_in, in, N * Cin * side * side);
+  return rc;
+}
+int kvae_dec_up_bwd_flags(const float *x, const float *W, const float *out, const float *g_out, float *g_x, float *w_partials,
+                          float *b_partials, int64_t N, int32_t Cin, int32_t side, int32_t flags, void *) {
+  if (!x || !W || !out || !g_out || !w_partials || !b_partials) return KVAE_ERR_NULL;
+  if (N < 1 || (flags & ~(KVAE_UP_G_PREMASKED | KVAE_UP_MASK_GX))) return KVAE_ERR_ARG;
+  const int rc = kvae_dec_up_bwd(x, W, out, g_out, g_x, w_partials, b_partials, N, Cin, side, nullptr);
+  if (!rc && g_x && (flags & KVAE_UP_MASK_GX)) kv_relu_mask_host(g_x, x, N * Cin * side * side);
+  return rc;
+}
 }  // extern "C"
 #endif

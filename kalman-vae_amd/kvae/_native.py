@@ -17,7 +17,7 @@ LIB_PATH = _HERE / "lib" / "libkvae_lgssm.so"
 KVAE_MAX_DIM = 16
 KVAE_MAX_K = 16
 LSTM_MAX_H, LSTM_MAX_I = 52, 16
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 _STATUS = {1: "KVAE_ERR_DIMS (n, m, p must be in [1,16]; B, T >= 1)", 2: "KVAE_ERR_NULL", 3: "KVAE_ERR_LAUNCH",
            4: "KVAE_ERR_ARG"}
@@ -107,7 +107,8 @@ SYMBOLS = (
     "kvae_bias_shuffle_act_bwd", "kvae_bias_partial_rows", "kvae_colsum", "kvae_colsum2", "kvae_clip_adam",
     "kvae_regime_fwd", "kvae_regime_bwd", "kvae_regime_decode", "kvae_regime_decode_ws_bytes", "kvae_bigru_fwd",
     "kvae_bigru_bwd", "kvae_bce_frames_fwd", "kvae_bce_frames_bwd", "kvae_dec_head_fwd", "kvae_dec_head_bwd",
-    "kvae_dec_head_loss_fwd", "kvae_dec_head_loss_bwd",
+    "kvae_dec_head_loss_fwd", "kvae_dec_head_loss_bwd", "kvae_dec_head_bwd_masked", "kvae_dec_head_loss_bwd_masked",
+    "kvae_dec_up_bwd_flags",
     "kvae_enc_stem_fwd", "kvae_enc_stem_bwd", "kvae_conv_edge_partial_rows", "kvae_enc_mid_fwd", "kvae_enc_mid_bwd",
     "kvae_enc_mid_partial_rows", "kvae_dec_up_fwd", "kvae_dec_up_bwd", "kvae_dec_up_partial_rows",
     "kvae_dec_up_set_workgroups", "kvae_enc_head_fwd", "kvae_enc_head_bwd", "kvae_dec_fc_fwd", "kvae_dec_fc_bwd",
@@ -205,6 +206,10 @@ class LgssmLib:
         d.kvae_dec_head_loss_fwd.restype = C.c_int
         d.kvae_dec_head_loss_bwd.argtypes = [vp] * 9 + [C.c_int64, C.c_int32, C.c_int32, vp]
         d.kvae_dec_head_loss_bwd.restype = C.c_int
+        d.kvae_dec_head_bwd_masked.argtypes = d.kvae_dec_head_bwd.argtypes
+        d.kvae_dec_head_bwd_masked.restype = C.c_int
+        d.kvae_dec_head_loss_bwd_masked.argtypes = d.kvae_dec_head_loss_bwd.argtypes
+        d.kvae_dec_head_loss_bwd_masked.restype = C.c_int
         d.kvae_enc_stem_fwd.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, vp]
         d.kvae_enc_stem_fwd.restype = C.c_int
         d.kvae_enc_stem_bwd.argtypes = [vp] * 6 + [C.c_int64, C.c_int32, C.c_int32, vp]
@@ -218,6 +223,8 @@ class LgssmLib:
         d.kvae_dec_up_fwd.restype = C.c_int
         d.kvae_dec_up_bwd.argtypes = [vp] * 7 + [C.c_int64, C.c_int32, C.c_int32, vp]
         d.kvae_dec_up_bwd.restype = C.c_int
+        d.kvae_dec_up_bwd_flags.argtypes = [vp] * 7 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp]
+        d.kvae_dec_up_bwd_flags.restype = C.c_int
         d.kvae_dec_up_partial_rows.argtypes = [C.c_int64, C.c_int32]
         d.kvae_enc_head_fwd.argtypes = [vp] * 9 + [C.c_int64, C.c_int32, C.c_int32, C.c_float, vp]
         d.kvae_enc_head_fwd.restype = C.c_int

@@ -6,6 +6,8 @@
     two loss terms (csrc/vae_heads.h, vae_loss.h);
   * BiasShuffleAct / conv_block - for any OTHER convolution shape: the library convolution followed by ONE fused
     bias + PixelShuffle + ReLU pass instead of three (csrc/vae_epilogue.h)."""
+import os
+
 import torch
 
 from .. import _native as N
@@ -59,6 +61,26 @@ def conv_block(x, conv, r=1, relu=True):
     return BiasShuffleAct.apply(y, conv.bias, r, relu)
 
 
+UP_G_PREMASKED, UP_MASK_GX = 1, 2   # KVAE_UP_G_PREMASKED, KVAE_UP_MASK_GX
+
+
+def premask_plan(kinds):
+    """Where the decoder's ReLU masks are applied in the backward pass.  kinds: one entry per convolution of the decoder, in
+    order - "up" (DecoderUp, ends in a ReLU), "head" (DecoderHead / DecoderHeadBernoulli) or anything else (conv_block).
+    Returns one (g_premasked, mask_gx) pair per convolution: where a fused "up" feeds a fused "up" or "head", the consumer's
+    backward masks the data gradient it makes (mask_gx) and the producer's backward takes it as it is (g_premasked) - decided
+    here, once, for both sides.  A masked gradient is not the gradient of the activation, so only Decoder._decode, where each
+    activation has exactly one consumer, asks for this.  KVAE_PREMASK=0 keeps every mask in the producer, KVAE_PREMASK=head
+    moves only the one the head applies (A/B runs)."""
+    plan = [[False, False] for _ in kinds]
+    mode = os.environ.get("KVAE_PREMASK", "1")
+    if mode != "0":
+        for i in range(len(kinds) - 1):
+            if kinds[i] == "up" and kinds[i + 1] in (("head",) if mode == "head" else ("up", "head")):
+                plan[i][0] = plan[i + 1][1] = True
+    return [tuple(p) for p in plan]
+
+
 class DecoderHead(torch.autograd.Function):
     """logits[N,1,2s,2s] = pixel_shuffle_2(conv3x3(h[N,32,s,s], W[4,32,3,3]) + b) as ONE direct-convolution kernel
     (csrc/vae_conv_edge.h; reference kvae/vae/vae.py:103-104).  A 4-output-channel implicit GEMM has nothing to
@@ -74,7 +96,8 @@ class DecoderHead(torch.autograd.Function):
                 and conv.bias is not None)
 
     @staticmethod
-    def forward(ctx, h, weight, bias):
+    def forward(ctx, h, weight, bias, mask_gh=False):
+        """mask_gh (premask_plan): the gradient handed back for h is h > 0 ? g_h : 0, for a DecoderUp with g_premasked."""
         h, weight, bias = h.contiguous(), weight.contiguous(), bias.contiguous()
         Nb, Cin, s, _ = h.shape
         logits = torch.empty(Nb, 1, 2 * s, 2 * s, device=h.device, dtype=torch.float32)
@@ -83,6 +106,7 @@ class DecoderHead(torch.autograd.Function):
         lib.check(lib.dll.kvae_dec_head_fwd(N.ptr(h), N.ptr(weight), N.ptr(bias), N.ptr(logits), N.ptr(scratch), Nb, Cin, s,
                                             N.stream_for(h)), "kvae_dec_head_fwd")
         ctx.save_for_backward(h, weight)
+        ctx.mask_gh = bool(mask_gh)
         return logits
 
     @staticmethod
@@ -96,11 +120,11 @@ class DecoderHead(torch.autograd.Function):
         wp = torch.empty(rows, weight.numel(), device=h.device, dtype=torch.float32)
         bp = torch.empty(rows, 4, device=h.device, dtype=torch.float32)
         scratch = torch.empty(DecoderHead.SCRATCH, device=h.device, dtype=torch.float32)
-        lib.check(lib.dll.kvae_dec_head_bwd(N.ptr(h), N.ptr(weight), N.ptr(g), N.ptr(g_h) if g_h is not None else None,
-                                            N.ptr(wp), N.ptr(bp), N.ptr(scratch), Nb, Cin, s, N.stream_for(h)),
-                  "kvae_dec_head_bwd")
+        bwd = lib.dll.kvae_dec_head_bwd_masked if ctx.mask_gh else lib.dll.kvae_dec_head_bwd
+        lib.check(bwd(N.ptr(h), N.ptr(weight), N.ptr(g), N.ptr(g_h) if g_h is not None else None,
+                      N.ptr(wp), N.ptr(bp), N.ptr(scratch), Nb, Cin, s, N.stream_for(h)), "kvae_dec_head_bwd")
         gw, gb = colsum_pair(wp, bp)
-        return g_h, gw.view_as(weight), gb
+        return g_h, gw.view_as(weight), gb, None
 
 
 class DecoderHeadBernoulli(torch.autograd.Function):
@@ -108,12 +132,14 @@ class DecoderHeadBernoulli(torch.autograd.Function):
     x_recon = sigmoid(logits) (None unless `with_recon`) and frame_ll[N] = -sum_pixels BCEWithLogits(logits, x) (reference
     kvae/vae/losses.py:85-87) from the one forward kernel.  The backward of frame_ll alone - the training step - is one
     persistent kernel that forms the gradient of the logits in registers; a gradient handed to `logits` as well takes
-    kvae_bce_frames_bwd + kvae_dec_head_bwd.  x takes no gradient."""
+    kvae_bce_frames_bwd + kvae_dec_head_bwd.  x takes no gradient.  Optional arguments: with_recon (default True), then
+    mask_gh (default False) as in DecoderHead."""
 
     @staticmethod
-    def forward(ctx, h, weight, bias, x, *with_recon):
-        ctx.n_opt = len(with_recon)
-        with_recon = with_recon[0] if with_recon else True
+    def forward(ctx, h, weight, bias, x, *opt):
+        ctx.n_opt = len(opt)
+        with_recon = opt[0] if opt else True
+        ctx.mask_gh = bool(opt[1]) if len(opt) > 1 else False
         h, weight, bias, x = h.contiguous(), weight.contiguous(), bias.contiguous(), x.contiguous()
         Nb, Cin, s, _ = h.shape
         logits = torch.empty(Nb, 1, 2 * s, 2 * s, device=h.device, dtype=torch.float32)
@@ -144,9 +170,9 @@ class DecoderHeadBernoulli(torch.autograd.Function):
         scratch = torch.empty(DecoderHead.SCRATCH, device=h.device, dtype=torch.float32)
         if g_logits is None:
             g_ll = g_ll.contiguous()
-            lib.check(lib.dll.kvae_dec_head_loss_bwd(N.ptr(h), N.ptr(weight), N.ptr(logits), N.ptr(x), N.ptr(g_ll), _optr(g_h),
-                                                     N.ptr(wp), N.ptr(bp), N.ptr(scratch), Nb, Cin, s, N.stream_for(h)),
-                      "kvae_dec_head_loss_bwd")
+            bwd = lib.dll.kvae_dec_head_loss_bwd_masked if ctx.mask_gh else lib.dll.kvae_dec_head_loss_bwd
+            lib.check(bwd(N.ptr(h), N.ptr(weight), N.ptr(logits), N.ptr(x), N.ptr(g_ll), _optr(g_h),
+                          N.ptr(wp), N.ptr(bp), N.ptr(scratch), Nb, Cin, s, N.stream_for(h)), "kvae_dec_head_loss_bwd")
         else:
             g = g_logits.contiguous()
             if g_ll is not None:
@@ -154,8 +180,9 @@ class DecoderHeadBernoulli(torch.autograd.Function):
                 lib.check(lib.dll.kvae_bce_frames_bwd(N.ptr(logits), N.ptr(x), N.ptr(g_ll.contiguous()), N.ptr(gl), Nb,
                                                       logits.numel() // Nb, N.stream_for(h)), "kvae_bce_frames_bwd")
                 g = gl + g
-            lib.check(lib.dll.kvae_dec_head_bwd(N.ptr(h), N.ptr(weight), N.ptr(g), _optr(g_h), N.ptr(wp), N.ptr(bp),
-                                                N.ptr(scratch), Nb, Cin, s, N.stream_for(h)), "kvae_dec_head_bwd")
+            bwd = lib.dll.kvae_dec_head_bwd_masked if ctx.mask_gh else lib.dll.kvae_dec_head_bwd
+            lib.check(bwd(N.ptr(h), N.ptr(weight), N.ptr(g), _optr(g_h), N.ptr(wp), N.ptr(bp),
+                          N.ptr(scratch), Nb, Cin, s, N.stream_for(h)), "kvae_dec_head_bwd")
         gw, gb = colsum_pair(wp, bp)
         return (g_h, gw.view_as(weight), gb, None) + (None,) * ctx.n_opt
 
@@ -247,7 +274,9 @@ class EncoderMid(torch.autograd.Function):
 class DecoderUp(torch.autograd.Function):
     """out[N,32,2s,2s] = relu(pixel_shuffle_2(conv3x3(x[N,32,s,s], W[128,32,3,3]) + b)), s in {8, 4}: implicit GEMMs on the
     exact-f32 matrix cores with the weights stationary in registers (csrc/vae_conv_up.h; reference kvae/vae/vae.py:92-101).
-    Bias, PixelShuffle and ReLU are part of the kernels in both directions."""
+    Bias, PixelShuffle and ReLU are part of the kernels in both directions.  g_premasked / mask_gx (premask_plan, from
+    Decoder._decode only): the gradient of `out` arrives with this block's ReLU mask already applied by the layer above (the
+    gradient kernels then never read `out`) / the gradient handed back for x carries the mask of the block below, x > 0."""
 
     CHUNK = 16384   # frames per launch (32-bit byte offsets inside a launch)
 
@@ -258,7 +287,8 @@ class DecoderUp(torch.autograd.Function):
                 and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is not None)
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
+    def forward(ctx, x, weight, bias, g_premasked=False, mask_gx=False):
+        ctx.flags = (UP_G_PREMASKED if g_premasked else 0) | (UP_MASK_GX if mask_gx else 0)
         x, weight, bias = x.contiguous(), weight.contiguous(), bias.contiguous()
         Nb, Cin, s, _ = x.shape
         out = torch.empty(Nb, 32, 2 * s, 2 * s, device=x.device, dtype=torch.float32)
@@ -281,12 +311,16 @@ class DecoderUp(torch.autograd.Function):
             rows = lib.dll.kvae_dec_up_partial_rows(b - a, s)
             wp = torch.empty(rows, weight.numel(), device=x.device, dtype=torch.float32)
             bp = torch.empty(rows, 128, device=x.device, dtype=torch.float32)
-            lib.check(N.timed(f"dec_up_bwd_s{s}", x, lambda: lib.dll.kvae_dec_up_bwd(
-                N.ptr(x[a:b]), N.ptr(weight), N.ptr(out[a:b]), N.ptr(g[a:b]), N.ptr(g_x[a:b]) if g_x is not None else None, N.ptr(wp),
-                N.ptr(bp), b - a, Cin, s, N.stream_for(x))), "kvae_dec_up_bwd")
+            args = (N.ptr(x[a:b]), N.ptr(weight), N.ptr(out[a:b]), N.ptr(g[a:b]), N.ptr(g_x[a:b]) if g_x is not None else None,
+                    N.ptr(wp), N.ptr(bp), b - a, Cin, s)
+            if ctx.flags:
+                lib.check(N.timed(f"dec_up_bwd_s{s}", x, lambda: lib.dll.kvae_dec_up_bwd_flags(*args, ctx.flags, N.stream_for(x))),
+                          "kvae_dec_up_bwd_flags")
+            else:
+                lib.check(N.timed(f"dec_up_bwd_s{s}", x, lambda: lib.dll.kvae_dec_up_bwd(*args, N.stream_for(x))), "kvae_dec_up_bwd")
             cw, cb = colsum_pair(wp, bp)
             gw, gb = _acc(gw, cw), _acc(gb, cb)
-        return g_x, gw.view_as(weight), gb
+        return g_x, gw.view_as(weight), gb, None, None
 
 
 def _optr(t):

@@ -12,7 +12,8 @@ import torch.nn as nn
 
 from kvae import _native
 from kvae.utils.config import KVAEConfig
-from kvae.vae.fused import DecoderFc, DecoderHead, DecoderHeadBernoulli, DecoderUp, EncoderHead, EncoderMid, EncoderStem, conv_block
+from kvae.vae.fused import (DecoderFc, DecoderHead, DecoderHeadBernoulli, DecoderUp, EncoderHead, EncoderMid, EncoderStem, conv_block,
+                            premask_plan)
 
 
 def _conv_out(size, k, s, p):
@@ -95,17 +96,26 @@ class Decoder(nn.Module):
         if not fused:
             return self.deconv_layers(h), None, None
         layers = list(self.deconv_layers)   # conv -> PixelShuffle(2) [-> ReLU] triples, fused per conv
-        for i, layer in enumerate(layers):
-            if isinstance(layer, nn.Conv2d):
-                relu = i + 2 < len(layers) and isinstance(layers[i + 2], nn.ReLU)
-                if not relu and x is not None and i + 2 == len(layers) and self.head_loss_supported(h, layer, x):
-                    return DecoderHeadBernoulli.apply(h, layer.weight, layer.bias, x, with_recon)
-                if not relu and DecoderHead.supported(h, layer):     # 4 output channels: direct kernel
-                    h = DecoderHead.apply(h, layer.weight, layer.bias)
-                elif relu and DecoderUp.supported(h, layer):         # 32 -> 128 + shuffle + ReLU on the f32 matrix cores
-                    h = DecoderUp.apply(h, layer.weight, layer.bias)
-                else:
-                    h = conv_block(h, layer, r=2, relu=relu)
+        convs = [(i, layer, i + 2 < len(layers) and isinstance(layers[i + 2], nn.ReLU))
+                 for i, layer in enumerate(layers) if isinstance(layer, nn.Conv2d)]
+        # which kernel each convolution takes, known from the shapes before any of them runs: every block doubles the side and
+        # leaves out_channels / 4 channels.  premask_plan then says, for both sides of each pair of fused neighbours at once,
+        # where the ReLU mask of the backward pass is applied (each h below has exactly one consumer).
+        kinds, shape = [], h
+        for _, layer, relu in convs:
+            kinds.append("up" if relu and DecoderUp.supported(shape, layer) else
+                         "head" if not relu and DecoderHead.supported(shape, layer) else "block")
+            shape = torch.empty(shape.shape[0], layer.out_channels // 4, 2 * shape.shape[2], 2 * shape.shape[3], device="meta")
+        plan = premask_plan(kinds)
+        for (i, layer, relu), kind, (g_premasked, mask_gx) in zip(convs, kinds, plan):
+            if kind == "head" and x is not None and i + 2 == len(layers) and self.head_loss_supported(h, layer, x):
+                return DecoderHeadBernoulli.apply(h, layer.weight, layer.bias, x, with_recon, mask_gx)
+            if kind == "head":                                       # 4 output channels: direct kernel
+                h = DecoderHead.apply(h, layer.weight, layer.bias, mask_gx)
+            elif kind == "up":                                       # 32 -> 128 + shuffle + ReLU on the f32 matrix cores
+                h = DecoderUp.apply(h, layer.weight, layer.bias, g_premasked, mask_gx)
+            else:
+                h = conv_block(h, layer, r=2, relu=relu)
         return h, None, None
 
     def forward(self, a: torch.Tensor) -> torch.Tensor:

@@ -6,13 +6,17 @@
 #include "vae_conv_up_wino.h"
 int main() {
   const int64_t N = 12800;
-  float *W, *o, *g, *gx;
-  hipMalloc(&W, 36864 * 4); hipMalloc(&o, N * 8192 * 4); hipMalloc(&g, N * 8192 * 4); hipMalloc(&gx, N * 2048 * 4);
-  hipMemset(W, 0, 36864 * 4); hipMemset(o, 0, N * 8192 * 4); hipMemset(g, 0, N * 8192 * 4);
+  float *W, *x, *o, *g, *gx;
+  hipMalloc(&W, 36864 * 4); hipMalloc(&x, N * 2048 * 4); hipMalloc(&o, N * 8192 * 4); hipMalloc(&g, N * 8192 * 4); hipMalloc(&gx, N * 2048 * 4);
+  hipMemset(W, 0, 36864 * 4); hipMemset(x, 0, N * 2048 * 4); hipMemset(o, 0, N * 8192 * 4); hipMemset(g, 0, N * 8192 * 4);
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-  for (int rep = 0; rep < 3; ++rep) kvae::k_dec_up_bwd_data_wino<8><<<256, 512>>>(W, o, g, gx, N);
+  // -DSTAMP_FORM="8, true, true": the pre-masked kernel that also masks g_x (default: the kernel that reads `out`)
+#ifndef STAMP_FORM
+#define STAMP_FORM 8
+#endif
+  for (int rep = 0; rep < 3; ++rep) kvae::k_dec_up_bwd_data_wino<STAMP_FORM><<<256, 512>>>(W, x, o, g, gx, N);
   hipEventRecord(e0);
-  kvae::k_dec_up_bwd_data_wino<8><<<256, 512>>>(W, o, g, gx, N);
+  kvae::k_dec_up_bwd_data_wino<STAMP_FORM><<<256, 512>>>(W, x, o, g, gx, N);
   hipEventRecord(e1);
   hipDeviceSynchronize();
   float ms; hipEventElapsedTime(&ms, e0, e1);

@@ -10,9 +10,13 @@ int main() {
   hipMalloc(&x, N * 2048 * 4); hipMalloc(&wp, 256 * 36864 * 4); hipMalloc(&bp, 256 * 128 * 4); hipMalloc(&o, N * 8192 * 4); hipMalloc(&g, N * 8192 * 4); 
   hipMemset(x, 0, N * 2048 * 4); hipMemset(o, 0, N * 8192 * 4); hipMemset(g, 0, N * 8192 * 4);
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-  for (int rep = 0; rep < 3; ++rep) kvae::k_dec_up_wrw_wino<8><<<256, 512>>>(x, o, g, wp, bp, N);
+  // -DSTAMP_FORM="8, true": the pre-masked kernel (default: the kernel that reads `out`)
+#ifndef STAMP_FORM
+#define STAMP_FORM 8
+#endif
+  for (int rep = 0; rep < 3; ++rep) kvae::k_dec_up_wrw_wino<STAMP_FORM><<<256, 512>>>(x, o, g, wp, bp, N);
   hipEventRecord(e0);
-  kvae::k_dec_up_wrw_wino<8><<<256, 512>>>(x, o, g, wp, bp, N);
+  kvae::k_dec_up_wrw_wino<STAMP_FORM><<<256, 512>>>(x, o, g, wp, bp, N);
   hipEventRecord(e1);
   hipDeviceSynchronize();
   float ms; hipEventElapsedTime(&ms, e0, e1);
