@@ -17,6 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lds_decl.h"
+
 namespace kvae {
 namespace mixw {
 
@@ -140,7 +142,7 @@ __global__ __launch_bounds__(256) void k_mix_bwd_wave(const float *__restrict__ 
 // are folded in lane order through LDS (a fixed order, whatever the launch)
 __global__ __launch_bounds__(256) void k_mix_bwd_fold(const float *__restrict__ partials, float *__restrict__ g_base, int nslab,
                                                       int KE) {
-  __shared__ float red[8][33];
+  KV_LDS(float, red, [8][33]);
   const int el = threadIdx.x & 31, sl = threadIdx.x >> 5;
   const int i = blockIdx.x * 32 + el;
   float s = 0.f;
@@ -160,6 +162,58 @@ __global__ __launch_bounds__(256) void k_mix_bwd_fold(const float *__restrict__ 
   for (int j = 1; j < 8; ++j) t += red[j][el];
   g_base[i] = t;
 }
+
+// ---- launch geometry (host side).  The product passes FWD_MAX_SLABS / MAX_SLABS and what its partials buffer holds; the
+// emulated workgroups of the test tier pass smaller caps, so that slabs of more than 16 rows run at a few hundred rows.
+constexpr int FWD_MAX_SLABS = 4096;   // about four wavefronts per SIMD
+
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// (E >= 128: with a record of 40 floats - n = 4 - a wavefront per row leaves 54 lanes idle and the element-wise kernels win)
+inline bool mix_wave_ok(const float *a, const float *b, const float *c, int K, int E) {
+  return (E & 3) == 0 && E >= 128 && E <= 768 && K <= 8 && aligned16(b) && aligned16(c) && a != nullptr;
+}
+inline int64_t mix_wave_slabs(int64_t rows, int64_t cap) {   // at least 8 rows per wavefront
+  const int64_t want = (rows + 7) / 8;
+  return want < 1 ? 1 : (want > cap ? cap : want);
+}
+struct MixGeom {
+  int64_t per;      // rows per slab (one wavefront)
+  int nslab;        // slabs that hold a row
+  unsigned blocks;  // workgroups of four wavefronts
+};
+inline MixGeom mix_fwd_geometry(int64_t rows, int64_t max_slabs) {
+  const int64_t slabs = mix_wave_slabs(rows, max_slabs);
+  MixGeom g;
+  g.per = (rows + slabs - 1) / slabs;
+  g.nslab = (int)((rows + g.per - 1) / g.per);
+  g.blocks = (unsigned)((slabs + 3) / 4);
+  return g;
+}
+// one register-resident base gradient per wavefront, one K x E partial per slab: partials_cap is what the caller's buffer holds
+inline MixGeom mix_bwd_geometry(int64_t rows, int64_t max_slabs, int64_t partials_cap) {
+  int64_t slabs = mix_wave_slabs(rows, max_slabs);
+  slabs = slabs < partials_cap ? slabs : partials_cap;
+  MixGeom g;
+  g.per = (rows + slabs - 1) / slabs;
+  g.nslab = (int)((rows + g.per - 1) / g.per);
+  g.blocks = (unsigned)((g.nslab + 3) / 4);
+  return g;
+}
+inline unsigned mix_fold_blocks(int K, int E) { return (unsigned)((K * E + 31) / 32); }
+// L(KMAX, EJ) with the instance that holds K base records of E floats in registers
+#define KVAE_MIXW_DISPATCH(L)                        \
+  do {                                               \
+    const int ej = (E + 255) / 256;                  \
+    if (K <= 4) {                                    \
+      if (ej == 1) L(4, 1);                          \
+      else if (ej == 2) L(4, 2);                     \
+      else L(4, 3);                                  \
+    } else {                                         \
+      if (ej == 1) L(8, 1);                          \
+      else if (ej == 2) L(8, 2);                     \
+      else L(8, 3);                                  \
+    }                                                \
+  } while (0)
 
 }  // namespace mixw
 }  // namespace kvae

@@ -17,10 +17,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lds_decl.h"
+
 namespace kvae {
 
 constexpr int WG_MAX_ROW_TILES = 16;    // R <= 256 gradient rows
 constexpr int WG_MAX_CHUNKS = 256;      // split-K partials (one workgroup per CU)
+constexpr int WG_FILL = 512;            // workgroups the split aims at over all problems and column groups (two per CU)
 
 struct WgradProblem {
   const float *d;      // [N, R] rows of d_pre / g_logit, row stride d_stride
@@ -71,8 +74,8 @@ __global__ __launch_bounds__(256) void k_rnn_wgrad_partial(const WgradBatch batc
   typedef float f4 __attribute__((ext_vector_type(4)));
   constexpr int RP = WgLds<RT>::RP, XP = WgLds<RT>::XP, QB = WgLds<RT>::QB;
   constexpr int XN = QB / 4;
-  __shared__ float sD[QB * RP];
-  __shared__ float sX[QB * XP];
+  KV_LDS(float, sD, [QB * RP]);
+  KV_LDS(float, sX, [QB * XP]);
   const WgradProblem &P = batch.p[blockIdx.z];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int R = P.R, T = P.T;
@@ -192,7 +195,7 @@ __global__ __launch_bounds__(256) void k_rnn_wgrad_partial(const WgradBatch batc
 // folded in lane order through LDS - a fixed order, whatever the launch
 __global__ __launch_bounds__(256) void k_rnn_wgrad_final(const WgradBatch batch, const float *__restrict__ partials,
                                                          int64_t partial_stride, int chunks) {
-  __shared__ float red[8][33];
+  KV_LDS(float, red, [8][33]);
   const WgradProblem &P = batch.p[blockIdx.y];
   const int C = P.H + P.I + (P.bias ? 1 : 0), Cpad = (C + 15) / 16 * 16;
   const int el = threadIdx.x & 31, cl = threadIdx.x >> 5;
@@ -223,5 +226,70 @@ __global__ __launch_bounds__(256) void k_rnn_wgrad_final(const WgradBatch batch,
     P.g_b[row] = t;
   }
 }
+
+// ---- launch geometry (host side; P is WgradProblem or the C ABI's kvae_wgrad_problem, which has the same fields) ----------
+// The product passes WG_MAX_CHUNKS and WG_FILL; the emulated workgroups of the test tier pass smaller caps, so that chunks of
+// several stages run at a few hundred rows.
+template <class P> inline int wg_cols(const P &p) { return p.H + p.I + (p.bias ? 1 : 0); }
+template <class P> inline int wg_cpad(const P &p) { return (wg_cols(p) + 15) / 16 * 16; }
+// 0, 1 (a null operand) or 2 (a size outside the kernels' limits: R <= 256 rows, C <= 256 columns, whole sequences)
+template <class P> inline int wg_check(const P &p) {
+  const int C = wg_cols(p);
+  if (!p.d || (p.H > 0 && !p.h) || (p.I > 0 && !p.x)) return 1;
+  if (p.N < 1 || p.R < 1 || p.R > 16 * WG_MAX_ROW_TILES || p.H < 0 || p.I < 0 || C < 1 || C > 256 || p.T < 1 || p.shift < -1 ||
+      p.shift > 1 || p.N % p.T != 0)
+    return 2;
+  return 0;
+}
+// partials[problem][chunk][R][Cpad] with every problem at the stride of the largest R * Cpad of the batch
+template <class P> inline int64_t wg_ws_floats(const P *probs, int n, int max_chunks) {
+  int64_t per = 0;
+  for (int i = 0; i < n; ++i) {
+    const int64_t e = (int64_t)probs[i].R * wg_cpad(probs[i]);
+    per = e > per ? e : per;
+  }
+  return per * max_chunks * n;
+}
+struct WgGeom {
+  int chunks, groups, rt;      // grid (chunks, groups, n) of k_rnn_wgrad_partial<rt>
+  int64_t stride;              // floats of partials per problem
+  int64_t final_blocks;        // grid (final_blocks, n) of k_rnn_wgrad_final
+};
+inline int wg_rt_instance(int row_tiles) {
+  return row_tiles <= 1 ? 1 : (row_tiles <= 4 ? 4 : (row_tiles <= 10 ? 10 : (row_tiles <= 13 ? 13 : 16)));
+}
+// split-K: about `fill` workgroups over all problems and column groups, at least one 32-row stage each, at most max_chunks
+template <class P> inline WgGeom wg_geometry(const P *probs, int n, int max_chunks, int fill) {
+  int max_rt = 0, max_groups = 0;
+  int64_t max_n = 0, max_elems = 0, per = 0;
+  for (int i = 0; i < n; ++i) {
+    const P &p = probs[i];
+    const int rt = (p.R + 15) / 16, ct = wg_cpad(p) / 16;
+    max_rt = rt > max_rt ? rt : max_rt;
+    max_groups = (ct + 3) / 4 > max_groups ? (ct + 3) / 4 : max_groups;
+    max_n = p.N > max_n ? p.N : max_n;
+    const int64_t e = (int64_t)p.R * wg_cols(p), ep = (int64_t)p.R * wg_cpad(p);
+    max_elems = e > max_elems ? e : max_elems;
+    per = ep > per ? ep : per;
+  }
+  int chunks = (int)((max_n + 31) / 32);
+  const int share = fill / (n * max_groups);
+  chunks = chunks > share ? share : chunks;
+  chunks = chunks > max_chunks ? max_chunks : (chunks < 1 ? 1 : chunks);
+  WgGeom g;
+  g.chunks = chunks, g.groups = max_groups, g.rt = wg_rt_instance(max_rt);
+  g.stride = per * max_chunks;
+  g.final_blocks = (max_elems + 31) / 32;
+  return g;
+}
+// L(RT) with the instance wg_geometry chose
+#define KVAE_WGRAD_DISPATCH(rt, L) \
+  do {                             \
+    if ((rt) == 1) L(1);           \
+    else if ((rt) == 4) L(4);      \
+    else if ((rt) == 10) L(10);    \
+    else if ((rt) == 13) L(13);    \
+    else L(16);                    \
+  } while (0)
 
 }  // namespace kvae

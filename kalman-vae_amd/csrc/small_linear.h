@@ -10,11 +10,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lds_decl.h"
+
 namespace kvae {
 
 constexpr int SL_MAX_W = 12288;   // floats of W in LDS (48 KiB; the staged rows of x take the rest of 60 KiB)
 constexpr int SL_MAX_F = 128;
 constexpr int SL_SOFTMAX_MAX_O = 16;
+constexpr int SL_MIN_BLOCKS = 256;   // the forward halves its rows per block (down to 16) while that leaves fewer blocks than this
 constexpr int SL_BATCH = 10;      // row elements fetched back to back before their FMAs (a load per FMA waits out its latency)
 
 // W [O,F] into LDS with rows padded to F + 1 floats: threads of one row of x that work on different outputs read
@@ -53,18 +56,24 @@ __device__ __forceinline__ void sl_stage_rows(const float *__restrict__ x, int64
     }
   }
 }
-__host__ __device__ inline int sl_rows_per_block(int F, int O, int64_t N) {   // what fits 60 KiB of LDS next to W, at most 64;
-  const int room = (15360 - O * (F + 1)) / (F + 1);                             // fewer when that leaves CUs without a block
+// ---- launch geometry (host side): what fits 60 KiB of LDS next to W, at most 64 rows per block; fewer while that leaves CUs
+// without a block (min_blocks: SL_MIN_BLOCKS in the product, so 32 rows from 8192 and 64 rows from 16384 rows on)
+inline int sl_rows_per_block(int F, int O, int64_t N, int min_blocks) {
+  const int room = (15360 - O * (F + 1)) / (F + 1);
   int rows = room >= 64 ? 64 : (room >= 32 ? 32 : 16);
-  while (rows > 16 && N / rows < 256) rows >>= 1;
+  while (rows > 16 && N / rows < min_blocks) rows >>= 1;
   return rows;
 }
+inline size_t sl_fwd_lds_floats(int F, int O, int rows) { return (size_t)O * (F + 1) + (size_t)rows * (F + 1); }   // W | rows of x
+inline int64_t sl_fwd_blocks(int64_t N, int rows) { return (N + rows - 1) / rows; }
+inline size_t sl_bwd_lds_floats(int F, int O) { return (size_t)O * (F + 1); }                                      // W
+inline int64_t sl_bwd_blocks(int64_t N, int F) { return (N * ((F + 3) / 4) + 255) / 256; }                         // thread per (row, 4 inputs)
 
 // thread per (row, 4 outputs), `rows` rows per block
 __global__ __launch_bounds__(256) void k_linear_fwd(const float *__restrict__ x, int64_t xs, int64_t N, int F,
                                                     const float *__restrict__ W, const float *__restrict__ b, int O,
                                                     float *__restrict__ y, int rows) {
-  extern __shared__ float sh_w[];
+  KV_LDS_DYN(float, sh_w);
   float *sh_x = sh_w + O * (F + 1);
   const int64_t n0 = (int64_t)blockIdx.x * rows;
   sl_stage_w_nosync(W, sh_w, O, F);
@@ -96,7 +105,7 @@ __global__ __launch_bounds__(256) void k_linear_fwd(const float *__restrict__ x,
 __global__ __launch_bounds__(256) void k_linear_softmax_fwd(const float *__restrict__ x, int64_t xs, int64_t N, int F,
                                                             const float *__restrict__ W, const float *__restrict__ b, int O,
                                                             float *__restrict__ y, int rows) {
-  extern __shared__ float sh_w[];
+  KV_LDS_DYN(float, sh_w);
   float *sh_x = sh_w + O * (F + 1);
   const int64_t n0 = (int64_t)blockIdx.x * rows;
   sl_stage_w_nosync(W, sh_w, O, F);
@@ -137,7 +146,7 @@ __global__ __launch_bounds__(256) void k_linear_softmax_fwd(const float *__restr
 __global__ __launch_bounds__(256) void k_linear_bwd_input(const float *__restrict__ g, int64_t N, int F,
                                                           const float *__restrict__ W, int O, float *__restrict__ dx,
                                                           int64_t dxs) {
-  extern __shared__ float sh_w[];
+  KV_LDS_DYN(float, sh_w);
   sl_stage_w(W, sh_w, O, F);
   const int FG = (F + 3) / 4;
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -170,7 +179,7 @@ __global__ __launch_bounds__(256) void k_linear_softmax_bwd_input(const float *_
                                                                   int64_t N, int F, const float *__restrict__ W, int O,
                                                                   float *__restrict__ gl_out, float *__restrict__ dx,
                                                                   int64_t dxs) {
-  extern __shared__ float sh_w[];
+  KV_LDS_DYN(float, sh_w);
   sl_stage_w(W, sh_w, O, F);
   const int FG = (F + 3) / 4;
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;

@@ -138,6 +138,14 @@ int kvae_wemu_regime_fwd(const float *, const float *, const float *, const floa
                          const float *, int);
 int kvae_wemu_regime_bwd(const float *, const float *, const float *, const float *, const float *, const float *, const float *,
                          const float *, float *, float *, int, int, int, float, const float *);
+// wave_emu_reduce.cpp: the weight-gradient reduction, the streaming mixture kernels and the linear heads on emulated workgroups
+int64_t kvae_wemu_wgrad_ws_floats(const kvae_wgrad_problem *, int32_t);
+int kvae_wemu_wgrad(const kvae_wgrad_problem *, int32_t, float *);
+int kvae_wemu_mix_fwd(const float *, const float *, float *, int64_t, int32_t, int32_t);
+int kvae_wemu_mix_bwd(const float *, const float *, const float *, float *, float *, float *, int64_t, int32_t, int32_t, int32_t,
+                      int64_t);
+void kvae_wemu_linear_fwd(const float *, int64_t, int64_t, int, const float *, const float *, int, int, float *);
+void kvae_wemu_linear_bwd_input(const float *, const float *, int64_t, int, const float *, int, float *, float *, int64_t);
 }
 static int g_wave_emu = 0;
 static bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -246,6 +254,7 @@ int kvae_lgssm_elbo(const kvae_lgssm_problem *prob, const float *mus_smooth, con
 int kvae_mix_fwd(const float *alpha, const float *base, float *out, int64_t rows, int32_t K, int32_t E, void *) {
   if (!alpha || !base || !out) return KVAE_ERR_NULL;
   if (rows < 1 || K < 1 || K > KVAE_MAX_K || E < 1) return KVAE_ERR_ARG;
+  if (g_wave_emu && kvae_wemu_mix_fwd(alpha, base, out, rows, K, E)) return KVAE_OK;   // the gate of kvae_lgssm.hip: mix_wave.h
   for (int64_t i = 0; i < rows * E; ++i) mix_fwd_elem(alpha, base, out, i, K, E);
   return KVAE_OK;
 }
@@ -254,6 +263,9 @@ int kvae_mix_bwd(const float *alpha, const float *base, const float *g_out, floa
                  int64_t rows, int32_t K, int32_t E, int32_t accumulate_alpha, void *) {
   if (!alpha || !base || !g_out || !g_alpha || !g_base || !partials) return KVAE_ERR_NULL;
   if (rows < 1 || K < 1 || K > KVAE_MAX_K || E < 1) return KVAE_ERR_ARG;
+  if (g_wave_emu && kvae_wemu_mix_bwd(alpha, base, g_out, g_alpha, g_base, partials, rows, K, E, accumulate_alpha,
+                                      kvae_mix_bwd_partials(rows)))
+    return KVAE_OK;   // the gate of kvae_lgssm.hip: k_mix_bwd_wave + k_mix_bwd_fold
   for (int64_t i = 0; i < rows * K; ++i) mix_bwd_alpha_elem(base, g_out, g_alpha, i, K, E, accumulate_alpha);
   const int64_t nblk = kvae_mix_bwd_partials(rows);
   for (int64_t blk = 0; blk < nblk; ++blk)
@@ -893,10 +905,13 @@ int kvae_lgssm_emission_means(const kvae_lgssm_problem *prob, const float *ms, c
 }
 
 // ---- alpha-network parameter gradients and linear heads: plain-loop twins of rnn_wgrad.h / small_linear.h --------------
-int64_t kvae_rnn_wgrad_ws_floats(const kvae_wgrad_problem *, int32_t) { return 1; }
+int64_t kvae_rnn_wgrad_ws_floats(const kvae_wgrad_problem *probs, int32_t n) {
+  return g_wave_emu ? kvae_wemu_wgrad_ws_floats(probs, n) : 1;   // the kernels' split-K partials; the twin below needs none
+}
 int kvae_rnn_wgrad(const kvae_wgrad_problem *probs, int32_t n, float *ws, void *) {
   if (!probs || !ws) return KVAE_ERR_NULL;
   if (n < 1 || n > 4) return KVAE_ERR_ARG;
+  if (g_wave_emu) return kvae_wemu_wgrad(probs, n, ws);   // k_rnn_wgrad_partial<RT> + k_rnn_wgrad_final
   for (int i = 0; i < n; ++i) {
     const kvae_wgrad_problem &p = probs[i];
     const int C = p.H + p.I + (p.bias ? 1 : 0);
@@ -930,6 +945,10 @@ int kvae_linear_fwd(const float *x, int64_t xs, int64_t N, int32_t F, const floa
                     float *y, void *) {
   if (!x || !W || !y) return KVAE_ERR_NULL;
   if (N < 1 || F < 1 || F > 128 || O < 1 || (int64_t)O * F > 12288 || (softmax && O > 16)) return KVAE_ERR_DIMS;
+  if (g_wave_emu) {   // k_linear_fwd / k_linear_softmax_fwd
+    kvae_wemu_linear_fwd(x, xs, N, F, W, b, O, softmax, y);
+    return KVAE_OK;
+  }
   for (int64_t n = 0; n < N; ++n) {
     float mx = -INFINITY;
     for (int o = 0; o < O; ++o) {
@@ -950,6 +969,10 @@ int kvae_linear_bwd_input(const float *g, const float *y, int64_t N, int32_t F, 
                           int64_t dxs, void *) {
   if (!g || !W || !dx || (y && !g_logit)) return KVAE_ERR_NULL;
   if (N < 1 || F < 1 || F > 128 || O < 1 || (int64_t)O * F > 12288 || (y && O > 16)) return KVAE_ERR_DIMS;
+  if (g_wave_emu) {   // k_linear_bwd_input / k_linear_softmax_bwd_input
+    kvae_wemu_linear_bwd_input(g, y, N, F, W, O, g_logit, dx, dxs);
+    return KVAE_OK;
+  }
   for (int64_t n = 0; n < N; ++n) {
     float gl[256], dot = 0.f;
     for (int o = 0; o < O && y; ++o) dot = std::fma(g[n * O + o], y[n * O + o], dot);

@@ -27,6 +27,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <functional>
@@ -48,16 +49,28 @@ class Barrier {
  public:
   Barrier(unsigned n, const char *scope) : n_(n), scope_(scope) {}
   void wait() {
-    std::unique_lock<std::mutex> lk(m_);
-    const unsigned gen = gen_;
-    if (++count_ == n_) {
-      count_ = 0, ++gen_;
+    // Arrivals are counted on an atomic and a waiter first polls the generation, yielding its core between looks: with 256 lane
+    // threads on a few cores a condition variable alone costs one mutex hand-over and one wake-up per lane and rendezvous (half
+    // a millisecond per block barrier).  A waiter that has polled kSpins times sleeps on the condition variable, under the
+    // deadline; the generation changes under the mutex, so that sleeper cannot miss it.
+    const unsigned gen = gen_.load(std::memory_order_acquire);
+    if (count_.fetch_add(1, std::memory_order_acq_rel) + 1 == n_) {
+      count_.store(0, std::memory_order_relaxed);   // (before the generation: whoever sees the new generation sees the reset)
+      {
+        std::lock_guard<std::mutex> lk(m_);
+        gen_.store(gen + 1, std::memory_order_release);
+      }
       cv_.notify_all();
       return;
     }
+    for (int i = 0; i < kSpins; ++i) {
+      if (gen_.load(std::memory_order_acquire) != gen) return;
+      std::this_thread::yield();
+    }
+    std::unique_lock<std::mutex> lk(m_);
     // (a deadline on the system clock: the wait is then pthread_cond_timedwait, which thread sanitizers know releases the mutex;
     // wait_for is pthread_cond_clockwait, which gcc 11's does not intercept - it reports the barrier itself as a double lock)
-    if (!cv_.wait_until(lk, std::chrono::system_clock::now() + std::chrono::seconds(kDeadlineSeconds), [&] { return gen_ != gen; })) {
+    if (!cv_.wait_until(lk, std::chrono::system_clock::now() + std::chrono::seconds(kDeadlineSeconds), [&] { return gen_.load(std::memory_order_acquire) != gen; })) {
       fprintf(stderr, "wave_emu: %s-scope rendezvous not reached by all %u lanes within %d s (lane %d, block %u waiting)\n",
               scope_, n_, kDeadlineSeconds, lane_id(), t_bid.x);
       fflush(stderr);
@@ -70,7 +83,8 @@ class Barrier {
   std::condition_variable cv_;
   const unsigned n_;
   const char *scope_;
-  unsigned count_ = 0, gen_ = 0;
+  static constexpr int kSpins = 4096;
+  std::atomic<unsigned> count_{0}, gen_{0};
 };
 
 struct Wave {
@@ -213,30 +227,55 @@ inline void launch(unsigned blocks, const std::function<void()> &body) {
   }
 }
 
-// launch_wg: a grid of workgroups of `threads` lanes (a multiple of 64, at most 256) with `dyn_bytes` of dynamic LDS, one
-// after the other (x fastest), every lane of a workgroup a host thread
+// launch_wg: a grid of workgroups of `threads` lanes (a multiple of 64, at most 256) with `dyn_bytes` of dynamic LDS, in
+// ascending order (x fastest), every lane of a workgroup a host thread.  The lane threads PERSIST over the blocks of a launch
+// (256 fresh threads per workgroup made a launch of a few hundred small blocks cost seconds): lane l runs lane l of block 0, 1,
+// 2, ... in turn.  What belongs to a block is still made for it alone - its Block (the block barrier, NaN-filled LDS objects of
+// exact size) and its Waves (barriers, operand buffers) are built by the first lane that enters the block and destroyed by the
+// last one that leaves it, and every lane resets its parity counters and takes the block's index on entry - so nothing a block
+// did is visible to the next one.  There is no rendezvous BETWEEN blocks: a lane that has left block k enters block k + 1 and
+// waits at its first barrier (under that barrier's own deadline), as workgroups of one launch overlap on the card.
+struct BlockSlot {
+  BlockSlot(unsigned threads, size_t dyn_bytes) : blk(threads, dyn_bytes), waves(threads / 64), inside(threads) {}
+  Block blk;
+  std::vector<Wave> waves;
+  unsigned inside;   // lanes that have not left the block yet
+};
 inline void launch_wg(Dim3 grid, unsigned threads, size_t dyn_bytes, const std::function<void()> &body) {
   if (threads == 0 || threads % 64 != 0 || threads > 256) {
     fprintf(stderr, "wave_emu: a workgroup of %u threads is not 1..4 whole wavefronts\n", threads);
     abort();
   }
-  const unsigned waves = threads / 64;
-  for (unsigned bz = 0; bz < grid.z; ++bz)
-    for (unsigned by = 0; by < grid.y; ++by)
-      for (unsigned bx = 0; bx < grid.x; ++bx) {
-        Block blk(threads, dyn_bytes);
-        std::vector<Wave> w(waves);
-        std::vector<std::thread> th;
-        th.reserve(threads);
-        for (unsigned l = 0; l < threads; ++l)
-          th.emplace_back([&, l] {
-            t_block = &blk, t_wave = &w[l / 64], t_par = 0, t_rpar = 0;
-            t_tid = {l, 0, 0}, t_bid = {bx, by, bz}, t_gdim = grid, t_bdim = {threads, 1, 1};
-            body();
-            t_block = nullptr;
-          });
-        for (auto &t : th) t.join();
+  const uint64_t nblocks = (uint64_t)grid.x * grid.y * grid.z;
+  std::mutex m;
+  std::map<uint64_t, BlockSlot *> live;
+  std::vector<std::thread> th;
+  th.reserve(threads);
+  for (unsigned l = 0; l < threads; ++l)
+    th.emplace_back([&, l] {
+      for (uint64_t b = 0; b < nblocks; ++b) {
+        BlockSlot *slot;
+        {
+          std::lock_guard<std::mutex> lk(m);
+          BlockSlot *&s = live[b];
+          if (!s) s = new BlockSlot(threads, dyn_bytes);
+          slot = s;
+        }
+        t_block = &slot->blk, t_wave = &slot->waves[l / 64], t_par = 0, t_rpar = 0;
+        t_tid = {l, 0, 0}, t_gdim = grid, t_bdim = {threads, 1, 1};
+        t_bid = {(unsigned)(b % grid.x), (unsigned)(b / grid.x % grid.y), (unsigned)(b / ((uint64_t)grid.x * grid.y))};
+        body();
+        t_block = nullptr, t_wave = nullptr;
+        bool last;
+        {
+          std::lock_guard<std::mutex> lk(m);
+          last = --slot->inside == 0;
+          if (last) live.erase(b);
+        }
+        if (last) delete slot;
       }
+    });
+  for (auto &t : th) t.join();
 }
 
 }  // namespace wemu
@@ -267,6 +306,7 @@ struct alignas(16) float4 {
 #define __builtin_amdgcn_permlane32_swap(a, b, fi, bc) wemu::permlane_swap((a), (b), 32)
 #define __builtin_amdgcn_rcpf(x) (1.0f / (x))
 #define __builtin_amdgcn_s_waitcnt(x) ((void)0)
+#define __builtin_amdgcn_sched_barrier(x) ((void)0)
 #define __builtin_amdgcn_sqrtf(x) sqrtf((x))
 #define __logf(x) logf((x))
 #define __expf(x) expf((x))

@@ -18,9 +18,10 @@
 using namespace kvae;
 
 // launches so far: 0 / 1 LSTM fwd / bwd, 2 / 3 bi-GRU fwd / bwd, 4 / 5 regime lane-grid fwd / bwd, 6 / 7 regime thread-per-
-// sequence fwd / bwd, 8 / 9 regime LDS bodies fwd / bwd (run by hostsim.cpp, noted here)
-constexpr int kKinds = 10;
-static int g_launches[kKinds] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+// sequence fwd / bwd, 8 / 9 regime LDS bodies fwd / bwd (run by hostsim.cpp, noted here); 10 .. 32: the reduction, mixture and
+// linear-head kernels, one index per instance (wave_emu_reduce.cpp)
+constexpr int kKinds = 33;
+static int g_launches[kKinds] = {};
 // the switches of the GPU dispatch: KVAE_REGIME_TPP (kvae_lgssm.hip: 1 lane grid up to the batch threshold, then thread per
 // sequence; 2 thread per sequence always; 0 the LDS bodies) and the threshold itself, settable here so that the thread-per-
 // sequence kernels run at a batch the emulation can afford
@@ -30,31 +31,45 @@ static int g_regime_mode = 1, g_regime_grid_max_b = KVAE_REGIME_GRID_MAX_B;
 
 // a kernel for the emulator itself: three wavefronts, a static and a dynamic LDS array, a block-wide barrier between a write
 // and the read of ANOTHER wavefront's element, __shfl_xor inside the wavefront.  out[block * 192 + tid] = what the lane read.
-static void k_selftest(float *out, int n_dyn) {
+// The lane threads persist over the blocks of a launch, so the kernel also reports what must NOT have come over from the block
+// before: `fresh` counts lanes that enter with a parity counter set, or find an LDS element that is not the NaN fill.  Blocks
+// leave both in a state the next one would notice: wavefront 1 of an odd block makes one exchange more than the others (its
+// parity ends odd) and every lane overwrites its LDS elements.
+static void k_selftest(float *out, int *fresh, int n_dyn) {
   KV_LDS(float, stat, [192]);
   KV_LDS_DYN(float, dyn);
   const int tid = threadIdx.x, nt = blockDim.x;
-  stat[tid] = (float)(tid + 1000 * blockIdx.x);
-  if (tid < n_dyn) dyn[tid] = (float)(2 * tid);
+  const int blk = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+  const bool stale = wemu::t_par != 0 || wemu::t_rpar != 0 || stat[tid] == stat[tid] || (tid < n_dyn && dyn[tid] == dyn[tid]);
+  if (stale) __atomic_fetch_add(fresh, 1, __ATOMIC_RELAXED);
+  stat[tid] = (float)(tid + 1000 * blk);
+  if (tid < n_dyn) dyn[tid] = (float)(2 * tid + blk);
   __syncthreads();
   const float other = stat[(tid + 64) % nt];                    // written by the next wavefront
   const float pair = __shfl_xor((float)tid, 1, 64);             // lane tid ^ 1 of this wavefront
   const float d = dyn[(tid + 1) % n_dyn];
+  float extra = 0.f;
+  if ((blk & 1) && (tid >> 6) == 1) extra = __shfl_xor((float)tid, 2, 64) - (float)(tid ^ 2);   // 0; one exchange more
+  if ((tid >> 4) == 2) extra += (float)__builtin_amdgcn_mov_dpp(tid, 0x140, 0xf, 0xf, true) - (float)((tid & ~15) | (15 - (tid & 15)));
   __syncthreads();
-  out[blockIdx.x * nt + tid] = other + 0.5f * pair + 0.25f * d;
+  out[blk * nt + tid] = other + 0.5f * pair + 0.25f * d + extra + 4096.f * blockIdx.y + 16384.f * blockIdx.z;
 }
 
 extern "C" {
 
-// 0 if launch_wg, the block barrier, both kinds of LDS and __shfl_xor behave; the number of wrong elements otherwise
+// 0 if launch_wg, the block barrier, both kinds of LDS and __shfl_xor behave and no state of a block reaches the next one (a 3-D
+// grid of 2 x 3 x 2 blocks on persistent lane threads); the number of wrong elements otherwise
 int kvae_wemu_selftest(void) {
-  const int blocks = 2, nt = 192, n_dyn = 7;
+  const int gx = 2, gy = 3, gz = 2, blocks = gx * gy * gz, nt = 192, n_dyn = 7;
   std::vector<float> out((size_t)blocks * nt, NAN);
-  wemu::launch_wg({(unsigned)blocks, 1, 1}, nt, n_dyn * sizeof(float), [&] { k_selftest(out.data(), n_dyn); });
-  int bad = 0;
+  int fresh = 0;
+  wemu::launch_wg({(unsigned)gx, (unsigned)gy, (unsigned)gz}, nt, n_dyn * sizeof(float), [&] { k_selftest(out.data(), &fresh, n_dyn); });
+  int bad = fresh;
   for (int b = 0; b < blocks; ++b)
     for (int t = 0; t < nt; ++t) {
-      const float want = (float)((t + 64) % nt + 1000 * b) + 0.5f * (float)(t ^ 1) + 0.25f * (float)(2 * ((t + 1) % n_dyn));
+      const int by = b / gx % gy, bz = b / (gx * gy);
+      const float want = (float)((t + 64) % nt + 1000 * b) + 0.5f * (float)(t ^ 1) + 0.25f * (float)(2 * ((t + 1) % n_dyn) + b) +
+                         4096.f * by + 16384.f * bz;
       bad += out[(size_t)b * nt + t] != want;
     }
   return bad;

@@ -420,21 +420,25 @@ def _per_step_ratio(got, ref):
 # ---- recurrent chain kernels (lstm_fast.h, gru_fast.h, regime_grid.h / regime_tpp.h / regime.h), one (b,t) slice at a time ----
 # Bars = 4 x YARDSTICK (the factor values_vs_fp64_oracle uses for "as good as float32 can be"), where the yardstick of a quantity
 # is the largest per-slice ratio of the FLOAT32 TORCH restatement of the operation (nn.LSTM, nn.GRU, regime_chain run in float32)
-# against its float64 run, over the case lists of both tiers (tests/test_wave_emu_rnn.py, tests/test_hostsim_ops.py,
+# against its float64 run, over the case lists of both tiers (tests/test_wave_emu_rnn.py, tests/test_wave_emu_reduce.py, tests/test_hostsim_ops.py,
 # tests/test_gpu_parity.py; rerun: the case functions with yardstick=True).  Largest ratios the kernels reach against the same
 # float64 run, emulated workgroups (expf, a division) | gfx950 (__expf, v_rcp):
 #   lstm.h 4.3e-7 | 7.8e-7   lstm.gates 3.5e-7 | 5.8e-7   lstm.c_seq 4.1e-7 | 7.3e-7   lstm.dx 1.7e-6 | 6.1e-6   lstm.param 3.3e-7 | 3.5e-7
 #   gru.h 2.6e-7 | 3.2e-7    gru.dx 1.2e-6 | 7.6e-6       gru.param 3.5e-7 | 3.0e-7
 #   regime.y 4.2e-7 | 5.2e-7  log_q 2.4e-6 | 2.2e-6  log_p 6.5e-7 | 6.4e-7  g_logits 2.7e-5 | 3.3e-5  g_init 2.3e-5 | 1.5e-5
-#   wgrad.wh / wx / b  - | 3.2e-7 / 4.0e-6 / 1.4e-5    mix.out / g_alpha / g_base  - | 2.4e-7 / 1.5e-6 / 1.9e-7
-#   linear.y / dx / dw / db  - | 1.2e-6 / 2.2e-5 / 2.2e-6 / 7.2e-7      (-: plain-loop twins on the CPU tier, not the kernels)
-# Less than a factor 2 under the bar: lstm.gates (1.16 x on gfx950, 1.9 x emulated), lstm.c_seq (1.45 x on gfx950); DESIGN section 2.
+#   wgrad.wh / wx / b  4.8e-7 | 5.1e-7 / 1.9e-6 | 4.0e-6 / 1.2e-5 | 2.1e-5
+#   mix.out / g_alpha / g_base  1.7e-7 | 2.4e-7 / 3.2e-6 | 4.5e-6 / 1.9e-7 | 2.9e-7
+#   linear.y / dx / dw / db  6.9e-7 | 1.2e-6 / 1.1e-5 | 2.2e-5 / 2.0e-6 | 2.2e-6 / 7.7e-7 | 7.2e-7
+#   (wgrad / mix / linear, emulated: the product's kernels on emulated workgroups, tests/test_wave_emu_reduce.py - every case of
+#   that file; gfx950: the _ROW_CASES, _EDGE, _LARGE and batch lists of tests/test_gpu_parity.py)
+# Less than a factor 2 under the bar: lstm.gates (1.16 x on gfx950, 1.9 x emulated), lstm.c_seq (1.45 x on gfx950), wgrad.b (1.86 x on
+# gfx950); DESIGN section 2.
 RNN_YARDSTICK = {   # float32 torch against float64 torch, largest per-slice ratio over the CPU and the GPU case lists
     "lstm.h": 3.96e-7, "lstm.gates": 1.69e-7, "lstm.c_seq": 2.65e-7, "lstm.dx": 6.61e-6, "lstm.param": 2.90e-6,
     "gru.h": 2.56e-7, "gru.dx": 8.04e-6, "gru.param": 6.16e-7,
-    "mix.out": 2.42e-7, "mix.g_alpha": 5.29e-6, "mix.g_base": 6.11e-7,
-    "linear.y": 1.65e-6, "linear.dx": 2.20e-5, "linear.dw": 1.24e-6, "linear.db": 6.38e-7,
-    "wgrad.wh": 7.05e-7, "wgrad.wx": 8.23e-6, "wgrad.b": 7.30e-6,
+    "mix.out": 2.42e-7, "mix.g_alpha": 8.74e-6, "mix.g_base": 6.11e-7,
+    "linear.y": 1.65e-6, "linear.dx": 2.64e-5, "linear.dw": 1.24e-6, "linear.db": 8.09e-7,
+    "wgrad.wh": 1.48e-6, "wgrad.wx": 1.01e-5, "wgrad.b": 9.78e-6,
     "regime.y": 9.32e-7, "regime.log_q": 2.43e-6, "regime.log_p": 6.48e-7, "regime.g_logits": 3.35e-5, "regime.g_init": 2.32e-5,
 }
 RNN_STEP_TOL = {k: 4.0 * v for k, v in RNN_YARDSTICK.items()}   # the bars of lstm_per_step / bigru_per_step / regime_per_step
@@ -1158,14 +1162,38 @@ def rnn_wgrad_vs_torch(DEV):
 WGRAD_ROW_CASES = [(3, 7, 50, 2, R, -1) for R in (5, 37, 150, 200, 250)] + [
     (3, 7, 50, 2, 150, 1), (3, 7, 50, 2, 250, 1), (5, 1, 50, 2, 200, -1), (5, 1, 50, 2, 150, 1), (2, 9, 13, 3, 37, 0),
     (3, 7, 50, 0, 150, 1), (4, 11, 0, 2, 150, 0)]
-WGRAD_ROW_CASES_LARGE = [(256, 50, 50, 2, 200, -1), (256, 50, 50, 2, 150, 1)]   # GPU tier only
+# GPU tier only.  The last four: ~26000 rows are 256 chunks of 104 rows - three full 32-row stages and a partial one, the step index
+# advanced by 32 % T = 32 (T = 37) and 0 (T = 32) per stage, chunk starts inside a sequence, the first and the last step masked
+WGRAD_ROW_CASES_LARGE = [(256, 50, 50, 2, 200, -1), (256, 50, 50, 2, 150, 1)] + [
+    (Bsz, T, 13, 3, 37, shift) for Bsz, T in ((703, 37), (813, 32)) for shift in (-1, 1)]
+
+# Batches (a list of (Bsz, T, H, I, R, shift) per call), both tiers:
+#   the product's default path (lgssm_ops.py, the coupled alpha-LSTM backward): the 200 gate rows of the LSTM with the K = 3 rows of
+#     its head, so the head runs under k_rnn_wgrad_partial<13> with D columns 3 .. 207 clamped to column 2;
+#   four problems with R = 5 / 60 / 150 / 250 (one, four, ten and sixteen row tiles under <16>), C = 17 (one column group) next to
+#     C = 101 (two: the second group's blocks of the narrow problems have four dead wavefronts that still load) and N = 21 / 44 / 5 /
+#     70 in one call (three chunks: the second and third of the N = 5 problem start at or past its end);
+#   the ABI limits R = 256, C = 256.
+WGRAD_BATCH_CASES = [
+    [(3, 7, 50, 2, 200, -1), (3, 7, 50, 0, 3, 0)],
+    [(3, 7, 13, 3, 5, -1), (4, 11, 100, 0, 60, 1), (5, 1, 13, 3, 150, 0), (10, 7, 98, 2, 250, -1)],
+    [(3, 3, 200, 55, 256, 1)],
+]
+# (Bsz, T, H, I, R, shift, chunk cap): chunks of four or five stages, the last one partial, the second (and third) chunk starting
+# inside a sequence, for every shift and T = 1, 3 (32 % T = 2), 32 (0), 33 (32), 64 (32).  The emulated tier runs them through the
+# chunk-cap setter (N = 198 .. 320); the cap is the number of chunks the same shapes get on the card from N = 8192 rows on.
+WGRAD_STAGE_CASES = [(Bsz, T, 13, 3, 37, shift, cap) for Bsz, T, cap in ((198, 1, 2), (66, 3, 2), (7, 32, 2), (6, 33, 2), (5, 64, 3))
+                     for shift in (-1, 0, 1)]
 
 
-def rnn_wgrad_per_row(DEV, Bsz, T, H, I, R, shift, yardstick=False):
-    """kvae_rnn_wgrad against the float64 product D^T [h_shifted | x | 1], one OUTPUT ROW at a time (a gate row of dW_hh, dW_ih
-    and db; the floor of _per_step_ratio applies per row).  The hidden operand is a column slice of a wider [N, 2H] sequence
-    when shift = +1 (the reverse GRU direction's layout: row stride 2H)."""
-    from kvae.kalman.lgssm_ops import rnn_wgrad
+def wgrad_instance(batch):
+    """RT of the k_rnn_wgrad_partial instance a batch of (Bsz, T, H, I, R, shift) runs under (rnn_wgrad.h: wg_rt_instance)."""
+    tiles = max((c[4] + 15) // 16 for c in batch)
+    return next(rt for rt in (1, 4, 10, 13, 16) if tiles <= rt)
+
+
+def _wgrad_problem(DEV, Bsz, T, H, I, R, shift, yardstick):
+    """One problem of rnn_wgrad_per_row: (problem dict | float32 torch result, float64 reference)."""
     g = torch.Generator().manual_seed(100 * R + 10 * T + shift + 1)
     n = Bsz * T
     d = torch.randn(n, R, generator=g)
@@ -1178,19 +1206,47 @@ def rnn_wgrad_per_row(DEV, Bsz, T, H, I, R, shift, yardstick=False):
     dd = d.double()
     want = (dd.t() @ hs.double(), dd.t() @ x[:, :I].double(), dd.sum(0))
     if yardstick:
-        got = (d.t() @ hs, d.t() @ x[:, :I], d.sum(0))
-    else:
-        prob = dict(d=d.to(DEV))
-        if H:
-            prob.update(h=h2.reshape(n, -1).to(DEV)[:, col:col + H], shift=shift, T=T)
-        if I:
-            prob.update(x=x[:, :I].contiguous().to(DEV))
-        (got,) = rnn_wgrad(prob["d"], [prob])
+        return (d.t() @ hs, d.t() @ x[:, :I], d.sum(0)), want
+    prob = dict(d=d.to(DEV))
+    if H:
+        prob.update(h=h2.reshape(n, -1).to(DEV)[:, col:col + H], shift=shift, T=T)
+    if I:
+        prob.update(x=x[:, :I].contiguous().to(DEV))
+    return prob, want
+
+
+def rnn_wgrad_batch_per_row(DEV, batch, yardstick=False):
+    """kvae_rnn_wgrad on up to four problems in ONE call against the float64 products D^T [h_shifted | x | 1], one OUTPUT ROW at a
+    time (a gate row of dW_hh, dW_ih and db; the floor of _per_step_ratio applies per row).  The hidden operand is a column slice
+    of a wider [N, 2H] sequence when shift = +1 (the reverse GRU direction's layout: row stride 2H)."""
+    from kvae.kalman.lgssm_ops import rnn_wgrad
+    made = [_wgrad_problem(DEV, *c, yardstick) for c in batch]
+    got = [m[0] for m in made] if yardstick else rnn_wgrad(made[0][0]["d"], [m[0] for m in made])
     out = {}
-    for name, a, b in zip(("wgrad.wh", "wgrad.wx", "wgrad.b"), got, want):
-        if a is not None and b.numel():
-            _check_steps(name, a.reshape(R, 1, -1), b.reshape(R, 1, -1), RNN_STEP_TOL[name], out)
+    for c, res, (_, want) in zip(batch, got, made):
+        R = c[4]
+        for name, a, b in zip(("wgrad.wh", "wgrad.wx", "wgrad.b"), res, want):
+            if a is not None and b.numel():
+                _check_steps(name, a.reshape(R, 1, -1), b.reshape(R, 1, -1), RNN_STEP_TOL[name], out)
     return out
+
+
+def rnn_wgrad_per_row(DEV, Bsz, T, H, I, R, shift, yardstick=False):
+    """rnn_wgrad_batch_per_row on one problem."""
+    return rnn_wgrad_batch_per_row(DEV, [(Bsz, T, H, I, R, shift)], yardstick)
+
+
+def rnn_wgrad_refusals(DEV):
+    """One past each ABI limit: R = 257 rows, C = H + I + 1 = 257 columns, a row count that is not whole sequences - refused with an
+    error code (RuntimeError from the bridge), nothing launched."""
+    import pytest
+    from kvae.kalman.lgssm_ops import rnn_wgrad
+    for Bsz, T, H, I, R, bad_n in [(1, 3, 13, 3, 257, False), (1, 3, 200, 56, 5, False), (1, 3, 13, 3, 5, True)]:
+        prob, _ = _wgrad_problem(DEV, Bsz, T, H, I, R, -1, False)
+        if bad_n:
+            prob["T"] = 2
+        with pytest.raises(RuntimeError):
+            rnn_wgrad(prob["d"], [prob])
 
 
 def small_linear_vs_torch(DEV):
@@ -1300,7 +1356,22 @@ def mix_vs_torch(DEV):
 # stage (21, 37, 17, 45) and K below the instance's KMAX (2, 5, 6), a K above their limit, and the large cases of mix_vs_torch
 MIX_ROW_CASES = [(3, 7, 3, 48), (3, 7, 2, 40), (37, 1, 5, 768), (1, 17, 6, 48), (5, 9, 3, 768), (2, 5, 8, 768), (4, 6, 9, 40),
                  (1, 1, 2, 12), (2, 3, 3, 42), (3, 7, 7, 544)]
-MIX_ROW_CASES_LARGE = [(256, 50, 3, 40), (32, 100, 7, 48), (64, 33, 3, 544)]   # GPU tier only
+# GPU tier only.  The last one: 33000 rows are above 32768, where both slab caps bind (forward 4096 slabs of 9 rows; backward 2048
+# slabs of 17 rows - more than the 16 the partials buffer allows below that, and not a multiple of the four rows of an RB group)
+MIX_ROW_CASES_LARGE = [(256, 50, 3, 40), (32, 100, 7, 48), (64, 33, 3, 544), (33, 1000, 2, 128)]
+# both tiers: one row; 1041 rows = 66 slabs of 16 rows (k_mix_bwd_fold takes a second round of 64 slabs, the last slab holds one row)
+MIX_ROW_CASES_EDGE = [(1, 1, 3, 128), (1, 1041, 2, 128)]
+# (Bsz, T, K, E, forward slab cap, backward slab cap) for the emulated tier's setters: 37 rows in 2 slabs of 19 rows, 75 rows in 3
+# slabs of 25 (more than 16 rows per slab, not a multiple of 4: the last RB group of every slab is ragged), K above 4 once
+MIX_CAPPED_CASES = [(37, 1, 2, 128, 2, 2), (3, 25, 5, 260, 3, 3)]
+
+
+def mix_instance(K, E):
+    """(KMAX, EJ) of the streaming instance (mix_wave.h: KVAE_MIXW_DISPATCH), or None where the gate sends the call to the
+    element-wise kernels (pointers of torch allocations are 16-byte aligned)."""
+    if E % 4 or E < 128 or E > 768 or K > 8:
+        return None
+    return (4 if K <= 4 else 8, (E + 255) // 256)
 
 
 def mix_per_row(DEV, Bsz, T, K, E, yardstick=False):
@@ -1325,11 +1396,49 @@ def mix_per_row(DEV, Bsz, T, K, E, yardstick=False):
     return out
 
 
+def mix_accumulate_guarded(DEV, rows, K, E, misalign=None):
+    """kvae_mix_bwd through the C ABI with accumulate_alpha = 1 and then 0, g_alpha / g_base / partials in guarded buffers of exactly
+    the sizes the ABI states (partials: kvae_mix_bwd_partials(rows) x K x E): g_alpha += on the first call, overwritten on the
+    second, per row against float64; no guard element written.  misalign = "partials" / "g_out" puts that buffer 4 bytes past a
+    16-byte boundary: the gate then sends the call to the element-wise kernels, same results."""
+    from kvae import _native as N
+    from step_cases import Guarded
+    g = torch.Generator().manual_seed(7 * rows + K + E)
+    alpha = torch.softmax(torch.randn(rows, K, generator=g), -1)
+    base, gout, ga0 = torch.randn(K, E, generator=g), torch.randn(rows, E, generator=g), torch.randn(rows, K, generator=g)
+    al, bs = Guarded(DEV, rows * K, init=alpha), Guarded(DEV, K * E, init=base)
+    go = Guarded(DEV, rows * E, off=1 if misalign == "g_out" else 0, init=gout)
+    lib = N.lib_for(al.t)
+    part = Guarded(DEV, lib.dll.kvae_mix_bwd_partials(rows) * K * E, off=1 if misalign == "partials" else 0)
+    g_alpha, g_base = Guarded(DEV, rows * K, init=ga0), Guarded(DEV, K * E)
+    want_a, want_b = gout.double() @ base.double().T, alpha.double().T @ gout.double()
+    out = {}
+    for acc in (1, 0):
+        rc = lib.dll.kvae_mix_bwd(al.ptr, bs.ptr, go.ptr, g_alpha.ptr, g_base.ptr, part.ptr, rows, K, E, acc, N.stream_for(al.t))
+        assert rc == 0, rc
+        got_a = g_alpha.cpu().view(rows, K).double() - (ga0.double() if acc else 0.0)
+        _check_steps("mix.g_alpha", got_a.view(1, rows, K), want_a.view(1, rows, K), RNN_STEP_TOL["mix.g_alpha"], out)
+        _check_steps("mix.g_base", g_base.cpu().view(K, 1, E), want_b.view(K, 1, E), RNN_STEP_TOL["mix.g_base"], out)
+        for name, buf in (("alpha", al), ("base", bs), ("g_out", go), ("g_alpha", g_alpha), ("g_base", g_base), ("partials", part)):
+            assert buf.guards_intact(), (name, "guard written", acc)
+    return out
+
+
 # (leading shape, F, O, softmax, strided): the heads of small_linear_vs_torch, single rows, and a row count of one
 LINEAR_ROW_CASES = [((6, 9), 50, 3, True, False), ((5, 8), 100, 9, False, False), ((3, 4), 100, 49, False, False),
                     ((7,), 100, 7, False, True), ((2, 3), 17, 5, False, False), ((1, 1), 50, 7, True, False),
                     ((3,), 100, 16, True, True)]
-LINEAR_ROW_CASES_LARGE = [((256, 50), 50, 7, True, False), ((256, 50), 100, 49, False, False)]   # GPU tier only
+# GPU tier only.  The last two: 16500 >= 16384 rows take 64 rows per block (u up to 15 in sl_stage_rows), the last block has 52
+LINEAR_ROW_CASES_LARGE = [((256, 50), 50, 7, True, False), ((256, 50), 100, 49, False, False), ((16500,), 17, 5, False, False),
+                          ((33, 500), 50, 7, True, False)]
+# both tiers: F = 128 with the largest O that fits SL_MAX_W (96 x 129 floats of W leave room for 16 rows), the softmax at O = 1
+# and at its limit O = 16, O = 5 (not a multiple of the 4 outputs per thread) on strided rows, one block
+LINEAR_ROW_CASES_EDGE = [((5,), 128, 96, False, False), ((3,), 50, 1, True, False), ((21,), 50, 16, True, False),
+                         ((13,), 17, 5, False, True)]
+# (leading shape, F, O, softmax, strided, least block count, rows per block it gives) for the emulated tier's setter: 70 rows at
+# 64 (2 blocks, 6 rows in the last), 32 (3 blocks) and 16 (5 blocks) rows per block; 40 rows in ONE block of 64
+LINEAR_BLOCK_CASES = [((70,), 17, 5, False, False, 1, 64), ((70,), 17, 5, False, False, 2, 32), ((70,), 17, 5, False, False, -1, 16),
+                      ((70,), 50, 7, True, True, 1, 64), ((70,), 50, 7, True, False, 2, 32), ((40,), 17, 5, False, True, 0, 64)]
 
 
 def small_linear_per_row(DEV, lead, F, O, softmax, strided, yardstick=False):

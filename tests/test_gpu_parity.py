@@ -428,14 +428,32 @@ def test_rnn_wgrad_per_row_gpu(Bsz, T, H, I, R, shift):
     print(parity_cases.rnn_wgrad_per_row(DEV, Bsz, T, H, I, R, shift))
 
 
-@pytest.mark.parametrize("Bsz,T,K,E", parity_cases.MIX_ROW_CASES + parity_cases.MIX_ROW_CASES_LARGE)
+@pytest.mark.parametrize("batch", parity_cases.WGRAD_BATCH_CASES, ids=lambda b: "+".join(str(c[4]) for c in b))
+def test_rnn_wgrad_batched_gpu(batch):
+    """Several problems in one pair of launches: the product's LSTM + head pair (the K-row head under k_rnn_wgrad_partial<13>), four
+    problems of different R, column groups and N, the ABI limits R = C = 256; the refusals one past each limit."""
+    print(parity_cases.rnn_wgrad_batch_per_row(DEV, batch))
+
+
+def test_rnn_wgrad_refusals_gpu():
+    parity_cases.rnn_wgrad_refusals(DEV)
+
+
+@pytest.mark.parametrize("Bsz,T,K,E", parity_cases.MIX_ROW_CASES + parity_cases.MIX_ROW_CASES_EDGE + parity_cases.MIX_ROW_CASES_LARGE)
 def test_mix_per_row_gpu(Bsz, T, K, E):
     """The streaming mixture kernels (and their element-wise fallback) one (b,t) row at a time against float64: ragged row
     counts, K below the instance's KMAX."""
     print(parity_cases.mix_per_row(DEV, Bsz, T, K, E))
 
 
-@pytest.mark.parametrize("lead,F,O,softmax,strided", parity_cases.LINEAR_ROW_CASES + parity_cases.LINEAR_ROW_CASES_LARGE)
+@pytest.mark.parametrize("rows,K,E,misalign", [(21, 3, 768, None), (37, 5, 132, None), (21, 3, 768, "partials")])
+def test_mix_accumulate_flag_guarded_gpu(rows, K, E, misalign):
+    """accumulate_alpha through the C ABI with every buffer between guard records; a misaligned partials buffer takes the
+    element-wise kernels."""
+    print(parity_cases.mix_accumulate_guarded(DEV, rows, K, E, misalign))
+
+
+@pytest.mark.parametrize("lead,F,O,softmax,strided", parity_cases.LINEAR_ROW_CASES + parity_cases.LINEAR_ROW_CASES_LARGE + parity_cases.LINEAR_ROW_CASES_EDGE)   # (appended: the ids count)
 def test_small_linear_per_row_gpu(lead, F, O, softmax, strided):
     """The four small_linear.h kernels one row at a time against float64 (contiguous rows and the strided rows of h_seq[:, 0])."""
     print(parity_cases.small_linear_per_row(DEV, lead, F, O, softmax, strided))

@@ -358,18 +358,21 @@ def test_training_phases_hostsim(name, kind, hostsim_backend):
 
 @pytest.mark.parametrize("Bsz,T,H,I,R,shift", parity_cases.WGRAD_ROW_CASES)
 def test_rnn_wgrad_per_row_hostsim(hostsim_backend, Bsz, T, H, I, R, shift):
-    """The plain-loop twin of kvae_rnn_wgrad at the shapes the GPU tier runs through every k_rnn_wgrad_partial<RT> instance:
-    the case function and its float64 reference are checked here before they are trusted there."""
+    """The plain-loop twin of kvae_rnn_wgrad at the shapes that reach every k_rnn_wgrad_partial<RT> instance: the case function
+    and its float64 reference on code that shares nothing with the kernels.  The kernels themselves run the same cases on emulated
+    workgroups in tests/test_wave_emu_reduce.py and on the card in tests/test_gpu_parity.py."""
     parity_cases.rnn_wgrad_per_row("cpu", Bsz, T, H, I, R, shift)
 
 
 @pytest.mark.parametrize("Bsz,T,K,E", parity_cases.MIX_ROW_CASES)
 def test_mix_per_row_hostsim(hostsim_backend, Bsz, T, K, E):
+    """The element-wise twins (the streaming kernels: tests/test_wave_emu_reduce.py, tests/test_gpu_parity.py)."""
     parity_cases.mix_per_row("cpu", Bsz, T, K, E)
 
 
 @pytest.mark.parametrize("lead,F,O,softmax,strided", parity_cases.LINEAR_ROW_CASES)
 def test_small_linear_per_row_hostsim(hostsim_backend, lead, F, O, softmax, strided):
+    """The plain-loop twins (the four kernels: tests/test_wave_emu_reduce.py, tests/test_gpu_parity.py)."""
     parity_cases.small_linear_per_row("cpu", lead, F, O, softmax, strided)
 
 
