@@ -539,30 +539,14 @@ int kvae_lstm_bwd(const float *g_h, const float *gates, const float *c_seq, cons
 // ---------------------------------------------------------------------------------------------
 // imputation read-out: a = C_t mu_t for the smoothed and the filtered means in one launch (model.py:279-288)
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_emission_means(kvae_stack C, const float *__restrict__ ms, const float *__restrict__ mf,
-                                                        float *__restrict__ a_s, float *__restrict__ a_f, int64_t BT, int T, int n,
-                                                        int p) {
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= BT * p) return;
-  const int64_t q = idx / p;
-  const int i = (int)(idx % p);
-  const float *c = C.ptr + (q / T) * C.sb + (q % T) * C.st + (int64_t)i * n;
-  float s = 0.f, f = 0.f;
-  for (int k = 0; k < n; ++k) {
-    const float ck = c[k];
-    if (ms) s = fmaf(ck, ms[q * n + k], s);
-    if (mf) f = fmaf(ck, mf[q * n + k], f);
-  }
-  if (a_s) a_s[idx] = s;
-  if (a_f) a_f[idx] = f;
-}
+#include "emission_means.h"
 extern "C" int kvae_lgssm_emission_means(const kvae_lgssm_problem *prob, const float *mus_smooth, const float *mus_filt,
                                          float *a_imputed, float *a_filtered, void *stream) {
   if (!prob || !prob->C.ptr || (!mus_smooth != !a_imputed) || (!mus_filt != !a_filtered) || (!a_imputed && !a_filtered))
     return KVAE_ERR_NULL;
   if (prob->B < 1 || prob->T < 1 || prob->n < 1 || prob->p < 1 || prob->n > KVAE_MAX_DIM || prob->p > KVAE_MAX_DIM) return KVAE_ERR_DIMS;
   const int64_t BT = (int64_t)prob->B * prob->T;
-  k_emission_means<<<dim3((unsigned)((BT * prob->p + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(
+  k_emission_means<<<dim3(emission_blocks(BT, prob->p)), dim3(256), 0, (hipStream_t)stream>>>(
       prob->C, mus_smooth, mus_filt, a_imputed, a_filtered, BT, prob->T, prob->n, prob->p);
   return launch_status("k_emission_means");
 }

@@ -10,9 +10,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lds_decl.h"
+#include "vae_epilogue.h"   // epi_grid: the capped grid of the element-wise launches
+
 namespace kvae {
 
 constexpr int HD_F = 512, HD_A = 2, HD_WAVES = 512;   // partial rows = waves of the backward grids
+
+// ---- launch geometry of the scalar head (host side): kvae_vae.hip and the test-only emulated workgroups call the same functions
+constexpr int LOSS_HEAD_FWD_THREADS = 1024;           // k_loss_head_fwd is ONE workgroup of this size
+inline unsigned loss_head_bwd_grid(int64_t n, int64_t cap = EPI_MAX_BLOCKS) { return epi_grid(n, cap); }
 
 __device__ __forceinline__ float hd_wave_sum(float v) {
 #pragma unroll
@@ -202,7 +209,7 @@ __global__ __launch_bounds__(1024) void k_loss_head_fwd(const float *__restrict_
                                                         float *__restrict__ coef, int64_t n) {
   // one block of 1024 threads, dwordx4 loads: a handful of memory round trips in total (a narrower block turns the
   // reduction into a 50-deep chain of dependent global loads, slower than the launches it replaces)
-  __shared__ float red[3][1024];
+  KV_LDS(float, red, [3][1024]);
   float s0 = 0.f, s1 = 0.f, s2 = 0.f;
   const int64_t n4 = ((n & 3) == 0 && ((((uintptr_t)lpx | (uintptr_t)regf | (uintptr_t)mask) & 15) == 0)) ? n / 4 : 0;
   // mask == NULL means "every frame observed".  Loads are always issued from a VALID address (lpx stands in) and the value

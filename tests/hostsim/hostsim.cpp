@@ -146,6 +146,18 @@ int kvae_wemu_mix_bwd(const float *, const float *, const float *, float *, floa
                       int64_t);
 void kvae_wemu_linear_fwd(const float *, int64_t, int64_t, int, const float *, const float *, int, int, float *);
 void kvae_wemu_linear_bwd_input(const float *, const float *, int64_t, int, const float *, int, float *, float *, int64_t);
+// wave_emu_step.cpp: clip + Adam, the scalar loss head, the column sums, the emission read-out and the conv epilogues
+void kvae_wemu_clip_adam(float *, const float *, float *, float *, int64_t, const int32_t *, int32_t, const float *, float *,
+                         const float *, float, float, float, float, float, float, const float *, float *, float *);
+void kvae_wemu_loss_head_fwd(const float *, const float *, const float *, const float *, const float *, float, float, float,
+                             const float *, float *, float *, int64_t);
+void kvae_wemu_loss_head_bwd(const float *, const float *, const float *, float *, float *, float *, int64_t);
+void kvae_wemu_colsum(const float *, float *, int64_t, int64_t);
+void kvae_wemu_colsum2(const float *, float *, int64_t, int64_t, const float *, float *, int64_t, int64_t);
+void kvae_wemu_emission_means(const kvae_lgssm_problem *, const float *, const float *, float *, float *);
+int64_t kvae_wemu_bias_partial_rows(int64_t);
+void kvae_wemu_epilogue_fwd(const float *, const float *, float *, int64_t, int32_t, int32_t, int32_t, int32_t, int32_t);
+void kvae_wemu_epilogue_bwd(const float *, const float *, float *, float *, int64_t, int32_t, int32_t, int32_t, int32_t, int32_t);
 }
 static int g_wave_emu = 0;
 static bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -318,14 +330,22 @@ int kvae_bias_shuffle_act_fwd(const float *in, const float *bias, float *out, in
                               int32_t r, int32_t relu, void *) {
   if (!in || !bias || !out) return KVAE_ERR_NULL;
   if (N < 1 || C < 1 || H < 1 || W < 1 || r < 1) return KVAE_ERR_ARG;
+  if (g_wave_emu) {   // k_vae_epilogue_fwd_v4<1 | 2> / k_vae_epilogue_fwd
+    kvae_wemu_epilogue_fwd(in, bias, out, N, C, H, W, r, relu);
+    return KVAE_OK;
+  }
   const EpiShape s{N, C, H, W, r};
   for (int64_t o = 0; o < N * C * H * W * r * r; ++o) epi_fwd_elem(s, in, bias, out, o, relu);
   return KVAE_OK;
 }
-int64_t kvae_bias_partial_rows(int64_t N) { return (N + 31) / 32; }
+int64_t kvae_bias_partial_rows(int64_t N) { return g_wave_emu ? kvae_wemu_bias_partial_rows(N) : (N + 31) / 32; }
 int kvae_colsum(const float *partials, float *out, int64_t rows, int64_t cols, void *) {
   if (!partials || !out) return KVAE_ERR_NULL;
   if (rows < 1 || cols < 1) return KVAE_ERR_ARG;
+  if (g_wave_emu) {   // k_colsum_v4 / k_colsum
+    kvae_wemu_colsum(partials, out, rows, cols);
+    return KVAE_OK;
+  }
   for (int64_t c = 0; c < cols; ++c) {
     float s = 0.f;
     for (int64_t r = 0; r < rows; ++r) s += partials[r * cols + c];
@@ -338,6 +358,10 @@ int kvae_clip_adam(float *p, const float *g, float *m, float *v, int64_t n, cons
                    float wd, float clip, const float *div_dev, float *norm_out, float *ws, void *) {
   if (!p || !g || !m || !v || !seg_steps || !ws) return KVAE_ERR_NULL;
   if (n < 1 || n_seg < 1 || n_seg > 1024 || (!seg_of && n_seg != 1)) return KVAE_ERR_ARG;
+  if (g_wave_emu) {   // k_grad_sumsq + k_clip_adam
+    kvae_wemu_clip_adam(p, g, m, v, n, seg_of, n_seg, seg_active, seg_steps, lr_dev, lr, beta1, beta2, eps, wd, clip, div_dev, norm_out, ws);
+    return KVAE_OK;
+  }
   const float inv = div_dev ? 1.0f / std::fmax(*div_dev, 1.0f) : 1.0f;
   auto on = [&](int64_t i) { return !seg_active || seg_active[seg_of ? seg_of[i] : 0] != 0.f; };
   double ss = 0.0;
@@ -364,6 +388,10 @@ int kvae_colsum2(const float *pa, float *oa, int64_t rows_a, int64_t cols_a, con
                  int64_t cols_b, void *s) {
   if (!pa || !oa || !pb || !ob) return KVAE_ERR_NULL;   // refused before either job runs, as the entry point of kvae_vae.hip
   if (rows_a < 1 || cols_a < 1 || rows_b < 1 || cols_b < 1) return KVAE_ERR_ARG;
+  if (g_wave_emu) {   // k_colsum_v4_pair, or two single launches
+    kvae_wemu_colsum2(pa, oa, rows_a, cols_a, pb, ob, rows_b, cols_b);
+    return KVAE_OK;
+  }
   const int rc = kvae_colsum(pa, oa, rows_a, cols_a, s);
   return rc ? rc : kvae_colsum(pb, ob, rows_b, cols_b, s);
 }
@@ -371,6 +399,10 @@ int kvae_bias_shuffle_act_bwd(const float *g_out, const float *out, float *g_in,
                               int32_t H, int32_t W, int32_t r, int32_t relu, void *) {
   if (!g_out || !g_in || (relu && !out)) return KVAE_ERR_NULL;
   if (N < 1 || C < 1 || H < 1 || W < 1 || r < 1) return KVAE_ERR_ARG;
+  if (g_wave_emu) {   // k_vae_epilogue_bwd_bias / k_vae_epilogue_bwd
+    kvae_wemu_epilogue_bwd(g_out, out, g_in, bias_partials, N, C, H, W, r, relu);
+    return KVAE_OK;
+  }
   const EpiShape s{N, C, H, W, r};
   const int64_t vol = (int64_t)C * H * W * r * r;
   for (int64_t o = 0; o < N * vol; ++o) epi_bwd_elem(s, g_out, out, g_in, o, relu);
@@ -857,6 +889,10 @@ int kvae_loss_head_fwd(const float *lpx, const float *regf, const float *mask, c
                        float scale, float vae_w, float kf_w, const float *w_dev, float *out, float *coef, int64_t n, void *) {
   if (!lpx || !regf || !elbo_kf || !beta || !out || !coef) return KVAE_ERR_NULL;
   if (n < 1) return KVAE_ERR_ARG;
+  if (g_wave_emu) {   // k_loss_head_fwd
+    kvae_wemu_loss_head_fwd(lpx, regf, mask, elbo_kf, beta, scale, vae_w, kf_w, w_dev, out, coef, n);
+    return KVAE_OK;
+  }
   float s0 = 0.f, s1 = 0.f, s2 = 0.f;
   for (int64_t i = 0; i < n; ++i) {
     const float mk = mask ? mask[i] : 1.f;
@@ -875,6 +911,10 @@ int kvae_loss_head_bwd(const float *g, const float *coef, const float *mask, flo
                        int64_t n, void *) {
   if (!g || !coef || !g_lpx || !g_regf || !g_kf) return KVAE_ERR_NULL;
   if (n < 1) return KVAE_ERR_ARG;
+  if (g_wave_emu) {   // k_loss_head_bwd
+    kvae_wemu_loss_head_bwd(g, coef, mask, g_lpx, g_regf, g_kf, n);
+    return KVAE_OK;
+  }
   for (int64_t i = 0; i < n; ++i) {
     const float mk = mask ? mask[i] : 1.f;
     g_lpx[i] = g[0] * coef[0] * mk;
@@ -887,6 +927,10 @@ int kvae_loss_head_bwd(const float *g, const float *coef, const float *mask, flo
 int kvae_lgssm_emission_means(const kvae_lgssm_problem *prob, const float *ms, const float *mf, float *a_s, float *a_f, void *) {
   if (!prob || !prob->C.ptr || (!ms != !a_s) || (!mf != !a_f) || (!a_s && !a_f)) return KVAE_ERR_NULL;
   if (prob->B < 1 || prob->T < 1 || prob->n < 1 || prob->p < 1 || prob->n > KVAE_MAX_DIM || prob->p > KVAE_MAX_DIM) return KVAE_ERR_DIMS;
+  if (g_wave_emu) {   // k_emission_means
+    kvae_wemu_emission_means(prob, ms, mf, a_s, a_f);
+    return KVAE_OK;
+  }
   const int n = prob->n, p = prob->p;
   for (int64_t b = 0; b < prob->B; ++b)
     for (int64_t t = 0; t < prob->T; ++t)

@@ -12,12 +12,15 @@
 // cores, with DPP traffic inside group-dependent branches, legal on the hardware where a DPP move only needs its own row - run
 // here too.  A wave-scope instruction that only some lanes reach (or a row-scope one only some lanes of a row reach) would wait
 // forever: every barrier has a deadline, past which the harness names the scope, the lane and the block and aborts.
-// Workgroups of more than one wavefront (launch_wg: 64, 128, 192 or 256 threads, the recurrent kernels of csrc/lstm_fast.h and
-// gru_fast.h): one host thread per lane of every wavefront of the block; __syncthreads() meets every lane of the BLOCK, all the
+// Workgroups of more than one wavefront (launch_wg: whole wavefronts up to the hardware's 1024 threads - the recurrent kernels of
+// csrc/lstm_fast.h and gru_fast.h at 256, k_colsum_v4 at 512, k_loss_head_fwd at 1024; blockIdx.x / .y / .z follow the grid): one host thread per lane of every wavefront of the block; __syncthreads() meets every lane of the BLOCK, all the
 // cross-lane instructions keep the scope above (their wavefront, or their row).  A __shared__ array of a kernel (KV_LDS /
 // KV_LDS16 of csrc/lds_decl.h) and the launch's dynamic LDS (KV_LDS_DYN) are heap allocations of exactly their size, made by the
 // first lane that reaches the declaration, filled with NaNs, freed when the block has ended: AddressSanitizer sees their bounds
 // (a static array of a template kernel is a COMDAT object, which it does not pad), and a read of an element no lane wrote is a NaN.
+// atomicAdd(float *, float) on an LDS or a global word is a real atomic of the host (a compare-exchange loop on the 32-bit word):
+// the lanes are host threads, so ThreadSanitizer sees an atomic and AddressSanitizer its address; the order of the adds is as
+// free as on the card.
 // Arithmetic of the MFMA shims: k-ascending fmaf chains in fp32, which is what the kernels' parity argument assumes.
 // This is a sanitizer / debug harness, slow by design (a barrier per instruction): tiny problems only.
 #pragma once
@@ -227,10 +230,10 @@ inline void launch(unsigned blocks, const std::function<void()> &body) {
   }
 }
 
-// launch_wg: a grid of workgroups of `threads` lanes (a multiple of 64, at most 256) with `dyn_bytes` of dynamic LDS, in
+// launch_wg: a grid of workgroups of `threads` lanes (a multiple of 64, at most 1024) with `dyn_bytes` of dynamic LDS, in
 // ascending order (x fastest), every lane of a workgroup a host thread.  The lane threads PERSIST over the blocks of a launch
-// (256 fresh threads per workgroup made a launch of a few hundred small blocks cost seconds): lane l runs lane l of block 0, 1,
-// 2, ... in turn.  What belongs to a block is still made for it alone - its Block (the block barrier, NaN-filled LDS objects of
+// (256 fresh threads per workgroup made a launch of a few hundred small blocks cost seconds) and over launches (LanePool below):
+// lane l runs lane l of block 0, 1, 2, ... in turn.  What belongs to a block is still made for it alone - its Block (the block barrier, NaN-filled LDS objects of
 // exact size) and its Waves (barriers, operand buffers) are built by the first lane that enters the block and destroyed by the
 // last one that leaves it, and every lane resets its parity counters and takes the block's index on entry - so nothing a block
 // did is visible to the next one.  There is no rendezvous BETWEEN blocks: a lane that has left block k enters block k + 1 and
@@ -241,41 +244,80 @@ struct BlockSlot {
   std::vector<Wave> waves;
   unsigned inside;   // lanes that have not left the block yet
 };
+// The lane threads also persist from launch to launch: a pool of host threads that grows to the widest workgroup asked for and
+// sleeps between launches (a column-sum case list is several hundred launches of 512 lanes, the loss head's 1024 lanes per launch;
+// fresh threads cost more than the kernels, most of all under ThreadSanitizer).  Worker l is lane l of every launch that has that
+// many lanes; the pool is never torn down (its threads are detached and sleep when the process ends).
+class LanePool {
+ public:
+  static LanePool &get() {
+    static LanePool *pool = new LanePool;
+    return *pool;
+  }
+  void run(unsigned lanes, const std::function<void(unsigned)> &job) {   // job(l) for l = 0 .. lanes - 1, each on its own thread
+    std::lock_guard<std::mutex> one_launch(launch_);
+    std::unique_lock<std::mutex> lk(m_);
+    while (workers_ < lanes) {
+      std::thread(&LanePool::work, this, workers_, gen_).detach();
+      ++workers_;
+    }
+    job_ = &job, lanes_ = lanes, pending_ = lanes, ++gen_;
+    wake_.notify_all();
+    while (pending_ != 0) done_.wait(lk);
+    job_ = nullptr;
+  }
+
+ private:
+  void work(unsigned l, uint64_t seen) {
+    std::unique_lock<std::mutex> lk(m_);
+    for (;;) {
+      while (gen_ == seen) wake_.wait(lk);
+      seen = gen_;
+      if (l >= lanes_) continue;
+      const std::function<void(unsigned)> *job = job_;
+      lk.unlock();
+      (*job)(l);
+      lk.lock();
+      if (--pending_ == 0) done_.notify_one();
+    }
+  }
+  std::mutex launch_, m_;
+  std::condition_variable wake_, done_;
+  const std::function<void(unsigned)> *job_ = nullptr;
+  unsigned workers_ = 0, lanes_ = 0, pending_ = 0;
+  uint64_t gen_ = 0;
+};
 inline void launch_wg(Dim3 grid, unsigned threads, size_t dyn_bytes, const std::function<void()> &body) {
-  if (threads == 0 || threads % 64 != 0 || threads > 256) {
-    fprintf(stderr, "wave_emu: a workgroup of %u threads is not 1..4 whole wavefronts\n", threads);
+  if (threads == 0 || threads % 64 != 0 || threads > 1024) {
+    fprintf(stderr, "wave_emu: a workgroup of %u threads is not 1..16 whole wavefronts\n", threads);
     abort();
   }
   const uint64_t nblocks = (uint64_t)grid.x * grid.y * grid.z;
   std::mutex m;
   std::map<uint64_t, BlockSlot *> live;
-  std::vector<std::thread> th;
-  th.reserve(threads);
-  for (unsigned l = 0; l < threads; ++l)
-    th.emplace_back([&, l] {
-      for (uint64_t b = 0; b < nblocks; ++b) {
-        BlockSlot *slot;
-        {
-          std::lock_guard<std::mutex> lk(m);
-          BlockSlot *&s = live[b];
-          if (!s) s = new BlockSlot(threads, dyn_bytes);
-          slot = s;
-        }
-        t_block = &slot->blk, t_wave = &slot->waves[l / 64], t_par = 0, t_rpar = 0;
-        t_tid = {l, 0, 0}, t_gdim = grid, t_bdim = {threads, 1, 1};
-        t_bid = {(unsigned)(b % grid.x), (unsigned)(b / grid.x % grid.y), (unsigned)(b / ((uint64_t)grid.x * grid.y))};
-        body();
-        t_block = nullptr, t_wave = nullptr;
-        bool last;
-        {
-          std::lock_guard<std::mutex> lk(m);
-          last = --slot->inside == 0;
-          if (last) live.erase(b);
-        }
-        if (last) delete slot;
+  LanePool::get().run(threads, [&](unsigned l) {
+    for (uint64_t b = 0; b < nblocks; ++b) {
+      BlockSlot *slot;
+      {
+        std::lock_guard<std::mutex> lk(m);
+        BlockSlot *&s = live[b];
+        if (!s) s = new BlockSlot(threads, dyn_bytes);
+        slot = s;
       }
-    });
-  for (auto &t : th) t.join();
+      t_block = &slot->blk, t_wave = &slot->waves[l / 64], t_par = 0, t_rpar = 0;
+      t_tid = {l, 0, 0}, t_gdim = grid, t_bdim = {threads, 1, 1};
+      t_bid = {(unsigned)(b % grid.x), (unsigned)(b / grid.x % grid.y), (unsigned)(b / ((uint64_t)grid.x * grid.y))};
+      body();
+      t_block = nullptr, t_wave = nullptr;
+      bool last;
+      {
+        std::lock_guard<std::mutex> lk(m);
+        last = --slot->inside == 0;
+        if (last) live.erase(b);
+      }
+      if (last) delete slot;
+    }
+  });
 }
 
 }  // namespace wemu
@@ -283,6 +325,20 @@ inline void launch_wg(Dim3 grid, unsigned threads, size_t dyn_bytes, const std::
 struct alignas(16) float4 {
   float x, y, z, w;
 };
+struct alignas(8) float2 {
+  float x, y;
+};
+inline float4 make_float4(float x, float y, float z, float w) { return float4{x, y, z, w}; }
+inline float2 make_float2(float x, float y) { return float2{x, y}; }
+
+// atomicAdd on an LDS or global float: returns the old value, as HIP's
+inline float atomicAdd(float *addr, float v) {
+  uint32_t *word = reinterpret_cast<uint32_t *>(addr);
+  uint32_t seen = __atomic_load_n(word, __ATOMIC_RELAXED);
+  while (!__atomic_compare_exchange_n(word, &seen, wemu::fbits(wemu::bitsf(seen) + v), true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {
+  }
+  return wemu::bitsf(seen);
+}
 
 // ---- what the kernel headers see ----------------------------------------------------------------------------------------------
 #define __device__
@@ -296,7 +352,7 @@ struct alignas(16) float4 {
 #define blockDim (wemu::t_bdim)
 #define __syncthreads() wemu::sync_block()
 #define __shfl(v, src, w) wemu::shfl((v), (src), (w))
-#define __shfl_xor(v, mask, w) wemu::shfl_xor((v), (mask), (w))
+#define __shfl_xor(v, mask, ...) wemu::shfl_xor((v), (mask), 64)   // (the width, where a kernel gives one, is the wavefront)
 #define __ballot(p) wemu::ballot((p))
 #define __any(p) wemu::any((p))
 #define __builtin_amdgcn_mov_dpp(v, ctrl, rm, bm, bc) wemu::mov_dpp((v), (ctrl), (rm), (bm), (bc))

@@ -19,8 +19,9 @@ using namespace kvae;
 
 // launches so far: 0 / 1 LSTM fwd / bwd, 2 / 3 bi-GRU fwd / bwd, 4 / 5 regime lane-grid fwd / bwd, 6 / 7 regime thread-per-
 // sequence fwd / bwd, 8 / 9 regime LDS bodies fwd / bwd (run by hostsim.cpp, noted here); 10 .. 32: the reduction, mixture and
-// linear-head kernels, one index per instance (wave_emu_reduce.cpp)
-constexpr int kKinds = 33;
+// linear-head kernels, one index per instance (wave_emu_reduce.cpp); 33 .. 45: the optimizer, loss-head, column-sum, emission and
+// conv-epilogue kernels, one index per instance (wave_emu_step.cpp)
+constexpr int kKinds = 46;
 static int g_launches[kKinds] = {};
 // the switches of the GPU dispatch: KVAE_REGIME_TPP (kvae_lgssm.hip: 1 lane grid up to the batch threshold, then thread per
 // sequence; 2 thread per sequence always; 0 the LDS bodies) and the threshold itself, settable here so that the thread-per-

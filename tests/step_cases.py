@@ -1,8 +1,9 @@
 """The kernels BETWEEN the compute kernels of a training step, one element at a time: kvae_clip_adam (k_grad_sumsq + k_clip_adam,
-csrc/kvae_vae.hip), kvae_loss_head_fwd/bwd (csrc/vae_heads.h), kvae_colsum / kvae_colsum2 with the two-pass folding of
-_native.colsum / colsum_pair, and kvae_lgssm_emission_means.  Device-agnostic case functions taking (lib, DEV, ...): the GPU tier
-(tests/test_gpu_step_kernels.py) runs them on the gfx950 library, the CPU tier (tests/test_step_kernels.py) on the plain-loop twins
-of tests/hostsim/hostsim.cpp.
+csrc/clip_adam.h), kvae_loss_head_fwd/bwd (csrc/vae_heads.h), kvae_colsum / kvae_colsum2 (csrc/colsum.h) with the two-pass folding
+of _native.colsum / colsum_pair, kvae_lgssm_emission_means (csrc/emission_means.h) and kvae_bias_shuffle_act_fwd/bwd
+(csrc/vae_epilogue.h).  Device-agnostic case functions taking (lib, DEV, ...): the GPU tier (tests/test_gpu_step_kernels.py) runs
+them on the gfx950 library, the CPU tiers on the same kernels on emulated workgroups (tests/test_wave_emu_step.py) and on the
+plain-loop twins of tests/hostsim/hostsim.cpp (tests/test_step_kernels.py).
 
 Reference: a float64 restatement of the operation on the same float32 input values.  For clip_adam every scalar (lr, beta1, beta2,
 eps, weight_decay, clip) is first rounded through float32 - that is what ctypes.c_float hands the kernel, and with the exact
@@ -30,18 +31,20 @@ KVAE_ERR_DIMS, KVAE_ERR_NULL, KVAE_ERR_ARG = 1, 2, 4
 # Ratios: adam.m / adam.v / adam.upd per segment and step, max|err| / max(max|ref| on the segment, 1e-2 max|ref| on the buffer),
 # upd = p_after - p_before formed in float64; adam.norm relative; head.* relative to the float64 sum of the absolute contributions
 # the scalar is built from; head.coef relative; head.g per element relative to max|ref|; colsum per column relative to
-# sum_r |x[r, c]|; emission per (b, t) by parity_cases._per_step_ratio.
-# Largest ratios the implementations reach against the same float64 runs, host twin | gfx950:
-#   adam.m 2.5e-07 | 2.5e-07   adam.v 2.7e-07 | 2.7e-07   adam.upd 4.1e-06 | 4.1e-06   adam.norm 5.3e-08 | 6.5e-08
-#   head.recon 6.3e-08 | 7.5e-08   head.reg 9.3e-08 | 1.4e-08   head.vae 5.8e-08 | 8.3e-08   head.tot 7.1e-08 | 1.1e-07
-#   head.coef 6.5e-08 | 6.5e-08   head.g 8.1e-08 | 8.1e-08
-#   colsum 1.7e-07 | 1.4e-07   emission 5.9e-07 | 5.9e-07
+# sum_r |x[r, c]|; emission per (b, t) by parity_cases._per_step_ratio; epi.bias per (partial row, channel) and per channel over
+# all rows, relative to the sum of |g| over the same elements.
+# Largest ratios the implementations reach against the same float64 runs, host twin | emulated kernels | gfx950:
+#   adam.m 2.5e-07 | 2.5e-07 | 2.5e-07   adam.v 2.7e-07 | 2.7e-07 | 2.7e-07   adam.upd 4.1e-06 | 4.1e-06 | 4.1e-06
+#   adam.norm 5.3e-08 | 6.5e-08 | 6.5e-08   head.recon 6.3e-08 | 7.5e-08 | 7.5e-08   head.reg 9.3e-08 | 1.0e-08 | 1.4e-08
+#   head.vae 5.8e-08 | 7.9e-08 | 8.3e-08   head.tot 7.1e-08 | 7.0e-08 | 1.1e-07   head.coef 6.5e-08 | 6.5e-08 | 6.5e-08
+#   head.g 8.1e-08 | 8.1e-08 | 8.1e-08   colsum 1.7e-07 | 1.4e-07 | 1.4e-07   emission 5.9e-07 | 4.0e-07 | 5.9e-07
+#   epi.bias 1.2e-07 | 9.2e-08 | 9.2e-08
 # Less than a factor 2 under the bar: none on gfx950 (smallest head.tot 2.55 x, head.vae 2.79 x); on the host twin head.reg, 1.95 x
 # (the twin sums the frames in one sequential float32 loop).  DESIGN section 2.
 YARDSTICK = {   # float32 torch restatement against the float64 reference, largest ratio over every case list
     "adam.m": 2.49e-7, "adam.v": 2.69e-7, "adam.upd": 4.13e-6, "adam.norm": 6.73e-8,
     "head.recon": 6.33e-8, "head.reg": 4.53e-8, "head.vae": 5.81e-8, "head.tot": 7.09e-8, "head.coef": 6.50e-8, "head.g": 8.09e-8,
-    "colsum": 1.39e-7, "emission": 5.09e-7,
+    "colsum": 1.39e-7, "emission": 5.09e-7, "epi.bias": 8.04e-8,
 }
 TOL = {k: 4.0 * v for k, v in YARDSTICK.items()}
 
@@ -316,8 +319,8 @@ def adam_rejects(lib, DEV):
 
 def adam_repeatable(lib, DEV, id_):
     """The same call from the same state twice: p, m, v and norm_out equal bit for bit (k_clip_adam: every block folds the same
-    partials in the same order)."""
-    spec, gen, n, n_seg, seg_of, gscale, p0, m0, v0, steps0 = _adam_problem(adam_case_by_id(id_))
+    partials in the same order).  id_: a case id, or a case of the caller's own."""
+    spec, gen, n, n_seg, seg_of, gscale, p0, m0, v0, steps0 = _adam_problem(adam_case_by_id(id_) if isinstance(id_, str) else id_)
     grad = torch.randn(n, generator=gen) * gscale
     runs = []
     for _ in range(2):
@@ -507,10 +510,10 @@ HEAD_IDS = [c["id"] for c in HEAD_CASES]
 HEAD_BWD_N = 256 * 32 * 256 + 3   # past epi_grid's 8192 blocks: the grid-stride round of k_loss_head_bwd
 
 
-def head_bwd_large(lib, DEV, impl="kernel", bars=None, worst=None):
-    """The backward alone at n = 2097155 with a coef of the test's own: every element, the last three included."""
+def head_bwd_large(lib, DEV, impl="kernel", bars=None, worst=None, n=HEAD_BWD_N):
+    """The backward alone at n = 2097155 with a coef of the test's own: every element, the last three included.  (n: the emulated
+    tier lowers epi_grid's cap and runs the same rounds at a few thousand elements.)"""
     bars = TOL if bars is None else bars
-    n = HEAD_BWD_N
     gen = torch.Generator().manual_seed(77)
     mk = (torch.rand(n, generator=gen) < 0.7).float()
     coef, g = torch.tensor([-3.25e-4, -7.5e-3, 0.8]), torch.tensor([2.5])
@@ -770,6 +773,170 @@ def emission_rejects(lib, DEV):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# 5. kvae_bias_shuffle_act_fwd / bwd (csrc/vae_epilogue.h), per element through the C ABI
+# ---------------------------------------------------------------------------------------------------------------------------
+# Forward: one float32 add, a permutation and a select - `out` equals float32 torch on the CPU bit for bit.  Backward: g_in is a
+# select and a permutation (bit for bit, and bit-repeatable); bias_partials [kvae_bias_partial_rows(N), C r^2] is zeroed by the call
+# and summed with float atomics whose order is free, so it is compared, per row and summed over the rows, against float64 sums of
+# the same elements relative to the sum of |g| (key epi.bias), with no repeatability assertion.
+# (N, C, H, W, r), floats `in` / `out` sit past a 16-byte boundary, the kernel the gate of csrc/vae_epilogue.h picks
+EPI_FWD_CASES = [
+    ((3, 5, 3, 4, 1), 0, 0, "epi.fwd_v4<1>"),
+    ((2, 3, 3, 2, 2), 0, 0, "epi.fwd_v4<2>"),      # W / 2 = 1: one quad per output row
+    ((2, 3, 3, 6, 2), 0, 0, "epi.fwd_v4<2>"),      # three quads per output row
+    ((2, 3, 3, 5, 1), 0, 0, "epi.fwd"),            # scalar by shape: W % 4 != 0
+    ((2, 3, 3, 3, 2), 0, 0, "epi.fwd"),            # odd W at r = 2
+    ((2, 3, 5, 7, 3), 0, 0, "epi.fwd"),            # r = 3
+    ((3, 5, 3, 4, 1), 1, 0, "epi.fwd"),            # scalar by pointer: `in` 4 bytes past a 16-byte boundary
+    ((2, 3, 3, 6, 2), 0, 1, "epi.fwd"),            # ... and `out`
+    ((2, 65, 1, 2, 2), 0, 0, "epi.fwd_v4<2>"),     # 260 input channels
+]
+# total / 4 (v4) and total (scalar) just above epi_grid's 8192 x 256 with a ragged remainder: a second grid-stride round of 4 quads
+# and of 28 elements.  With the cap lowered to 3 blocks (CPU tier): two full rounds of 768 and a third of 264.
+EPI_STRIDE_CARD = [((174763, 2, 1, 6, 2), "epi.fwd_v4<2>"), ((233020, 1, 1, 1, 3), "epi.fwd")]
+EPI_STRIDE_EMU = [((150, 2, 1, 6, 2), "epi.fwd_v4<2>"), ((200, 1, 1, 1, 3), "epi.fwd")]
+# (N, C, H, W, r), relu, bias partials wanted, floats g_in sits past a 16-byte boundary
+EPI_BWD_CASES = (
+    [((n, 3, 2, 2, 2), 1, True, 0) for n in (1, 31, 32, 33, 65)]      # the 32-sample chunk: one short row, full rows, 1 + 1, 2 + 1
+    + [((2, 3, 5, 7, 2), 1, True, 0),                                 # 420 positions per sample: a ragged second block
+       ((2, 65, 1, 2, 2), 1, True, 0),                                # 260 channels: more bins than the 256 threads that zero them
+       ((2, 65, 1, 2, 2), 0, True, 0),
+       ((33, 3, 2, 2, 2), 0, True, 0),                                # relu = 0: `out` is NULL
+       ((3, 5, 3, 4, 1), 1, True, 0), ((2, 3, 5, 7, 3), 1, True, 1),   # r = 1, r = 3 (g_in one float past the boundary)
+       ((2, 3, 5, 7, 3), 1, False, 0), ((3, 5, 3, 4, 1), 0, False, 0), ((2, 3, 3, 3, 2), 1, False, 1)])   # k_vae_epilogue_bwd
+EPI_BWD_STRIDE_CARD, EPI_BWD_STRIDE_EMU = (233020, 1, 1, 1, 3), (200, 1, 1, 1, 3)   # k_vae_epilogue_bwd past epi_grid's cap
+
+
+def case_id(v):
+    """A pytest id without blanks: (2, 3, 3, 6, 2) -> 2x3x3x6x2."""
+    return "x".join(str(e) for e in v) if isinstance(v, tuple) else str(v)
+
+
+def epi_inputs(shape, seed=0):
+    """x [N, C r^2, H, W] and bias [C r^2] of the forward; g and `out` [N, C, H r, W r] of the backward.  x holds three elements
+    whose sum with the bias is exactly +0.0; `out` starts with +0.0, -0.0 and a NaN (the mask is out > 0)."""
+    N, Cc, H, W, r = shape
+    gen = torch.Generator().manual_seed(9000 + seed + 7 * N + W)
+    x, b = torch.randn(N, Cc * r * r, H, W, generator=gen), torch.randn(Cc * r * r, generator=gen)
+    flat = x.view(N, Cc * r * r, -1)
+    for ch in range(min(3, Cc * r * r)):
+        flat[N - 1, ch, 0] = -b[ch]
+    g, out = torch.randn(N, Cc, H * r, W * r, generator=gen), torch.randn(N, Cc, H * r, W * r, generator=gen)
+    o = out.view(-1)
+    o[0], o[1], o[2] = 0.0, -0.0, math.nan
+    return x, b, g, out
+
+
+def epi_fwd_case(lib, DEV, shape, off_in=0, off_out=0):
+    """Both values of relu: `out` bit for bit against torch (pixel_shuffle(x + b), then relu), the sentinels around it intact, the
+    input untouched."""
+    N, Cc, H, W, r = shape
+    x, b, _, _ = epi_inputs(shape)
+    pre = torch.nn.functional.pixel_shuffle(x + b.view(1, -1, 1, 1), r)
+    b_d = b.to(DEV)
+    X = Guarded(DEV, x.numel(), off_in, init=x)
+    for relu in (0, 1):
+        ref = torch.relu(pre) if relu else pre
+        out = Guarded(DEV, x.numel(), off_out)
+        rc = lib.dll.kvae_bias_shuffle_act_fwd(X.ptr, _p(b_d), out.ptr, N, Cc, H, W, r, relu, None)
+        _sync(DEV)
+        assert rc == 0, (shape, relu)
+        assert out.guards_intact() and X.guards_intact(), (shape, relu, "written outside the output")
+        got = out.cpu()
+        same = _bits(got) == _bits(ref.reshape(-1))
+        assert bool(same.all()), (shape, relu, off_in, off_out, "first differing element", int((~same).int().argmax()),
+                                  int((~same).sum()))
+        assert torch.equal(_bits(X.cpu()), _bits(x.reshape(-1))), (shape, "the input was written")
+
+
+def _epi_bias_ratios(rows, ref_in, per_chunk):
+    """Largest |err| / sum |g| per (partial row, channel) and per channel over all rows; rows: [R, Cin] (float32 or float64 sums),
+    ref_in: the float32 values of g_in [N, Cin, H, W]."""
+    N = ref_in.shape[0]
+    g64 = ref_in.double()
+    worst = 0.0
+    tot_ref, tot_abs = g64.sum((0, 2, 3)), g64.abs().sum((0, 2, 3))
+    parts = [(rows.double().sum(0), tot_ref, tot_abs)]
+    for k in range(rows.shape[0]):
+        chunk = g64[k * per_chunk:min((k + 1) * per_chunk, N)]
+        parts.append((rows[k].double(), chunk.sum((0, 2, 3)), chunk.abs().sum((0, 2, 3))))
+    for got, ref, mag in parts:
+        err = (got - ref).abs()
+        ratio = torch.where(err == 0, torch.zeros_like(err), err / mag.clamp_min(1e-300))
+        ratio = torch.where(torch.isnan(ratio), torch.full_like(ratio, math.inf), ratio)
+        worst = max(worst, float(ratio.max()))
+    return worst
+
+
+def epi_bwd_case(lib, DEV, shape, relu, want_bias, off=0, per_chunk=32, impl="kernel", bars=None, worst=None):
+    """g_in bit for bit against torch (pixel_unshuffle of g where out > 0) and bit-repeatable over two calls; bias_partials of exactly
+    kvae_bias_partial_rows(N) x C r^2 floats, pre-filled with the sentinel (the call zeroes it), under the epi.bias bar; the guards
+    around both intact.  impl "f32": the float32 torch sums of the same elements (the yardstick)."""
+    bars = TOL if bars is None else bars
+    N, Cc, H, W, r = shape
+    Cin = Cc * r * r
+    _, _, g, out = epi_inputs(shape, seed=1)
+    masked = torch.where(out > 0, g, torch.zeros(())) if relu else g
+    ref_in = torch.nn.functional.pixel_unshuffle(masked, r)
+    assert ref_in.shape == (N, Cin, H, W)
+    rows = (N + per_chunk - 1) // per_chunk
+    if impl == "f32":
+        if want_bias:
+            f32 = torch.stack([ref_in[k * per_chunk:(k + 1) * per_chunk].sum((0, 2, 3)) for k in range(rows)])
+            _note(worst, "epi.bias", _epi_bias_ratios(f32, ref_in, per_chunk))
+        return
+    assert lib.dll.kvae_bias_partial_rows(N) == rows, (N, per_chunk)
+    g_d, out_d = g.to(DEV), (out.to(DEV) if relu else None)
+    runs = []
+    for _ in range(2):
+        G = Guarded(DEV, g.numel(), off)
+        BP = Guarded(DEV, rows * Cin) if want_bias else None
+        rc = lib.dll.kvae_bias_shuffle_act_bwd(_p(g_d), _p(out_d), G.ptr, BP.ptr if BP else None, N, Cc, H, W, r, relu, None)
+        _sync(DEV)
+        assert rc == 0, (shape, relu, want_bias)
+        assert G.guards_intact(), (shape, relu, want_bias, "written outside g_in")
+        got = G.cpu()
+        same = _bits(got) == _bits(ref_in.reshape(-1))
+        assert bool(same.all()), (shape, relu, want_bias, "g_in: first differing element", int((~same).int().argmax()), int((~same).sum()))
+        if want_bias:
+            assert BP.guards_intact(), (shape, relu, "written outside bias_partials")
+            ratio = _epi_bias_ratios(BP.cpu().view(rows, Cin), ref_in, per_chunk)
+            _note(worst, "epi.bias", ratio)
+            assert ratio < bars["epi.bias"], (shape, relu, "epi.bias", ratio, bars["epi.bias"])
+        runs.append(got)
+    assert torch.equal(_bits(runs[0]), _bits(runs[1])), (shape, "g_in is not repeatable")
+    assert torch.equal(_bits(g_d.cpu()), _bits(g)), (shape, "g_out was written")
+
+
+def epi_rejects(lib, DEV):
+    """NULL operands (KVAE_ERR_NULL; for the backward `out` only with relu), any extent below 1 (KVAE_ERR_ARG): nothing written."""
+    shape = (2, 3, 3, 2, 2)
+    N, Cc, H, W, r = shape
+    x, b, g, out = epi_inputs(shape)
+    n, Cin = x.numel(), Cc * r * r
+    x_d, b_d, g_d, out_d = x.to(DEV), b.to(DEV), g.to(DEV), out.to(DEV)
+    O, G, BP = Guarded(DEV, n), Guarded(DEV, n), Guarded(DEV, Cin)
+    fwd, bwd = lib.dll.kvae_bias_shuffle_act_fwd, lib.dll.kvae_bias_shuffle_act_bwd
+    assert fwd(None, _p(b_d), O.ptr, N, Cc, H, W, r, 1, None) == KVAE_ERR_NULL
+    assert fwd(_p(x_d), None, O.ptr, N, Cc, H, W, r, 1, None) == KVAE_ERR_NULL
+    assert fwd(_p(x_d), _p(b_d), None, N, Cc, H, W, r, 1, None) == KVAE_ERR_NULL
+    assert bwd(None, _p(out_d), G.ptr, BP.ptr, N, Cc, H, W, r, 1, None) == KVAE_ERR_NULL
+    assert bwd(_p(g_d), _p(out_d), None, BP.ptr, N, Cc, H, W, r, 1, None) == KVAE_ERR_NULL
+    assert bwd(_p(g_d), None, G.ptr, BP.ptr, N, Cc, H, W, r, 1, None) == KVAE_ERR_NULL      # relu needs `out`
+    for k in range(5):
+        for bad in (0, -1):
+            ext = [N, Cc, H, W, r]
+            ext[k] = bad
+            assert fwd(_p(x_d), _p(b_d), O.ptr, *ext, 1, None) == KVAE_ERR_ARG, ext
+            assert bwd(_p(g_d), _p(out_d), G.ptr, BP.ptr, *ext, 1, None) == KVAE_ERR_ARG, ext
+    _sync(DEV)
+    assert O.untouched() and G.untouched() and BP.untouched(), "a refused call wrote"
+    assert bwd(_p(g_d), None, G.ptr, BP.ptr, N, Cc, H, W, r, 0, None) == 0                  # ... and only with relu
+    _sync(DEV)
+    assert G.guards_intact() and BP.guards_intact()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 def yardsticks():
     """The float32 torch restatements against the float64 references over every case list: the numbers YARDSTICK holds."""
     worst = {}
@@ -791,6 +958,8 @@ def yardsticks():
     for B, T, n, p in EMISSION_SHAPES:
         for layout in EMISSION_LAYOUTS:
             emission_ops("cpu", B, T, n, p, layout, impl="f32", bars=free, worst=worst)
+    for shape, relu, want_bias, off in EPI_BWD_CASES:
+        epi_bwd_case(None, "cpu", shape, relu, want_bias, off, impl="f32", bars=free, worst=worst)
     return worst
 
 

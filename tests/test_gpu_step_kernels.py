@@ -1,6 +1,8 @@
 """GPU tier of tests/step_cases.py: kvae_clip_adam (k_grad_sumsq + k_clip_adam), kvae_loss_head_fwd/bwd, kvae_colsum / kvae_colsum2
-with the folding of _native.colsum / colsum_pair, and kvae_lgssm_emission_means on the gfx950 library, per element against float64
-under bars of 4 x the float32 yardstick.  The CPU tier (tests/test_step_kernels.py) runs the same cases on the plain-loop twins."""
+with the folding of _native.colsum / colsum_pair, kvae_lgssm_emission_means and kvae_bias_shuffle_act_fwd/bwd on the gfx950 library,
+per element against float64 under bars of 4 x the float32 yardstick (the conv epilogue's permutation and select: bit for bit
+against float32 torch).  The CPU tiers run the same cases on the product's kernels on emulated workgroups
+(tests/test_wave_emu_step.py) and on the plain-loop twins (tests/test_step_kernels.py)."""
 import pytest
 
 import step_cases as cases
@@ -83,6 +85,30 @@ def test_emission_means_c_abi(lib, B, T, n, p):
 
 def test_emission_means_rejects(lib):
     cases.emission_rejects(lib, DEV)
+
+
+@pytest.mark.parametrize("shape,off_in,off_out,kernel", cases.EPI_FWD_CASES, ids=cases.case_id)
+def test_epilogue_fwd_per_element(lib, shape, off_in, off_out, kernel):
+    cases.epi_fwd_case(lib, DEV, shape, off_in, off_out)
+
+
+@pytest.mark.parametrize("shape,kernel", cases.EPI_STRIDE_CARD, ids=cases.case_id)
+def test_epilogue_fwd_grid_stride(lib, shape, kernel):
+    """total / 4 (float4 kernel) and total (scalar kernel) just above epi_grid's 8192 x 256: a second, ragged grid-stride round."""
+    cases.epi_fwd_case(lib, DEV, shape)
+
+
+@pytest.mark.parametrize("shape,relu,want_bias,off", cases.EPI_BWD_CASES, ids=cases.case_id)
+def test_epilogue_bwd_per_element(lib, shape, relu, want_bias, off):
+    cases.epi_bwd_case(lib, DEV, shape, relu, want_bias, off, worst=_WORST)
+
+
+def test_epilogue_bwd_grid_stride(lib):
+    cases.epi_bwd_case(lib, DEV, cases.EPI_BWD_STRIDE_CARD, 1, False)
+
+
+def test_epilogue_rejects(lib):
+    cases.epi_rejects(lib, DEV)
 
 
 def test_report_largest_ratios():

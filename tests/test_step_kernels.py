@@ -1,8 +1,10 @@
-"""CPU tier of tests/step_cases.py: the cases of tests/test_gpu_step_kernels.py on the PLAIN-LOOP TWINS of tests/hostsim/hostsim.cpp
-(kvae_clip_adam, kvae_loss_head_fwd/bwd, kvae_colsum, kvae_colsum2, kvae_lgssm_emission_means) and, through them, the Python
-wrappers (LossHead.apply, _native.colsum / colsum_pair, lgssm_ops.emission_means).  The twins are separate re-implementations, so
-this tier checks the CASES, the float64 REFERENCES, the YARDSTICKS and the wrappers' own logic - not the kernels: those live in
-.hip units, outside the emulated-workgroup tier, and are held by the GPU tier alone."""
+"""CPU tier of tests/step_cases.py on the PLAIN-LOOP TWINS of tests/hostsim/hostsim.cpp (kvae_clip_adam, kvae_loss_head_fwd/bwd,
+kvae_colsum, kvae_colsum2, kvae_lgssm_emission_means, kvae_bias_shuffle_act_fwd/bwd with the emulation off) and, through them, the
+Python wrappers (LossHead.apply, _native.colsum / colsum_pair, lgssm_ops.emission_means).  The twins are separate
+re-implementations: this tier checks the CASES, the float64 REFERENCES, the YARDSTICKS the bars derive from and the wrappers' own
+logic, quickly and at the GPU tier's sizes.  The kernels themselves - csrc/clip_adam.h, vae_heads.h, colsum.h, emission_means.h,
+vae_epilogue.h - run the same case functions on emulated workgroups in tests/test_wave_emu_step.py, and on the card in
+tests/test_gpu_step_kernels.py (DESIGN sections 2, 5 and 8)."""
 import pytest
 import torch
 
@@ -110,3 +112,17 @@ def test_emission_means_c_abi(hostsim_backend, B, T, n, p):
 
 def test_emission_means_rejects(hostsim_backend):
     cases.emission_rejects(hostsim_backend, DEV)
+
+
+@pytest.mark.parametrize("shape,off_in,off_out,kernel", cases.EPI_FWD_CASES, ids=cases.case_id)
+def test_epilogue_fwd_per_element(hostsim_backend, shape, off_in, off_out, kernel):
+    cases.epi_fwd_case(hostsim_backend, DEV, shape, off_in, off_out)
+
+
+@pytest.mark.parametrize("shape,relu,want_bias,off", cases.EPI_BWD_CASES, ids=cases.case_id)
+def test_epilogue_bwd_per_element(hostsim_backend, shape, relu, want_bias, off):
+    cases.epi_bwd_case(hostsim_backend, DEV, shape, relu, want_bias, off)
+
+
+def test_epilogue_rejects(hostsim_backend):
+    cases.epi_rejects(hostsim_backend, DEV)
