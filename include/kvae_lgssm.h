@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 #define KVAE_MAX_DIM 16
-#define KVAE_ABI_VERSION 21
+#define KVAE_ABI_VERSION 22
 
 typedef enum {
   KVAE_OK = 0,
@@ -768,6 +768,76 @@ typedef struct {
  * nor a statistic is asked for), the reduction (skipped when no statistic is asked for), seq_ll. */
 int kvae_lgssm_switching_em(const kvae_sws_problem *prob, const kvae_em_stats *st, void *stream);
 int64_t kvae_lgssm_switching_em_ws_floats(int32_t B, int32_t K, int32_t n, int32_t m);
+
+/* ---- Rao-Blackwellised particle filter of the switching model (kvae/model/model.py KVAE.particle_filter_regimes) ----------------
+ * The model and operands of kvae_lgssm_switching_filter, without its GPB2 collapse: G independent replicate filters of N particles
+ * for each of B sequences.  Particle (b, g, i) holds a regime r, a log weight lw (normalised inside its replicate) and an exact
+ * Kalman belief (mu, Sigma).  Every step t, with W = exp(lw) the weights before the step:
+ *   for every regime j: the predict of regime j and l_j = log N(a_t; C mu_p, C Sigma_p C^T + R) by the ladder of
+ *       kvae_lgssm_predictive (0 on a hidden step) - the per-pair statements of the switching filter
+ *   log c_j = log P[r, j] + l_j   (the uniform matrix 1/K in place of P at step 0 without a carried state)
+ *   inc = logsumexp_j log c_j     e_j = exp(log c_j - max_j log c_j)
+ *   ll_t = log sum_i W_i exp(inc_i)   (0 on a hidden step)        lw'_i = lw_i + inc_i - ll_t          W' = exp(lw')
+ *   regime_filt_t(j) = sum_i W'_i e_ij / sum_j e_ij               (Rao-Blackwellised over the draw)
+ *   draw s = the lowest j with e_0 + .. + e_j > theta sum_j e_j, theta = pf_regime[b,g,t,i]; the last j with e_j > 0 if none
+ *   belief = the measurement update under regime s (gain times mask_t, Joseph form, symmetrised); r = s
+ *   mus_filt_t, Sigmas_filt_t = the moment match of the N beliefs under W';   ess_t = 1 / sum_i W'_i^2
+ *   levels_t = the largest ladder level over the (i, j) with P[r_i, j] > 0
+ *   resample (systematic) when ess_threshold >= 1, or when 0 < ess_threshold < 1 and ess_t < ess_threshold N:
+ *       position_i = (phi + i) / N, phi = pf_resample[b,g,t]; ancestors_t[i] = the first slot whose inclusive cumulative W' exceeds
+ *       position_i (the last slot if none; the kernel's scan is a fixed-order tree sum, monotone up to rounding, and the search
+ *       may settle on a neighbour whose own weight is below that rounding); particles copy (r, mu, Sigma) from their ancestor,
+ *       lw = -log N.
+ *       Without resampling ancestors_t = identity.
+ * The fully adapted proposal makes inc independent of the draw: exp(sum_t ll_t) is an unbiased estimate of p(a | u) for any N.
+ * out_* is the state after the last step's resampling decision; a call that carries it in (state_*: all four or none), with the
+ * matching slices of the draws, continues the stream with the same bits.  paths [B,G,N,T]: the lineage of final slot n, walked
+ * back over ancestors / regimes by a second kernel (needs both).  seq_ll reads ll.
+ * Built for fp32, K <= 8, n <= 4, m <= 4, p == 2, N in {64, 128, 256}: one workgroup of N / 64 wavefronts per (b, g), lane =
+ * particle, belief and weight in registers, the dynamics in LDS (csrc/lgssm_spf.h).  No atomics, every reduction in a fixed
+ * order, every output element written once; two calls give the same bits, any output may be NULL and the bits of the others do
+ * not depend on it. */
+typedef struct {
+  int32_t B, G, T, K, N, n, m, p;
+  float ess_threshold;        /* in [0, 1]: 0 never resamples, 1 always (no comparison), else ess_t < ess_threshold N      */
+  const float *A;             /* [K,n,n]                                                                                 */
+  const float *Bm;            /* [K,n,m]                                                                                 */
+  const float *Q;             /* [K,n,n]                                                                                 */
+  const float *C;             /* [p,n]                                                                                   */
+  const float *R;             /* [p,p]                                                                                   */
+  const float *P;             /* [K,K]    transition matrix, rows sum to 1                                               */
+  const float *mu0;           /* [n]      read only without a carried state                                              */
+  const float *Sigma0;        /* [n,n]                                                                                   */
+  const float *y;             /* [B,T,p]                                                                                 */
+  const float *u;             /* [B,T,m]                                                                                 */
+  const float *mask;          /* [B,T] 1 = observed, or NULL: every step observed                                        */
+  const float *pf_regime;     /* [B,G,T,N] uniform draws in [0,1) of the regime of every particle and step               */
+  const float *pf_resample;   /* [B,G,T]   uniform draws in [0,1) of the systematic resampling                           */
+  const float *state_log_w;   /* [B,G,N]       carried state in: all four or none                                        */
+  const int32_t *state_regime;/* [B,G,N]                                                                                 */
+  const float *state_mu;      /* [B,G,N,n]                                                                               */
+  const float *state_Sigma;   /* [B,G,N,n,n]                                                                             */
+  float *ll;                  /* [B,G,T]   outputs: each may be NULL                                                     */
+  float *seq_ll;              /* [B,G]     sum_t ll in a fixed order; needs ll                                           */
+  float *regime_filt;         /* [B,G,T,K]                                                                               */
+  float *mus_filt;            /* [B,G,T,n]                                                                               */
+  float *Sigmas_filt;         /* [B,G,T,n,n]                                                                             */
+  float *ess;                 /* [B,G,T]                                                                                 */
+  int32_t *resampled;         /* [B,G,T]   1 where step t resampled                                                      */
+  int32_t *regimes;           /* [B,G,T,N] the draw of slot i at step t, before resampling                               */
+  int32_t *ancestors;         /* [B,G,T,N]                                                                               */
+  int32_t *levels;            /* [B,G,T]                                                                                 */
+  int32_t *paths;             /* [B,G,N,T] needs regimes and ancestors                                                   */
+  float *out_log_w;           /* [B,G,N]       carried state out                                                         */
+  int32_t *out_regime;        /* [B,G,N]                                                                                 */
+  float *out_mu;              /* [B,G,N,n]                                                                               */
+  float *out_Sigma;           /* [B,G,N,n,n]                                                                             */
+} kvae_spf_problem;
+/* KVAE_ERR_NULL: prob or a required input NULL, seq_ll without ll, or paths without regimes and ancestors; KVAE_ERR_DIMS: B, G or
+ * T < 1; KVAE_ERR_ARG: a shape outside what is built (K outside [1,8], n or m outside [1,4], p != 2, N not 64, 128 or 256), an
+ * ess_threshold outside [0,1], a partly given carried state, or more replicates than one grid holds.  Nothing is written on
+ * error.  At most three launches: the sweep, the lineages, seq_ll. */
+int kvae_lgssm_switching_pf(const kvae_spf_problem *prob, void *stream);
 
 /* ---- misc --------------------------------------------------------------------------------- */
 int kvae_abi_version(void);

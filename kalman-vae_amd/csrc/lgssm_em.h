@@ -243,3 +243,7 @@ extern "C" int kvae_lgssm_switching_em(const kvae_sws_problem *prob, const kvae_
 extern "C" int64_t kvae_lgssm_switching_em_ws_floats(int32_t B, int32_t K, int32_t n, int32_t m) { return kvae_em::em_ws_floats(B, K, n, m); }
 extern "C" int kvae_wemu_switching_em_launches(int which) { return which >= 0 && which <= 3 ? kvae_em::emu_launches()[which] : -1; }
 #endif
+
+#if defined(KVAE_WAVE_EMU)
+#include "lgssm_spf.h"    // likewise kvae_lgssm_switching_pf
+#endif

@@ -17,7 +17,7 @@ LIB_PATH = _HERE / "lib" / "libkvae_lgssm.so"
 KVAE_MAX_DIM = 16
 KVAE_MAX_K = 16
 LSTM_MAX_H, LSTM_MAX_I = 52, 16
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 _STATUS = {1: "KVAE_ERR_DIMS (n, m, p must be in [1,16]; B, T >= 1)", 2: "KVAE_ERR_NULL", 3: "KVAE_ERR_LAUNCH",
            4: "KVAE_ERR_ARG"}
@@ -95,6 +95,14 @@ class EmStats(C.Structure):  # kvae_em_stats
     _fields_ = [(k, C.c_void_p) for k in ("ws", "N", "S11", "S10", "S00", "counts", "Syz", "Szz", "Syy", "Nobs", "z0", "z0z0", "nseq")]
 
 
+class SpfProblem(C.Structure):  # kvae_spf_problem
+    _fields_ = ([(k, C.c_int32) for k in ("B", "G", "T", "K", "N", "n", "m", "p")] + [("ess_threshold", C.c_float)]
+                + [(k, C.c_void_p) for k in ("A", "Bm", "Q", "C", "R", "P", "mu0", "Sigma0", "y", "u", "mask", "pf_regime", "pf_resample",
+                                             "state_log_w", "state_regime", "state_mu", "state_Sigma", "ll", "seq_ll", "regime_filt",
+                                             "mus_filt", "Sigmas_filt", "ess", "resampled", "regimes", "ancestors", "levels", "paths",
+                                             "out_log_w", "out_regime", "out_mu", "out_Sigma")])
+
+
 class InputGrads(C.Structure):  # kvae_lgssm_input_grads
     _fields_ = [("gA", Stack), ("gB", Stack), ("gC", Stack), ("gQ", Stack),
                 ("gY", C.c_void_p), ("gU", C.c_void_p), ("g_mu0", C.c_void_p), ("g_Sigma0", C.c_void_p)]
@@ -117,7 +125,7 @@ SYMBOLS = (
     "kvae_lgssm_posterior_sample_ws_floats", "kvae_lgssm_predictive", "kvae_lgssm_predictive_bwd",
     "kvae_lgssm_switching_filter", "kvae_lgssm_switching_smoother", "kvae_lgssm_switching_marginal",
     "kvae_lgssm_switching_marginal_bwd", "kvae_lgssm_switching_marginal_ws_floats", "kvae_lgssm_switching_em",
-    "kvae_lgssm_switching_em_ws_floats", "kvae_rnn_wgrad", "kvae_rnn_wgrad_ws_floats", "kvae_linear_fwd",
+    "kvae_lgssm_switching_em_ws_floats", "kvae_lgssm_switching_pf", "kvae_rnn_wgrad", "kvae_rnn_wgrad_ws_floats", "kvae_linear_fwd",
     "kvae_linear_bwd_input", "kvae_abi_version", "kvae_last_error", "kvae_build_info",
 )
 
@@ -164,6 +172,8 @@ class LgssmLib:
         d.kvae_lgssm_switching_em.restype = C.c_int
         d.kvae_lgssm_switching_em_ws_floats.argtypes = [C.c_int32] * 4
         d.kvae_lgssm_switching_em_ws_floats.restype = C.c_int64
+        d.kvae_lgssm_switching_pf.argtypes = [C.POINTER(SpfProblem), vp]
+        d.kvae_lgssm_switching_pf.restype = C.c_int
         d.kvae_lgssm_smooth_bwd.argtypes = [P, S, S, G, vp, C.c_int, vp]
         d.kvae_lgssm_smooth_bwd.restype = C.c_int
         d.kvae_lgssm_elbo.argtypes = [P, vp, vp, vp, vp, vp, vp, vp, vp, G, vp]

@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from ..noise import normal as _normal
+from ..noise import uniform as _uniform
 from . import lgssm_ops
 from .lgssm_ops import LgssmElbo, LgssmSmooth
 from .operands import NO_PASS, StepOperands
@@ -266,6 +267,31 @@ class KalmanFilter(nn.Module):
         return lgssm_ops.switching_filter(dyn.A.detach(), dyn.B.detach(), dyn.Q.detach(), dyn.C[0].detach(), self.R,
                                           dyn._prior_matrix(dev, dt), self.mu0, self.Sigma0, Y, U, self._mask(mask, Y), want=want,
                                           state=state)
+
+    @torch.no_grad()
+    def particle_filter_regimes(self, Y, U, mask=None, num_particles=256, replicates=1, ess_threshold=0.5, state=None,
+                                want=lgssm_ops._SPF_OUTPUTS):
+        """The generative switching model filtered on its own WITHOUT the GPB2 collapse (switching dynamics only): a
+        Rao-Blackwellised particle filter over the model of filter_regimes - `replicates` independent filters of `num_particles`
+        particles per sequence, each particle a regime history and an exact Kalman belief - lgssm_ops.switching_pf;
+        include/kvae_lgssm.h kvae_lgssm_switching_pf.  exp(log_lik_seq) is an unbiased estimate of p(a | u) for any number of
+        particles, regime_filt is consistent, and `paths` are joint draws of regime paths from the model's own posterior.  The
+        uniform draws are made here, before the launch (noise slots pf_regime [B,G,T,N], pf_resample [B,G,T]).  state: the "state"
+        entry of an earlier call continues that stream.  Returns switching_pf's dict, per replicate; entries not named in `want`
+        are None."""
+        dyn = self.dyn_params
+        if not dyn.is_switching_dynamics:
+            raise ValueError("particle_filter_regimes needs switching dynamics (SwitchingDynamicsParameter): the alpha-network of "
+                             "the lstm dynamics has no regime chain to filter")
+        if int(num_particles) < 1 or int(replicates) < 1:
+            raise ValueError(f"particle_filter_regimes: num_particles and replicates must be >= 1, got {num_particles}, {replicates}")
+        dev, dt = Y.device, Y.dtype
+        Bsz, T = Y.shape[0], Y.shape[1]
+        theta = _uniform("pf_regime", (Bsz, int(replicates), T, int(num_particles)), dev, dt)
+        phi = _uniform("pf_resample", (Bsz, int(replicates), T), dev, dt)
+        return lgssm_ops.switching_pf(dyn.A.detach(), dyn.B.detach(), dyn.Q.detach(), dyn.C[0].detach(), self.R,
+                                      dyn._prior_matrix(dev, dt), self.mu0, self.Sigma0, Y, U, theta, phi, self._mask(mask, Y),
+                                      ess_threshold=ess_threshold, want=want, state=state)
 
     @torch.no_grad()
     def smooth_regimes(self, Y, U, mask=None, state=None, want=lgssm_ops._SWS_OUTPUTS):

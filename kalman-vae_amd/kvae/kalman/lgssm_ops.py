@@ -11,18 +11,19 @@ a whole step record, a single tensor carries its gradient) or a plain tensor tha
 ([r,c]) or per-step ([B,T,r,c]).
 
 This module is the bridge only.  The read-outs (regime_decode, rollout, posterior_paths, predictive, log_marginal,
-switching_filter, switching_smoother, switching_log_marginal, switching_em_statistics) dispatch between their kernel and its restatement in torch ops;
+switching_filter, switching_smoother, switching_log_marginal, switching_em_statistics, switching_pf) dispatch between their kernel and its restatement in torch ops;
 the restatements - also the float64 references of the tests - and safe_cholesky / safe_cholesky_items live in lgssm_torch (no
 native library behind it) and are re-exported here.
 """
 import ctypes as C
+import math
 from typing import NamedTuple, Optional
 
 import torch
 
 from .. import _native as N
-from .lgssm_torch import (_DECODE_OUTPUTS, _EM_OUTPUTS, _EM_PARAMS, _EM_STATS, _LOG_2PI, _PRED_OUTPUTS, _SWF_OUTPUTS, _SWS_OUTPUTS, _SWS_SMOOTH, _bt,  # noqa: F401 (re-exported)
-                          _swf_state, _want, log_marginal_torch, posterior_paths_torch, predictive_torch, regime_decode_torch,
+from .lgssm_torch import (_DECODE_OUTPUTS, _EM_OUTPUTS, _EM_PARAMS, _EM_STATS, _LOG_2PI, _PRED_OUTPUTS, _SPF_OUTPUTS, _SWF_OUTPUTS, _SWS_OUTPUTS, _SWS_SMOOTH, _bt,  # noqa: F401 (re-exported)
+                          SPF_PARTICLES, _spf_draws, _spf_state, _swf_state, _want, lineages, switching_pf_torch, log_marginal_torch, posterior_paths_torch, predictive_torch, regime_decode_torch,
                           rollout_torch, safe_cholesky, safe_cholesky_items, switching_em_mstep, switching_em_statistics_torch,
                           switching_filter_torch, switching_log_marginal_torch, switching_smoother_torch)
 
@@ -1021,6 +1022,107 @@ def _swf_problem(pr, A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, state, want):
     if out["state"] is not None:
         pr.out_log_w, pr.out_mu, pr.out_Sigma = (out["state"][k].data_ptr() for k in ("log_w", "mu", "Sigma"))
     return out, pr, (A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, st, ll)
+
+
+# ------------------------------------------------------------------------------------------------
+# Rao-Blackwellised particle filter of the switching model (kvae_lgssm_switching_pf, csrc/lgssm_spf.h)
+# ------------------------------------------------------------------------------------------------
+def switching_pf_supported(K, n, m, p, num_particles, ref=None):
+    """Shapes / tensors kvae_lgssm_switching_pf is built for (include/kvae_lgssm.h: the switching filter's, and 64, 128 or 256
+    particles per replicate); the rest takes switching_pf_torch."""
+    return switching_filter_supported(K, n, m, p, ref) and num_particles in SPF_PARTICLES
+
+
+@torch.no_grad()
+def switching_pf(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, pf_regime, pf_resample, mask=None, ess_threshold=0.5, want=_SPF_OUTPUTS,
+                 state=None, impl=None):
+    """The Rao-Blackwellised particle filter of the generative switching model (semantics: include/kvae_lgssm.h,
+    kvae_lgssm_switching_pf): the model and operands of switching_filter, without the GPB2 collapse - G
+    replicate filters of N particles per sequence, each particle a regime history and an exact Kalman belief.  pf_regime [B,G,T,N]
+    and pf_resample [B,G,T] are the uniform draws in [0,1) of the regimes and of the systematic resampling (G and N are their
+    shape).  ess_threshold in [0,1]: 0 never resamples, 1 always, else when ess_t < ess_threshold N.  state: None or the "state"
+    entry of an earlier call (log_w [B,G,N], regime [B,G,N] int32, mu [B,G,N,n], Sigma [B,G,N,n,n]), which - with the matching
+    slices of the draws - continues that stream with the same bits.  want: which of "log_lik" [B,G,T] (its exp-sum over t is an
+    unbiased estimate of p(a | u)), "log_lik_seq" [B,G], "regime_filt" [B,G,T,K], "mus_filt" [B,G,T,n], "Sigmas_filt" [B,G,T,n,n],
+    "ess" [B,G,T], "resampled" [B,G,T] (bool), "regimes" / "ancestors" [B,G,T,N] (int32: the draw of slot i at step t before
+    resampling; the slot it was copied from), "levels" [B,G,T] (int32), "paths" [B,G,N,T] (int32: the regime lineage of every final
+    slot - joint draws of regime paths), "path_log_w" [B,G,N] (their final log weights), "state" to compute; entries not asked for
+    are None.  At most three launches, no host synchronisation, no gradients.
+    impl: None = the HIP kernel where it is built (switching_pf_supported), else switching_pf_torch; "hip" / "torch" force one."""
+    want = _want("switching_pf", _SPF_OUTPUTS, want)
+    if impl not in (None, "hip", "torch"):
+        raise ValueError(f"switching_pf: impl must be None, 'hip' or 'torch', got {impl!r}")
+    if not 0.0 <= float(ess_threshold) <= 1.0:
+        raise ValueError(f"switching_pf: ess_threshold must be in [0, 1], got {ess_threshold}")
+    K, n, m = A.shape[0], A.shape[1], Bm.shape[2]
+    Bsz, T, p = Y.shape
+    G, Np = _spf_draws(pf_regime, pf_resample, Bsz, T)
+    supported = switching_pf_supported(K, n, m, p, Np, Y)
+    if impl == "hip" and not supported:
+        raise ValueError(f"switching_pf: impl='hip' needs fp32 tensors on a HIP device, K <= {SWF_SUPPORTED['max_K']}, "
+                         f"n <= {SWF_SUPPORTED['max_n']}, m <= {SWF_SUPPORTED['max_m']}, p == {SWF_SUPPORTED['p']} and {SPF_PARTICLES} "
+                         f"particles; got K = {K}, n = {n}, m = {m}, p = {p}, {Np} particles, {Y.dtype} on {Y.device}")
+    if impl == "torch" or not supported:
+        return switching_pf_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, pf_regime, pf_resample, mask, ess_threshold, state, want)
+    dev = Y.device
+    A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, pf_regime, pf_resample = (
+        _f32c(t.detach().to(dev)) for t in (A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, pf_regime, pf_resample))
+    mask = None if mask is None else _f32c(mask.detach().to(dev).reshape(Bsz, T))
+    st = _spf_state(state, Bsz, G, Np, n)
+    if st is not None:
+        st = (_f32c(st[0].detach().to(dev)), st[1].detach().to(device=dev, dtype=torch.int32).contiguous(), _f32c(st[2].detach().to(dev)),
+              _f32c(st[3].detach().to(dev)))
+    i32 = lambda *s: _empty(dev, *s, dt=torch.int32)
+    shapes = dict(log_lik_seq=(Bsz, G), regime_filt=(Bsz, G, T, K), mus_filt=(Bsz, G, T, n), Sigmas_filt=(Bsz, G, T, n, n), ess=(Bsz, G, T))
+    out = {k: (_empty(dev, *shapes[k]) if (k in want and k in shapes) else None) for k in _SPF_OUTPUTS}
+    ll = _empty(dev, Bsz, G, T) if ("log_lik" in want or "log_lik_seq" in want) else None   # the sequence sums read log_lik
+    out["log_lik"] = ll if "log_lik" in want else None
+    paths = "paths" in want
+    regimes = i32(Bsz, G, T, Np) if ("regimes" in want or paths) else None                  # the lineage walk reads both
+    ancestors = i32(Bsz, G, T, Np) if ("ancestors" in want or paths) else None
+    out["regimes"], out["ancestors"] = (regimes if "regimes" in want else None), (ancestors if "ancestors" in want else None)
+    resampled = i32(Bsz, G, T) if "resampled" in want else None
+    if "levels" in want:
+        out["levels"] = i32(Bsz, G, T)
+    if paths:
+        out["paths"] = i32(Bsz, G, Np, T)
+    so = None
+    if "state" in want or "path_log_w" in want:
+        so = {"log_w": _empty(dev, Bsz, G, Np)}
+        if "state" in want:
+            so.update(regime=i32(Bsz, G, Np), mu=_empty(dev, Bsz, G, Np, n), Sigma=_empty(dev, Bsz, G, Np, n, n))
+            out["state"] = so
+        if "path_log_w" in want:
+            out["path_log_w"] = so["log_w"]
+    pr = N.SpfProblem()
+    pr.B, pr.G, pr.T, pr.K, pr.N, pr.n, pr.m, pr.p, pr.ess_threshold = Bsz, G, T, K, Np, n, m, p, float(ess_threshold)
+    pr.A, pr.Bm, pr.Q, pr.C, pr.R, pr.P = (t.data_ptr() for t in (A, Bm, Q, Cm, R, P))
+    pr.mu0, pr.Sigma0, pr.y, pr.u, pr.mask = mu0.data_ptr(), Sigma0.data_ptr(), Y.data_ptr(), U.data_ptr(), N.ptr(mask)
+    pr.pf_regime, pr.pf_resample = pf_regime.data_ptr(), pf_resample.data_ptr()
+    if st is not None:
+        pr.state_log_w, pr.state_regime, pr.state_mu, pr.state_Sigma = (t.data_ptr() for t in st)
+    pr.ll, pr.seq_ll, pr.regime_filt, pr.mus_filt = N.ptr(ll), N.ptr(out["log_lik_seq"]), N.ptr(out["regime_filt"]), N.ptr(out["mus_filt"])
+    pr.Sigmas_filt, pr.ess, pr.resampled, pr.regimes = N.ptr(out["Sigmas_filt"]), N.ptr(out["ess"]), N.ptr(resampled), N.ptr(regimes)
+    pr.ancestors, pr.levels, pr.paths = N.ptr(ancestors), N.ptr(out["levels"]), N.ptr(out["paths"])
+    if so is not None:
+        pr.out_log_w = so["log_w"].data_ptr()
+        if "state" in want:
+            pr.out_regime, pr.out_mu, pr.out_Sigma = (so[k].data_ptr() for k in ("regime", "mu", "Sigma"))
+    lib = N.lib_for(Y)
+    lib.check(N.timed("switching_pf", Y, lambda: lib.dll.kvae_lgssm_switching_pf(C.byref(pr), N.stream_for(Y))), "kvae_lgssm_switching_pf")
+    if resampled is not None:
+        out["resampled"] = resampled != 0
+    return out
+
+
+def combine_replicates(log_lik):
+    """What the replicates of one sequence say together, from log_lik [B,G,T]: (log_lik_seq_mean [B] = the logmeanexp over the
+    replicates of their sums over t - still an unbiased estimate of p(a | u) after exp -, weights [B,G,T] = exp(cumulative log_lik)
+    normalised over the replicates: the weights under which the replicate average of regime_filt is consistent)."""
+    cum = log_lik.cumsum(-1)
+    G = log_lik.shape[1]
+    mean = torch.logsumexp(cum[..., -1], 1) - math.log(G)   # (a Python constant: nothing is copied to the device)
+    return mean, torch.softmax(cum, 1)
 
 
 # ------------------------------------------------------------------------------------------------

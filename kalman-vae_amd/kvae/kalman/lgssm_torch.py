@@ -668,3 +668,174 @@ def switching_log_marginal_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=Non
     ll = torch.stack(lls, 1)
     return {"ll": ll, "seq_ll": ll.sum(1), "levels": torch.stack(levels, 1)}
 
+
+
+_SPF_OUTPUTS = ("log_lik", "log_lik_seq", "regime_filt", "mus_filt", "Sigmas_filt", "ess", "resampled", "regimes", "ancestors", "levels",
+                "paths", "path_log_w", "state")
+_SPF_FORCE = ("regimes", "resampled", "ancestors")
+SPF_PARTICLES = (64, 128, 256)
+
+
+def _spf_state(state, Bsz, G, N, n):
+    if state is None:
+        return None
+    lw, reg, mu, Sig = state["log_w"], state["regime"], state["mu"], state["Sigma"]
+    if lw.shape != (Bsz, G, N) or reg.shape != (Bsz, G, N) or mu.shape != (Bsz, G, N, n) or Sig.shape != (Bsz, G, N, n, n):
+        raise ValueError(f"switching_pf: state must hold log_w [{Bsz},{G},{N}], regime [{Bsz},{G},{N}], mu [{Bsz},{G},{N},{n}], Sigma "
+                         f"[{Bsz},{G},{N},{n},{n}], got {tuple(lw.shape)}, {tuple(reg.shape)}, {tuple(mu.shape)}, {tuple(Sig.shape)}")
+    return lw, reg, mu, Sig
+
+
+def _spf_draws(pf_regime, pf_resample, Bsz, T):
+    if pf_regime.dim() != 4 or pf_regime.shape[0] != Bsz or pf_regime.shape[2] != T:
+        raise ValueError(f"switching_pf: pf_regime must be [B,G,T,N] = [{Bsz},G,{T},N], got {tuple(pf_regime.shape)}")
+    G, N = pf_regime.shape[1], pf_regime.shape[3]
+    if pf_resample.shape != (Bsz, G, T):
+        raise ValueError(f"switching_pf: pf_resample must be [{Bsz},{G},{T}], got {tuple(pf_resample.shape)}")
+    return G, N
+
+
+def lineages(regimes, ancestors):
+    """paths [B,G,N,T] of the final slots: slot n's lineage walked back over ancestors [B,G,T,N] / regimes [B,G,T,N] -
+    i = n; for t = T-1 .. 0: i = ancestors_t[i], paths[n, t] = regimes_t[i]."""
+    Bsz, G, T, N = regimes.shape
+    i = torch.arange(N, device=regimes.device).expand(Bsz, G, N)
+    cols = [None] * T
+    for t in range(T - 1, -1, -1):
+        i = ancestors[:, :, t].long().gather(-1, i)
+        cols[t] = regimes[:, :, t].gather(-1, i)
+    return torch.stack(cols, -1)
+
+
+@torch.no_grad()
+def switching_pf_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, pf_regime, pf_resample, mask=None, ess_threshold=0.5, state=None,
+                       want=_SPF_OUTPUTS, force=None, margins=False):
+    """The equations of kvae_lgssm_switching_pf (include/kvae_lgssm.h) in torch ops, vectorised over (B, G, particle, regime), in
+    the dtype of A: shapes outside the kernel's, non-fp32 and host tensors, and (in float64) the reference the kernel is tested
+    against.  The per-regime Kalman steps use the helpers of switching_filter_torch.  T steps of about forty small launches.
+    Same arguments and returns as switching_pf.  force: a dict with any of "regimes" [B,G,T,N], "resampled" [B,G,T], "ancestors"
+    [B,G,T,N] - recorded decisions replayed in place of this run's own (a free-running comparison of two precisions is meaningless
+    once one boundary decision differs).  margins: also return "margin_regime" [B,G,T,N] (the distance of theta sum_j e_j from the
+    nearest boundary of the cumulative e, over sum_j e_j), "margin_ancestor" [B,G,T,N] (of the position from the nearest cumulative
+    weight) and "margin_ess" [B,G,T] (|ess - ess_threshold N|): how close this run's decisions were to going the other way."""
+    want = _want("switching_pf", _SPF_OUTPUTS, want)
+    force = {} if force is None else dict(force)
+    if any(k not in _SPF_FORCE for k in force):
+        raise ValueError(f"switching_pf_torch: force may hold {_SPF_FORCE}, got {tuple(force)}")
+    if not 0.0 <= float(ess_threshold) <= 1.0:
+        raise ValueError(f"switching_pf: ess_threshold must be in [0, 1], got {ess_threshold}")
+    dt, dev = A.dtype, Y.device
+    K, n = A.shape[0], A.shape[1]
+    Bsz, T, p = Y.shape
+    G, N = _spf_draws(pf_regime, pf_resample, Bsz, T)
+    A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, pf_regime, pf_resample = (
+        t.detach().to(device=dev, dtype=dt) for t in (A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, pf_regime, pf_resample))
+    mask = None if mask is None else mask.detach().to(device=dev, dtype=dt).reshape(Bsz, T)
+    st = _spf_state(state, Bsz, G, N, n)
+    nlogN = -torch.tensor(float(N), device=dev, dtype=dt).log()
+    if st is None:
+        lw = nlogN.expand(Bsz, G, N)
+        reg = torch.zeros(Bsz, G, N, device=dev, dtype=torch.long)
+        mu, Sig = mu0.expand(Bsz, G, N, n), Sigma0.expand(Bsz, G, N, n, n)
+    else:
+        lw, mu, Sig = (t.detach().to(device=dev, dtype=dt) for t in (st[0], st[2], st[3]))
+        reg = st[1].detach().to(dev).long()
+    eye = torch.eye(n, device=dev, dtype=dt)
+    logP = P.log()
+    luni = torch.full((), 1.0 / K, device=dev, dtype=dt).log()
+    slots = torch.arange(N, device=dev)
+    inf = float("inf")
+    outs = {k: [] for k in ("log_lik", "regime_filt", "mus_filt", "Sigmas_filt", "ess", "resampled", "regimes", "ancestors", "levels",
+                            "margin_regime", "margin_ancestor", "margin_ess")}
+    for t in range(T):
+        mk = torch.ones(Bsz, device=dev, dtype=dt) if mask is None else mask[:, t]
+        observed = mk != 0
+        # ---- every particle under every regime: [B, G, i, j, ...] ----
+        mp = torch.einsum("jrc,bgic->bgijr", A, mu) + torch.einsum("jrc,bc->bjr", Bm, U[:, t])[:, None, None]
+        Sp = torch.einsum("jre,bgiec,jdc->bgijrd", A, Sig, A) + Q
+        res = Y[:, t, None, None, None, :] - mp @ Cm.mT
+        S = Cm @ Sp @ Cm.mT + R
+        S = 0.5 * (S + S.mT)
+        L, lv = safe_cholesky_items(S)
+        lij = _observed_only(_gauss_ll(L, res)[0], observed[:, None, None, None])
+        lp = luni.expand(Bsz, G, N, K) if (t == 0 and st is None) else logP[reg]
+        logc = lp + lij
+        mx = logc.amax(-1, keepdim=True)
+        e = (logc - mx).exp()
+        se = e[..., 0]
+        for j in range(1, K):
+            se = se + e[..., j]
+        inc = mx.squeeze(-1) + se.log()
+        # ---- the weights ----
+        a = lw + inc
+        top = a.amax(-1, keepdim=True)
+        ex = (a - top).exp()
+        tot = ex.sum(-1, keepdim=True)
+        ll = (top + tot.log()).squeeze(-1)
+        lwn = (a - top) - tot.log()
+        Wn = ex / tot
+        rf = (Wn.unsqueeze(-1) * (e / se.unsqueeze(-1))).sum(2)
+        ess = 1.0 / (Wn * Wn).sum(-1)
+        # ---- the draw ----
+        thr = pf_regime[:, :, t] * se
+        cs = torch.zeros_like(se)
+        s = torch.full_like(reg, -1)
+        last = torch.zeros_like(reg)
+        gap = torch.full_like(se, inf)
+        for j in range(K):
+            cs = cs + e[..., j]
+            s = torch.where((s < 0) & (cs > thr), torch.full_like(s, j), s)
+            last = torch.where(e[..., j] > 0, torch.full_like(last, j), last)
+            if j < K - 1:
+                gap = torch.minimum(gap, (cs - thr).abs())
+        s = torch.where(s < 0, last, s)
+        if "regimes" in force:
+            s = force["regimes"][:, :, t].to(dev).long()
+        # ---- the measurement update under the drawn regime ----
+        pick = lambda v: v.gather(3, s.reshape(Bsz, G, N, 1, *([1] * (v.dim() - 4))).expand(Bsz, G, N, 1, *v.shape[4:])).squeeze(3)
+        mps, Sps, Ss, rs_ = pick(mp), pick(Sp), pick(S), pick(res)
+        Kg = torch.linalg.solve(Ss, Cm @ Sps).mT * mk[:, None, None, None, None]
+        muf = mps + (Kg @ rs_.unsqueeze(-1)).squeeze(-1)
+        IKC = eye - Kg @ Cm
+        Sf = IKC @ Sps @ IKC.mT + Kg @ R @ Kg.mT
+        Sf = 0.5 * (Sf + Sf.mT)
+        m_ = (Wn.unsqueeze(-1) * muf).sum(2)
+        dd = muf - m_.unsqueeze(2)
+        V = (Wn[..., None, None] * (Sf + dd.unsqueeze(-1) * dd.unsqueeze(-2))).sum(2)
+        # ---- systematic resampling ----
+        if ess_threshold >= 1.0:
+            rs = torch.ones(Bsz, G, device=dev, dtype=torch.bool)
+        elif ess_threshold <= 0.0:
+            rs = torch.zeros(Bsz, G, device=dev, dtype=torch.bool)
+        else:
+            rs = ess < ess_threshold * N
+        if "resampled" in force:
+            rs = force["resampled"][:, :, t].to(dev) != 0
+        cum = Wn.cumsum(-1)
+        pos = (pf_resample[:, :, t, None] + slots.to(dt)) / N
+        anc = torch.searchsorted(cum, pos.contiguous(), right=True).clamp(max=N - 1)
+        above = torch.where(anc < N - 1, (cum.gather(-1, anc) - pos).abs(), torch.full_like(pos, inf))   # the last slot takes the rest
+        below = torch.where(anc > 0, (pos - cum.gather(-1, (anc - 1).clamp(min=0))).abs(), torch.full_like(pos, inf))
+        if "ancestors" in force:
+            anc = force["ancestors"][:, :, t].to(dev).long()
+        anc = torch.where(rs.unsqueeze(-1), anc, slots.expand(Bsz, G, N))
+        mu = muf.gather(2, anc[..., None].expand(Bsz, G, N, n))
+        Sig = Sf.gather(2, anc[..., None, None].expand(Bsz, G, N, n, n))
+        reg = s.gather(2, anc)
+        lw = torch.where(rs.unsqueeze(-1), nlogN.expand(Bsz, G, N), lwn)
+        # ---- outputs of the step ----
+        outs["log_lik"].append(torch.where(observed.unsqueeze(-1), ll, torch.zeros_like(ll)))
+        outs["regime_filt"].append(rf), outs["mus_filt"].append(m_), outs["Sigmas_filt"].append(V), outs["ess"].append(ess)
+        outs["resampled"].append(rs), outs["regimes"].append(s.to(torch.int32)), outs["ancestors"].append(anc.to(torch.int32))
+        outs["levels"].append(torch.where(lp > -inf, lv, torch.zeros_like(lv)).amax((2, 3)))
+        outs["margin_regime"].append(gap / se), outs["margin_ancestor"].append(torch.minimum(above, below))
+        outs["margin_ess"].append((ess - ess_threshold * N).abs())
+    full = {k: torch.stack(v, 2) for k, v in outs.items()}
+    full["log_lik_seq"] = full["log_lik"].sum(2)
+    full["paths"] = lineages(full["regimes"], full["ancestors"])
+    full["path_log_w"] = lw
+    full["state"] = {"log_w": lw, "regime": reg.to(torch.int32), "mu": mu, "Sigma": Sig}
+    out = {k: (full[k] if k in want else None) for k in _SPF_OUTPUTS}
+    if margins:
+        out.update({k: full[k] for k in ("margin_regime", "margin_ancestor", "margin_ess")})
+    return out

@@ -512,6 +512,45 @@ class KVAE(nn.Module):
             return out
 
     @torch.no_grad()
+    def particle_filter_regimes(self, x, u=None, mask=None, num_particles=256, replicates=1, ess_threshold=0.5, sample_a=False,
+                                state=None, decode=False):
+        """filter_regimes without its GPB2 approximation (switching dynamics only; no counterpart in the reference): a
+        Rao-Blackwellised particle filter over the same generative switching model - `replicates` (G) independent filters of
+        `num_particles` (N) particles per sequence, every particle a regime history with an exact Kalman belief -
+        kvae_lgssm_switching_pf.  It is the yardstick of the GPB2 read-outs, and its lineages are joint samples of regime paths.
+
+        1. Encode x, as filter_regimes does.  u [B,T,m] or None = zeros; mask [B,T] optional (1 = observed).
+        2. Per replicate: log_lik [B,G,T] (0 on hidden steps), log_lik_seq [B,G] - exp of it is an UNBIASED estimate of
+           p(a | u) for any N -, regime_filt [B,G,T,K] (consistent in N), mus_filt [B,G,T,n], Sigmas_filt [B,G,T,n,n], ess
+           [B,G,T], resampled [B,G,T] (bool), regimes / ancestors [B,G,T,N] (int32), levels [B,G,T], paths [B,G,N,T] (int32: the
+           regime lineage of every final slot) with path_log_w [B,G,N], state.
+        3. Combined: log_lik_seq_mean [B] = the logmeanexp of log_lik_seq over the replicates (still unbiased); regime_filt_mean
+           [B,T,K] = the replicate average of regime_filt weighted by exp(cumulative log_lik) (the plain average is biased);
+           regimes_map [B,T] (int64) = its argmax (lowest index on ties); a_filt [B,T,p] = C mus_filt under the same weights.
+        4. ess_threshold in [0,1]: 0 never resamples, 1 resamples at every step, else when ess_t < ess_threshold N.  N in
+           {64, 128, 256} runs the HIP kernel, anything else its restatement in torch ops.
+        5. state=prev["state"] continues a stream; with injected draws (kvae.noise pf_regime / pf_resample) the chunks give the
+           bits of the whole-sequence call.  decode=True: x_filt = decoder(a_filt).
+        Also returns a_vae and n_obs [B].  No host synchronisation.  Training mode, tau and parameters are left as they were."""
+        dyn = self.kalman_filter.dyn_params
+        if not dyn.is_switching_dynamics:
+            raise ValueError('particle_filter_regimes needs a model with dynamics = "switching" (config.dynamics_model); this one has '
+                             f'"{self.config.dynamics_model}"')
+        with self._readout("particle_filter_regimes", x, u, mask, sample=bool(sample_a)) as (a_vae, _, _, u, mask):
+            out = self.kalman_filter.particle_filter_regimes(a_vae, u, mask, num_particles=num_particles, replicates=replicates,
+                                                             ess_threshold=ess_threshold, state=state)
+            out["log_lik_seq_mean"], w = lgssm_ops.combine_replicates(out["log_lik"])
+            rf = (w.unsqueeze(-1) * out["regime_filt"]).sum(1)
+            out["regime_filt_mean"] = rf
+            out["regimes_map"] = (rf == rf.max(-1, keepdim=True).values).to(torch.int8).argmax(-1)   # lowest index among the maxima
+            out["a_filt"] = (w.unsqueeze(-1) * out["mus_filt"]).sum(1) @ dyn.C[0].detach().to(rf.dtype).mT
+            out["a_vae"] = a_vae
+            out["n_obs"] = self._n_obs(mask, a_vae)
+            if decode:
+                out["x_filt"] = self._decode_latents(out["a_filt"], a_vae.dtype)
+            return out
+
+    @torch.no_grad()
     def smooth_regimes(self, x, u=None, mask=None, sample_a=False, state=None, decode=False):
         """What the generative switching model believes on its own, given the WHOLE sequence (switching dynamics only; no
         counterpart in the reference): filter_regimes forwards, then the GPB2 smoothing pass backwards over the beliefs and pair

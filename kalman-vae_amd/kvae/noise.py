@@ -21,13 +21,17 @@ KalmanFilter.sample_posterior / KVAE.sample_imputations (no counterpart either) 
 KVAE.log_likelihood (no counterpart either) draws one, before the filter runs:
   * ll_a        ~ N(0,1)  [B,S,T,p]   the proposal draws a_s = a_mu + sqrt(a_var) ll_a_s (its regime draws take `gumbel`,
                                       one row per (b, s): [B*S,T,K])
+
+KalmanFilter.particle_filter_regimes / KVAE.particle_filter_regimes (no counterpart either) draw two, before their launches:
+  * pf_regime   ~ U[0,1)  [B,G,T,N]   the regime draw of every particle of every replicate at every step
+  * pf_resample ~ U[0,1)  [B,G,T]     the offset of the systematic resampling of every replicate at every step
 """
 import contextlib
 
 import torch
 
 _slots = {"eps_a": None, "eps_z": None, "gumbel": None, "gen_z0": None, "gen_z": None, "gen_a": None, "gen_gumbel": None,
-          "post_z": None, "post_a": None, "ll_a": None}
+          "post_z": None, "post_a": None, "ll_a": None, "pf_regime": None, "pf_resample": None}
 
 
 def take(name):
@@ -50,12 +54,18 @@ def gumbel(slot, shape, device, dtype):
     return v.to(device=device, dtype=dtype).reshape(shape)
 
 
+def uniform(slot, shape, device, dtype):
+    """As normal(), the fresh draw being uniform on [0, 1)."""
+    v = take(slot)
+    return torch.rand(shape, device=device, dtype=dtype) if v is None else v.to(device=device, dtype=dtype).reshape(shape)
+
+
 @contextlib.contextmanager
 def inject(eps_a=None, eps_z=None, gumbel=None, gen_z0=None, gen_z=None, gen_a=None, gen_gumbel=None, post_z=None, post_a=None,
-           ll_a=None):
+           ll_a=None, pf_regime=None, pf_resample=None):
     old = dict(_slots)
     _slots.update(eps_a=eps_a, eps_z=eps_z, gumbel=gumbel, gen_z0=gen_z0, gen_z=gen_z, gen_a=gen_a, gen_gumbel=gen_gumbel,
-                  post_z=post_z, post_a=post_a, ll_a=ll_a)
+                  post_z=post_z, post_a=post_a, ll_a=ll_a, pf_regime=pf_regime, pf_resample=pf_resample)
     try:
         yield
     finally:

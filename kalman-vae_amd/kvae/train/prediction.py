@@ -65,3 +65,31 @@ def regime_filter_scores(model, batch_or_x, mask=None, u=None):
             "log_lik_per_step_map": float(sc["log_lik_seq"].sum() / n_obs),
             "regime_agreement": float((fr["regimes"] == dec["regimes"]).double().mean()),
             "regime_kl": float(kl.mean())}
+
+
+def particle_filter_scores(model, batch_or_x, mask=None, u=None, num_particles=256, replicates=4, ess_threshold=0.5):
+    """The size of the GPB2 approximation on x [B,T,...] (or a batch, as prediction_scores takes it): KVAE.particle_filter_regimes
+    - unbiased in the likelihood, consistent in the regimes - next to KVAE.filter_regimes.  Switching dynamics only.  Python floats:
+      log_lik_per_step_pf    sum over sequences of log_lik_seq_mean (the logmeanexp over the replicates) / observed steps
+      log_lik_per_step_gpb2  the same for filter_regimes' log_lik_seq
+      gpb2_gap_per_step      their difference, particle filter minus GPB2
+      pf_std                 the spread of log_lik_seq over the replicates (standard deviation, mean over sequences; 0 for one)
+      regime_tv              mean over (b, t) of the total variation between regime_filt_mean and filter_regimes' regime_filt
+      ess_mean               mean effective sample size over replicates and steps"""
+    if isinstance(batch_or_x, dict):
+        x = batch_or_x["images"]
+    elif isinstance(batch_or_x, (tuple, list)):
+        x = batch_or_x[0]
+    else:
+        x = batch_or_x
+    dev = next(model.parameters()).device
+    x = x.to(dev)
+    pf = model.particle_filter_regimes(x, u=u, mask=mask, num_particles=num_particles, replicates=replicates, ess_threshold=ess_threshold)
+    fr = model.filter_regimes(x, u=u, mask=mask)
+    n_obs = fr["n_obs"].sum().clamp(min=1.0)
+    seq = pf["log_lik_seq"].double()
+    ll_pf, ll_gpb2 = float(pf["log_lik_seq_mean"].double().sum() / n_obs), float(fr["log_lik_seq"].double().sum() / n_obs)
+    tv = 0.5 * (pf["regime_filt_mean"].double() - fr["regime_filt"].double()).abs().sum(-1)
+    return {"log_lik_per_step_pf": ll_pf, "log_lik_per_step_gpb2": ll_gpb2, "gpb2_gap_per_step": ll_pf - ll_gpb2,
+            "pf_std": float(seq.std(1, unbiased=True).mean()) if seq.shape[1] > 1 else 0.0,
+            "regime_tv": float(tv.mean()), "ess_mean": float(pf["ess"].double().mean())}
