@@ -170,7 +170,7 @@ int kvae_bce_frames_bwd(const float *logits, const float *x, const float *g_fram
 
 #include "vae_conv_edge.h"
 extern "C" {
-int64_t kvae_conv_edge_partial_rows(int64_t N) { return N < 1024 ? (N < 1 ? 1 : N) : 1024; }   // four workgroups per CU
+int64_t kvae_conv_edge_partial_rows(int64_t N) { return conv_edge_partial_rows(N); }
 
 int kvae_dec_head_fwd(const float *in, const float *W, const float *bias, float *logits, float *w_scratch, int64_t N,
                       int32_t Cin, int32_t side, void *stream) {
@@ -250,7 +250,7 @@ int kvae_enc_stem_fwd(const float *x, const float *W, const float *bias, float *
   if (!x || !W || !bias || !out) return KVAE_ERR_NULL;
   if (N < 1) return KVAE_ERR_ARG;
   if (Cout != ES_CO || side != ES_IN) return KVAE_ERR_DIMS;
-  k_enc_stem_fwd<<<dim3((unsigned)N), dim3(256), 0, (hipStream_t)stream>>>(x, W, bias, out, relu_bits);
+  k_enc_stem_fwd<<<dim3(es_fwd_grid(N)), dim3(256), 0, (hipStream_t)stream>>>(x, W, bias, out, relu_bits);
   return launch_status("k_enc_stem_fwd");
 }
 int kvae_enc_stem_bwd(const float *x, const float *out, const uint32_t *relu_bits, const float *g_out, float *w_partials,
@@ -259,29 +259,26 @@ int kvae_enc_stem_bwd(const float *x, const float *out, const uint32_t *relu_bit
   if (N < 1) return KVAE_ERR_ARG;
   if (Cout != ES_CO || side != ES_IN) return KVAE_ERR_DIMS;
   static const int mfma = getenv("KVAE_STEM_MFMA") ? atoi(getenv("KVAE_STEM_MFMA")) : 1;   // 0: VALU version, 2: mask from out (A/B runs)
-  const dim3 grid((unsigned)kvae_conv_edge_partial_rows(N));
-  if (mfma == 1 && relu_bits) k_enc_stem_wrw_mfma<true><<<grid, dim3(256), 0, (hipStream_t)stream>>>(x, out, relu_bits, g_out, w_partials, b_partials, N);
-  else if (!out) return KVAE_ERR_NULL;
-  else if (mfma) k_enc_stem_wrw_mfma<false><<<grid, dim3(256), 0, (hipStream_t)stream>>>(x, out, relu_bits, g_out, w_partials, b_partials, N);
+  const dim3 grid((unsigned)conv_edge_partial_rows(N));
+  const int kernel = es_wrw_kernel(mfma, relu_bits != nullptr, out != nullptr);
+  if (kernel == ES_WRW_REFUSED) return KVAE_ERR_NULL;
+  if (kernel == ES_WRW_MFMA_BITS) k_enc_stem_wrw_mfma<true><<<grid, dim3(256), 0, (hipStream_t)stream>>>(x, out, relu_bits, g_out, w_partials, b_partials, N);
+  else if (kernel == ES_WRW_MFMA_OUT) k_enc_stem_wrw_mfma<false><<<grid, dim3(256), 0, (hipStream_t)stream>>>(x, out, relu_bits, g_out, w_partials, b_partials, N);
   else k_enc_stem_wrw<<<grid, dim3(256), 0, (hipStream_t)stream>>>(x, out, g_out, w_partials, b_partials, N);
   return launch_status("k_enc_stem_wrw");
 }
 }  // extern "C"
 
 #include "vae_conv_mid.h"
-static inline int64_t enc_mid_grid(int64_t N, int32_t side) {
-  const int64_t fpi = side == 16 ? 2 : 8, iters = (N + fpi - 1) / fpi;
-  return iters < 256 ? (iters < 1 ? 1 : iters) : 256;   // one persistent workgroup per CU
-}
 extern "C" {
-int64_t kvae_enc_mid_partial_rows(int64_t N, int32_t side) { return enc_mid_grid(N, side); }
+int64_t kvae_enc_mid_partial_rows(int64_t N, int32_t side) { return em_grid(N, side); }
 
 int kvae_enc_mid_fwd(const float *in, const float *W, const float *bias, float *out, int64_t N, int32_t C, int32_t side,
                      void *stream) {
   if (!in || !W || !bias || !out) return KVAE_ERR_NULL;
-  if (N < 1 || (N + 256 * 8) * EM_C * side * side * 4 >= EM_MAX_BYTES) return KVAE_ERR_ARG;   // 32-bit byte offsets
+  if (!em_launch_ok(N, side)) return KVAE_ERR_ARG;   // 32-bit byte offsets
   if (C != EM_C || (side != 16 && side != 8)) return KVAE_ERR_DIMS;
-  const dim3 grid((unsigned)enc_mid_grid(N, side));
+  const dim3 grid((unsigned)em_grid(N, side));
   if (side == 16) k_enc_mid_fwd<16><<<grid, dim3(256), 0, (hipStream_t)stream>>>(in, W, bias, out, N);
   else k_enc_mid_fwd<8><<<grid, dim3(256), 0, (hipStream_t)stream>>>(in, W, bias, out, N);
   return launch_status("k_enc_mid_fwd");
@@ -289,9 +286,9 @@ int kvae_enc_mid_fwd(const float *in, const float *W, const float *bias, float *
 int kvae_enc_mid_bwd(const float *in, const float *W, const float *out, const float *g_out, float *g_in,
                      float *w_partials, float *b_partials, int64_t N, int32_t C, int32_t side, void *stream) {
   if (!in || !W || !out || !g_out || !w_partials || !b_partials) return KVAE_ERR_NULL;
-  if (N < 1 || (N + 256 * 8) * EM_C * side * side * 4 >= EM_MAX_BYTES) return KVAE_ERR_ARG;
+  if (!em_launch_ok(N, side)) return KVAE_ERR_ARG;
   if (C != EM_C || (side != 16 && side != 8)) return KVAE_ERR_DIMS;
-  const dim3 grid((unsigned)enc_mid_grid(N, side));
+  const dim3 grid((unsigned)em_grid(N, side));
   if (g_in) {
     if (side == 16) k_enc_mid_bwd_data<16><<<grid, dim3(256), 0, (hipStream_t)stream>>>(W, out, g_out, g_in, N);
     else k_enc_mid_bwd_data<8><<<grid, dim3(256), 0, (hipStream_t)stream>>>(W, out, g_out, g_in, N);

@@ -12,10 +12,29 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lds_decl.h"
+#if !defined(KVAE_WAVE_EMU)   // the decoder head (below) is not on the test-only emulated workgroups; the stem needs none of this
 #include "vae_loss.h"
+#endif
 
 namespace kvae {
 
+// Launch geometry, host side (kvae_vae.hip; the test-only emulated workgroups call the same functions with a lower cap).
+// Rows of weight-gradient partials = persistent workgroups of k_dec_head_bwd / k_enc_stem_wrw*: one per frame up to the cap.
+constexpr int CE_MAX_ROWS = 1024;   // four workgroups per CU
+inline int64_t conv_edge_partial_rows(int64_t N, int64_t cap = CE_MAX_ROWS) { return N < cap ? (N < 1 ? 1 : N) : cap; }
+// The stem's forward: one workgroup per frame.
+inline unsigned es_fwd_grid(int64_t N) { return (unsigned)N; }
+// Which weight-gradient kernel of the stem runs.  mode: KVAE_STEM_MFMA (1, the default: the matrix cores with the mask words of the
+// forward where the caller has them; 2: the matrix cores with the mask from `out`; 0: the VALU version).
+enum { ES_WRW_REFUSED = -1, ES_WRW_VALU = 0, ES_WRW_MFMA_BITS = 1, ES_WRW_MFMA_OUT = 2 };
+inline int es_wrw_kernel(int mode, bool have_bits, bool have_out) {
+  if (mode == 1 && have_bits) return ES_WRW_MFMA_BITS;
+  if (!have_out) return ES_WRW_REFUSED;
+  return mode ? ES_WRW_MFMA_OUT : ES_WRW_VALU;
+}
+
+#if !defined(KVAE_WAVE_EMU)   // the decoder head is not on the emulated workgroups: its host twin is a plain loop
 // ------------------------------------------------------------------------------------------------------------------
 // decoder head: in [N,32,16,16] -> logits [N,1,32,32] = pixel_shuffle_2(conv3x3(in, W[4,32,3,3]) + b[4])
 // ------------------------------------------------------------------------------------------------------------------
@@ -293,6 +312,7 @@ __global__ __launch_bounds__(256, 2) void k_dec_head_bwd(const float *__restrict
 // (An f32-MFMA version of this weight gradient - D[ci 32][(co, tap) 36 of 48] += A[ci][4 pixels] B[4 pixels][(co, tap)], the
 //  gradient read at the tap-shifted pixel from zero-bordered planes, 24 accumulator registers, four workgroups per CU - was
 //  written and measured in round 2: 143 us against 153 alone, no difference on the training step; not kept.)
+#endif   // !KVAE_WAVE_EMU
 
 // ------------------------------------------------------------------------------------------------------------------
 // encoder stem: x [N,1,32,32] -> out [N,32,16,16] = relu(conv3x3_stride2_pad1(x, W[32,1,3,3]) + b[32])
@@ -311,7 +331,7 @@ __device__ __forceinline__ void es_load_tile(float *tile, const float *__restric
 __global__ __launch_bounds__(256) void k_enc_stem_fwd(const float *__restrict__ x, const float *__restrict__ W,
                                                       const float *__restrict__ bias, float *__restrict__ out,
                                                       uint32_t *__restrict__ relu_bits) {
-  __shared__ float tile[34 * ES_TS];
+  KV_LDS(float, tile, [34 * ES_TS]);
   const int64_t n = blockIdx.x;
   es_load_tile(tile, x + n * 1024);
   __syncthreads();
@@ -339,8 +359,8 @@ __global__ __launch_bounds__(256) void k_enc_stem_fwd(const float *__restrict__ 
 __global__ __launch_bounds__(256) void k_enc_stem_wrw(const float *__restrict__ x, const float *__restrict__ out,
                                                       const float *__restrict__ g_out, float *__restrict__ partial,
                                                       float *__restrict__ partial_b, int64_t N) {
-  __shared__ float tile[34 * ES_TS];
-  __shared__ float gt[ES_CO * 257];
+  KV_LDS(float, tile, [34 * ES_TS]);
+  KV_LDS(float, gt, [ES_CO * 257]);
   const int co = threadIdx.x & 31, grp = threadIdx.x >> 5;
   float acc[9], accb = 0.f;
 #pragma unroll
@@ -399,13 +419,13 @@ __global__ __launch_bounds__(256) void k_enc_stem_wrw_mfma(const float *__restri
                                                            const uint32_t *__restrict__ relu_bits, const float *__restrict__ g_out,
                                                            float *__restrict__ partial,
                                                            float *__restrict__ partial_b, int64_t N) {
-  __shared__ float tile[34 * ES_TS];
+  KV_LDS(float, tile, [34 * ES_TS]);
   // channel planes 260 floats apart: the masked gradient goes in as one ds_write_b128 per 16 bytes loaded.  With the 257 of the
   // VALU version a wave's 64 scalar writes hit 8 banks - 32 eight-way-conflicting writes per thread and frame were the whole
   // kernel: 158 us whether the products ran on the VALU or the matrix cores, with or without `out`, with or without prefetch.
   constexpr int GS = 260;
-  __shared__ __attribute__((aligned(16))) float gt[ES_CO * GS];
-  __shared__ __attribute__((aligned(16))) uint32_t mw[256];
+  KV_LDS16(float, gt, [ES_CO * GS]);
+  KV_LDS16(uint32_t, mw, [256]);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
   const int tap = j < 9 ? j : 8;
   const float *tb = tile + (8 * wv) * ES_TS + 2 * g + (tap / 3) * ES_TS + tap % 3;   // pixel (4 wv + (s >> 2), 4 (s & 3) + g), tap j

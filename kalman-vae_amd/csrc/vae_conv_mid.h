@@ -15,6 +15,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lds_decl.h"
+
 namespace kvae {
 
 typedef float em_f16 __attribute__((ext_vector_type(16)));
@@ -40,6 +42,19 @@ __device__ __forceinline__ void em_load_weights(float *Wl, const float *__restri
 
 constexpr int EM_OOB = 1 << 24;   // float index 64 MiB past the start of LDS
 constexpr int64_t EM_MAX_BYTES = (int64_t)1 << 31;   // one launch addresses its tensors with 32-bit byte offsets
+constexpr int EM_MAX_WGS = 256;                      // one persistent workgroup per CU
+
+// Launch geometry of the three passes, host side (kvae_vae.hip; the test-only emulated workgroups call the same functions with a
+// lower cap).  The grid: one workgroup per iteration up to the cap.
+inline int64_t em_grid(int64_t N, int32_t side, int64_t cap = EM_MAX_WGS) {
+  const int64_t fpi = side == 16 ? 2 : 8, iters = (N + fpi - 1) / fpi;
+  return iters < cap ? (iters < 1 ? 1 : iters) : cap;
+}
+// What one launch may address: the prefetch of the last round reaches `cap` iterations (of at most 8 frames) past the end, and that
+// byte offset must still be below 2^31 - it is computed in 32 bits and has to land OUTSIDE the buffer resource, not wrap into it.
+inline bool em_launch_ok(int64_t N, int32_t side, int64_t cap = EM_MAX_WGS) {
+  return N >= 1 && (N + cap * 8) * EM_C * side * side * 4 < EM_MAX_BYTES;
+}
 
 // Global traffic goes through raw buffer instructions: out-of-range lanes (the ragged last iteration, the prefetch
 // past the end) load zeros / drop their stores in hardware, so the loops carry no branches around memory operations
@@ -50,7 +65,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t em_rsrc(const void *p, int64_t
 }
 __device__ __forceinline__ float4 em_ld4(__amdgpu_buffer_rsrc_t r, uint32_t byte_off) {
   const em_u4 v = __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0);
-  return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+  return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
 }
 __device__ __forceinline__ void em_st4(__amdgpu_buffer_rsrc_t r, uint32_t byte_off, const float4 v) {
   const em_u4 u = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
@@ -77,7 +92,7 @@ template <int S>
 __global__ __launch_bounds__(256) void k_enc_mid_fwd(const float *__restrict__ in, const float *__restrict__ W,
                                                      const float *__restrict__ bias, float *__restrict__ out, int64_t N) {
   using D = EmDims<S>;
-  __shared__ float lds[EM_W + D::IT_IN + D::IT_OUT];
+  KV_LDS(float, lds, [EM_W + D::IT_IN + D::IT_OUT]);
   float *Wl = lds, *fr = lds + EM_W, *ot = fr + D::IT_IN;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, q = lane & 31, half = lane >> 5;
   em_load_weights(Wl, W, true);
@@ -137,7 +152,7 @@ __global__ __launch_bounds__(256) void k_enc_mid_fwd(const float *__restrict__ i
       for (int u = 0; u < 4; ++u) {
         const int k = g * 4 + u, tap = k / 16, jj = k % 16, ky = tap / 3, kx = tap % 3;
         av[g][u] = Wl[abase + (tap * 32 + 2 * jj) * 32];
-        bw[g][u] = fr[(ky == 0 ? (kx == 0 ? b_tl : b_t) : (kx == 0 ? b_l : bbase)) + ky * S + kx + 2 * jj * D::PLANE];
+        bw[g][u] = KV_LDS_RD(fr, (ky == 0 ? (kx == 0 ? b_tl : b_t) : (kx == 0 ? b_l : bbase)) + ky * S + kx + 2 * jj * D::PLANE);
       }
     };
     rd(0);
@@ -176,7 +191,7 @@ template <int S>
 __global__ __launch_bounds__(256) void k_enc_mid_bwd_data(const float *__restrict__ W, const float *__restrict__ out,
                                                           const float *__restrict__ g_out, float *__restrict__ g_in, int64_t N) {
   using D = EmDims<S>;
-  __shared__ float lds[EM_W + D::IT_OUT + D::IT_IN];
+  KV_LDS(float, lds, [EM_W + D::IT_OUT + D::IT_IN]);
   float *Wl = lds, *gm = lds + EM_W, *ot = gm + D::IT_OUT;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, q = lane & 31, half = lane >> 5;
   em_load_weights(Wl, W, false);
@@ -228,7 +243,7 @@ __global__ __launch_bounds__(256) void k_enc_mid_bwd_data(const float *__restric
         const int en = g / 4, jj = (g % 4) * 4 + u, ph = E_CLS[en] >> 1, pw = E_CLS[en] & 1;
         const int dy = (ph == 1 && E_KY[en] == 0) ? 1 : 0, dx = (pw == 1 && E_KX[en] == 0) ? 1 : 0;   // oh = a + dy
         av[g][u] = Wl[abase + ((E_KY[en] * 3 + E_KX[en]) * 32 + 2 * jj) * 32];
-        bw[g][u] = gm[(dy ? (dx ? g_br : g_b) : (dx ? g_r : gbase)) + 2 * jj * D::PF + dy * D::OS + dx];
+        bw[g][u] = KV_LDS_RD(gm, (dy ? (dx ? g_br : g_b) : (dx ? g_r : gbase)) + 2 * jj * D::PF + dy * D::OS + dx);
       }
     };
     rd(0);
@@ -274,8 +289,8 @@ __global__ __launch_bounds__(256) void k_enc_mid_wrw(const float *__restrict__ i
                                                      float *__restrict__ b_partials, int64_t N) {
   using D = EmDims<S>;
   constexpr int CSP = D::PLANE + 1, GSP = D::PF + 1;
-  __shared__ float lds[D::FPI * EM_C * GSP + D::FPI * EM_C * CSP];
-  float *gm = lds, *xin = lds + D::FPI * EM_C * GSP;   // gm first: the (discarded) row/column -1 reads of xin stay in LDS
+  KV_LDS(float, lds, [D::FPI * EM_C * GSP + D::FPI * EM_C * CSP]);
+  float *gm = lds, *xin = lds + D::FPI * EM_C * GSP;   // (every row / column -1 read of xin takes an out-of-range base, x_t / x_l / x_tl below: none lands in gm)
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, q = lane & 31, half = lane >> 5;
   const int64_t iters = (N + D::FPI - 1) / D::FPI, total_in = N * D::FRAME, total_out = N * EM_C * D::PF;
   // this wave's 16 pixel pairs: S = 16 -> frame wv/2, pixels [32*(wv&1), +32); S = 8 -> frames 2wv, 2wv+1, all 16 pixels
@@ -342,7 +357,7 @@ __global__ __launch_bounds__(256) void k_enc_mid_wrw(const float *__restrict__ i
 #pragma unroll
       for (int tap = 0; tap < 9; ++tap) {
         const bool zt = tap / 3 == 0 && ohr == 0, zl = tap % 3 == 0 && owr == 0;
-        bw[i][tap] = xin[(zt ? (zl ? x_tl : x_t) : (zl ? x_l : bbase)) + fi * EM_C * CSP + (2 * ohr + tap / 3) * S + 2 * owr + tap % 3];
+        bw[i][tap] = KV_LDS_RD(xin, (zt ? (zl ? x_tl : x_t) : (zl ? x_l : bbase)) + fi * EM_C * CSP + (2 * ohr + tap / 3) * S + 2 * owr + tap % 3);
       }
     };
     rd(0);

@@ -9,8 +9,8 @@ argument order, tuple layouts and tensor shapes:
 Additions over the reference: condition, sample_posterior, predictive (exact log p(a_t | a_{0:t-1}, u), no tape),
 log_marginal / marginal (the same density, differentiable: the exact LGSSM training objective) and filter_regimes (the causal
 switching Kalman filter over the generative switching model).
-What differs is the execution: one launch (one wavefront per sequence, the whole T loop and the
-RTS sweep inside the kernel) replaces ~580 aten calls per time step, and the backward is a
+What differs is the execution: one launch (sixteen sequences per wavefront at (4,4,2), one wavefront
+per sequence at the other shapes; the whole T loop and the RTS sweep inside the kernel) replaces ~580 aten calls per time step, and the backward is a
 hand-derived adjoint kernel instead of an autograd tape.  Inputs must live on a HIP device.
 Everything native is reached through lgssm_ops (the bridge; it also lays out the packed step record: Slots, alpha_lstm_slots,
 slot_view); the read-outs' torch restatements it falls back to are lgssm_torch's.  Which operand form a pass used - a packed

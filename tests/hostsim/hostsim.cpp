@@ -158,6 +158,14 @@ void kvae_wemu_emission_means(const kvae_lgssm_problem *, const float *, const f
 int64_t kvae_wemu_bias_partial_rows(int64_t);
 void kvae_wemu_epilogue_fwd(const float *, const float *, float *, int64_t, int32_t, int32_t, int32_t, int32_t, int32_t);
 void kvae_wemu_epilogue_bwd(const float *, const float *, float *, float *, int64_t, int32_t, int32_t, int32_t, int32_t, int32_t);
+// wave_emu_conv.cpp: the encoder's stride-2 layers and its stem on emulated workgroups
+int64_t kvae_wemu_enc_mid_rows(int64_t, int32_t);
+int64_t kvae_wemu_conv_edge_rows(int64_t);
+int kvae_wemu_enc_mid_gate(int64_t, int32_t);
+void kvae_wemu_enc_mid_fwd(const float *, const float *, const float *, float *, int64_t, int32_t);
+void kvae_wemu_enc_mid_bwd(const float *, const float *, const float *, const float *, float *, float *, float *, int64_t, int32_t);
+void kvae_wemu_enc_stem_fwd(const float *, const float *, const float *, float *, uint32_t *, int64_t);
+int kvae_wemu_enc_stem_bwd(const float *, const float *, const uint32_t *, const float *, float *, float *, int64_t);
 }
 static int g_wave_emu = 0;
 static bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -531,7 +539,9 @@ extern "C" int kvae_lgssm_alpha_lstm_bwd(const kvae_lgssm_problem *, const kvae_
 
 // Direct convolutions of the VAE's thin layers: plain loops with the same argument checks as the HIP launchers.
 extern "C" {
-int64_t kvae_conv_edge_partial_rows(int64_t N) { return N < 1024 ? (N < 1 ? 1 : N) : 1024; }
+int64_t kvae_conv_edge_partial_rows(int64_t N) {   // (emulated: conv_edge_partial_rows of vae_conv_edge.h, the cap a test may lower)
+  return g_wave_emu ? kvae_wemu_conv_edge_rows(N) : (N < 1024 ? (N < 1 ? 1 : N) : 1024);
+}
 
 int kvae_dec_head_fwd(const float *in, const float *W, const float *bias, float *logits, float *w_scratch, int64_t N,
                       int32_t Cin, int32_t side, void *) {
@@ -586,11 +596,15 @@ int kvae_dec_head_bwd(const float *in, const float *W, const float *g_logits, fl
   }
   return KVAE_OK;
 }
-int kvae_enc_stem_fwd(const float *x, const float *W, const float *bias, float *out, uint32_t *, int64_t N, int32_t Cout,
+int kvae_enc_stem_fwd(const float *x, const float *W, const float *bias, float *out, uint32_t *relu_bits, int64_t N, int32_t Cout,
                       int32_t side, void *) {
   if (!x || !W || !bias || !out) return KVAE_ERR_NULL;
   if (N < 1) return KVAE_ERR_ARG;
   if (Cout != 32 || side != 32) return KVAE_ERR_DIMS;
+  if (g_wave_emu) {   // k_enc_stem_fwd
+    kvae_wemu_enc_stem_fwd(x, W, bias, out, relu_bits, N);
+    return KVAE_OK;
+  }
   const int S = side, O = side / 2;
   for (int64_t n = 0; n < N; ++n)
     for (int co = 0; co < Cout; ++co)
@@ -607,11 +621,12 @@ int kvae_enc_stem_fwd(const float *x, const float *W, const float *bias, float *
         }
   return KVAE_OK;
 }
-int kvae_enc_stem_bwd(const float *x, const float *out, const uint32_t *, const float *g_out, float *w_partials,
-                      float *b_partials, int64_t N, int32_t Cout, int32_t side, void *) {   // (mask always from out here)
-  if (!x || !out || !g_out || !w_partials || !b_partials) return KVAE_ERR_NULL;
+int kvae_enc_stem_bwd(const float *x, const float *out, const uint32_t *relu_bits, const float *g_out, float *w_partials,
+                      float *b_partials, int64_t N, int32_t Cout, int32_t side, void *) {   // (the twin: mask always from out)
+  if (!x || (g_wave_emu ? (!out && !relu_bits) : !out) || !g_out || !w_partials || !b_partials) return KVAE_ERR_NULL;
   if (N < 1) return KVAE_ERR_ARG;
   if (Cout != 32 || side != 32) return KVAE_ERR_DIMS;
+  if (g_wave_emu) return kvae_wemu_enc_stem_bwd(x, out, relu_bits, g_out, w_partials, b_partials, N);   // k_enc_stem_wrw / _mfma<.>
   const int S = side, O = side / 2;
   const int64_t rows = kvae_conv_edge_partial_rows(N);
   memset(w_partials, 0, sizeof(float) * rows * Cout * 9);
@@ -643,13 +658,19 @@ static int64_t enc_mid_grid_sim(int64_t N, int32_t side) {
   const int64_t fpi = side == 16 ? 2 : 8, iters = (N + fpi - 1) / fpi;
   return iters < 256 ? (iters < 1 ? 1 : iters) : 256;
 }
-int64_t kvae_enc_mid_partial_rows(int64_t N, int32_t side) { return enc_mid_grid_sim(N, side); }
+int64_t kvae_enc_mid_partial_rows(int64_t N, int32_t side) {   // (emulated: em_grid of vae_conv_mid.h, the cap a test may lower)
+  return g_wave_emu ? kvae_wemu_enc_mid_rows(N, side) : enc_mid_grid_sim(N, side);
+}
 
 int kvae_enc_mid_fwd(const float *in, const float *W, const float *bias, float *out, int64_t N, int32_t C, int32_t side,
                      void *) {
   if (!in || !W || !bias || !out) return KVAE_ERR_NULL;
-  if (N < 1) return KVAE_ERR_ARG;
+  if (N < 1 || (g_wave_emu && kvae_wemu_enc_mid_gate(N, side))) return KVAE_ERR_ARG;
   if (C != 32 || (side != 16 && side != 8)) return KVAE_ERR_DIMS;
+  if (g_wave_emu) {   // k_enc_mid_fwd<16 | 8>
+    kvae_wemu_enc_mid_fwd(in, W, bias, out, N, side);
+    return KVAE_OK;
+  }
   const int S = side, O = side / 2;
   for (int64_t n = 0; n < N; ++n)
     for (int co = 0; co < C; ++co)
@@ -670,8 +691,12 @@ int kvae_enc_mid_fwd(const float *in, const float *W, const float *bias, float *
 int kvae_enc_mid_bwd(const float *in, const float *W, const float *out, const float *g_out, float *g_in,
                      float *w_partials, float *b_partials, int64_t N, int32_t C, int32_t side, void *) {
   if (!in || !W || !out || !g_out || !w_partials || !b_partials) return KVAE_ERR_NULL;
-  if (N < 1) return KVAE_ERR_ARG;
+  if (N < 1 || (g_wave_emu && kvae_wemu_enc_mid_gate(N, side))) return KVAE_ERR_ARG;
   if (C != 32 || (side != 16 && side != 8)) return KVAE_ERR_DIMS;
+  if (g_wave_emu) {   // k_enc_mid_bwd_data<16 | 8> (g_in given), k_enc_mid_wrw<16 | 8>
+    kvae_wemu_enc_mid_bwd(in, W, out, g_out, g_in, w_partials, b_partials, N, side);
+    return KVAE_OK;
+  }
   const int S = side, O = side / 2;
   const int64_t rows = kvae_enc_mid_partial_rows(N, side);
   memset(w_partials, 0, sizeof(float) * rows * C * C * 9);

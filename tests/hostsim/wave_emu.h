@@ -21,6 +21,11 @@
 // atomicAdd(float *, float) on an LDS or a global word is a real atomic of the host (a compare-exchange loop on the 32-bit word):
 // the lanes are host threads, so ThreadSanitizer sees an atomic and AddressSanitizer its address; the order of the adds is as
 // free as on the card.
+// What the encoder's convolution kernels (csrc/vae_conv_mid.h, the stem of vae_conv_edge.h) lean on the hardware for is explicit
+// here: a raw buffer access (make_buffer_rsrc, raw_buffer_load_b128, raw_buffer_store_b128 / _b32) below num_records is the plain
+// access, one at or past it returns zeros / is dropped and is counted, one that straddles it aborts; an LDS read that may leave
+// the allocation on purpose (KV_LDS_RD) is the real read inside the workgroup's LDS object, 0 from kLdsOob elements on, an abort
+// between the two.
 // Arithmetic of the MFMA shims: k-ascending fmaf chains in fp32, which is what the kernels' parity argument assumes.
 // This is a sanitizer / debug harness, slow by design (a barrier per instruction): tiny problems only.
 #pragma once
@@ -111,14 +116,28 @@ struct Block {
     if (posix_memalign(&ptr, 16, bytes ? bytes : 1) != 0) abort();   // exactly `bytes`: the next byte is a redzone
     memset(ptr, 0xFF, bytes);                                         // NaNs
     lds_.emplace(key, ptr);
+    bytes_.emplace(key, bytes);
     return ptr;
   }
   void *dyn_shared() { return shared(-1, dyn_bytes_); }
+  // the LDS object of this workgroup that holds address p: its first byte and one past its last, or false
+  bool object_of(const void *p, const char **lo, const char **hi) {
+    std::lock_guard<std::mutex> lk(m_);
+    for (auto &kv : lds_) {
+      const char *b = static_cast<const char *>(kv.second), *e = b + bytes_[kv.first];
+      if (static_cast<const char *>(p) >= b && static_cast<const char *>(p) < e) {
+        *lo = b, *hi = e;
+        return true;
+      }
+    }
+    return false;
+  }
   Barrier bar;
 
  private:
   std::mutex m_;
   std::map<int, void *> lds_;
+  std::map<int, size_t> bytes_;
   const size_t dyn_bytes_;
 };
 inline thread_local Block *t_block = nullptr;
@@ -215,6 +234,92 @@ inline V4 mfma_16x16x4(float x, float y, V4 c) {        // A[i][k] on lane i + 1
   return c;
 }
 
+template <class V16>
+inline V16 mfma_32x32x2(float x, float y, V16 c) {      // A[i][k] on lane i + 32 k, B[k][j] on lane j + 32 k, D[(r & 3) + 8 (r >> 2) + 4 h][j] in reg r of lane (j, h)
+  const int p = t_par;
+  t_par ^= 1;
+  const int l = lane_id(), j = l & 31, h = l >> 5;
+  t_wave->a[p][l] = fbits(x), t_wave->b[p][l] = fbits(y);
+  sync();
+  for (int r = 0; r < 16; ++r) {
+    const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+    for (int k = 0; k < 2; ++k) c[r] = fmaf(bitsf(t_wave->a[p][row + 32 * k]), bitsf(t_wave->b[p][j + 32 * k]), c[r]);
+  }
+  return c;
+}
+
+// Raw buffer resources (stride 0): base + num_records bytes.  An access wholly below num_records is the plain access at
+// base + offset (AddressSanitizer sees the real address: a resource longer than its tensor becomes a report); one wholly at or
+// past it loads zeros / is dropped and is counted (oob_loads / oob_stores, read and reset by whoever launches); one that straddles
+// num_records is nothing the product issues, and how the hardware range-checks inside an access must not decide a test: abort.
+struct Rsrc {
+  char *base;
+  uint32_t num_records;
+};
+typedef unsigned int U4 __attribute__((vector_size(16)));   // what `unsigned int ext_vector_type(4)` is in a host build
+inline std::atomic<long> oob_loads{0}, oob_stores{0};
+inline thread_local const char *t_kernel = "?";         // named by the launcher, for the abort messages below
+inline Rsrc make_rsrc(void *p, int, int num_records, int) { return Rsrc{static_cast<char *>(p), (uint32_t)num_records}; }
+inline int buffer_class(const Rsrc &r, uint32_t off, uint32_t bytes) {   // 1 inside, 0 outside, -1 straddling
+  return (uint64_t)off + bytes <= r.num_records ? 1 : (off >= r.num_records ? 0 : -1);
+}
+inline int buffer_range(const Rsrc &r, uint32_t off, uint32_t bytes, const char *what) {   // 1 inside, 0 outside
+  const int c = buffer_class(r, off, bytes);
+  if (c >= 0) return c;
+  fprintf(stderr, "wave_emu: %s of %u bytes at offset %u straddles num_records = %u (kernel %s, block %u, lane %u)\n", what, bytes, off,
+          r.num_records, t_kernel, t_bid.x, t_tid.x);
+  fflush(stderr);
+  abort();
+}
+inline U4 buffer_load_b128(const Rsrc &r, uint32_t voff, uint32_t soff) {
+  U4 out = {0, 0, 0, 0};
+  if (buffer_range(r, voff + soff, 16, "buffer load")) memcpy(&out, r.base + (voff + soff), 16);
+  else oob_loads.fetch_add(1, std::memory_order_relaxed);
+  return out;
+}
+template <class V>
+inline void buffer_store_b128(const V &v, const Rsrc &r, uint32_t voff, uint32_t soff) {
+  if (buffer_range(r, voff + soff, 16, "buffer store")) {
+    memcpy(r.base + (voff + soff), &v, 16);
+  } else {
+    oob_stores.fetch_add(1, std::memory_order_relaxed);
+  }
+}
+inline void buffer_store_b32(uint32_t v, const Rsrc &r, uint32_t voff, uint32_t soff) {
+  if (buffer_range(r, voff + soff, 4, "buffer store")) memcpy(r.base + (voff + soff), &v, 4);
+  else oob_stores.fetch_add(1, std::memory_order_relaxed);
+}
+
+// KV_LDS_RD of csrc/lds_decl.h: a DS read whose address may lie outside the workgroup's LDS on purpose.  The index counts from
+// `arr`, a pointer into one LDS object of the workgroup: inside that object the real read (sanitizer-checked, NaN where no lane
+// wrote), at kLdsOob elements or above the 0 the hardware returns, anywhere between - an address the card would also answer,
+// with a neighbour's data or with 0 depending on the allocation - abort.
+constexpr long kLdsOob = 1 << 24;
+// `arr` sits `before` elements into its object and `after` elements before its end: 1 the real read, 0 out of range, -1 between
+inline int lds_class(long before, long after, long i) { return i >= -before && i < after ? 1 : (i >= kLdsOob ? 0 : -1); }
+inline thread_local const char *t_lds_lo = nullptr, *t_lds_hi = nullptr;   // the object of this lane's last KV_LDS_RD (reset per block)
+template <class T>
+inline T lds_read(const T *arr, long i, const char *name) {
+  const char *&lo = t_lds_lo, *&hi = t_lds_hi;
+  const char *base = reinterpret_cast<const char *>(arr);
+  if (base < lo || base >= hi) {
+    if (!t_block || !t_block->object_of(arr, &lo, &hi)) {
+      fprintf(stderr, "wave_emu: KV_LDS_RD(%s, %ld): not an LDS array of this workgroup (kernel %s, block %u, lane %u)\n", name, i,
+              t_kernel, t_bid.x, t_tid.x);
+      fflush(stderr);
+      abort();
+    }
+  }
+  const int c = lds_class((long)((base - lo) / (long)sizeof(T)), (long)((hi - base) / (long)sizeof(T)), i);
+  if (c == 0) return T(0);
+  if (c == 1) return arr[i];
+  fprintf(stderr, "wave_emu: KV_LDS_RD(%s, %ld) is outside the workgroup's LDS object (%ld elements before it .. %ld after) and below the "
+          "out-of-range base %ld (kernel %s, block %u, lane %u)\n", name, i, (long)((base - lo) / (long)sizeof(T)),
+          (long)((hi - base) / (long)sizeof(T)), kLdsOob, t_kernel, t_bid.x, t_tid.x);
+  fflush(stderr);
+  abort();
+}
+
 // launch: `blocks` one-wavefront workgroups, one after the other, 64 threads each
 inline void launch(unsigned blocks, const std::function<void()> &body) {
   for (unsigned blk = 0; blk < blocks; ++blk) {
@@ -304,7 +409,7 @@ inline void launch_wg(Dim3 grid, unsigned threads, size_t dyn_bytes, const std::
         if (!s) s = new BlockSlot(threads, dyn_bytes);
         slot = s;
       }
-      t_block = &slot->blk, t_wave = &slot->waves[l / 64], t_par = 0, t_rpar = 0;
+      t_block = &slot->blk, t_wave = &slot->waves[l / 64], t_par = 0, t_rpar = 0, t_lds_lo = t_lds_hi = nullptr;
       t_tid = {l, 0, 0}, t_gdim = grid, t_bdim = {threads, 1, 1};
       t_bid = {(unsigned)(b % grid.x), (unsigned)(b / grid.x % grid.y), (unsigned)(b / ((uint64_t)grid.x * grid.y))};
       body();
@@ -328,6 +433,11 @@ struct alignas(16) float4 {
 struct alignas(8) float2 {
   float x, y;
 };
+struct alignas(16) uint4 {
+  uint32_t x, y, z, w;
+};
+inline float __uint_as_float(uint32_t u) { return wemu::bitsf(u); }
+inline uint32_t __float_as_uint(float x) { return wemu::fbits(x); }
 inline float4 make_float4(float x, float y, float z, float w) { return float4{x, y, z, w}; }
 inline float2 make_float2(float x, float y) { return float2{x, y}; }
 
@@ -358,6 +468,12 @@ inline float atomicAdd(float *addr, float v) {
 #define __builtin_amdgcn_mov_dpp(v, ctrl, rm, bm, bc) wemu::mov_dpp((v), (ctrl), (rm), (bm), (bc))
 #define __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, x, y, z) wemu::mfma_4x4x1((a), (b), (c))
 #define __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, x, y, z) wemu::mfma_16x16x4((a), (b), (c))
+#define __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, x, y, z) wemu::mfma_32x32x2((a), (b), (c))
+#define __amdgpu_buffer_rsrc_t wemu::Rsrc
+#define __builtin_amdgcn_make_buffer_rsrc(p, stride, num, flags) wemu::make_rsrc((p), (stride), (num), (flags))
+#define __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, aux) wemu::buffer_load_b128((r), (voff), (soff))
+#define __builtin_amdgcn_raw_buffer_store_b128(v, r, voff, soff, aux) wemu::buffer_store_b128((v), (r), (voff), (soff))
+#define __builtin_amdgcn_raw_buffer_store_b32(v, r, voff, soff, aux) wemu::buffer_store_b32((v), (r), (voff), (soff))
 #define __builtin_amdgcn_permlane16_swap(a, b, fi, bc) wemu::permlane_swap((a), (b), 16)
 #define __builtin_amdgcn_permlane32_swap(a, b, fi, bc) wemu::permlane_swap((a), (b), 32)
 #define __builtin_amdgcn_rcpf(x) (1.0f / (x))

@@ -20,8 +20,9 @@ using namespace kvae;
 // launches so far: 0 / 1 LSTM fwd / bwd, 2 / 3 bi-GRU fwd / bwd, 4 / 5 regime lane-grid fwd / bwd, 6 / 7 regime thread-per-
 // sequence fwd / bwd, 8 / 9 regime LDS bodies fwd / bwd (run by hostsim.cpp, noted here); 10 .. 32: the reduction, mixture and
 // linear-head kernels, one index per instance (wave_emu_reduce.cpp); 33 .. 45: the optimizer, loss-head, column-sum, emission and
-// conv-epilogue kernels, one index per instance (wave_emu_step.cpp)
-constexpr int kKinds = 46;
+// conv-epilogue kernels, one index per instance (wave_emu_step.cpp); 46 .. 55: the encoder's convolution kernels, one index per
+// instance (wave_emu_conv.cpp)
+constexpr int kKinds = 56;
 static int g_launches[kKinds] = {};
 // the switches of the GPU dispatch: KVAE_REGIME_TPP (kvae_lgssm.hip: 1 lane grid up to the batch threshold, then thread per
 // sequence; 2 thread per sequence always; 0 the LDS bodies) and the threshold itself, settable here so that the thread-per-
@@ -56,10 +57,13 @@ static void k_selftest(float *out, int *fresh, int n_dyn) {
   out[blk * nt + tid] = other + 0.5f * pair + 0.25f * d + extra + 4096.f * blockIdx.y + 16384.f * blockIdx.z;
 }
 
+extern "C" int kvae_wemu_conv_selftest(void);   // wave_emu_conv.cpp: the 32x32x2 MFMA map, raw buffer accesses, KV_LDS_RD
+
 extern "C" {
 
 // 0 if launch_wg, the block barrier, both kinds of LDS and __shfl_xor behave and no state of a block reaches the next one (a 3-D
-// grid of 2 x 3 x 2 blocks on persistent lane threads); the number of wrong elements otherwise
+// grid of 2 x 3 x 2 blocks on persistent lane threads) and the 32x32x2 MFMA map, the buffer accesses in and out of range and the
+// three outcomes of an LDS read that may leave the allocation do too; the number of wrong elements otherwise
 int kvae_wemu_selftest(void) {
   const int gx = 2, gy = 3, gz = 2, blocks = gx * gy * gz, nt = 192, n_dyn = 7;
   std::vector<float> out((size_t)blocks * nt, NAN);
@@ -73,7 +77,7 @@ int kvae_wemu_selftest(void) {
                          4096.f * by + 16384.f * bz;
       bad += out[(size_t)b * nt + t] != want;
     }
-  return bad;
+  return bad + kvae_wemu_conv_selftest();
 }
 
 int kvae_wemu_rnn_launches(int which) { return which >= 0 && which < kKinds ? g_launches[which] : -1; }
