@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 #define KVAE_MAX_DIM 16
-#define KVAE_ABI_VERSION 22
+#define KVAE_ABI_VERSION 23
 
 typedef enum {
   KVAE_OK = 0,
@@ -838,6 +838,48 @@ typedef struct {
  * ess_threshold outside [0,1], a partly given carried state, or more replicates than one grid holds.  Nothing is written on
  * error.  At most three launches: the sweep, the lineages, seq_ll. */
 int kvae_lgssm_switching_pf(const kvae_spf_problem *prob, void *stream);
+
+/* ---- multi-horizon forecasts of the switching model, GPB2 (kvae/model/model.py KVAE.forecast_regimes) ---------------------------
+ * Forward: kvae_lgssm_switching_filter over `filt` (the same fields and NULL rules, a carried state allowed, every output the bits
+ * of that call's) which also keeps, per step t, what it hands to step t + 1: the collapsed per-regime beliefs (hist_mu, hist_Sigma)
+ * and the log weights log w'(j) (hist_lw) - the history of kvae_lgssm_switching_marginal.  Forecast: for every origin t = t0 .. T-1
+ * (o = t - t0) and horizon h = 1 .. H, from (log w, mu^k, Sigma^k) = the history of step t, ONE horizon step is the filter's hidden
+ * step - its statements, with P always (never the uniform matrix of a first step), gain times 0 - on u_all[t + h]:
+ *   pair (i -> j): mu_p = A_j mu^i + B_j u, Sigma_p = A_j Sigma^i A_j^T + Q_j, a_ij = C mu_p, S_ij = sym(C Sigma_p C^T + R)
+ *   pw_ij = w(i) P[i,j]                         regime_fore(j) = sum_i pw_ij                    (= regime_filt_t P^h, exact)
+ *   a_fore = sum_ij pw_ij a_ij                  S_fore = sum_ij pw_ij (S_ij + (a_ij - a_fore)(a_ij - a_fore)^T)   (exact moments)
+ *   l_ij = log N(a_{t+h}; a_ij, S_ij) by the ladder of kvae_lgssm_predictive
+ *   ll_fore = logsumexp_ij(log w(i) + log P[i,j] + l_ij)   where t + h < T and mask_{t+h} != 0, else exactly 0
+ *             (= log p(a_{t+h} | a_{0:t}, u): exact at h = 1, K^2 components in place of K^{h+1} beyond)
+ *   levels_fore = the largest ladder level over the pairs with pw_ij > 0 (where there is no target frame, of a_{t+h} = 0)
+ *   collapse over i with W_{i|j} = pw_ij / sum_i pw_ij (one-hot at i = j in a dead column) -> (log w'(j), mu'^j, Sigma'^j) for h + 1
+ *   mus_fore / Sigmas_fore = the moment match of the K collapsed Gaussians under w'                              (exact moments)
+ * Outputs are indexed [b, o, h - 1] with T_o = T - t0 origins (t0 = 0: every origin; t0 = T - 1: the last one, the online case).
+ * A hidden origin is legitimate: its state is whatever the filter holds there.  Built for the filter's shapes (fp32, K <= 8,
+ * n <= 4, m <= 4, p == 2): one wavefront per (sequence, origin) on the filter's 8 x 8 grid, everything in registers
+ * (csrc/lgssm_swh.h).  At most three launches: forward, forecast (grid B T_o; skipped when none of its outputs is asked for),
+ * seq_ll.  No atomics, every output element written once, two calls give the same bits; any output may be NULL and the bits of
+ * the others do not depend on it. */
+typedef struct {
+  kvae_swf_problem filt;      /* the forward pass: inputs and filter outputs, as kvae_lgssm_switching_filter; filt.u is [B,T,m] */
+  float *hist_lw;             /* [B,T,K]      workspace, required: written by the forward, read by the forecast              */
+  float *hist_mu;             /* [B,T,K,n]                                                                                   */
+  float *hist_Sigma;          /* [B,T,K,n,n]                                                                                 */
+  int32_t H;                  /* horizons 1 .. H                                                                             */
+  int32_t t0;                 /* first origin, 0 <= t0 < T                                                                   */
+  const float *u_all;         /* [B,T+H,m]    required: u_all[:, :T] holds what filt.u holds                                 */
+  float *regime_fore;         /* [B,T_o,H,K]    outputs: each may be NULL                                                    */
+  float *a_fore;              /* [B,T_o,H,p]                                                                                 */
+  float *S_fore;              /* [B,T_o,H,p,p]                                                                               */
+  float *mus_fore;            /* [B,T_o,H,n]                                                                                 */
+  float *Sigmas_fore;         /* [B,T_o,H,n,n]                                                                               */
+  float *ll_fore;             /* [B,T_o,H]                                                                                   */
+  int32_t *levels_fore;       /* [B,T_o,H]                                                                                   */
+} kvae_swh_problem;
+/* The error codes of kvae_lgssm_switching_filter over `filt`; in addition KVAE_ERR_NULL: prob, a history buffer or u_all NULL;
+ * KVAE_ERR_DIMS: H < 1; KVAE_ERR_ARG: t0 outside [0, T), or more (sequence, origin) items than one grid holds.  Nothing is
+ * written on error. */
+int kvae_lgssm_switching_forecast(const kvae_swh_problem *prob, void *stream);
 
 /* ---- misc --------------------------------------------------------------------------------- */
 int kvae_abi_version(void);

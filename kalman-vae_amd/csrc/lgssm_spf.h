@@ -401,4 +401,6 @@ extern "C" int kvae_lgssm_switching_pf(const kvae_spf_problem *prob, void *) {
   return KVAE_OK;
 }
 extern "C" int kvae_wemu_switching_pf_launches(int which) { return which >= 0 && which <= 2 ? kvae_spf::emu_launches()[which] : -1; }
+
+#include "lgssm_swh.h"    // likewise kvae_lgssm_switching_forecast
 #endif

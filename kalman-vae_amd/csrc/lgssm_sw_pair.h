@@ -1,8 +1,8 @@
 // lgssm_sw_pair.h — the per-pair statements of the GPB2 kernels on the 8 x 8 lane grid, written once: the switching filter
-// (csrc/lgssm_swf.h), the switching smoother (csrc/lgssm_sws.h), the adjoint of the regime marginal (csrc/lgssm_swm.h) and the E-step
-// of EM (csrc/lgssm_em.h) are composed of them, so where two kernels must give the same bits (the smoother's predict and the
-// filter's, the adjoint's recomputed step and the forward's, the E-step's smoother outputs and the smoother's) they run the same
-// statements.  lane = 8 g + k owns the pair (regime k on the side that is "along the lanes", regime g "on the groups"); A_g, B_g,
+// (csrc/lgssm_swf.h), the switching smoother (csrc/lgssm_sws.h), the adjoint of the regime marginal (csrc/lgssm_swm.h), the E-step
+// of EM (csrc/lgssm_em.h) and the multi-horizon forecast (csrc/lgssm_swh.h) are composed of them, so where two kernels must give
+// the same bits (the smoother's predict and the filter's, the adjoint's recomputed step and the forward's, the E-step's smoother
+// outputs and the smoother's, the forecast's horizon step and the filter's hidden step) they run the same statements.  lane = 8 g + k owns the pair (regime k on the side that is "along the lanes", regime g "on the groups"); A_g, B_g,
 // Q_g sit in registers padded with zeros to 4 x 4 (run-time n, m <= 4).
 // Everything here is a __forceinline__ function over references to float[4] / float[4][4] (or a small struct of them): after
 // inlining a result that a caller does not read is dead code.  No per-lane array is indexed at run time (every loop is unrolled
@@ -245,6 +245,65 @@ __device__ __forceinline__ void hand_over(int src, bool live, float pad, float s
       const float x = __shfl(S[r][c], src, 64);
       So[r][c] = live ? x : 0.0f;
       So[c][r] = So[r][c];
+    }
+  }
+}
+
+// ---- the collapse of a step over i, inside column j: regime j's belief (mc, the upper triangle of Sc), on the groups ----
+__device__ __forceinline__ void collapse_pairs(float W, const float (&muf)[4], const float (&Sf)[4][4], float (&mc)[4], float (&Sc)[4][4]) {
+  float d[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    mc[r] = oct_sum(W * muf[r]);
+    d[r] = muf[r] - mc[r];
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+#pragma unroll
+    for (int c = r; c < 4; ++c) Sc[r][c] = oct_sum(W * fmaf(d[r], d[c], Sf[r][c]));
+  }
+}
+
+// ---- the moment match of the K^2 pair forecasts under the prior weights pw = w(i) P[i,j]: row q of a_pred [., 2] and of
+// S [., 2, 2]; either may be NULL ----
+__device__ __forceinline__ void forecast_outputs(const Lane &ln, const Update &U, float pw, int64_t q, float *a_pred, float *S_out) {
+  if (a_pred || S_out) {
+    const float a0 = wave_sum(pw * U.ap[0]), a1 = wave_sum(pw * U.ap[1]);
+    if (a_pred && ln.lane == 0) a_pred[q * 2] = a0, a_pred[q * 2 + 1] = a1;
+    if (S_out) {
+      const float e0 = U.ap[0] - a0, e1 = U.ap[1] - a1;
+      const float o00 = wave_sum(pw * fmaf(e0, e0, U.S00)), o01 = wave_sum(pw * fmaf(e0, e1, U.S01));
+      const float o11 = wave_sum(pw * fmaf(e1, e1, U.S11));
+      if (ln.lane == 0) {
+        float *o = S_out + q * 4;
+        o[0] = o00, o[1] = o01, o[2] = o01, o[3] = o11;
+      }
+    }
+  }
+}
+
+// ---- the moment match of the K collapsed Gaussians (mc, Sc: on the groups) under wj = w'(j): row q of mus [., n] and of
+// Sigmas [., n, n]; either may be NULL.  The operands are already equal inside a group (wj = 0 on the groups past K), so the sum
+// over the groups is all there is ----
+__device__ __forceinline__ void belief_outputs(const Lane &ln, int n, float wj, const float (&mc)[4], const float (&Sc)[4][4], int64_t q,
+                                               float *mus, float *Sigmas) {
+  if (mus || Sigmas) {
+    float mm[4], dd[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      mm[r] = xg8<0>(wj * mc[r]);
+      dd[r] = mc[r] - mm[r];
+      if (mus && ln.lane == 0 && r < n) mus[q * n + r] = mm[r];
+    }
+    if (Sigmas) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+#pragma unroll
+        for (int c = r; c < 4; ++c) {
+          const float v = xg8<0>(wj * fmaf(dd[r], dd[c], Sc[r][c]));
+          if (ln.lane == 0 && c < n) Sigmas[q * n * n + r * n + c] = v, Sigmas[q * n * n + c * n + r] = v;
+        }
+      }
     }
   }
 }

@@ -24,19 +24,17 @@
 
 namespace kvae_swf {
 
-using kvae::rdec::xg8;
 using kvae::rgrid::oct_sum;
 using kvae_sw::padded;
 using kvae_sw::wave_max;
-using kvae_sw::wave_sum;
 
 constexpr int MAX_K = 8, MAX_N = 4, MAX_M = 4;
 
 // What the smoother's forward (csrc/lgssm_sws.h, k_sws_fwd) keeps of every step: the collapsed per-regime beliefs - the values the
 // sweep hands to step t + 1 - the pair weights W of that step, and the weights after the last step.  The forward of the
 // differentiable log-likelihood (csrc/lgssm_swm.h, k_swm_fwd: HIST = 2) keeps the beliefs and, in place of W and w, the log weights
-// log w' handed to step t + 1; its adjoint recomputes W.  The filter's own sweep (HIST = 0) holds none of it and compiles to what
-// it was.
+// log w' handed to step t + 1; its adjoint recomputes W, and the forecast (csrc/lgssm_swh.h, k_swh_fwd: HIST = 2 as well) starts
+// every origin from them.  The filter's own sweep (HIST = 0) holds none of it and compiles to what it was.
 struct History {
   float *mu;      // [B,T,K,n]
   float *Sigma;   // [B,T,K,n,n]
@@ -107,17 +105,8 @@ __device__ inline void sweep_wave(const kvae_swf_problem &P, const History H = H
     const float lwn = (wt.cmx + logf(wt.se)) - tot;                 // log w'(j), on the groups
     const float rf = vg ? expf(lwn) : 0.0f;
     // ---- collapse over i ----
-    float mc[4], Sc[4][4], d[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      mc[r] = oct_sum(W * U.muf[r]);
-      d[r] = U.muf[r] - mc[r];
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int c = r; c < 4; ++c) Sc[r][c] = oct_sum(W * fmaf(d[r], d[c], U.Sf[r][c]));
-    }
+    float mc[4], Sc[4][4];
+    kvae_sw::collapse_pairs(W, U.muf, U.Sf, mc, Sc);
     // ---- the step's outputs ----
     if (P.regime_pred && vg && k == 0) P.regime_pred[q * K + g] = rp;
     if (P.regime_filt && vg && k == 0) P.regime_filt[q * K + g] = rf;
@@ -126,39 +115,8 @@ __device__ inline void sweep_wave(const kvae_swf_problem &P, const History H = H
       const float lv = wave_max(pw > 0.0f ? (float)U.tl.level : 0.0f);
       if (lane == 0) P.levels[q] = (int32_t)lv;
     }
-    if (P.a_pred || P.S_out) {   // moment match of the K^2 pair forecasts under the prior weights
-      const float a0 = wave_sum(pw * U.ap[0]), a1 = wave_sum(pw * U.ap[1]);
-      if (P.a_pred && lane == 0) P.a_pred[q * 2] = a0, P.a_pred[q * 2 + 1] = a1;
-      if (P.S_out) {
-        const float e0 = U.ap[0] - a0, e1 = U.ap[1] - a1;
-        const float o00 = wave_sum(pw * fmaf(e0, e0, U.S00)), o01 = wave_sum(pw * fmaf(e0, e1, U.S01));
-        const float o11 = wave_sum(pw * fmaf(e1, e1, U.S11));
-        if (lane == 0) {
-          float *o = P.S_out + q * 4;
-          o[0] = o00, o[1] = o01, o[2] = o01, o[3] = o11;
-        }
-      }
-    }
-    if (P.mus_filt || P.Sigmas_filt) {   // moment match of the K collapsed Gaussians under w': the operands are already equal
-      const float wj = rf;               // inside a group (rf = 0 on the groups past K), so the sum over the groups is all there is
-      float mm[4], dd[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        mm[r] = xg8<0>(wj * mc[r]);
-        dd[r] = mc[r] - mm[r];
-        if (P.mus_filt && lane == 0 && r < n) P.mus_filt[q * n + r] = mm[r];
-      }
-      if (P.Sigmas_filt) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-#pragma unroll
-          for (int c = r; c < 4; ++c) {
-            const float v = xg8<0>(wj * fmaf(dd[r], dd[c], Sc[r][c]));
-            if (lane == 0 && c < n) P.Sigmas_filt[q * n * n + r * n + c] = v, P.Sigmas_filt[q * n * n + c * n + r] = v;
-          }
-        }
-      }
-    }
+    kvae_sw::forecast_outputs(ln, U, pw, q, P.a_pred, P.S_out);               // moment match of the K^2 pair forecasts
+    kvae_sw::belief_outputs(ln, n, rf, mc, Sc, q, P.mus_filt, P.Sigmas_filt);   // moment match of the K collapsed Gaussians under w'
     if constexpr (HIST != 0) {   // the step's history: every live lane its own W, one lane per group the belief of regime j = g
       const bool w = vg && k == 0;
       const int64_t s = q * K + g;

@@ -310,6 +310,24 @@ class KalmanFilter(nn.Module):
                                             dyn._prior_matrix(dev, dt), self.mu0, self.Sigma0, Y, U, self._mask(mask, Y), want=want,
                                             state=state)
 
+    @torch.no_grad()
+    def forecast_regimes(self, Y, U, horizon, mask=None, origins="all", state=None, want=lgssm_ops._SWH_OUTPUTS):
+        """The generative switching model looking ahead (switching dynamics only): filter_regimes over Y [B,T,p], then from the
+        filter's state at every origin t the forecast of steps t+1 .. t+horizon, each horizon step the filter's hidden step -
+        lgssm_ops.switching_forecast; include/kvae_lgssm.h kvae_lgssm_switching_forecast.  U [B,T+horizon,m] or None = zeros.
+        origins: "all" (T_o = T) or "last" (T_o = 1).  state: as filter_regimes.  Returns filter_regimes' dict (the same bits) plus,
+        indexed [b, origin, h-1], regime_fore [B,T_o,H,K], a_fore [B,T_o,H,p], S_fore [B,T_o,H,p,p], mus_fore [B,T_o,H,n],
+        Sigmas_fore [B,T_o,H,n,n] (exact under the model), log_lik_fore [B,T_o,H] = log p(a_{t+h} | a_{0:t}, u) (0 where the target
+        is hidden or past the end), levels_fore [B,T_o,H]; entries not named in `want` are None."""
+        dyn = self.dyn_params
+        if not dyn.is_switching_dynamics:
+            raise ValueError("forecast_regimes needs switching dynamics (SwitchingDynamicsParameter): the alpha-network of the lstm "
+                             "dynamics has no regime chain to forecast")
+        dev, dt = Y.device, Y.dtype
+        return lgssm_ops.switching_forecast(dyn.A.detach(), dyn.B.detach(), dyn.Q.detach(), dyn.C[0].detach(), self.R,
+                                            dyn._prior_matrix(dev, dt), self.mu0, self.Sigma0, Y, U, horizon, self._mask(mask, Y),
+                                            origins=origins, want=want, state=state)
+
     def regime_log_marginal(self, Y, U, mask=None):
         """log p(a | u) of the generative switching model with the regimes summed out under GPB2 collapse, DIFFERENTIABLY (switching
         dynamics only): filter_regimes' log_lik / log_lik_seq / levels - the same bits - with a tape through A_k, B_k, Q_k, the

@@ -11,7 +11,7 @@ a whole step record, a single tensor carries its gradient) or a plain tensor tha
 ([r,c]) or per-step ([B,T,r,c]).
 
 This module is the bridge only.  The read-outs (regime_decode, rollout, posterior_paths, predictive, log_marginal,
-switching_filter, switching_smoother, switching_log_marginal, switching_em_statistics, switching_pf) dispatch between their kernel and its restatement in torch ops;
+switching_filter, switching_smoother, switching_log_marginal, switching_em_statistics, switching_pf, switching_forecast) dispatch between their kernel and its restatement in torch ops;
 the restatements - also the float64 references of the tests - and safe_cholesky / safe_cholesky_items live in lgssm_torch (no
 native library behind it) and are re-exported here.
 """
@@ -22,10 +22,10 @@ from typing import NamedTuple, Optional
 import torch
 
 from .. import _native as N
-from .lgssm_torch import (_DECODE_OUTPUTS, _EM_OUTPUTS, _EM_PARAMS, _EM_STATS, _LOG_2PI, _PRED_OUTPUTS, _SPF_OUTPUTS, _SWF_OUTPUTS, _SWS_OUTPUTS, _SWS_SMOOTH, _bt,  # noqa: F401 (re-exported)
-                          SPF_PARTICLES, _spf_draws, _spf_state, _swf_state, _want, lineages, switching_pf_torch, log_marginal_torch, posterior_paths_torch, predictive_torch, regime_decode_torch,
+from .lgssm_torch import (_DECODE_OUTPUTS, _EM_OUTPUTS, _EM_PARAMS, _EM_STATS, _LOG_2PI, _PRED_OUTPUTS, _SPF_OUTPUTS, _SWF_OUTPUTS, _SWH_FORE, _SWH_OUTPUTS, _SWS_OUTPUTS, _SWS_SMOOTH, _bt,  # noqa: F401 (re-exported)
+                          SPF_PARTICLES, _spf_draws, _spf_state, _swf_state, _swh_args, _want, lineages, switching_pf_torch, log_marginal_torch, posterior_paths_torch, predictive_torch, regime_decode_torch,
                           rollout_torch, safe_cholesky, safe_cholesky_items, switching_em_mstep, switching_em_statistics_torch,
-                          switching_filter_torch, switching_log_marginal_torch, switching_smoother_torch)
+                          switching_filter_torch, switching_forecast_torch, switching_log_marginal_torch, switching_smoother_torch)
 
 
 class Slots(NamedTuple):
@@ -1172,6 +1172,63 @@ def switching_smoother(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, want=_S
               "kvae_lgssm_switching_smoother")
     if out["regime_pairs"] is not None:
         out["regime_pairs"] = out["regime_pairs"][:, :T - 1]   # nothing is written at T = 1
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# multi-horizon forecasts of the switching model, GPB2 (kvae_lgssm_switching_forecast, csrc/lgssm_swh.h)
+# ------------------------------------------------------------------------------------------------
+def switching_forecast_supported(K, n, m, p, ref=None):
+    """Shapes / tensors kvae_lgssm_switching_forecast is built for: the filter's (switching_filter_supported); the rest takes
+    switching_forecast_torch."""
+    return switching_filter_supported(K, n, m, p, ref)
+
+
+@torch.no_grad()
+def switching_forecast(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U_all, horizon, mask=None, origins="all", want=_SWH_OUTPUTS, state=None,
+                       impl=None):
+    """Forecasts of the generative switching model at the horizons h = 1 .. H from every step of a sequence (semantics:
+    include/kvae_lgssm.h, kvae_lgssm_switching_forecast): switching_filter forwards over Y [B,T,p] with the
+    same arguments, then from the filter's state at every origin t, H of the filter's hidden steps on U_all[:, t + h].  U_all
+    [B,T+H,m], or None for zeros.  origins: "all" (t = 0 .. T-1, T_o = T) or "last" (t = T-1, T_o = 1: the online case after a
+    carried state).  want: any of switching_filter's outputs - the bits of that call's - and, indexed [b, t - t0, h - 1],
+    "regime_fore" [B,T_o,H,K] = p(s_{t+h} | a_{0:t}), "a_fore" [B,T_o,H,p], "S_fore" [B,T_o,H,p,p] the mean and covariance of
+    a_{t+h} | a_{0:t}, "mus_fore" [B,T_o,H,n], "Sigmas_fore" [B,T_o,H,n,n] those of z_{t+h} (all exact under the model), "log_lik_fore"
+    [B,T_o,H] = log p(a_{t+h} | a_{0:t}, u) where the target lies inside the sequence and is observed, else exactly 0 (exact at
+    h = 1, the GPB2 mixture beyond), "levels_fore" [B,T_o,H] (int32); entries not asked for are None.  At most three launches
+    (forward, forecast, log_lik_seq), no host synchronisation, no gradients.
+    impl: None = the HIP kernel where it is built (switching_forecast_supported), else switching_forecast_torch; "hip" / "torch"
+    force one."""
+    want = _want("switching_forecast", _SWH_OUTPUTS, want)
+    if impl not in (None, "hip", "torch"):
+        raise ValueError(f"switching_forecast: impl must be None, 'hip' or 'torch', got {impl!r}")
+    K, n, m = A.shape[0], A.shape[1], Bm.shape[2]
+    Bsz, T, p = Y.shape
+    H, t0, U_all = _swh_args("switching_forecast", Bm, Y, U_all, horizon, origins)
+    supported = switching_forecast_supported(K, n, m, p, Y)
+    if impl == "hip" and not supported:
+        raise ValueError(f"switching_forecast: impl='hip' needs fp32 tensors on a HIP device and K <= {SWF_SUPPORTED['max_K']}, "
+                         f"n <= {SWF_SUPPORTED['max_n']}, m <= {SWF_SUPPORTED['max_m']}, p == {SWF_SUPPORTED['p']}; got K = {K}, "
+                         f"n = {n}, m = {m}, p = {p}, {Y.dtype} on {Y.device}")
+    if impl == "torch" or not supported:
+        return switching_forecast_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U_all, H, mask, origins, state, want)
+    dev, To = Y.device, T - t0
+    U_all = _f32c(U_all.detach().to(dev))
+    fp = N.SwhProblem()
+    out, _, keep = _swf_problem(fp.filt, A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U_all[:, :T], mask, state,
+                                tuple(w for w in want if w in _SWF_OUTPUTS))
+    hist = (_empty(dev, Bsz, T, K), _empty(dev, Bsz, T, K, n), _empty(dev, Bsz, T, K, n, n))
+    fp.hist_lw, fp.hist_mu, fp.hist_Sigma = (t.data_ptr() for t in hist)
+    fp.H, fp.t0, fp.u_all = H, t0, U_all.data_ptr()
+    shapes = dict(regime_fore=(K,), a_fore=(p,), S_fore=(p, p), mus_fore=(n,), Sigmas_fore=(n, n), log_lik_fore=(), levels_fore=())
+    out.update({k: (_empty(dev, Bsz, To, H, *shapes[k], dt=torch.int32 if k == "levels_fore" else torch.float32) if k in want else None)
+                for k in _SWH_FORE})
+    fp.regime_fore, fp.a_fore, fp.S_fore = N.ptr(out["regime_fore"]), N.ptr(out["a_fore"]), N.ptr(out["S_fore"])
+    fp.mus_fore, fp.Sigmas_fore = N.ptr(out["mus_fore"]), N.ptr(out["Sigmas_fore"])
+    fp.ll_fore, fp.levels_fore = N.ptr(out["log_lik_fore"]), N.ptr(out["levels_fore"])
+    lib = N.lib_for(Y)
+    lib.check(N.timed("switching_forecast", Y, lambda: lib.dll.kvae_lgssm_switching_forecast(C.byref(fp), N.stream_for(Y))),
+              "kvae_lgssm_switching_forecast")
     return out
 
 

@@ -10,6 +10,8 @@ _LOG_2PI = 1.8378770664093453
 _SWF_OUTPUTS = ("regime_filt", "regime_pred", "log_lik", "log_lik_seq", "a_pred", "S", "mus_filt", "Sigmas_filt", "levels", "state")
 _SWS_SMOOTH = ("regime_smooth", "regime_pairs", "mus_smooth", "Sigmas_smooth")
 _SWS_OUTPUTS = _SWF_OUTPUTS + _SWS_SMOOTH
+_SWH_FORE = ("regime_fore", "a_fore", "S_fore", "mus_fore", "Sigmas_fore", "log_lik_fore", "levels_fore")
+_SWH_OUTPUTS = _SWF_OUTPUTS + _SWH_FORE
 
 
 def _want(op, outputs, want):
@@ -271,66 +273,82 @@ def _swf_forward(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, state, history=Fal
         mu, Sig = mu0.expand(Bsz, K, n), Sigma0.expand(Bsz, K, n, n)
     else:
         lw, mu, Sig = (t.detach().to(device=dev, dtype=dt) for t in st)
-    eye = torch.eye(n, device=dev, dtype=dt)
-    eyeK = torch.eye(K, device=dev, dtype=dt)
     uniform = torch.full((K, K), 1.0 / K, device=dev, dtype=dt)
-    ninf = torch.full((), -float("inf"), device=dev, dtype=dt)
     outs = {k: [] for k in ("regime_filt", "regime_pred", "log_lik", "a_pred", "S", "mus_filt", "Sigmas_filt", "levels")}
-    hist = {k: [] for k in ("mu", "Sigma", "W")} if history else None
+    hist = {k: [] for k in ("mu", "Sigma", "W", "lw")} if history else None
     for t in range(T):
         Pt = uniform if (t == 0 and st is None) else P
         mk = torch.ones(Bsz, device=dev, dtype=dt) if mask is None else mask[:, t]
-        observed = mk != 0
-        # ---- the K^2 filter steps: [B, i, j, ...] ----
-        mp = torch.einsum("jrc,bic->bijr", A, mu) + torch.einsum("jrc,bc->bjr", Bm, U[:, t]).unsqueeze(1)
-        Sp = torch.einsum("jre,biec,jdc->bijrd", A, Sig, A) + Q
-        ap = mp @ Cm.mT
-        res = Y[:, t, None, None, :] - ap
-        S = Cm @ Sp @ Cm.mT + R
-        S = 0.5 * (S + S.mT)
-        L, lv = safe_cholesky_items(S)
-        lij = _observed_only(_gauss_ll(L, res)[0], observed[:, None, None])
-        Kg = torch.linalg.solve(S, Cm @ Sp).mT * mk[:, None, None, None, None]      # S^-1 (Sigma_pred C^T)^T, transposed
-        muf = mp + (Kg @ res.unsqueeze(-1)).squeeze(-1)
-        IKC = eye - Kg @ Cm
-        Sf = IKC @ Sp @ IKC.mT + Kg @ R @ Kg.mT
-        Sf = 0.5 * (Sf + Sf.mT)
-        # ---- weights ----
-        logc = lw.unsqueeze(-1) + Pt.log() + lij                                     # [B, i, j]
-        pw = lw.exp().unsqueeze(-1) * Pt
-        cmx = logc.amax(1)                                                           # [B, j]
-        dead = cmx == ninf
-        ex = torch.where(dead.unsqueeze(1), eyeK.expand(Bsz, K, K), (logc - torch.where(dead, torch.zeros_like(cmx), cmx).unsqueeze(1)).exp())
-        se = ex.sum(1)
-        W = ex / se.unsqueeze(1)
-        mx = cmx.amax(-1, keepdim=True)
-        tot = mx.squeeze(-1) + (se * (cmx - mx).exp()).sum(-1).log()
-        lw = (cmx + se.log()) - tot.unsqueeze(-1)
-        rf = lw.exp()
-        # ---- collapse over i ----
-        mu = (W.unsqueeze(-1) * muf).sum(1)                                          # [B, j, n]
-        d = muf - mu.unsqueeze(1)
-        Sig = (W[..., None, None] * (Sf + d.unsqueeze(-1) * d.unsqueeze(-2))).sum(1)
-        Sig = 0.5 * (Sig + Sig.mT)
+        s = _swf_step(A, Bm, Q, Cm, R, Pt, lw, mu, Sig, Y[:, t], U[:, t], mk)
+        lw, mu, Sig = s["lw"], s["mu"], s["Sigma"]
         if history:
-            hist["mu"].append(mu), hist["Sigma"].append(Sig), hist["W"].append(W)
-        # ---- outputs of the step ----
-        outs["regime_pred"].append(pw.sum(1))
-        outs["regime_filt"].append(rf)
-        outs["log_lik"].append(torch.where(observed, tot, torch.zeros_like(tot)))
-        outs["levels"].append(torch.where(pw > 0, lv, torch.zeros_like(lv)).amax((1, 2)))
-        a = (pw.unsqueeze(-1) * ap).sum((1, 2))
-        e = ap - a[:, None, None, :]
-        outs["a_pred"].append(a)
-        outs["S"].append((pw[..., None, None] * (S + e.unsqueeze(-1) * e.unsqueeze(-2))).sum((1, 2)))
-        m_ = (rf.unsqueeze(-1) * mu).sum(1)
-        dd = mu - m_.unsqueeze(1)
-        outs["mus_filt"].append(m_)
-        outs["Sigmas_filt"].append((rf[..., None, None] * (Sig + dd.unsqueeze(-1) * dd.unsqueeze(-2))).sum(1))
+            hist["mu"].append(mu), hist["Sigma"].append(Sig), hist["W"].append(s["W"]), hist["lw"].append(lw)
+        for k in outs:
+            outs[k].append(s[k])
     full = {k: torch.stack(v, 1) for k, v in outs.items()}
     full["log_lik_seq"] = full["log_lik"].sum(1)
     full["state"] = {"log_w": lw, "mu": mu, "Sigma": Sig}
     return full, ({k: torch.stack(v, 1) for k, v in hist.items()} if history else None), (A, Bm, Q, Cm, U)
+
+
+def _swf_step(A, Bm, Q, Cm, R, Pt, lw, mu, Sig, y, u, mk, score=False):
+    """One step of the sweep over a batch [N, ...] (the sequences of the filter; the (sequence, origin) items of the forecast): from
+    the carried (lw [N,K], mu [N,K,n], Sig [N,K,n,n]) under the transition matrix Pt, the frame y [N,p], the input u [N,m] and the
+    mask mk [N].  Returns the step's outputs under the names of _SWF_OUTPUTS, the collapsed beliefs it hands on (lw, mu, Sigma) and
+    the pair weights W [N,i,j].  score: also "scored" [N] = logsumexp_ij(lw_i + log Pt[i,j] + l_ij) with the pair densities of y
+    whatever mk says - the density of a frame that the step itself does not condition on."""
+    dev, dt = A.device, A.dtype
+    K, n = A.shape[0], A.shape[1]
+    N = lw.shape[0]
+    eye = torch.eye(n, device=dev, dtype=dt)
+    eyeK = torch.eye(K, device=dev, dtype=dt)
+    ninf = torch.full((), -float("inf"), device=dev, dtype=dt)
+    observed = mk != 0
+    # ---- the K^2 filter steps: [N, i, j, ...] ----
+    mp = torch.einsum("jrc,bic->bijr", A, mu) + torch.einsum("jrc,bc->bjr", Bm, u).unsqueeze(1)
+    Sp = torch.einsum("jre,biec,jdc->bijrd", A, Sig, A) + Q
+    ap = mp @ Cm.mT
+    res = y[:, None, None, :] - ap
+    S = Cm @ Sp @ Cm.mT + R
+    S = 0.5 * (S + S.mT)
+    L, lv = safe_cholesky_items(S)
+    lraw = _gauss_ll(L, res)[0]
+    lij = _observed_only(lraw, observed[:, None, None])
+    Kg = torch.linalg.solve(S, Cm @ Sp).mT * mk[:, None, None, None, None]      # S^-1 (Sigma_pred C^T)^T, transposed
+    muf = mp + (Kg @ res.unsqueeze(-1)).squeeze(-1)
+    IKC = eye - Kg @ Cm
+    Sf = IKC @ Sp @ IKC.mT + Kg @ R @ Kg.mT
+    Sf = 0.5 * (Sf + Sf.mT)
+
+    def weights(logc):   # (the column softmax W_{i|j}, logsumexp_ij, log w'(j)); a dead column is one-hot at i = j
+        cmx = logc.amax(1)                                                       # [N, j]
+        dead = cmx == ninf
+        ex = torch.where(dead.unsqueeze(1), eyeK.expand(N, K, K), (logc - torch.where(dead, torch.zeros_like(cmx), cmx).unsqueeze(1)).exp())
+        se = ex.sum(1)
+        mx = cmx.amax(-1, keepdim=True)
+        tot = mx.squeeze(-1) + (se * (cmx - mx).exp()).sum(-1).log()
+        return ex / se.unsqueeze(1), tot, (cmx + se.log()) - tot.unsqueeze(-1)
+
+    # ---- weights ----
+    logp = lw.unsqueeze(-1) + Pt.log()                                           # [N, i, j]
+    pw = lw.exp().unsqueeze(-1) * Pt
+    W, tot, lw = weights(logp + lij)
+    rf = lw.exp()
+    # ---- collapse over i ----
+    mu = (W.unsqueeze(-1) * muf).sum(1)                                          # [N, j, n]
+    d = muf - mu.unsqueeze(1)
+    Sig = (W[..., None, None] * (Sf + d.unsqueeze(-1) * d.unsqueeze(-2))).sum(1)
+    Sig = 0.5 * (Sig + Sig.mT)
+    # ---- outputs of the step ----
+    a = (pw.unsqueeze(-1) * ap).sum((1, 2))
+    e = ap - a[:, None, None, :]
+    m_, V_ = _moment_match(rf, mu, Sig)
+    out = dict(lw=lw, mu=mu, Sigma=Sig, W=W, regime_pred=pw.sum(1), regime_filt=rf, log_lik=torch.where(observed, tot, torch.zeros_like(tot)),
+               levels=torch.where(pw > 0, lv, torch.zeros_like(lv)).amax((1, 2)), a_pred=a,
+               S=(pw[..., None, None] * (S + e.unsqueeze(-1) * e.unsqueeze(-2))).sum((1, 2)), mus_filt=m_, Sigmas_filt=V_)
+    if score:
+        out["scored"] = weights(logp + lraw)[1]
+    return out
 
 
 @torch.no_grad()
@@ -348,6 +366,58 @@ def _moment_match(w, mu, Sig):
     m_ = (w.unsqueeze(-1) * mu).sum(1)
     dd = mu - m_.unsqueeze(1)
     return m_, (w[..., None, None] * (Sig + dd.unsqueeze(-1) * dd.unsqueeze(-2))).sum(1)
+
+
+def _swh_args(op, Bm, Y, U_all, horizon, origins):
+    """(H, t0, U_all [B,T+H,m]) of a forecast call, checked: horizon >= 1, origins "all" (t0 = 0) or "last" (t0 = T - 1), U_all
+    [B,T+H,m] or None = zeros in the dtype of Y."""
+    H = int(horizon)
+    Bsz, T, m = Y.shape[0], Y.shape[1], Bm.shape[2]
+    if H < 1:
+        raise ValueError(f"{op}: horizon must be >= 1, got {horizon}")
+    if origins not in ("all", "last"):
+        raise ValueError(f"{op}: origins must be 'all' or 'last', got {origins!r}")
+    if U_all is None:
+        U_all = torch.zeros(Bsz, T + H, m, device=Y.device, dtype=Y.dtype)
+    if tuple(U_all.shape) != (Bsz, T + H, m):
+        raise ValueError(f"{op}: U_all must be [B, T+H, m] = [{Bsz}, {T + H}, {m}], got {list(U_all.shape)}")
+    return H, (0 if origins == "all" else T - 1), U_all
+
+
+@torch.no_grad()
+def switching_forecast_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U_all, horizon, mask=None, origins="all", state=None, want=_SWH_OUTPUTS):
+    """The equations of kvae_lgssm_switching_forecast (include/kvae_lgssm.h) in torch ops, in the dtype of A: the sweep of
+    switching_filter_torch with its history kept, then H horizon steps - each the sweep's own step (_swf_step) with the mask at 0 -
+    vectorised over the B * T_o (sequence, origin) items.  The fallback of switching_forecast and (in float64) the reference its
+    kernel is tested against.  Same arguments and returns as switching_forecast."""
+    want = _want("switching_forecast", _SWH_OUTPUTS, want)
+    H, t0, U_all = _swh_args("switching_forecast", Bm, Y, U_all, horizon, origins)
+    Bsz, T, p = Y.shape
+    full, hist, (A, Bm, Q, Cm, _) = _swf_forward(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U_all[:, :T], mask, state, history=True)
+    dt, dev = A.dtype, Y.device
+    K, n, To = A.shape[0], A.shape[1], T - t0
+    R, P, Y, U_all = (t.detach().to(device=dev, dtype=dt) for t in (R, P, Y, U_all))
+    mask = None if mask is None else mask.detach().to(device=dev, dtype=dt).reshape(Bsz, T)
+    items = lambda t: t[:, t0:].reshape(Bsz * To, *t.shape[2:])                 # [B, T, ...] -> [B T_o, ...]
+    lw, mu, Sig = items(hist["lw"]), items(hist["mu"]), items(hist["Sigma"])
+    hidden = torch.zeros(Bsz * To, device=dev, dtype=dt)
+    origin = torch.arange(t0, T, device=dev)
+    outs = {k: [] for k in _SWH_FORE}
+    for h in range(1, H + 1):
+        step = origin + h                                                        # [T_o]
+        target = step < T
+        at = step.clamp(max=T - 1)
+        y = torch.where(target[None, :, None], Y[:, at], torch.zeros((), device=dev, dtype=dt)).reshape(Bsz * To, p)
+        observed = (target[None, :] if mask is None else target[None, :] & (mask[:, at] != 0)).expand(Bsz, To).reshape(Bsz * To)
+        s = _swf_step(A, Bm, Q, Cm, R, P, lw, mu, Sig, y, U_all[:, step].reshape(Bsz * To, -1), hidden, score=True)
+        lw, mu, Sig = s["lw"], s["mu"], s["Sigma"]
+        outs["regime_fore"].append(s["regime_pred"]), outs["a_fore"].append(s["a_pred"]), outs["S_fore"].append(s["S"])
+        outs["mus_fore"].append(s["mus_filt"]), outs["Sigmas_fore"].append(s["Sigmas_filt"]), outs["levels_fore"].append(s["levels"])
+        outs["log_lik_fore"].append(torch.where(observed, s["scored"], torch.zeros_like(s["scored"])))
+    for k, v in outs.items():
+        v = torch.stack(v, 1)                                                    # [B T_o, H, ...]
+        full[k] = v.reshape(Bsz, To, *v.shape[1:])
+    return {k: (full[k] if k in want else None) for k in _SWH_OUTPUTS}
 
 
 @torch.no_grad()

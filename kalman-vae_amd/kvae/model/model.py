@@ -582,6 +582,49 @@ class KVAE(nn.Module):
                 out["x_smooth"] = self._decode_latents(out["a_smooth"], a_vae.dtype)
             return out
 
+    @torch.no_grad()
+    def forecast_regimes(self, x, horizon, u=None, mask=None, sample_a=False, origins="all", state=None, decode=False):
+        """What the generative switching model expects AHEAD, from every step of a sequence (switching dynamics only; no
+        counterpart in the reference): filter_regimes over the T frames, then from the filter's state at every origin t the
+        forecast of steps t+1 .. t+H, H = horizon - kvae_lgssm_switching_forecast.  No measurement enters between origin and
+        target, so one horizon step is the filter's hidden step; the regime posterior network plays no part and nothing is drawn.
+
+        1. Encode x, as filter_regimes does.  Every output of filter_regimes but x_pred is returned, with the bits of that call.
+        2. origins="all": t = 0 .. T-1 (T_o = T); "last": t = T-1 (T_o = 1), the online case after a carried `state`.  A hidden
+           origin (mask [B,T], 1 = observed) is legitimate: its state is whatever the filter holds there.  u [B,T+H,m] or None =
+           zeros (generate's convention).
+        3. Indexed [b, origin, h-1]: regime_fore [B,T_o,H,K] = p(s_{t+h} | a_{0:t}) = regime_filt_t P^h; regimes_fore [B,T_o,H]
+           (int64) its argmax (lowest index on ties); a_fore [B,T_o,H,p], S_fore [B,T_o,H,p,p] the mean and covariance of
+           a_{t+h} | a_{0:t}; mus_fore [B,T_o,H,n], Sigmas_fore [B,T_o,H,n,n] those of z_{t+h}: all exact under the model.
+        4. log_lik_fore [B,T_o,H] = log p(a_{t+h} | a_{0:t}, u), the held-out density of the encoded target frame: exact at h = 1,
+           the GPB2 mixture of K^2 Gaussians beyond; exactly 0 where valid [B,T_o,H] (bool: t+h < T and the target is observed)
+           is False.  levels_fore [B,T_o,H]: the largest ladder level of the pair densities.
+        5. decode=True: x_fore [B,H,C,h,w] = decoder(a_fore) of the LAST origin only.
+        Also returns a_vae and n_obs [B].  No host synchronisation.  Training mode, tau and parameters are left as they were."""
+        dyn = self.kalman_filter.dyn_params
+        if not dyn.is_switching_dynamics:
+            raise ValueError('forecast_regimes needs a model with dynamics = "switching" (config.dynamics_model); this one has '
+                             f'"{self.config.dynamics_model}"')
+        H = int(horizon)
+        if H < 1:
+            raise ValueError(f"forecast_regimes: horizon must be >= 1, got {horizon}")
+        if origins not in ("all", "last"):
+            raise ValueError(f"forecast_regimes: origins must be 'all' or 'last', got {origins!r}")
+        T = x.shape[1]
+        with self._readout("forecast_regimes", x, u, mask, sample=bool(sample_a), horizon=H) as (a_vae, _, _, u_all, mask):
+            out = self.kalman_filter.forecast_regimes(a_vae, None if u is None else u_all, H, mask, origins=origins, state=state)
+            rf = out["regime_fore"]
+            out["regimes_fore"] = (rf == rf.max(-1, keepdim=True).values).to(torch.int8).argmax(-1)   # lowest index among the maxima
+            dev = a_vae.device
+            target = torch.arange(0 if origins == "all" else T - 1, T, device=dev)[:, None] + torch.arange(1, H + 1, device=dev)[None, :]
+            inside = (target < T).expand(x.shape[0], -1, -1)
+            out["valid"] = inside if mask is None else inside & (mask[:, target.clamp(max=T - 1)] != 0)
+            out["a_vae"] = a_vae
+            out["n_obs"] = self._n_obs(mask, a_vae)
+            if decode:
+                out["x_fore"] = self._decode_latents(out["a_fore"][:, -1], a_vae.dtype)
+            return out
+
     def fit_dynamics_em(self, batches, iters, update=("A", "B", "Q", "C", "P"), sample_a=False, min_count=None):
         """Closed-form EM for the generative switching model on the encoded sequences (switching dynamics only):
         kvae.train.em.fit_dynamics_em.  The encoder, the decoder and the regime posterior network are not touched.  Returns the
@@ -656,7 +699,8 @@ class KVAE(nn.Module):
            alpha_t, Q = kalman_filter.Q.  switching: pi_t = s_{t-1} P (sticky prior); with noise s_t = one_hot(argmax(log pi_t +
            Gumbel)), without noise s_t = pi_t - a mean-field read-out, not a sample; A_t|B_t|Q_t mixed by s_t, C_t = C_0.
            Both: z_t = A_t z_{t-1} + B_t u_t + L_{Q_t} eps_t, a_t = C_t z_t + L_R eta_t, and y_t = a_t feeds the next step.
-           Without noise the lstm rollout is the filter with the tail hidden: a_t = C_t mu_{t|t-1}.
+           Without noise the lstm rollout is the filter with the tail hidden: a_t = C_t mu_{t|t-1}.  For the forecast of a
+           switching model (exact mean, covariance and regime probabilities at every horizon) use forecast_regimes, not noise=False.
         4. x = decoder(a) through the frame VAE.
 
         Every draw is made here with torch before the one rollout launch (kvae.noise.inject: gen_z0, gen_z, gen_a, gen_gumbel).

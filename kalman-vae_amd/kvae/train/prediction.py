@@ -93,3 +93,38 @@ def particle_filter_scores(model, batch_or_x, mask=None, u=None, num_particles=2
     return {"log_lik_per_step_pf": ll_pf, "log_lik_per_step_gpb2": ll_gpb2, "gpb2_gap_per_step": ll_pf - ll_gpb2,
             "pf_std": float(seq.std(1, unbiased=True).mean()) if seq.shape[1] > 1 else 0.0,
             "regime_tv": float(tv.mean()), "ess_mean": float(pf["ess"].double().mean())}
+
+
+@torch.no_grad()
+def forecast_scores(model, batch_or_x, horizon, mask=None, u=None):
+    """Forecast skill against horizon on x [B,T,...] (or a batch, as prediction_scores takes it): KVAE.forecast_regimes from every
+    origin, scored against the encoded frames it forecasts - the counterpart of prediction_scores for h > 1.  Switching dynamics
+    only.  u [B,T+horizon,m] or None.  Python lists of length `horizon`, entry h-1 over the valid (b, t) - the target t+h lies
+    inside the sequence and is observed:
+      mse        mean squared error of a_fore against the encoded target, per component of a
+      mse_naive  the same for persistence (a_t as the forecast of a_{t+h}), over those of the targets whose origin is observed
+      log_lik    mean of log p(a_{t+h} | a_{0:t}, u)
+      nis_mean   mean of r^T S_fore^-1 r, r = a_{t+h} - a_fore: p (= 2) when the forecast is calibrated
+      count      the number of valid (b, t)
+    A horizon without a valid target gives count 0 and nan elsewhere."""
+    if isinstance(batch_or_x, dict):
+        x = batch_or_x["images"]
+    elif isinstance(batch_or_x, (tuple, list)):
+        x = batch_or_x[0]
+    else:
+        x = batch_or_x
+    dev = next(model.parameters()).device
+    x = x.to(dev)
+    H = int(horizon)
+    fc = model.forecast_regimes(x, H, u=u, mask=mask)
+    a = fc["a_vae"].double()
+    Bsz, T, p = a.shape
+    target = (torch.arange(T, device=dev)[:, None] + torch.arange(1, H + 1, device=dev)[None, :]).clamp(max=T - 1)   # [T,H]
+    valid = fc["valid"]
+    r = a[:, target] - fc["a_fore"].double()                                                   # [B,T,H,p]
+    nis = (r.unsqueeze(-2) @ torch.linalg.solve(fc["S_fore"].double(), r.unsqueeze(-1))).reshape(Bsz, T, H)
+    origin = valid if mask is None else valid & (mask.to(dev)[:, :, None] != 0)
+    naive = a[:, target] - a[:, :, None, :]
+    mean = lambda v, w: (torch.where(w, v, torch.zeros_like(v)).sum((0, 1)) / w.sum((0, 1))).tolist()
+    return {"mse": mean((r * r).mean(-1), valid), "mse_naive": mean((naive * naive).mean(-1), origin),
+            "log_lik": mean(fc["log_lik_fore"].double(), valid), "nis_mean": mean(nis, valid), "count": valid.sum((0, 1)).tolist()}
