@@ -26,6 +26,10 @@ from . import lgssm_ops
 from .lgssm_ops import LgssmElbo, LgssmSmooth
 from .operands import NO_PASS, StepOperands
 
+# why a read-out of the generative switching model needs switching dynamics (_switching_operands' `why`)
+_NO_CHAIN = "the alpha-network of the lstm dynamics has no regime chain to "
+_EM_ONLY = "EM is built for the generative switching model, not for the alpha-network of the lstm dynamics"
+
 
 class KalmanFilter(nn.Module):
     def __init__(self, std_dyn, std_obs, mu0, Sigma0, dyn_params):
@@ -259,14 +263,8 @@ class KalmanFilter(nn.Module):
         Returns switching_filter's dict: regime_filt / regime_pred [B,T,K] = p(s_t | a_{0:t}) / p(s_t | a_{0:t-1}), log_lik [B,T]
         = log p(a_t | a_{0:t-1}, u) with the regimes summed out (0 on hidden steps), log_lik_seq [B], a_pred, S, mus_filt,
         Sigmas_filt, levels, state; entries not named in `want` are None."""
-        dyn = self.dyn_params
-        if not dyn.is_switching_dynamics:
-            raise ValueError("filter_regimes needs switching dynamics (SwitchingDynamicsParameter): the alpha-network of the lstm "
-                             "dynamics has no regime chain to filter")
-        dev, dt = Y.device, Y.dtype
-        return lgssm_ops.switching_filter(dyn.A.detach(), dyn.B.detach(), dyn.Q.detach(), dyn.C[0].detach(), self.R,
-                                          dyn._prior_matrix(dev, dt), self.mu0, self.Sigma0, Y, U, self._mask(mask, Y), want=want,
-                                          state=state)
+        ops = self._switching_operands("filter_regimes", Y, _NO_CHAIN + "filter")
+        return lgssm_ops.switching_filter(*ops, Y, U, self._mask(mask, Y), want=want, state=state)
 
     @torch.no_grad()
     def particle_filter_regimes(self, Y, U, mask=None, num_particles=256, replicates=1, ess_threshold=0.5, state=None,
@@ -279,19 +277,14 @@ class KalmanFilter(nn.Module):
         uniform draws are made here, before the launch (noise slots pf_regime [B,G,T,N], pf_resample [B,G,T]).  state: the "state"
         entry of an earlier call continues that stream.  Returns switching_pf's dict, per replicate; entries not named in `want`
         are None."""
-        dyn = self.dyn_params
-        if not dyn.is_switching_dynamics:
-            raise ValueError("particle_filter_regimes needs switching dynamics (SwitchingDynamicsParameter): the alpha-network of "
-                             "the lstm dynamics has no regime chain to filter")
+        ops = self._switching_operands("particle_filter_regimes", Y, _NO_CHAIN + "filter")
         if int(num_particles) < 1 or int(replicates) < 1:
             raise ValueError(f"particle_filter_regimes: num_particles and replicates must be >= 1, got {num_particles}, {replicates}")
         dev, dt = Y.device, Y.dtype
         Bsz, T = Y.shape[0], Y.shape[1]
         theta = _uniform("pf_regime", (Bsz, int(replicates), T, int(num_particles)), dev, dt)
         phi = _uniform("pf_resample", (Bsz, int(replicates), T), dev, dt)
-        return lgssm_ops.switching_pf(dyn.A.detach(), dyn.B.detach(), dyn.Q.detach(), dyn.C[0].detach(), self.R,
-                                      dyn._prior_matrix(dev, dt), self.mu0, self.Sigma0, Y, U, theta, phi, self._mask(mask, Y),
-                                      ess_threshold=ess_threshold, want=want, state=state)
+        return lgssm_ops.switching_pf(*ops, Y, U, theta, phi, self._mask(mask, Y), ess_threshold=ess_threshold, want=want, state=state)
 
     @torch.no_grad()
     def smooth_regimes(self, Y, U, mask=None, state=None, want=lgssm_ops._SWS_OUTPUTS):
@@ -301,14 +294,8 @@ class KalmanFilter(nn.Module):
         state: as filter_regimes; the smoothing is then conditional on this window alone.  Returns filter_regimes' dict (the
         same bits) plus regime_smooth [B,T,K] = p(s_t | a_{0:T-1}), regime_pairs [B,T-1,K,K] = p(s_t, s_{t+1} | a_{0:T-1}),
         mus_smooth [B,T,n], Sigmas_smooth [B,T,n,n]; entries not named in `want` are None."""
-        dyn = self.dyn_params
-        if not dyn.is_switching_dynamics:
-            raise ValueError("smooth_regimes needs switching dynamics (SwitchingDynamicsParameter): the alpha-network of the lstm "
-                             "dynamics has no regime chain to smooth")
-        dev, dt = Y.device, Y.dtype
-        return lgssm_ops.switching_smoother(dyn.A.detach(), dyn.B.detach(), dyn.Q.detach(), dyn.C[0].detach(), self.R,
-                                            dyn._prior_matrix(dev, dt), self.mu0, self.Sigma0, Y, U, self._mask(mask, Y), want=want,
-                                            state=state)
+        ops = self._switching_operands("smooth_regimes", Y, _NO_CHAIN + "smooth")
+        return lgssm_ops.switching_smoother(*ops, Y, U, self._mask(mask, Y), want=want, state=state)
 
     @torch.no_grad()
     def forecast_regimes(self, Y, U, horizon, mask=None, origins="all", state=None, want=lgssm_ops._SWH_OUTPUTS):
@@ -319,14 +306,8 @@ class KalmanFilter(nn.Module):
         indexed [b, origin, h-1], regime_fore [B,T_o,H,K], a_fore [B,T_o,H,p], S_fore [B,T_o,H,p,p], mus_fore [B,T_o,H,n],
         Sigmas_fore [B,T_o,H,n,n] (exact under the model), log_lik_fore [B,T_o,H] = log p(a_{t+h} | a_{0:t}, u) (0 where the target
         is hidden or past the end), levels_fore [B,T_o,H]; entries not named in `want` are None."""
-        dyn = self.dyn_params
-        if not dyn.is_switching_dynamics:
-            raise ValueError("forecast_regimes needs switching dynamics (SwitchingDynamicsParameter): the alpha-network of the lstm "
-                             "dynamics has no regime chain to forecast")
-        dev, dt = Y.device, Y.dtype
-        return lgssm_ops.switching_forecast(dyn.A.detach(), dyn.B.detach(), dyn.Q.detach(), dyn.C[0].detach(), self.R,
-                                            dyn._prior_matrix(dev, dt), self.mu0, self.Sigma0, Y, U, horizon, self._mask(mask, Y),
-                                            origins=origins, want=want, state=state)
+        ops = self._switching_operands("forecast_regimes", Y, _NO_CHAIN + "forecast")
+        return lgssm_ops.switching_forecast(*ops, Y, U, horizon, self._mask(mask, Y), origins=origins, want=want, state=state)
 
     def regime_log_marginal(self, Y, U, mask=None):
         """log p(a | u) of the generative switching model with the regimes summed out under GPB2 collapse, DIFFERENTIABLY (switching
@@ -335,20 +316,18 @@ class KalmanFilter(nn.Module):
         its adjoint.  The regime posterior network plays no part and no regime is drawn: zero variance, no tau.  It is the gradient
         of the GPB2 value: exact where the filter is exact (P = I, shared A / B / Q, t <= 1), elsewhere the gradient of the
         approximation.  R and the prior's P are constants.  Returns dict(ll [B,T], seq_ll [B], levels [B,T]); ll is 0 on hidden steps."""
-        dyn = self.dyn_params
-        if not dyn.is_switching_dynamics:
-            raise ValueError("regime_log_marginal needs switching dynamics (SwitchingDynamicsParameter): the alpha-network of the "
-                             "lstm dynamics has no regime chain to sum out")
-        return lgssm_ops.switching_log_marginal(dyn.A, dyn.B, dyn.Q, dyn.C[0], self.R, dyn._prior_matrix(Y.device, Y.dtype), self.mu0,
-                                                self.Sigma0, Y, U, self._mask(mask, Y))
+        ops = self._switching_operands("regime_log_marginal", Y, _NO_CHAIN + "sum out", detach=False)   # the tape runs through them
+        return lgssm_ops.switching_log_marginal(*ops, Y, U, self._mask(mask, Y))
 
-    def _em_operands(self, method, Y):
+    def _switching_operands(self, who, Y, why, detach=True):
+        """What every lgssm_ops.switching_* call opens with: (A_k, B_k, Q_k, the shared C, R, the prior's P on Y's device, mu0, Sigma0)
+        of the generative switching model, the parameters detached unless `detach` is False.  Without switching dynamics: ValueError,
+        `who` needs them because `why`."""
         dyn = self.dyn_params
         if not dyn.is_switching_dynamics:
-            raise ValueError(f"{method} needs switching dynamics (SwitchingDynamicsParameter): EM is built for the generative "
-                             "switching model, not for the alpha-network of the lstm dynamics")
-        return (dyn.A.detach(), dyn.B.detach(), dyn.Q.detach(), dyn.C[0].detach(), self.R, dyn._prior_matrix(Y.device, Y.dtype),
-                self.mu0, self.Sigma0)
+            raise ValueError(f"{who} needs switching dynamics (SwitchingDynamicsParameter): {why}")
+        params = (dyn.A, dyn.B, dyn.Q, dyn.C[0])
+        return (*(t.detach() if detach else t for t in params), self.R, dyn._prior_matrix(Y.device, Y.dtype), self.mu0, self.Sigma0)
 
     @torch.no_grad()
     def em_statistics(self, Y, U, mask=None, want=lgssm_ops._EM_OUTPUTS):
@@ -358,7 +337,7 @@ class KalmanFilter(nn.Module):
         regime posterior network plays no part.  Returns the sums over the batch (additive over batches: lgssm_ops.em_add),
         log_lik_seq [B] and smooth_regimes' four outputs; entries not named in `want` are None.  No host synchronisation: the call
         can be captured into a hipGraph."""
-        ops = self._em_operands("em_statistics", Y)
+        ops = self._switching_operands("em_statistics", Y, _EM_ONLY)
         return lgssm_ops.switching_em_statistics(*ops, Y, U, self._mask(mask, Y), want=want)
 
     @torch.no_grad()
@@ -374,7 +353,7 @@ class KalmanFilter(nn.Module):
         stats, skipped = switching_em_mstep's {"regimes": [...], "rows": [...], "B_held": [...], "emission": bool}).  The M-step
         reads the skipped lists back: it synchronises with the host and cannot be captured into a hipGraph (em_statistics can)."""
         update = lgssm_ops._want("em_step", lgssm_ops._EM_PARAMS, update)
-        ops = self._em_operands("em_step", self.mu0 if Y is None else Y)   # Y, U may be None when `stats` is given
+        ops = self._switching_operands("em_step", self.mu0 if Y is None else Y, _EM_ONLY)   # Y, U may be None when `stats` is given
         if stats is None:
             stats = self.em_statistics(Y, U, mask, want=lgssm_ops._EM_STATS + ("log_lik_seq",))
         dyn = self.dyn_params

@@ -50,10 +50,29 @@ def _empty(dev, *shape, dt=torch.float32):
     return torch.empty(*shape, device=dev, dtype=dt)
 
 
+_INT32_OUTPUTS = ("levels", "levels_fore", "resampled", "regimes", "ancestors", "paths")
+
+
 def _wanted(dev, outputs, want, shapes):
-    """{name: a fresh tensor of shapes[name] if the name is wanted, else None} over `outputs`; "levels" is int32."""
-    return {k: _empty(dev, *shapes[k], dt=torch.int32 if k == "levels" else torch.float32) if (k in want and k in shapes) else None
+    """{name: a fresh tensor of shapes[name] if the name is wanted, else None} over `outputs`; _INT32_OUTPUTS are int32."""
+    return {k: _empty(dev, *shapes[k], dt=torch.int32 if k in _INT32_OUTPUTS else torch.float32) if (k in want and k in shapes) else None
             for k in outputs}
+
+
+def _read_by(dev, out, name, readers, want, shape):
+    """The buffer of an output that the launches of other outputs read (the sequence sums read log_lik, the lineage walk reads the
+    regimes and ancestors): it exists when `name` or one of `readers` is wanted; out[name] holds it only when `name` itself is."""
+    mine = name in want
+    buf = _empty(dev, *shape, dt=torch.int32 if name in _INT32_OUTPUTS else torch.float32) if (mine or any(r in want for r in readers)) else None
+    out[name] = buf if mine else None
+    return buf
+
+
+def _bind(pr, fields):
+    """Point the ctypes struct `pr` at the tensors of {field: tensor or None} (None = NULL): the tensors, which must outlive the call."""
+    for k, t in fields.items():
+        setattr(pr, k, None if t is None else t.data_ptr())
+    return tuple(fields.values())
 
 
 def _f32c(t):
@@ -825,9 +844,8 @@ def _pred_problem(mp, Sp, Cm, packed, R, Y, mask, slots):
     p = Y.shape[-1]
     pr = N.PredProblem()
     pr.B, pr.T, pr.n, pr.p = Bsz, T, n, p
-    pr.mus_pred, pr.Sigmas_pred, pr.R, pr.y, pr.mask = mp.data_ptr(), Sp.data_ptr(), R.data_ptr(), Y.data_ptr(), N.ptr(mask)
     keep, pr.C = _stack(Cm, Bsz, T, p, n, packed, slots.C)
-    return pr, (mp, Sp, R, Y, mask, keep)
+    return pr, _bind(pr, dict(mus_pred=mp, Sigmas_pred=Sp, R=R, y=Y, mask=mask)) + (keep,)
 
 
 @torch.no_grad()
@@ -855,10 +873,8 @@ def predictive(mus_pred, Sigmas_pred, Cm, R, Y, mask=None, packed=None, slots=Sl
     packed = _f32c(packed.detach()) if packed is not None else None
     pr, keep = _pred_problem(mp, Sp, Cm.detach() if slots.C is None else Cm, packed, R, Y, mask, slots)
     out = _wanted(dev, _PRED_OUTPUTS, want, dict(nis=(Bsz, T), a_pred=(Bsz, T, p), S=(Bsz, T, p, p), levels=(Bsz, T), seq_ll=(Bsz,)))
-    ll = _empty(dev, Bsz, T) if ("ll" in want or "seq_ll" in want) else None   # the sequence sums read ll
-    out["ll"] = ll if "ll" in want else None
-    pr.ll, pr.nis, pr.a_pred, pr.S_out = N.ptr(ll), N.ptr(out["nis"]), N.ptr(out["a_pred"]), N.ptr(out["S"])
-    pr.levels, pr.seq_ll = N.ptr(out["levels"]), N.ptr(out["seq_ll"])
+    ll = _read_by(dev, out, "ll", ("seq_ll",), want, (Bsz, T))
+    _bind(pr, dict(ll=ll, nis=out["nis"], a_pred=out["a_pred"], S_out=out["S"], levels=out["levels"], seq_ll=out["seq_ll"]))
     lib = N.lib_for(Sp)
     lib.check(N.timed("predictive", Sp, lambda: lib.dll.kvae_lgssm_predictive(C.byref(pr), N.stream_for(Sp))), "kvae_lgssm_predictive")
     del keep
@@ -976,16 +992,7 @@ def switching_filter(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, want=_SWF
     One launch for the sweep (one more for log_lik_seq), no host synchronisation, no gradients.
     impl: None = the HIP kernel where it is built (switching_filter_supported), else switching_filter_torch; "hip" / "torch" force one."""
     want = _want("switching_filter", _SWF_OUTPUTS, want)
-    if impl not in (None, "hip", "torch"):
-        raise ValueError(f"switching_filter: impl must be None, 'hip' or 'torch', got {impl!r}")
-    K, n, m = A.shape[0], A.shape[1], Bm.shape[2]
-    Bsz, T, p = Y.shape
-    supported = switching_filter_supported(K, n, m, p, Y)
-    if impl == "hip" and not supported:
-        raise ValueError(f"switching_filter: impl='hip' needs fp32 tensors on a HIP device and K <= {SWF_SUPPORTED['max_K']}, "
-                         f"n <= {SWF_SUPPORTED['max_n']}, m <= {SWF_SUPPORTED['max_m']}, p == {SWF_SUPPORTED['p']}; got K = {K}, "
-                         f"n = {n}, m = {m}, p = {p}, {Y.dtype} on {Y.device}")
-    if impl == "torch" or not supported:
+    if not _sw_route("switching_filter", impl, switching_filter_supported, A, Bm, Y):
         return switching_filter_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, state, want)
     out, pr, keep = _swf_problem(N.SwfProblem(), A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, state, want)
     lib = N.lib_for(Y)
@@ -994,34 +1001,60 @@ def switching_filter(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, want=_SWF
     return out
 
 
+def _check_impl(op, impl):
+    if impl not in (None, "hip", "torch"):
+        raise ValueError(f"{op}: impl must be None, 'hip' or 'torch', got {impl!r}")
+
+
+def _sw_route(op, impl, supported, A, Bm, Y, particles=None, fp32_model=False):
+    """The routing rule of the switching read-outs: True when the HIP kernel runs, False for the restatement in torch ops.  ValueError
+    for an impl that is not None, "hip" or "torch" (_check_impl: the ops that check other arguments between the two errors call it
+    ahead of them), and for impl="hip" on what the kernel is not built for: supported(K, n, m, p, [particles,] Y) is False, or -
+    fp32_model - the model is not fp32."""
+    _check_impl(op, impl)
+    dims = (A.shape[0], A.shape[1], Bm.shape[2], Y.shape[2]) + (() if particles is None else (particles,))
+    ok = supported(*dims, Y) and not (fp32_model and A.dtype != torch.float32)
+    if impl == "hip" and not ok:
+        s, pf = SWF_SUPPORTED, ("", "") if particles is None else (f", {SPF_PARTICLES} particles", f", {particles} particles")
+        raise ValueError(f"{op}: impl='hip' needs fp32 tensors on a HIP device, K <= {s['max_K']}, n <= {s['max_n']}, m <= {s['max_m']}, "
+                         f"p == {s['p']}{pf[0]}; got K = {dims[0]}, n = {dims[1]}, m = {dims[2]}, p = {dims[3]}{pf[1]}, "
+                         f"{A.dtype} model and {Y.dtype} data on {Y.device}")
+    return ok and impl != "torch"
+
+
+_SW_OPERANDS = ("A", "Bm", "Q", "C", "R", "P", "mu0", "Sigma0", "y", "u")   # the fields kvae_swf_problem and kvae_spf_problem share
+
+
+def _sw_operands(pr, A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, **draws):
+    """Bind the ten model / data operands, the particle filter's `draws` (by field name) and the mask [B,T] (None = NULL) to the
+    problem `pr`, as contiguous fp32 tensors on Y's device: those tensors, which must outlive the call."""
+    dev = Y.device
+    named = {k: _f32c(t.detach().to(dev) if (t.requires_grad or t.device != dev) else t)   # (most arrive detached and in place)
+             for k, t in zip(_SW_OPERANDS + tuple(draws), (A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, *draws.values()))}
+    named["mask"] = None if mask is None else _f32c(mask.detach().to(dev).reshape(Y.shape[0], Y.shape[1]))
+    return _bind(pr, named)
+
+
 def _swf_problem(pr, A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, state, want):
     """Fill the kvae_swf_problem `pr` for the outputs of _SWF_OUTPUTS named in `want`: (the dict of outputs, pr, the tensors pr
     points to, which must outlive the call)."""
     K, n, m = A.shape[0], A.shape[1], Bm.shape[2]
     Bsz, T, p = Y.shape
     dev = Y.device
-    A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U = (_f32c(t.detach().to(dev)) for t in (A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U))
-    mask = None if mask is None else _f32c(mask.detach().to(dev).reshape(Bsz, T))
+    keep = _sw_operands(pr, A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask)
     st = _swf_state(state, Bsz, K, n)
     if st is not None:
-        st = tuple(_f32c(t.detach().to(dev)) for t in st)
+        st = _bind(pr, {"state_" + k: _f32c(t.detach().to(dev)) for k, t in zip(("log_w", "mu", "Sigma"), st)})
     out = _wanted(dev, _SWF_OUTPUTS, want, dict(regime_filt=(Bsz, T, K), regime_pred=(Bsz, T, K), log_lik_seq=(Bsz,), a_pred=(Bsz, T, p),
                                                 S=(Bsz, T, p, p), mus_filt=(Bsz, T, n), Sigmas_filt=(Bsz, T, n, n), levels=(Bsz, T)))
-    ll = _empty(dev, Bsz, T) if ("log_lik" in want or "log_lik_seq" in want) else None   # the sequence sums read log_lik
-    out["log_lik"] = ll if "log_lik" in want else None
+    ll = _read_by(dev, out, "log_lik", ("log_lik_seq",), want, (Bsz, T))
     if "state" in want:
         out["state"] = {"log_w": _empty(dev, Bsz, K), "mu": _empty(dev, Bsz, K, n), "Sigma": _empty(dev, Bsz, K, n, n)}
+        _bind(pr, {"out_" + k: t for k, t in out["state"].items()})
     pr.B, pr.T, pr.K, pr.n, pr.m, pr.p = Bsz, T, K, n, m, p
-    pr.A, pr.Bm, pr.Q, pr.C, pr.R, pr.P = (t.data_ptr() for t in (A, Bm, Q, Cm, R, P))
-    pr.mu0, pr.Sigma0, pr.y, pr.u, pr.mask = mu0.data_ptr(), Sigma0.data_ptr(), Y.data_ptr(), U.data_ptr(), N.ptr(mask)
-    if st is not None:
-        pr.state_log_w, pr.state_mu, pr.state_Sigma = (t.data_ptr() for t in st)
-    pr.regime_filt, pr.regime_pred, pr.ll, pr.seq_ll = N.ptr(out["regime_filt"]), N.ptr(out["regime_pred"]), N.ptr(ll), N.ptr(out["log_lik_seq"])
-    pr.a_pred, pr.S_out, pr.mus_filt, pr.Sigmas_filt = N.ptr(out["a_pred"]), N.ptr(out["S"]), N.ptr(out["mus_filt"]), N.ptr(out["Sigmas_filt"])
-    pr.levels = N.ptr(out["levels"])
-    if out["state"] is not None:
-        pr.out_log_w, pr.out_mu, pr.out_Sigma = (out["state"][k].data_ptr() for k in ("log_w", "mu", "Sigma"))
-    return out, pr, (A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, st, ll)
+    _bind(pr, dict(regime_filt=out["regime_filt"], regime_pred=out["regime_pred"], ll=ll, seq_ll=out["log_lik_seq"], a_pred=out["a_pred"],
+                   S_out=out["S"], mus_filt=out["mus_filt"], Sigmas_filt=out["Sigmas_filt"], levels=out["levels"]))
+    return out, pr, keep + (st, ll)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1050,68 +1083,43 @@ def switching_pf(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, pf_regime, pf_resample, 
     are None.  At most three launches, no host synchronisation, no gradients.
     impl: None = the HIP kernel where it is built (switching_pf_supported), else switching_pf_torch; "hip" / "torch" force one."""
     want = _want("switching_pf", _SPF_OUTPUTS, want)
-    if impl not in (None, "hip", "torch"):
-        raise ValueError(f"switching_pf: impl must be None, 'hip' or 'torch', got {impl!r}")
+    _check_impl("switching_pf", impl)
     if not 0.0 <= float(ess_threshold) <= 1.0:
         raise ValueError(f"switching_pf: ess_threshold must be in [0, 1], got {ess_threshold}")
     K, n, m = A.shape[0], A.shape[1], Bm.shape[2]
     Bsz, T, p = Y.shape
     G, Np = _spf_draws(pf_regime, pf_resample, Bsz, T)
-    supported = switching_pf_supported(K, n, m, p, Np, Y)
-    if impl == "hip" and not supported:
-        raise ValueError(f"switching_pf: impl='hip' needs fp32 tensors on a HIP device, K <= {SWF_SUPPORTED['max_K']}, "
-                         f"n <= {SWF_SUPPORTED['max_n']}, m <= {SWF_SUPPORTED['max_m']}, p == {SWF_SUPPORTED['p']} and {SPF_PARTICLES} "
-                         f"particles; got K = {K}, n = {n}, m = {m}, p = {p}, {Np} particles, {Y.dtype} on {Y.device}")
-    if impl == "torch" or not supported:
+    if not _sw_route("switching_pf", impl, switching_pf_supported, A, Bm, Y, particles=Np):
         return switching_pf_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, pf_regime, pf_resample, mask, ess_threshold, state, want)
     dev = Y.device
-    A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, pf_regime, pf_resample = (
-        _f32c(t.detach().to(dev)) for t in (A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, pf_regime, pf_resample))
-    mask = None if mask is None else _f32c(mask.detach().to(dev).reshape(Bsz, T))
+    pr = N.SpfProblem()
+    pr.B, pr.G, pr.T, pr.K, pr.N, pr.n, pr.m, pr.p, pr.ess_threshold = Bsz, G, T, K, Np, n, m, p, float(ess_threshold)
+    keep = _sw_operands(pr, A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, pf_regime=pf_regime, pf_resample=pf_resample)
     st = _spf_state(state, Bsz, G, Np, n)
     if st is not None:
-        st = (_f32c(st[0].detach().to(dev)), st[1].detach().to(device=dev, dtype=torch.int32).contiguous(), _f32c(st[2].detach().to(dev)),
-              _f32c(st[3].detach().to(dev)))
-    i32 = lambda *s: _empty(dev, *s, dt=torch.int32)
-    shapes = dict(log_lik_seq=(Bsz, G), regime_filt=(Bsz, G, T, K), mus_filt=(Bsz, G, T, n), Sigmas_filt=(Bsz, G, T, n, n), ess=(Bsz, G, T))
-    out = {k: (_empty(dev, *shapes[k]) if (k in want and k in shapes) else None) for k in _SPF_OUTPUTS}
-    ll = _empty(dev, Bsz, G, T) if ("log_lik" in want or "log_lik_seq" in want) else None   # the sequence sums read log_lik
-    out["log_lik"] = ll if "log_lik" in want else None
-    paths = "paths" in want
-    regimes = i32(Bsz, G, T, Np) if ("regimes" in want or paths) else None                  # the lineage walk reads both
-    ancestors = i32(Bsz, G, T, Np) if ("ancestors" in want or paths) else None
-    out["regimes"], out["ancestors"] = (regimes if "regimes" in want else None), (ancestors if "ancestors" in want else None)
-    resampled = i32(Bsz, G, T) if "resampled" in want else None
-    if "levels" in want:
-        out["levels"] = i32(Bsz, G, T)
-    if paths:
-        out["paths"] = i32(Bsz, G, Np, T)
-    so = None
-    if "state" in want or "path_log_w" in want:
-        so = {"log_w": _empty(dev, Bsz, G, Np)}
+        st = _bind(pr, {"state_" + k: t.detach().to(device=dev, dtype=torch.int32).contiguous() if k == "regime" else _f32c(t.detach().to(dev))
+                        for k, t in zip(("log_w", "regime", "mu", "Sigma"), st)})
+    out = _wanted(dev, _SPF_OUTPUTS, want, dict(log_lik_seq=(Bsz, G), regime_filt=(Bsz, G, T, K), mus_filt=(Bsz, G, T, n),
+                                                Sigmas_filt=(Bsz, G, T, n, n), ess=(Bsz, G, T), resampled=(Bsz, G, T), levels=(Bsz, G, T),
+                                                paths=(Bsz, G, Np, T)))
+    ll = _read_by(dev, out, "log_lik", ("log_lik_seq",), want, (Bsz, G, T))
+    regimes, ancestors = (_read_by(dev, out, k, ("paths",), want, (Bsz, G, T, Np)) for k in ("regimes", "ancestors"))
+    so = {}
+    if "state" in want or "path_log_w" in want:   # the final log weights are both the state's and the lineages'
+        so["log_w"] = _empty(dev, Bsz, G, Np)
         if "state" in want:
-            so.update(regime=i32(Bsz, G, Np), mu=_empty(dev, Bsz, G, Np, n), Sigma=_empty(dev, Bsz, G, Np, n, n))
+            so.update(regime=_empty(dev, Bsz, G, Np, dt=torch.int32), mu=_empty(dev, Bsz, G, Np, n), Sigma=_empty(dev, Bsz, G, Np, n, n))
             out["state"] = so
         if "path_log_w" in want:
             out["path_log_w"] = so["log_w"]
-    pr = N.SpfProblem()
-    pr.B, pr.G, pr.T, pr.K, pr.N, pr.n, pr.m, pr.p, pr.ess_threshold = Bsz, G, T, K, Np, n, m, p, float(ess_threshold)
-    pr.A, pr.Bm, pr.Q, pr.C, pr.R, pr.P = (t.data_ptr() for t in (A, Bm, Q, Cm, R, P))
-    pr.mu0, pr.Sigma0, pr.y, pr.u, pr.mask = mu0.data_ptr(), Sigma0.data_ptr(), Y.data_ptr(), U.data_ptr(), N.ptr(mask)
-    pr.pf_regime, pr.pf_resample = pf_regime.data_ptr(), pf_resample.data_ptr()
-    if st is not None:
-        pr.state_log_w, pr.state_regime, pr.state_mu, pr.state_Sigma = (t.data_ptr() for t in st)
-    pr.ll, pr.seq_ll, pr.regime_filt, pr.mus_filt = N.ptr(ll), N.ptr(out["log_lik_seq"]), N.ptr(out["regime_filt"]), N.ptr(out["mus_filt"])
-    pr.Sigmas_filt, pr.ess, pr.resampled, pr.regimes = N.ptr(out["Sigmas_filt"]), N.ptr(out["ess"]), N.ptr(resampled), N.ptr(regimes)
-    pr.ancestors, pr.levels, pr.paths = N.ptr(ancestors), N.ptr(out["levels"]), N.ptr(out["paths"])
-    if so is not None:
-        pr.out_log_w = so["log_w"].data_ptr()
-        if "state" in want:
-            pr.out_regime, pr.out_mu, pr.out_Sigma = (so[k].data_ptr() for k in ("regime", "mu", "Sigma"))
+    _bind(pr, dict(ll=ll, seq_ll=out["log_lik_seq"], regime_filt=out["regime_filt"], mus_filt=out["mus_filt"], Sigmas_filt=out["Sigmas_filt"],
+                   ess=out["ess"], resampled=out["resampled"], regimes=regimes, ancestors=ancestors, levels=out["levels"], paths=out["paths"],
+                   **{"out_" + k: t for k, t in so.items()}))
     lib = N.lib_for(Y)
     lib.check(N.timed("switching_pf", Y, lambda: lib.dll.kvae_lgssm_switching_pf(C.byref(pr), N.stream_for(Y))), "kvae_lgssm_switching_pf")
-    if resampled is not None:
-        out["resampled"] = resampled != 0
+    del keep, st
+    if out["resampled"] is not None:
+        out["resampled"] = out["resampled"] != 0
     return out
 
 
@@ -1147,31 +1155,38 @@ def switching_smoother(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, want=_S
     impl: None = the HIP kernel where it is built (switching_smoother_supported), else switching_smoother_torch; "hip" / "torch"
     force one."""
     want = _want("switching_smoother", _SWS_OUTPUTS, want)
-    if impl not in (None, "hip", "torch"):
-        raise ValueError(f"switching_smoother: impl must be None, 'hip' or 'torch', got {impl!r}")
-    K, n, m = A.shape[0], A.shape[1], Bm.shape[2]
-    Bsz, T, p = Y.shape
-    supported = switching_smoother_supported(K, n, m, p, Y)
-    if impl == "hip" and not supported:
-        raise ValueError(f"switching_smoother: impl='hip' needs fp32 tensors on a HIP device and K <= {SWF_SUPPORTED['max_K']}, "
-                         f"n <= {SWF_SUPPORTED['max_n']}, m <= {SWF_SUPPORTED['max_m']}, p == {SWF_SUPPORTED['p']}; got K = {K}, "
-                         f"n = {n}, m = {m}, p = {p}, {Y.dtype} on {Y.device}")
-    if impl == "torch" or not supported:
+    if not _sw_route("switching_smoother", impl, switching_smoother_supported, A, Bm, Y):
         return switching_smoother_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, state, want)
-    dev = Y.device
     sp = N.SwsProblem()
     out, _, keep = _swf_problem(sp.filt, A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, state, tuple(w for w in want if w in _SWF_OUTPUTS))
-    hist = (_empty(dev, Bsz, T, K, n), _empty(dev, Bsz, T, K, n, n), _empty(dev, Bsz, T, K, K), _empty(dev, Bsz, K))
-    sp.hist_mu, sp.hist_Sigma, sp.hist_W, sp.hist_w = (t.data_ptr() for t in hist)
-    out.update(_wanted(dev, _SWS_SMOOTH, want, dict(regime_smooth=(Bsz, T, K), regime_pairs=(Bsz, max(T - 1, 1), K, K),
-                                                    mus_smooth=(Bsz, T, n), Sigmas_smooth=(Bsz, T, n, n))))
-    sp.regime_smooth, sp.regime_pairs = N.ptr(out["regime_smooth"]), N.ptr(out["regime_pairs"])
-    sp.mus_smooth, sp.Sigmas_smooth = N.ptr(out["mus_smooth"]), N.ptr(out["Sigmas_smooth"])
+    hist = _bind(sp, _sw_history(Y, A, pairs=True))
+    out.update(_sws_outputs(sp, A, Y, want))
     lib = N.lib_for(Y)
     lib.check(N.timed("switching_smoother", Y, lambda: lib.dll.kvae_lgssm_switching_smoother(C.byref(sp), N.stream_for(Y))),
               "kvae_lgssm_switching_smoother")
+    del keep, hist
+    return out
+
+
+def _sw_history(Y, A, pairs):
+    """{field: a fresh buffer} of what the forward sweep keeps of every step for a second pass over it.  pairs: the smoother's and
+    EM's form (the beliefs per regime, the pair weights, the final weights), else the forecast's and the marginal's (the log weights
+    and the beliefs per regime)."""
+    (Bsz, T), (K, n), dev = Y.shape[:2], A.shape[:2], Y.device
+    if pairs:
+        return dict(hist_mu=_empty(dev, Bsz, T, K, n), hist_Sigma=_empty(dev, Bsz, T, K, n, n), hist_W=_empty(dev, Bsz, T, K, K),
+                    hist_w=_empty(dev, Bsz, K))
+    return dict(hist_lw=_empty(dev, Bsz, T, K), hist_mu=_empty(dev, Bsz, T, K, n), hist_Sigma=_empty(dev, Bsz, T, K, n, n))
+
+
+def _sws_outputs(sp, A, Y, want):
+    """The smoother's four outputs named in `want`, bound to the kvae_sws_problem `sp`."""
+    (Bsz, T), (K, n) = Y.shape[:2], A.shape[:2]
+    out = _wanted(Y.device, _SWS_SMOOTH, want, dict(regime_smooth=(Bsz, T, K), regime_pairs=(Bsz, max(T - 1, 1), K, K),
+                                                    mus_smooth=(Bsz, T, n), Sigmas_smooth=(Bsz, T, n, n)))
+    _bind(sp, out)
     if out["regime_pairs"] is not None:
-        out["regime_pairs"] = out["regime_pairs"][:, :T - 1]   # nothing is written at T = 1
+        out["regime_pairs"] = out["regime_pairs"][:, :T - 1]   # nothing is written at T = 1 (the view keeps the bound buffer alive)
     return out
 
 
@@ -1200,35 +1215,26 @@ def switching_forecast(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U_all, horizon, mask=
     impl: None = the HIP kernel where it is built (switching_forecast_supported), else switching_forecast_torch; "hip" / "torch"
     force one."""
     want = _want("switching_forecast", _SWH_OUTPUTS, want)
-    if impl not in (None, "hip", "torch"):
-        raise ValueError(f"switching_forecast: impl must be None, 'hip' or 'torch', got {impl!r}")
-    K, n, m = A.shape[0], A.shape[1], Bm.shape[2]
-    Bsz, T, p = Y.shape
+    _check_impl("switching_forecast", impl)
+    (K, n), (Bsz, T, p) = A.shape[:2], Y.shape
     H, t0, U_all = _swh_args("switching_forecast", Bm, Y, U_all, horizon, origins)
-    supported = switching_forecast_supported(K, n, m, p, Y)
-    if impl == "hip" and not supported:
-        raise ValueError(f"switching_forecast: impl='hip' needs fp32 tensors on a HIP device and K <= {SWF_SUPPORTED['max_K']}, "
-                         f"n <= {SWF_SUPPORTED['max_n']}, m <= {SWF_SUPPORTED['max_m']}, p == {SWF_SUPPORTED['p']}; got K = {K}, "
-                         f"n = {n}, m = {m}, p = {p}, {Y.dtype} on {Y.device}")
-    if impl == "torch" or not supported:
+    if not _sw_route("switching_forecast", impl, switching_forecast_supported, A, Bm, Y):
         return switching_forecast_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U_all, H, mask, origins, state, want)
-    dev, To = Y.device, T - t0
+    dev = Y.device
     U_all = _f32c(U_all.detach().to(dev))
     fp = N.SwhProblem()
     out, _, keep = _swf_problem(fp.filt, A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U_all[:, :T], mask, state,
                                 tuple(w for w in want if w in _SWF_OUTPUTS))
-    hist = (_empty(dev, Bsz, T, K), _empty(dev, Bsz, T, K, n), _empty(dev, Bsz, T, K, n, n))
-    fp.hist_lw, fp.hist_mu, fp.hist_Sigma = (t.data_ptr() for t in hist)
-    fp.H, fp.t0, fp.u_all = H, t0, U_all.data_ptr()
+    hist = _bind(fp, _sw_history(Y, A, pairs=False))
+    fp.H, fp.t0 = H, t0
     shapes = dict(regime_fore=(K,), a_fore=(p,), S_fore=(p, p), mus_fore=(n,), Sigmas_fore=(n, n), log_lik_fore=(), levels_fore=())
-    out.update({k: (_empty(dev, Bsz, To, H, *shapes[k], dt=torch.int32 if k == "levels_fore" else torch.float32) if k in want else None)
-                for k in _SWH_FORE})
-    fp.regime_fore, fp.a_fore, fp.S_fore = N.ptr(out["regime_fore"]), N.ptr(out["a_fore"]), N.ptr(out["S_fore"])
-    fp.mus_fore, fp.Sigmas_fore = N.ptr(out["mus_fore"]), N.ptr(out["Sigmas_fore"])
-    fp.ll_fore, fp.levels_fore = N.ptr(out["log_lik_fore"]), N.ptr(out["levels_fore"])
+    fore = _wanted(dev, _SWH_FORE, want, {k: (Bsz, T - t0, H, *s) for k, s in shapes.items()})
+    _bind(fp, dict(u_all=U_all, **{"ll_fore" if k == "log_lik_fore" else k: t for k, t in fore.items()}))
+    out.update(fore)
     lib = N.lib_for(Y)
     lib.check(N.timed("switching_forecast", Y, lambda: lib.dll.kvae_lgssm_switching_forecast(C.byref(fp), N.stream_for(Y))),
               "kvae_lgssm_switching_forecast")
+    del keep, hist
     return out
 
 
@@ -1239,8 +1245,7 @@ def _swm_problem(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, hist):
     """(kvae_swm_problem, tensors to keep alive) over the inputs and the history (lw, mu, Sigma); the output pointers are NULL."""
     sp = N.SwmProblem()
     _, _, keep = _swf_problem(sp.filt, A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, None, ())
-    sp.hist_lw, sp.hist_mu, sp.hist_Sigma = (t.data_ptr() for t in hist)
-    return sp, keep[:-1] + (hist,)
+    return sp, keep[:-1] + _bind(sp, dict(zip(("hist_lw", "hist_mu", "hist_Sigma"), hist)))
 
 
 class SwitchingLogLik(torch.autograd.Function):
@@ -1250,13 +1255,11 @@ class SwitchingLogLik(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask):
-        K, n = A.shape[0], A.shape[1]
         Bsz, T, _ = Y.shape
         dev = Y.device
-        hist = (_empty(dev, Bsz, T, K), _empty(dev, Bsz, T, K, n), _empty(dev, Bsz, T, K, n, n))
+        hist = tuple(_sw_history(Y, A, pairs=False).values())
         sp, keep = _swm_problem(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, hist)
-        ll, seq, levels = _empty(dev, Bsz, T), _empty(dev, Bsz), _empty(dev, Bsz, T, dt=torch.int32)
-        sp.filt.ll, sp.filt.seq_ll, sp.filt.levels = ll.data_ptr(), seq.data_ptr(), levels.data_ptr()
+        ll, seq, levels = _bind(sp.filt, dict(ll=_empty(dev, Bsz, T), seq_ll=_empty(dev, Bsz), levels=_empty(dev, Bsz, T, dt=torch.int32)))
         lib = N.lib_for(Y)
         lib.check(N.timed("switching_marginal", Y, lambda: lib.dll.kvae_lgssm_switching_marginal(C.byref(sp), N.stream_for(Y))),
                   "kvae_lgssm_switching_marginal")
@@ -1310,19 +1313,10 @@ def switching_log_marginal(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, sta
     impl: None = the HIP kernels where built (switching_filter_supported), else switching_log_marginal_torch; "hip" / "torch" force one."""
     if state is not None:
         raise ValueError("switching_log_marginal: a carried state is not differentiable here (state must be None)")
-    if impl not in (None, "hip", "torch"):
-        raise ValueError(f"switching_log_marginal: impl must be None, 'hip' or 'torch', got {impl!r}")
-    K, n, m = A.shape[0], A.shape[1], Bm.shape[2]
-    Bsz, T, p = Y.shape
-    supported = switching_filter_supported(K, n, m, p, Y) and A.dtype == torch.float32
-    if impl == "hip" and not supported:
-        raise ValueError(f"switching_log_marginal: impl='hip' needs fp32 tensors on a HIP device and K <= {SWF_SUPPORTED['max_K']}, "
-                         f"n <= {SWF_SUPPORTED['max_n']}, m <= {SWF_SUPPORTED['max_m']}, p == {SWF_SUPPORTED['p']}; got K = {K}, "
-                         f"n = {n}, m = {m}, p = {p}, {Y.dtype} on {Y.device}")
-    if impl == "torch" or not supported:
+    if not _sw_route("switching_log_marginal", impl, switching_filter_supported, A, Bm, Y, fp32_model=True):
         return switching_log_marginal_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask)
     dev = Y.device
-    mask = None if mask is None else mask.detach().to(dev).reshape(Bsz, T)
+    mask = None if mask is None else mask.detach().to(dev).reshape(Y.shape[0], Y.shape[1])
     ll, seq, levels = SwitchingLogLik.apply(*(t.to(dev) for t in (A, Bm, Q, Cm)), R.detach().to(dev), *(t.to(dev) for t in (P, mu0, Sigma0)), Y, U, mask)
     return {"ll": ll, "seq_ll": seq, "levels": levels}
 
@@ -1358,38 +1352,22 @@ def switching_em_statistics(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, wa
     want = _want("switching_em_statistics", _EM_OUTPUTS, want)
     if state is not None:
         raise ValueError("switching_em_statistics: a carried state is not accepted (the step into t = 0 needs the prior; state must be None)")
-    if impl not in (None, "hip", "torch"):
-        raise ValueError(f"switching_em_statistics: impl must be None, 'hip' or 'torch', got {impl!r}")
-    K, n, m = A.shape[0], A.shape[1], Bm.shape[2]
-    Bsz, T, p = Y.shape
-    supported = switching_em_supported(K, n, m, p, Y) and A.dtype == torch.float32
-    if impl == "hip" and not supported:
-        raise ValueError(f"switching_em_statistics: impl='hip' needs fp32 tensors on a HIP device and K <= {SWF_SUPPORTED['max_K']}, "
-                         f"n <= {SWF_SUPPORTED['max_n']}, m <= {SWF_SUPPORTED['max_m']}, p == {SWF_SUPPORTED['p']}; got K = {K}, "
-                         f"n = {n}, m = {m}, p = {p}, {A.dtype} on {Y.device}")
-    if impl == "torch" or not supported:
+    if not _sw_route("switching_em_statistics", impl, switching_em_supported, A, Bm, Y, fp32_model=True):
         return switching_em_statistics_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, want)
-    dev = Y.device
+    K, n, m, Bsz, dev = A.shape[0], A.shape[1], Bm.shape[2], Y.shape[0], Y.device
     sp, es = N.SwsProblem(), N.EmStats()
     out, _, keep = _swf_problem(sp.filt, A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, None, tuple(w for w in want if w == "log_lik_seq"))
     out = {"log_lik_seq": out["log_lik_seq"]}
-    hist = (_empty(dev, Bsz, T, K, n), _empty(dev, Bsz, T, K, n, n), _empty(dev, Bsz, T, K, K), _empty(dev, Bsz, K))
-    sp.hist_mu, sp.hist_Sigma, sp.hist_W, sp.hist_w = (t.data_ptr() for t in hist)
-    out.update(_wanted(dev, _SWS_SMOOTH, want, dict(regime_smooth=(Bsz, T, K), regime_pairs=(Bsz, max(T - 1, 1), K, K),
-                                                    mus_smooth=(Bsz, T, n), Sigmas_smooth=(Bsz, T, n, n))))
-    sp.regime_smooth, sp.regime_pairs = N.ptr(out["regime_smooth"]), N.ptr(out["regime_pairs"])
-    sp.mus_smooth, sp.Sigmas_smooth = N.ptr(out["mus_smooth"]), N.ptr(out["Sigmas_smooth"])
-    out.update(_wanted(dev, _EM_STATS, want, _em_shapes(K, n, m)))
+    hist = _bind(sp, _sw_history(Y, A, pairs=True))
+    out.update(_sws_outputs(sp, A, Y, want))
+    stats = _wanted(dev, _EM_STATS, want, _em_shapes(K, n, m))
+    out.update(stats)
     lib = N.lib_for(Y)
     ws = _empty(dev, Bsz, lib.dll.kvae_lgssm_switching_em_ws_floats(Bsz, K, n, m) // Bsz)
-    es.ws = ws.data_ptr()
-    for k in _EM_STATS:
-        setattr(es, k, N.ptr(out[k]))
+    _bind(es, dict(stats, ws=ws))
     lib.check(N.timed("switching_em", Y, lambda: lib.dll.kvae_lgssm_switching_em(C.byref(sp), C.byref(es), N.stream_for(Y))),
               "kvae_lgssm_switching_em")
-    del keep
-    if out["regime_pairs"] is not None:
-        out["regime_pairs"] = out["regime_pairs"][:, :T - 1]   # nothing is written at T = 1
+    del keep, hist
     if ws_out is not None:
         ws_out.append(ws)
     return {k: out[k] for k in _EM_OUTPUTS}

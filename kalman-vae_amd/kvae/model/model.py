@@ -174,6 +174,30 @@ class KVAE(nn.Module):
                 self.train(was_training)
         return block()
 
+    def _needs_switching(self, who):
+        if not self.kalman_filter.dyn_params.is_switching_dynamics:
+            raise ValueError(f'{who} needs a model with dynamics = "switching" (config.dynamics_model); this one has '
+                             f'"{self.config.dynamics_model}"')
+
+    def _switching_readout(self, who, x, u, mask, sample_a):
+        """Prelude of a read-out of the switching model: the dynamics are checked first, then _readout's mask and u."""
+        self._needs_switching(who)
+        return self._readout(who, x, u, mask, sample=bool(sample_a))
+
+    def _close_readout(self, out, a_vae, mask, decode, key, latents):
+        """What the read-outs of the generative switching model close with: a_vae, n_obs [B] and - `decode` - out[key] = the
+        decoder's frames of `latents`."""
+        out["a_vae"] = a_vae
+        out["n_obs"] = self._n_obs(mask, a_vae)
+        if decode:
+            out[key] = self._decode_latents(latents, a_vae.dtype)
+        return out
+
+    @staticmethod
+    def _argmax_lowest(p):
+        """argmax over the last axis, the lowest index among the maxima."""
+        return (p == p.max(-1, keepdim=True).values).to(torch.int8).argmax(-1)
+
     @staticmethod
     def _n_obs(mask, a):
         """Observed steps per sequence [B] of latents a [B,T,p] under mask [B,T] or None, on the device."""
@@ -420,10 +444,7 @@ class KVAE(nn.Module):
         4. decode=True (needs smooth): x_imputed = decoder(a_imputed).
         Also returns a_vae.  Training mode, tau and parameters are left as they were."""
         dyn = self.kalman_filter.dyn_params
-        if not dyn.is_switching_dynamics:
-            raise ValueError('decode_regimes needs a model with dynamics = "switching" (config.dynamics_model); this one has '
-                             f'"{self.config.dynamics_model}"')
-        prelude = self._readout("decode_regimes", x, u, mask, sample=bool(sample_a))   # its shape checks come before this one
+        prelude = self._switching_readout("decode_regimes", x, u, mask, sample_a)   # its shape checks come before this one
         if decode and not smooth:
             raise ValueError("decode_regimes: decode=True needs smooth=True (x_imputed is decoded from the smoothed latents)")
         with prelude as (a_vae, _, _, u, mask):
@@ -497,19 +518,10 @@ class KVAE(nn.Module):
         Also returns a_vae and n_obs [B].  Exact through t = 1, at every step when P is the identity or when all regimes share
         A, B, Q; otherwise the GPB2 approximation.  No host synchronisation.  Training mode, tau and
         parameters are left as they were."""
-        dyn = self.kalman_filter.dyn_params
-        if not dyn.is_switching_dynamics:
-            raise ValueError('filter_regimes needs a model with dynamics = "switching" (config.dynamics_model); this one has '
-                             f'"{self.config.dynamics_model}"')
-        with self._readout("filter_regimes", x, u, mask, sample=bool(sample_a)) as (a_vae, _, _, u, mask):
+        with self._switching_readout("filter_regimes", x, u, mask, sample_a) as (a_vae, _, _, u, mask):
             out = self.kalman_filter.filter_regimes(a_vae, u, mask, state=state)
-            rf = out["regime_filt"]
-            out["regimes"] = (rf == rf.max(-1, keepdim=True).values).to(torch.int8).argmax(-1)   # lowest index among the maxima
-            out["a_vae"] = a_vae
-            out["n_obs"] = self._n_obs(mask, a_vae)
-            if decode:
-                out["x_pred"] = self._decode_latents(out["a_pred"], a_vae.dtype)
-            return out
+            out["regimes"] = self._argmax_lowest(out["regime_filt"])
+            return self._close_readout(out, a_vae, mask, decode, "x_pred", out["a_pred"])
 
     @torch.no_grad()
     def particle_filter_regimes(self, x, u=None, mask=None, num_particles=256, replicates=1, ess_threshold=0.5, sample_a=False,
@@ -533,22 +545,15 @@ class KVAE(nn.Module):
            bits of the whole-sequence call.  decode=True: x_filt = decoder(a_filt).
         Also returns a_vae and n_obs [B].  No host synchronisation.  Training mode, tau and parameters are left as they were."""
         dyn = self.kalman_filter.dyn_params
-        if not dyn.is_switching_dynamics:
-            raise ValueError('particle_filter_regimes needs a model with dynamics = "switching" (config.dynamics_model); this one has '
-                             f'"{self.config.dynamics_model}"')
-        with self._readout("particle_filter_regimes", x, u, mask, sample=bool(sample_a)) as (a_vae, _, _, u, mask):
+        with self._switching_readout("particle_filter_regimes", x, u, mask, sample_a) as (a_vae, _, _, u, mask):
             out = self.kalman_filter.particle_filter_regimes(a_vae, u, mask, num_particles=num_particles, replicates=replicates,
                                                              ess_threshold=ess_threshold, state=state)
             out["log_lik_seq_mean"], w = lgssm_ops.combine_replicates(out["log_lik"])
             rf = (w.unsqueeze(-1) * out["regime_filt"]).sum(1)
             out["regime_filt_mean"] = rf
-            out["regimes_map"] = (rf == rf.max(-1, keepdim=True).values).to(torch.int8).argmax(-1)   # lowest index among the maxima
+            out["regimes_map"] = self._argmax_lowest(rf)
             out["a_filt"] = (w.unsqueeze(-1) * out["mus_filt"]).sum(1) @ dyn.C[0].detach().to(rf.dtype).mT
-            out["a_vae"] = a_vae
-            out["n_obs"] = self._n_obs(mask, a_vae)
-            if decode:
-                out["x_filt"] = self._decode_latents(out["a_filt"], a_vae.dtype)
-            return out
+            return self._close_readout(out, a_vae, mask, decode, "x_filt", out["a_filt"])
 
     @torch.no_grad()
     def smooth_regimes(self, x, u=None, mask=None, sample_a=False, state=None, decode=False):
@@ -568,19 +573,11 @@ class KVAE(nn.Module):
         regimes share A, B, Q; regime_smooth and regime_pairs are exact at T = 2; otherwise the GPB2 approximation (DESIGN.md
         section 15).  No host synchronisation.  Training mode, tau and parameters are left as they were."""
         dyn = self.kalman_filter.dyn_params
-        if not dyn.is_switching_dynamics:
-            raise ValueError('smooth_regimes needs a model with dynamics = "switching" (config.dynamics_model); this one has '
-                             f'"{self.config.dynamics_model}"')
-        with self._readout("smooth_regimes", x, u, mask, sample=bool(sample_a)) as (a_vae, _, _, u, mask):
+        with self._switching_readout("smooth_regimes", x, u, mask, sample_a) as (a_vae, _, _, u, mask):
             out = self.kalman_filter.smooth_regimes(a_vae, u, mask, state=state)
-            rs = out["regime_smooth"]
-            out["regimes"] = (rs == rs.max(-1, keepdim=True).values).to(torch.int8).argmax(-1)   # lowest index among the maxima
-            out["a_smooth"] = out["mus_smooth"] @ dyn.C[0].detach().to(rs.dtype).mT
-            out["a_vae"] = a_vae
-            out["n_obs"] = self._n_obs(mask, a_vae)
-            if decode:
-                out["x_smooth"] = self._decode_latents(out["a_smooth"], a_vae.dtype)
-            return out
+            out["regimes"] = self._argmax_lowest(out["regime_smooth"])
+            out["a_smooth"] = out["mus_smooth"] @ dyn.C[0].detach().to(out["regime_smooth"].dtype).mT
+            return self._close_readout(out, a_vae, mask, decode, "x_smooth", out["a_smooth"])
 
     @torch.no_grad()
     def forecast_regimes(self, x, horizon, u=None, mask=None, sample_a=False, origins="all", state=None, decode=False):
@@ -601,10 +598,7 @@ class KVAE(nn.Module):
            is False.  levels_fore [B,T_o,H]: the largest ladder level of the pair densities.
         5. decode=True: x_fore [B,H,C,h,w] = decoder(a_fore) of the LAST origin only.
         Also returns a_vae and n_obs [B].  No host synchronisation.  Training mode, tau and parameters are left as they were."""
-        dyn = self.kalman_filter.dyn_params
-        if not dyn.is_switching_dynamics:
-            raise ValueError('forecast_regimes needs a model with dynamics = "switching" (config.dynamics_model); this one has '
-                             f'"{self.config.dynamics_model}"')
+        self._needs_switching("forecast_regimes")   # before the checks of horizon and origins; _readout's of mask and u after them
         H = int(horizon)
         if H < 1:
             raise ValueError(f"forecast_regimes: horizon must be >= 1, got {horizon}")
@@ -613,17 +607,12 @@ class KVAE(nn.Module):
         T = x.shape[1]
         with self._readout("forecast_regimes", x, u, mask, sample=bool(sample_a), horizon=H) as (a_vae, _, _, u_all, mask):
             out = self.kalman_filter.forecast_regimes(a_vae, None if u is None else u_all, H, mask, origins=origins, state=state)
-            rf = out["regime_fore"]
-            out["regimes_fore"] = (rf == rf.max(-1, keepdim=True).values).to(torch.int8).argmax(-1)   # lowest index among the maxima
+            out["regimes_fore"] = self._argmax_lowest(out["regime_fore"])
             dev = a_vae.device
             target = torch.arange(0 if origins == "all" else T - 1, T, device=dev)[:, None] + torch.arange(1, H + 1, device=dev)[None, :]
             inside = (target < T).expand(x.shape[0], -1, -1)
             out["valid"] = inside if mask is None else inside & (mask[:, target.clamp(max=T - 1)] != 0)
-            out["a_vae"] = a_vae
-            out["n_obs"] = self._n_obs(mask, a_vae)
-            if decode:
-                out["x_fore"] = self._decode_latents(out["a_fore"][:, -1], a_vae.dtype)
-            return out
+            return self._close_readout(out, a_vae, mask, decode, "x_fore", out["a_fore"][:, -1])
 
     def fit_dynamics_em(self, batches, iters, update=("A", "B", "Q", "C", "P"), sample_a=False, min_count=None):
         """Closed-form EM for the generative switching model on the encoded sequences (switching dynamics only):

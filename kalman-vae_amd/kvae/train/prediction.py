@@ -7,6 +7,17 @@ log-likelihood and the mean normalised innovation squared (2 = a_dim for a calib
 import torch
 
 
+def _frames(model, batch_or_x):
+    """x [B,T,...] on the model's device, from x itself or a batch: a dict with "images", or a tuple whose first entry is x."""
+    if isinstance(batch_or_x, dict):
+        x = batch_or_x["images"]
+    elif isinstance(batch_or_x, (tuple, list)):
+        x = batch_or_x[0]
+    else:
+        x = batch_or_x
+    return x.to(next(model.parameters()).device)
+
+
 @torch.no_grad()
 def prediction_scores(model, batch_or_x, mask=None, u=None):
     """Scores of the filter's one-step-ahead predictions on x [B,T,...] (or a batch: a dict with "images", or a tuple whose
@@ -16,15 +27,7 @@ def prediction_scores(model, batch_or_x, mask=None, u=None):
       mse_naive         the same for the persistence prediction a_vae_{t-1}
       log_lik_per_step  sum of log p(a_t | a_{0:t-1}, u) over observed steps / their number
       nis_mean          mean normalised innovation squared over observed steps"""
-    if isinstance(batch_or_x, dict):
-        x = batch_or_x["images"]
-    elif isinstance(batch_or_x, (tuple, list)):
-        x = batch_or_x[0]
-    else:
-        x = batch_or_x
-    dev = next(model.parameters()).device
-    x = x.to(dev)
-    sc = model.score(x, u=u, mask=mask)
+    sc = model.score(_frames(model, batch_or_x), u=u, mask=mask)
     a, a_pred = sc["a_vae"], sc["a_pred"].to(sc["a_vae"].dtype)
     Bsz, T = a.shape[:2]
     mk = torch.ones(Bsz, T, device=a.device, dtype=a.dtype) if mask is None else mask.to(device=a.device, dtype=a.dtype)
@@ -46,16 +49,9 @@ def regime_filter_scores(model, batch_or_x, mask=None, u=None):
       log_lik_per_step_map   the same for score(): the density conditional on the posterior's most likely regime path
       regime_agreement       share of steps whose causal argmax regime equals decode_regimes' path
       regime_kl              mean over steps of KL(q(s_t) || p(s_t | a_{0:t})), q(s_t) the posterior network's marginals"""
-    if isinstance(batch_or_x, dict):
-        x = batch_or_x["images"]
-    elif isinstance(batch_or_x, (tuple, list)):
-        x = batch_or_x[0]
-    else:
-        x = batch_or_x
-    dev = next(model.parameters()).device
-    x = x.to(dev)
+    x = _frames(model, batch_or_x)
     fr = model.filter_regimes(x, u=u, mask=mask)
-    sc = model.score(x, u=u, mask=mask, regimes="map")
+    sc =model.score(x, u=u, mask=mask, regimes="map")
     dec = model.decode_regimes(x, u=u, mask=mask, smooth=False)
     n_obs = fr["n_obs"].sum().clamp(min=1.0)
     q, pf = dec["regime_probs"].double(), fr["regime_filt"].double()
@@ -76,14 +72,7 @@ def particle_filter_scores(model, batch_or_x, mask=None, u=None, num_particles=2
       pf_std                 the spread of log_lik_seq over the replicates (standard deviation, mean over sequences; 0 for one)
       regime_tv              mean over (b, t) of the total variation between regime_filt_mean and filter_regimes' regime_filt
       ess_mean               mean effective sample size over replicates and steps"""
-    if isinstance(batch_or_x, dict):
-        x = batch_or_x["images"]
-    elif isinstance(batch_or_x, (tuple, list)):
-        x = batch_or_x[0]
-    else:
-        x = batch_or_x
-    dev = next(model.parameters()).device
-    x = x.to(dev)
+    x = _frames(model, batch_or_x)
     pf = model.particle_filter_regimes(x, u=u, mask=mask, num_particles=num_particles, replicates=replicates, ess_threshold=ess_threshold)
     fr = model.filter_regimes(x, u=u, mask=mask)
     n_obs = fr["n_obs"].sum().clamp(min=1.0)
@@ -107,14 +96,8 @@ def forecast_scores(model, batch_or_x, horizon, mask=None, u=None):
       nis_mean   mean of r^T S_fore^-1 r, r = a_{t+h} - a_fore: p (= 2) when the forecast is calibrated
       count      the number of valid (b, t)
     A horizon without a valid target gives count 0 and nan elsewhere."""
-    if isinstance(batch_or_x, dict):
-        x = batch_or_x["images"]
-    elif isinstance(batch_or_x, (tuple, list)):
-        x = batch_or_x[0]
-    else:
-        x = batch_or_x
-    dev = next(model.parameters()).device
-    x = x.to(dev)
+    x = _frames(model, batch_or_x)
+    dev = x.device
     H = int(horizon)
     fc = model.forecast_regimes(x, H, u=u, mask=mask)
     a = fc["a_vae"].double()

@@ -9,23 +9,9 @@
 #define KVAE_WAVE_EMU 1
 #include "wave_emu.h"
 
-#include <random>
-#include <vector>
-
 #include "../../kalman-vae_amd/csrc/lgssm_em.h"
+#include "switching_fixture.h"
 
-typedef std::vector<float> vec;
-
-static bool finite_all(const vec &v) {
-  for (float x : v)
-    if (!std::isfinite(x)) return false;
-  return true;
-}
-static bool nan_all(const vec &v) {
-  for (float x : v)
-    if (!std::isnan(x)) return false;
-  return true;
-}
 static bool launched(const int (&before)[4], int f, int b, int r, int s) {
   const int want[4] = {f, b, r, s};
   for (int i = 0; i < 4; ++i)
@@ -37,24 +23,10 @@ static void counters(int (&c)[4]) {
 }
 
 static int run(int B, int T, int K, int n, int m, bool masked) {
-  const int p = 2, x = n + m;
-  std::mt19937 g(B * 1000 + T * 10 + K);
-  std::normal_distribution<float> nd(0.f, 1.f);
+  const int x = n + m;
+  SwitchingModel sw(B * 1000 + T * 10 + K, B, T, K, n, m, masked);
+  const vec &mask = sw.mask;
   const size_t items = (size_t)B * T, pitems = (size_t)B * (T > 1 ? T - 1 : 1);
-  vec A((size_t)K * n * n, 0.f), Bm((size_t)K * n * m), Q((size_t)K * n * n, 0.f), C((size_t)p * n), R = {0.05f, 0.f, 0.f, 0.05f},
-      Pm((size_t)K * K), mu0(n), Sigma0((size_t)n * n, 0.f), y(items * p), u(items * m), mask(masked ? items : 0);
-  for (int k = 0; k < K; ++k)
-    for (int i = 0; i < n; ++i) {
-      A[((size_t)k * n + i) * n + i] = 0.9f - 0.05f * k;
-      if (i + 1 < n) A[((size_t)k * n + i) * n + i + 1] = 0.1f * (k % 2 ? 1.f : -1.f);
-      Q[((size_t)k * n + i) * n + i] = 0.02f + 0.01f * k;
-    }
-  for (int i = 0; i < n; ++i) Sigma0[(size_t)i * n + i] = 0.5f;
-  for (auto *v : {&Bm, &C, &mu0, &y, &u})
-    for (auto &e : *v) e = 0.5f * nd(g);
-  for (int i = 0; i < K; ++i)
-    for (int j = 0; j < K; ++j) Pm[(size_t)i * K + j] = K == 1 ? 1.f : (i == j ? 0.8f : 0.2f / (K - 1));
-  for (size_t it = 0; it < mask.size(); ++it) mask[it] = it % 3 == 1 ? 0.f : 1.f;
   const size_t G = (size_t)K * (1 + n * n + n * x + x * x) + (size_t)K * K + 2 * n + n * n + 4 + 1 + n + n * n;
   if (kvae_lgssm_switching_em_ws_floats(B, K, n, m) != (int64_t)(B * G)) return 30;
   if (kvae_lgssm_switching_em_ws_floats(B, 0, n, m) != 0) return 31;
@@ -65,10 +37,8 @@ static int run(int B, int T, int K, int n, int m, bool masked) {
       Syz(2 * n, NAN), Szz((size_t)n * n, NAN), Syy(4, NAN), Nobs(1, NAN), z0(n, NAN), z0z0((size_t)n * n, NAN), nseq(1, NAN);
   kvae_sws_problem S{};
   kvae_swf_problem &P = S.filt;
-  P.B = B, P.T = T, P.K = K, P.n = n, P.m = m, P.p = p;
-  P.A = A.data(), P.Bm = Bm.data(), P.Q = Q.data(), P.C = C.data(), P.R = R.data(), P.P = Pm.data(), P.mu0 = mu0.data();
-  P.Sigma0 = Sigma0.data(), P.y = y.data(), P.u = u.data(), P.mask = masked ? mask.data() : nullptr;
-  P.ll = ll.data(), P.seq_ll = seq.data();
+  sw.bind(P);
+  P.ll =ll.data(), P.seq_ll = seq.data();
   S.hist_mu = hmu.data(), S.hist_Sigma = hS.data(), S.hist_W = hW.data(), S.hist_w = hw.data();
   S.regime_smooth = rs.data(), S.regime_pairs = rp.data(), S.mus_smooth = ms.data(), S.Sigmas_smooth = Ss.data();
   kvae_em_stats E{};
@@ -171,16 +141,7 @@ static int run(int B, int T, int K, int n, int m, bool masked) {
 }
 
 int main() {
-  const int shapes[8][5] = {{1, 1, 1, 4, 2}, {2, 1, 5, 4, 2}, {2, 2, 7, 4, 2}, {3, 4, 5, 3, 1}, {2, 5, 7, 4, 4}, {2, 3, 8, 2, 3}, {3, 2, 3, 1, 1},
-                            {1, 66, 2, 4, 2}};
-  int bad = 0;
-  for (const auto &s : shapes)
-    for (int variant = s[1] > 8 ? 1 : 0; variant < 2; ++variant) {   // the long one once
-      const int rc = run(s[0], s[1], s[2], s[3], s[4], variant == 1);
-      printf("(%d,%d,%d,%d,%d) %s %d\n", s[0], s[1], s[2], s[3], s[4], variant ? "masked" : "observed", rc);
-      bad += rc != 0;
-    }
-  if (bad) return 1;
-  printf("EM-ASAN-OK\n");
-  return 0;
+  const Shape shapes[] = {{1, 1, 1, 4, 2}, {2, 1, 5, 4, 2}, {2, 2, 7, 4, 2}, {3, 4, 5, 3, 1}, {2, 5, 7, 4, 4}, {2, 3, 8, 2, 3}, {3, 2, 3, 1, 1},
+                          {1, 66, 2, 4, 2}};
+  return run_shapes(shapes, "EM-ASAN-OK", [](const Shape &s, bool masked) { return run(s.B, s.T, s.K, s.n, s.m, masked); });
 }

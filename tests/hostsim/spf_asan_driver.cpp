@@ -9,47 +9,24 @@
 #define KVAE_WAVE_EMU 1
 #include "wave_emu.h"
 
-#include <random>
-#include <vector>
-
 #include "../../kalman-vae_amd/csrc/lgssm_spf.h"
-
-static bool finite_all(const std::vector<float> &v) {
-  for (float x : v)
-    if (!std::isfinite(x)) return false;
-  return true;
-}
+#include "switching_fixture.h"
 
 static int run(int B, int G, int T, int K, int n, int m, int N, float thr, bool masked) {
   const int p = 2;
-  std::mt19937 g(B * 1000 + T * 10 + K + N);
-  std::normal_distribution<float> nd(0.f, 1.f);
+  SwitchingModel sw(B * 1000 + T * 10 + K + N, B, T, K, n, m, masked);
+  const vec &mask = sw.mask;
   std::uniform_real_distribution<float> ud(0.f, 1.f);
-  const size_t items = (size_t)B * T, reps = (size_t)B * G, steps = reps * T, parts = reps * N;
-  std::vector<float> A((size_t)K * n * n, 0.f), Bm((size_t)K * n * m), Q((size_t)K * n * n, 0.f), C((size_t)p * n), R = {0.05f, 0.f, 0.f, 0.05f},
-      Pm((size_t)K * K), mu0(n), Sigma0((size_t)n * n, 0.f), y(items * p), u(items * m), mask(masked ? items : 0), th(steps * N), ph(steps);
-  for (int k = 0; k < K; ++k)
-    for (int i = 0; i < n; ++i) {
-      A[((size_t)k * n + i) * n + i] = 0.9f - 0.05f * k;
-      if (i + 1 < n) A[((size_t)k * n + i) * n + i + 1] = 0.1f * (k % 2 ? 1.f : -1.f);
-      Q[((size_t)k * n + i) * n + i] = 0.02f + 0.01f * k;
-    }
-  for (int i = 0; i < n; ++i) Sigma0[(size_t)i * n + i] = 0.5f;
-  for (auto *v : {&Bm, &C, &mu0, &y, &u})
-    for (auto &x : *v) x = 0.5f * nd(g);
+  const size_t reps = (size_t)B * G, steps = reps * T, parts = reps * N;
+  std::vector<float> th(steps * N), ph(steps);   // the draws: after the model, from its generator
   for (auto *v : {&th, &ph})
-    for (auto &x : *v) x = std::min(ud(g), 0.99999994f);
-  for (int i = 0; i < K; ++i)
-    for (int j = 0; j < K; ++j) Pm[(size_t)i * K + j] = K == 1 ? 1.f : (i == j ? 0.8f : 0.2f / (K - 1));
-  for (size_t it = 0; it < mask.size(); ++it) mask[it] = it % 3 == 1 ? 0.f : 1.f;
+    for (auto &x : *v) x = std::min(ud(sw.g), 0.99999994f);
   std::vector<float> ll(steps, NAN), seq(reps, NAN), rf(steps * K, NAN), mf(steps * n, NAN), Sf(steps * n * n, NAN), ess(steps, NAN),
       olw(parts, NAN), omu(parts * n, NAN), oS(parts * n * n, NAN);
   std::vector<int32_t> rs(steps, -1), rg(steps * N, -1), an(steps * N, -1), levels(steps, -1), paths(parts * T, -1), oreg(parts, -1);
   kvae_spf_problem P{};
-  P.B = B, P.G = G, P.T = T, P.K = K, P.N = N, P.n = n, P.m = m, P.p = p, P.ess_threshold = thr;
-  P.A = A.data(), P.Bm = Bm.data(), P.Q = Q.data(), P.C = C.data(), P.R = R.data(), P.P = Pm.data(), P.mu0 = mu0.data();
-  P.Sigma0 = Sigma0.data(), P.y = y.data(), P.u = u.data(), P.mask = masked ? mask.data() : nullptr;
-  P.pf_regime = th.data(), P.pf_resample = ph.data();
+  sw.bind(P);
+  P.G = G, P.N = N, P.ess_threshold = thr, P.pf_regime = th.data(), P.pf_resample = ph.data();
   P.ll = ll.data(), P.seq_ll = seq.data(), P.regime_filt = rf.data(), P.mus_filt = mf.data(), P.Sigmas_filt = Sf.data(), P.ess = ess.data();
   P.resampled = rs.data(), P.regimes = rg.data(), P.ancestors = an.data(), P.levels = levels.data(), P.paths = paths.data();
   P.out_log_w = olw.data(), P.out_regime = oreg.data(), P.out_mu = omu.data(), P.out_Sigma = oS.data();
@@ -92,27 +69,14 @@ static int run(int B, int G, int T, int K, int n, int m, int N, float thr, bool 
   // the second half from the carried state of the first, with its slices of the draws: the bits of the whole
   if (T >= 2) {
     const int T1 = T / 2, T2 = T - T1;
-    std::vector<float> y1((size_t)B * T1 * p), u1((size_t)B * T1 * m), k1(masked ? (size_t)B * T1 : 0), y2((size_t)B * T2 * p),
-        u2((size_t)B * T2 * m), k2(masked ? (size_t)B * T2 : 0), th1(reps * T1 * N), th2(reps * T2 * N), ph1(reps * T1), ph2(reps * T2),
-        rfa(reps * T1 * K, NAN), rfb(reps * T2 * K, NAN), lw1(parts, NAN), mu1(parts * n, NAN), S1(parts * n * n, NAN), lw2(parts, NAN);
+    std::vector<float> y1 = chunk(sw.y, T, p, 0, T1), u1 = chunk(sw.u, T, m, 0, T1), k1 = chunk(mask, T, 1, 0, T1), y2 = chunk(sw.y, T, p, T1, T),
+        u2 = chunk(sw.u, T, m, T1, T), k2 = chunk(mask, T, 1, T1, T), th1 = chunk(th, T, N, 0, T1), th2 = chunk(th, T, N, T1, T),
+        ph1 = chunk(ph, T, 1, 0, T1), ph2 = chunk(ph, T, 1, T1, T), rfa(reps * T1 * K, NAN), rfb(reps * T2 * K, NAN), lw1(parts, NAN),
+        mu1(parts * n, NAN), S1(parts * n * n, NAN), lw2(parts, NAN);
     std::vector<int32_t> reg1(parts, -1), reg2(parts, -1);
-    for (int b = 0; b < B; ++b)
-      for (int t = 0; t < T; ++t) {
-        const size_t src = (size_t)b * T + t, dst = t < T1 ? (size_t)b * T1 + t : (size_t)b * T2 + (t - T1);
-        for (int c = 0; c < p; ++c) (t < T1 ? y1 : y2)[dst * p + c] = y[src * p + c];
-        for (int c = 0; c < m; ++c) (t < T1 ? u1 : u2)[dst * m + c] = u[src * m + c];
-        if (masked) (t < T1 ? k1 : k2)[dst] = mask[src];
-      }
-    for (size_t r = 0; r < reps; ++r)
-      for (int t = 0; t < T; ++t) {
-        const size_t src = r * T + t, dst = t < T1 ? r * T1 + t : r * T2 + (t - T1);
-        (t < T1 ? ph1 : ph2)[dst] = ph[src];
-        for (int i = 0; i < N; ++i) (t < T1 ? th1 : th2)[dst * N + i] = th[src * N + i];
-      }
     kvae_spf_problem Pa{};
-    Pa.B = B, Pa.G = G, Pa.T = T1, Pa.K = K, Pa.N = N, Pa.n = n, Pa.m = m, Pa.p = p, Pa.ess_threshold = thr;
-    Pa.A = A.data(), Pa.Bm = Bm.data(), Pa.Q = Q.data(), Pa.C = C.data(), Pa.R = R.data(), Pa.P = Pm.data(), Pa.mu0 = mu0.data();
-    Pa.Sigma0 = Sigma0.data(), Pa.y = y1.data(), Pa.u = u1.data(), Pa.mask = masked ? k1.data() : nullptr;
+    sw.bind(Pa);
+    Pa.G = G, Pa.N = N, Pa.ess_threshold = thr, Pa.T = T1, Pa.y = y1.data(), Pa.u = u1.data(), Pa.mask = masked ? k1.data() : nullptr;
     Pa.pf_regime = th1.data(), Pa.pf_resample = ph1.data();
     Pa.regime_filt = rfa.data(), Pa.out_log_w = lw1.data(), Pa.out_regime = reg1.data(), Pa.out_mu = mu1.data(), Pa.out_Sigma = S1.data();
     if (kvae_lgssm_switching_pf(&Pa, nullptr)) return 14;
@@ -145,20 +109,8 @@ static int run(int B, int G, int T, int K, int n, int m, int N, float thr, bool 
 }
 
 int main() {
-  struct Shape {
-    int B, G, T, K, n, m, N;
-    float thr;
-  };
-  const Shape shapes[] = {{1, 1, 1, 1, 4, 2, 64, 0.5f},  {2, 1, 1, 5, 4, 2, 64, 1.f},  {2, 2, 4, 5, 3, 1, 64, 0.5f}, {1, 2, 5, 7, 4, 4, 256, 1.f},
-                          {2, 1, 3, 8, 2, 3, 128, 0.f},  {1, 1, 2, 3, 1, 1, 256, 0.5f}, {1, 1, 66, 2, 4, 2, 64, 0.5f}};
-  int bad = 0;
-  for (const auto &s : shapes)
-    for (int variant = s.T > 8 ? 1 : 0; variant < 2; ++variant) {   // the long one once
-      const int rc = run(s.B, s.G, s.T, s.K, s.n, s.m, s.N, s.thr, variant == 1);
-      printf("(%d,%d,%d,%d,%d,%d,%d,%g) %s %d\n", s.B, s.G, s.T, s.K, s.n, s.m, s.N, s.thr, variant ? "masked" : "observed", rc);
-      bad += rc != 0;
-    }
-  if (bad) return 1;
-  printf("SPF-ASAN-OK\n");
-  return 0;
+  // B, T, K, n, m, (no horizon,) G, N, ess_threshold
+  const Shape shapes[] = {{1, 1, 1, 4, 2, 0, 1, 64, 0.5f},  {2, 1, 5, 4, 2, 0, 1, 64, 1.f},    {2, 4, 5, 3, 1, 0, 2, 64, 0.5f}, {1, 5, 7, 4, 4, 0, 2, 256, 1.f},
+                          {2, 3, 8, 2, 3, 0, 1, 128, 0.f},  {1, 2, 3, 1, 1, 0, 1, 256, 0.5f}, {1, 66, 2, 4, 2, 0, 1, 64, 0.5f}};
+  return run_shapes(shapes, "SPF-ASAN-OK", [](const Shape &s, bool masked) { return run(s.B, s.G, s.T, s.K, s.n, s.m, s.N, s.thr, masked); });
 }

@@ -9,16 +9,8 @@
 #define KVAE_WAVE_EMU 1
 #include "wave_emu.h"
 
-#include <random>
-#include <vector>
-
 #include "../../kalman-vae_amd/csrc/lgssm_swh.h"
-
-static bool finite_all(const std::vector<float> &v) {
-  for (float x : v)
-    if (!std::isfinite(x)) return false;
-  return true;
-}
+#include "switching_fixture.h"
 
 struct Fore {
   std::vector<float> rf, af, Sf, mf, Sg, ll;
@@ -40,34 +32,15 @@ struct Fore {
 
 static int run(int B, int T, int K, int n, int m, int H, bool masked) {
   const int p = 2;
-  std::mt19937 g(B * 1000 + T * 10 + K + H);
-  std::normal_distribution<float> nd(0.f, 1.f);
+  SwitchingModel sw(B * 1000 + T * 10 + K + H, B, T, K, n, m, masked, H);
+  const vec &mask = sw.mask, &ua = sw.u_all;
   const size_t items = (size_t)B * T;
-  std::vector<float> A((size_t)K * n * n, 0.f), Bm((size_t)K * n * m), Q((size_t)K * n * n, 0.f), C((size_t)p * n), R = {0.05f, 0.f, 0.f, 0.05f},
-      Pm((size_t)K * K), mu0(n), Sigma0((size_t)n * n, 0.f), y(items * p), ua((size_t)B * (T + H) * m), u(items * m), mask(masked ? items : 0);
-  for (int k = 0; k < K; ++k)
-    for (int i = 0; i < n; ++i) {
-      A[((size_t)k * n + i) * n + i] = 0.9f - 0.05f * k;
-      if (i + 1 < n) A[((size_t)k * n + i) * n + i + 1] = 0.1f * (k % 2 ? 1.f : -1.f);
-      Q[((size_t)k * n + i) * n + i] = 0.02f + 0.01f * k;
-    }
-  for (int i = 0; i < n; ++i) Sigma0[(size_t)i * n + i] = 0.5f;
-  for (auto *v : {&Bm, &C, &mu0, &y, &ua})
-    for (auto &x : *v) x = 0.5f * nd(g);
-  for (int b = 0; b < B; ++b)
-    for (int t = 0; t < T; ++t)
-      for (int c = 0; c < m; ++c) u[((size_t)b * T + t) * m + c] = ua[((size_t)b * (T + H) + t) * m + c];
-  for (int i = 0; i < K; ++i)
-    for (int j = 0; j < K; ++j) Pm[(size_t)i * K + j] = K == 1 ? 1.f : (i == j ? 0.8f : 0.2f / (K - 1));
-  for (size_t it = 0; it < mask.size(); ++it) mask[it] = it % 3 == 1 ? 0.f : 1.f;
   std::vector<float> rf(items * K, NAN), ll(items, NAN), seq(B, NAN), ap(items * p, NAN), olw((size_t)B * K, NAN), omu((size_t)B * K * n, NAN),
       oS((size_t)B * K * n * n, NAN), hlw(items * K, NAN), hmu(items * K * n, NAN), hS(items * K * n * n, NAN);
   Fore all(items * H, K, n);
   kvae_swh_problem F{};
   kvae_swf_problem &P = F.filt;
-  P.B = B, P.T = T, P.K = K, P.n = n, P.m = m, P.p = p;
-  P.A = A.data(), P.Bm = Bm.data(), P.Q = Q.data(), P.C = C.data(), P.R = R.data(), P.P = Pm.data(), P.mu0 = mu0.data();
-  P.Sigma0 = Sigma0.data(), P.y = y.data(), P.u = u.data(), P.mask = masked ? mask.data() : nullptr;
+  sw.bind(P);
   P.regime_filt = rf.data(), P.ll = ll.data(), P.seq_ll = seq.data(), P.a_pred = ap.data();
   P.out_log_w = olw.data(), P.out_mu = omu.data(), P.out_Sigma = oS.data();
   F.hist_lw = hlw.data(), F.hist_mu = hmu.data(), F.hist_Sigma = hS.data(), F.H = H, F.t0 = 0, F.u_all = ua.data();
@@ -111,19 +84,10 @@ static int run(int B, int T, int K, int n, int m, int H, bool masked) {
   // the second half from the carried state of the first (without mu0 / Sigma0): the forecasts of its origins are the bits of the whole
   if (T >= 2) {
     const int T1 = T / 2, T2 = T - T1;
-    std::vector<float> y1((size_t)B * T1 * p), u1((size_t)B * T1 * m), k1(masked ? (size_t)B * T1 : 0), y2((size_t)B * T2 * p),
-        u2((size_t)B * T2 * m), ua2((size_t)B * (T2 + H) * m), k2(masked ? (size_t)B * T2 : 0), lw1((size_t)B * K, NAN), mu1((size_t)B * K * n, NAN),
-        S1((size_t)B * K * n * n, NAN), h1((size_t)B * T2 * K, NAN), h2((size_t)B * T2 * K * n, NAN), h3((size_t)B * T2 * K * n * n, NAN);
-    for (int b = 0; b < B; ++b) {
-      for (int t = 0; t < T; ++t) {
-        const size_t src = (size_t)b * T + t, dst = t < T1 ? (size_t)b * T1 + t : (size_t)b * T2 + (t - T1);
-        for (int c = 0; c < p; ++c) (t < T1 ? y1 : y2)[dst * p + c] = y[src * p + c];
-        for (int c = 0; c < m; ++c) (t < T1 ? u1 : u2)[dst * m + c] = u[src * m + c];
-        if (masked) (t < T1 ? k1 : k2)[dst] = mask[src];
-      }
-      for (int t = 0; t < T2 + H; ++t)
-        for (int c = 0; c < m; ++c) ua2[((size_t)b * (T2 + H) + t) * m + c] = ua[((size_t)b * (T + H) + T1 + t) * m + c];
-    }
+    std::vector<float> y1 = chunk(sw.y, T, p, 0, T1), u1 = chunk(sw.u, T, m, 0, T1), k1 = chunk(mask, T, 1, 0, T1), y2 = chunk(sw.y, T, p, T1, T),
+        u2 = chunk(sw.u, T, m, T1, T), ua2 = chunk(ua, T + H, m, T1, T + H), k2 = chunk(mask, T, 1, T1, T), lw1((size_t)B * K, NAN),
+        mu1((size_t)B * K * n, NAN), S1((size_t)B * K * n * n, NAN), h1((size_t)B * T2 * K, NAN), h2((size_t)B * T2 * K * n, NAN),
+        h3((size_t)B * T2 * K * n * n, NAN);
     kvae_swf_problem Pa = P;   // the first half: the filter alone keeps the state
     Pa.T = T1, Pa.y = y1.data(), Pa.u = u1.data(), Pa.mask = masked ? k1.data() : nullptr;
     Pa.regime_filt = nullptr, Pa.ll = nullptr, Pa.seq_ll = nullptr, Pa.a_pred = nullptr;
@@ -167,16 +131,7 @@ static int run(int B, int T, int K, int n, int m, int H, bool masked) {
 
 int main() {
   // B, T, K, n, m, H
-  const int shapes[8][6] = {{1, 1, 1, 4, 2, 1}, {2, 1, 5, 4, 2, 3}, {3, 4, 5, 3, 1, 2}, {2, 5, 7, 4, 4, 7},
-                            {2, 3, 8, 2, 3, 4}, {3, 2, 3, 1, 1, 1}, {2, 6, 8, 4, 2, 2}, {1, 66, 2, 4, 2, 3}};
-  int bad = 0;
-  for (const auto &s : shapes)
-    for (int variant = s[1] > 8 ? 1 : 0; variant < 2; ++variant) {   // the long one once
-      const int rc = run(s[0], s[1], s[2], s[3], s[4], s[5], variant == 1);
-      printf("(%d,%d,%d,%d,%d,%d) %s %d\n", s[0], s[1], s[2], s[3], s[4], s[5], variant ? "masked" : "observed", rc);
-      bad += rc != 0;
-    }
-  if (bad) return 1;
-  printf("SWH-ASAN-OK\n");
-  return 0;
+  const Shape shapes[] = {{1, 1, 1, 4, 2, 1}, {2, 1, 5, 4, 2, 3}, {3, 4, 5, 3, 1, 2}, {2, 5, 7, 4, 4, 7},
+                          {2, 3, 8, 2, 3, 4}, {3, 2, 3, 1, 1, 1}, {2, 6, 8, 4, 2, 2}, {1, 66, 2, 4, 2, 3}};
+  return run_shapes(shapes, "SWH-ASAN-OK", [](const Shape &s, bool masked) { return run(s.B, s.T, s.K, s.n, s.m, s.H, masked); });
 }

@@ -8,41 +8,16 @@
 #define KVAE_WAVE_EMU 1
 #include "wave_emu.h"
 
-#include <random>
-#include <vector>
-
 #include "../../kalman-vae_amd/csrc/lgssm_swm.h"
-
-static bool finite_all(const std::vector<float> &v) {
-  for (float x : v)
-    if (!std::isfinite(x)) return false;
-  return true;
-}
-static bool untouched(const std::vector<float> &v) {
-  for (float x : v)
-    if (!std::isnan(x)) return false;
-  return true;
-}
+#include "switching_fixture.h"
 
 static int run(int B, int T, int K, int n, int m, bool masked) {
   const int p = 2;
-  std::mt19937 g(B * 1000 + T * 10 + K);
-  std::normal_distribution<float> nd(0.f, 1.f);
+  SwitchingModel sw(B * 1000 + T * 10 + K, B, T, K, n, m, masked);
+  const vec &mask = sw.mask;
   const size_t items = (size_t)B * T;
-  std::vector<float> A((size_t)K * n * n, 0.f), Bm((size_t)K * n * m), Q((size_t)K * n * n, 0.f), C((size_t)p * n), R = {0.05f, 0.f, 0.f, 0.05f},
-      Pm((size_t)K * K), mu0(n), Sigma0((size_t)n * n, 0.f), y(items * p), u(items * m), mask(masked ? items : 0), gll(items), gseq(B);
-  for (int k = 0; k < K; ++k)
-    for (int i = 0; i < n; ++i) {
-      A[((size_t)k * n + i) * n + i] = 0.9f - 0.05f * k;
-      if (i + 1 < n) A[((size_t)k * n + i) * n + i + 1] = 0.1f * (k % 2 ? 1.f : -1.f);
-      Q[((size_t)k * n + i) * n + i] = 0.02f + 0.01f * k;
-    }
-  for (int i = 0; i < n; ++i) Sigma0[(size_t)i * n + i] = 0.5f;
-  for (auto *v : {&Bm, &C, &mu0, &y, &u, &gll, &gseq})
-    for (auto &x : *v) x = 0.5f * nd(g);
-  for (int i = 0; i < K; ++i)
-    for (int j = 0; j < K; ++j) Pm[(size_t)i * K + j] = K == 1 ? 1.f : (i == j ? 0.8f : 0.2f / (K - 1));
-  for (size_t it = 0; it < mask.size(); ++it) mask[it] = it % 3 == 1 ? 0.f : 1.f;
+  std::vector<float> gll(items), gseq(B);   // the upstreams: drawn after the model, from its stream
+  sw.draw(gll), sw.draw(gseq);
   const size_t G = (size_t)K * (2 * n * n + n * m) + 2 * n + (size_t)K * K + n + (size_t)n * n;
   if (kvae_lgssm_switching_marginal_ws_floats(B, K, n, m) != (int64_t)(B * G)) return 30;
   std::vector<float> ll(items, NAN), seq(B, NAN), hlw(items * K, NAN), hmu(items * K * n, NAN), hS(items * K * n * n, NAN);
@@ -50,10 +25,8 @@ static int run(int B, int T, int K, int n, int m, bool masked) {
       gP((size_t)K * K, NAN), gm(n, NAN), gS((size_t)n * n, NAN), gY(items * p, NAN), gU(items * m, NAN), llr(items, NAN);
   kvae_swm_problem M{};
   kvae_swf_problem &P = M.filt;
-  P.B = B, P.T = T, P.K = K, P.n = n, P.m = m, P.p = p;
-  P.A = A.data(), P.Bm = Bm.data(), P.Q = Q.data(), P.C = C.data(), P.R = R.data(), P.P = Pm.data(), P.mu0 = mu0.data();
-  P.Sigma0 = Sigma0.data(), P.y = y.data(), P.u = u.data(), P.mask = masked ? mask.data() : nullptr;
-  P.ll = ll.data(), P.seq_ll = seq.data();
+  sw.bind(P);
+  P.ll =ll.data(), P.seq_ll = seq.data();
   M.hist_lw = hlw.data(), M.hist_mu = hmu.data(), M.hist_Sigma = hS.data();
   kvae_swm_grads Gr{};
   Gr.g_ll = gll.data(), Gr.g_seq = gseq.data(), Gr.ws = ws.data();
@@ -79,7 +52,7 @@ static int run(int B, int T, int K, int n, int m, bool masked) {
     Ge = Gr, Ge.ws = nullptr;
     if (kvae_lgssm_switching_marginal_bwd(&M, &Ge, nullptr) != KVAE_ERR_NULL) return 8;
     for (const auto *v : {&ll, &seq, &hlw, &hmu, &hS, &ws, &gA, &gB, &gQ, &gC, &gP, &gm, &gS, &gY, &gU, &llr})
-      if (!untouched(*v)) return 9;
+      if (!nan_all(*v)) return 9;
   }
   const int b0 = kvae_wemu_switching_marginal_launches(0), b2 = kvae_wemu_switching_marginal_launches(2), b3 = kvae_wemu_switching_marginal_launches(3);
   if (kvae_lgssm_switching_marginal(&M, nullptr)) return 10;
@@ -131,16 +104,7 @@ static int run(int B, int T, int K, int n, int m, bool masked) {
 }
 
 int main() {
-  const int shapes[8][5] = {{1, 1, 1, 4, 2}, {2, 1, 5, 4, 2}, {2, 2, 7, 4, 2}, {3, 4, 5, 3, 1}, {2, 5, 7, 4, 4}, {2, 3, 8, 2, 3}, {3, 2, 3, 1, 1},
-                            {1, 66, 2, 4, 2}};
-  int bad = 0;
-  for (const auto &s : shapes)
-    for (int variant = s[1] > 8 ? 1 : 0; variant < 2; ++variant) {   // the long one once
-      const int rc = run(s[0], s[1], s[2], s[3], s[4], variant == 1);
-      printf("(%d,%d,%d,%d,%d) %s %d\n", s[0], s[1], s[2], s[3], s[4], variant ? "masked" : "observed", rc);
-      bad += rc != 0;
-    }
-  if (bad) return 1;
-  printf("SWM-ASAN-OK\n");
-  return 0;
+  const Shape shapes[] = {{1, 1, 1, 4, 2}, {2, 1, 5, 4, 2}, {2, 2, 7, 4, 2}, {3, 4, 5, 3, 1}, {2, 5, 7, 4, 4}, {2, 3, 8, 2, 3}, {3, 2, 3, 1, 1},
+                          {1, 66, 2, 4, 2}};
+  return run_shapes(shapes, "SWM-ASAN-OK", [](const Shape &s, bool masked) { return run(s.B, s.T, s.K, s.n, s.m, masked); });
 }

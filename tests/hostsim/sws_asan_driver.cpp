@@ -8,45 +8,19 @@
 #define KVAE_WAVE_EMU 1
 #include "wave_emu.h"
 
-#include <random>
-#include <vector>
-
 #include "../../kalman-vae_amd/csrc/lgssm_sws.h"
-
-static bool finite_all(const std::vector<float> &v) {
-  for (float x : v)
-    if (!std::isfinite(x)) return false;
-  return true;
-}
+#include "switching_fixture.h"
 
 static int run(int B, int T, int K, int n, int m, bool masked) {
-  const int p = 2;
-  std::mt19937 g(B * 1000 + T * 10 + K);
-  std::normal_distribution<float> nd(0.f, 1.f);
+  SwitchingModel sw(B * 1000 + T * 10 + K, B, T, K, n, m, masked);
   const size_t items = (size_t)B * T, pitems = (size_t)B * (T > 1 ? T - 1 : 1);
-  std::vector<float> A((size_t)K * n * n, 0.f), Bm((size_t)K * n * m), Q((size_t)K * n * n, 0.f), C((size_t)p * n), R = {0.05f, 0.f, 0.f, 0.05f},
-      Pm((size_t)K * K), mu0(n), Sigma0((size_t)n * n, 0.f), y(items * p), u(items * m), mask(masked ? items : 0);
-  for (int k = 0; k < K; ++k)
-    for (int i = 0; i < n; ++i) {
-      A[((size_t)k * n + i) * n + i] = 0.9f - 0.05f * k;
-      if (i + 1 < n) A[((size_t)k * n + i) * n + i + 1] = 0.1f * (k % 2 ? 1.f : -1.f);
-      Q[((size_t)k * n + i) * n + i] = 0.02f + 0.01f * k;
-    }
-  for (int i = 0; i < n; ++i) Sigma0[(size_t)i * n + i] = 0.5f;
-  for (auto *v : {&Bm, &C, &mu0, &y, &u})
-    for (auto &x : *v) x = 0.5f * nd(g);
-  for (int i = 0; i < K; ++i)
-    for (int j = 0; j < K; ++j) Pm[(size_t)i * K + j] = K == 1 ? 1.f : (i == j ? 0.8f : 0.2f / (K - 1));
-  for (size_t it = 0; it < mask.size(); ++it) mask[it] = it % 3 == 1 ? 0.f : 1.f;
   std::vector<float> rf(items * K, NAN), ll(items, NAN), seq(B, NAN), mf(items * n, NAN), olw((size_t)B * K, NAN), omu((size_t)B * K * n, NAN),
       oS((size_t)B * K * n * n, NAN);
   std::vector<float> hmu(items * K * n, NAN), hS(items * K * n * n, NAN), hW(items * K * K, NAN), hw((size_t)B * K, NAN);
   std::vector<float> rs(items * K, NAN), rp(pitems * K * K, NAN), ms(items * n, NAN), Ss(items * n * n, NAN);
   kvae_sws_problem S{};
   kvae_swf_problem &P = S.filt;
-  P.B = B, P.T = T, P.K = K, P.n = n, P.m = m, P.p = p;
-  P.A = A.data(), P.Bm = Bm.data(), P.Q = Q.data(), P.C = C.data(), P.R = R.data(), P.P = Pm.data(), P.mu0 = mu0.data();
-  P.Sigma0 = Sigma0.data(), P.y = y.data(), P.u = u.data(), P.mask = masked ? mask.data() : nullptr;
+  sw.bind(P);
   P.regime_filt = rf.data(), P.ll = ll.data(), P.seq_ll = seq.data(), P.mus_filt = mf.data();
   P.out_log_w = olw.data(), P.out_mu = omu.data(), P.out_Sigma = oS.data();
   S.hist_mu = hmu.data(), S.hist_Sigma = hS.data(), S.hist_W = hW.data(), S.hist_w = hw.data();
@@ -126,16 +100,7 @@ static int run(int B, int T, int K, int n, int m, bool masked) {
 }
 
 int main() {
-  const int shapes[8][5] = {{1, 1, 1, 4, 2}, {2, 1, 5, 4, 2}, {2, 2, 7, 4, 2}, {3, 4, 5, 3, 1}, {2, 5, 7, 4, 4}, {2, 3, 8, 2, 3}, {3, 2, 3, 1, 1},
-                            {1, 66, 2, 4, 2}};
-  int bad = 0;
-  for (const auto &s : shapes)
-    for (int variant = s[1] > 8 ? 1 : 0; variant < 2; ++variant) {   // the long one once
-      const int rc = run(s[0], s[1], s[2], s[3], s[4], variant == 1);
-      printf("(%d,%d,%d,%d,%d) %s %d\n", s[0], s[1], s[2], s[3], s[4], variant ? "masked" : "observed", rc);
-      bad += rc != 0;
-    }
-  if (bad) return 1;
-  printf("SWS-ASAN-OK\n");
-  return 0;
+  const Shape shapes[] = {{1, 1, 1, 4, 2}, {2, 1, 5, 4, 2}, {2, 2, 7, 4, 2}, {3, 4, 5, 3, 1}, {2, 5, 7, 4, 4}, {2, 3, 8, 2, 3}, {3, 2, 3, 1, 1},
+                          {1, 66, 2, 4, 2}};
+  return run_shapes(shapes, "SWS-ASAN-OK", [](const Shape &s, bool masked) { return run(s.B, s.T, s.K, s.n, s.m, masked); });
 }
