@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 #define KVAE_MAX_DIM 16
-#define KVAE_ABI_VERSION 23
+#define KVAE_ABI_VERSION 24
 
 typedef enum {
   KVAE_OK = 0,
@@ -880,6 +880,63 @@ typedef struct {
  * KVAE_ERR_DIMS: H < 1; KVAE_ERR_ARG: t0 outside [0, T), or more (sequence, origin) items than one grid holds.  Nothing is
  * written on error. */
 int kvae_lgssm_switching_forecast(const kvae_swh_problem *prob, void *stream);
+
+/* ---- approximate Viterbi decoder of the switching model (kvae/model/model.py KVAE.viterbi_regimes) ------------------------------
+ * The most likely regime path of the generative model of kvae_lgssm_switching_filter (Pavlovic, Rehg & MacCormick 2000): one
+ * survivor path per regime, each with its score J(i) = log p(a_{0:t}, s_{0:t} = survivor | u) and the EXACT Kalman belief
+ * (mu^i, Sigma^i) along it.  Step t runs the filter's K^2 pair steps (the same statements: mu_ij, Sigma_ij, l_ij, 0 on a hidden
+ * step; the two logarithms of l_ij are range-reduced, log x = e ln 2 + log m: a score is a sum over T steps), then per target regime j
+ *   c_ij = (J(i) + log P[i,j]) + l_ij        J'(j) = max_i c_ij        bp_t(j) = the LOWEST i that attains it
+ *   (mu'^j, Sigma'^j) = (mu_ij, Sigma_ij) of i = bp_t(j): a copy of the bits (an OR of the bit patterns over the column, the other
+ *   lanes zeroed), not arithmetic
+ * A column without a finite entry keeps J'(j) = -inf, bp_t(j) = j and the belief of pair (j, j): no NaN.  Without a carried state
+ * the first step starts every column from (mu0, Sigma0) with J = 0 and log(1/K) in place of log P, so J_0(j) = log(1/K) + l_0j and
+ * bp_0 = 0; with one (state_score / state_mu / state_Sigma: all three or none) the first step uses P like any other.  After the
+ * sweep path_log_joint = max_j J_{T-1}(j), path_{T-1} = the lowest arg max, path_{t-1} = bp_t(path_t).  The score of the returned
+ * path is the exact log p(a, s = path | u); only the search is approximate.  scores_t(j) = J_t(j); levels_t = the largest ladder
+ * level over the pairs with finite J(i) + log P[i,j]; mus_filt_t / Sigmas_filt_t = the survivor's belief at (t, path_t), the
+ * Kalman-filtered belief given path_{0:t}.  out_* is the state after the last step.  Chunks of a stream give the bits of the whole
+ * call in scores, backptr and out_*; a chunk's path is conditional on the chunk's own end, and backptr_0 of a later chunk points
+ * into the chunk before it.
+ * Built for the filter's shapes (fp32, K <= 8, n <= 4, m <= 4, p == 2): ONE launch, one wavefront per sequence on the filter's 8 x 8
+ * grid, everything in registers (csrc/lgssm_swv.h).  The back-pointers of a step are one word of 4 bits per target in ws_bp; the
+ * same wavefront walks them back after a fence and then gathers the survivor beliefs it kept in ws_mu / ws_Sigma along the path.
+ * No atomics, every output element written once, two calls give the same bits; any output may be NULL and the bits of the others
+ * do not depend on it. */
+typedef struct {
+  int32_t B, T, K, n, m, p;
+  const float *A;             /* [K,n,n]                                                                                 */
+  const float *Bm;            /* [K,n,m]                                                                                 */
+  const float *Q;             /* [K,n,n]                                                                                 */
+  const float *C;             /* [p,n]                                                                                   */
+  const float *R;             /* [p,p]                                                                                   */
+  const float *P;             /* [K,K]    transition matrix (unclamped)                                                  */
+  const float *mu0;           /* [n]      read only without a carried state                                              */
+  const float *Sigma0;        /* [n,n]                                                                                   */
+  const float *y;             /* [B,T,p]                                                                                 */
+  const float *u;             /* [B,T,m]                                                                                 */
+  const float *mask;          /* [B,T] 1 = observed, or NULL: every step observed                                        */
+  const float *state_score;   /* [B,K]     carried state in: all three or none                                           */
+  const float *state_mu;      /* [B,K,n]                                                                                 */
+  const float *state_Sigma;   /* [B,K,n,n]                                                                               */
+  int32_t *path;              /* [B,T]     outputs: each may be NULL.  Needs ws_bp                                       */
+  float *path_log_joint;      /* [B]                                                                                     */
+  float *scores;              /* [B,T,K]                                                                                 */
+  int32_t *backptr;           /* [B,T,K]                                                                                 */
+  float *mus_filt;            /* [B,T,n]   needs ws_bp and ws_mu                                                         */
+  float *Sigmas_filt;         /* [B,T,n,n] needs ws_bp and ws_Sigma                                                      */
+  int32_t *levels;            /* [B,T]                                                                                   */
+  float *out_score;           /* [B,K]     carried state out                                                             */
+  float *out_mu;              /* [B,K,n]                                                                                 */
+  float *out_Sigma;           /* [B,K,n,n]                                                                               */
+  uint32_t *ws_bp;            /* [B,T]       workspace: the back-pointer words                                           */
+  float *ws_mu;               /* [B,T,K,n]   workspace: the survivor means of every (t, j)                               */
+  float *ws_Sigma;            /* [B,T,K,n,n] workspace: the survivor covariances                                         */
+} kvae_swv_problem;
+/* KVAE_ERR_NULL: prob or a required input NULL, or an output without the workspace it needs; KVAE_ERR_DIMS: B or T < 1;
+ * KVAE_ERR_ARG: a shape outside what is built (K outside [1,8], n or m outside [1,4], p != 2) or a partly given carried state.
+ * Nothing is written on error. */
+int kvae_lgssm_switching_viterbi(const kvae_swv_problem *prob, void *stream);
 
 /* ---- misc --------------------------------------------------------------------------------- */
 int kvae_abi_version(void);

@@ -148,3 +148,7 @@ extern "C" int kvae_lgssm_switching_forecast(const kvae_swh_problem *prob, void 
 }
 extern "C" int kvae_wemu_switching_forecast_launches(int which) { return which >= 0 && which <= 2 ? kvae_swh::emu_launches()[which] : -1; }
 #endif
+
+#if defined(KVAE_WAVE_EMU)
+#include "lgssm_swv.h"    // likewise kvae_lgssm_switching_viterbi
+#endif

@@ -87,6 +87,25 @@ __device__ __forceinline__ LogSoft log_soft(float v, int k, bool vk) {
   return o;
 }
 
+// The backtrace over the T words of one sequence (4 bits per target state), from the state st of step T - 1: 64 steps at a time, the
+// words read back with one coalesced load (lane l <-> step t1 - l, step 0 has no word to follow), walked in registers by a
+// wave-uniform __shfl; emit(step, state) is then called on the lane that holds the step.  Shared with the Viterbi decoder of the
+// switching model (csrc/lgssm_swv.h).
+template <class Emit>
+__device__ __forceinline__ void walk_back(const uint32_t *bp, int T, int st, int lane, Emit &&emit) {
+  for (int t1 = T - 1; t1 >= 0; t1 -= 64) {   // lane l <-> step t1 - l
+    const int tl = t1 - lane, n = t1 + 1 < 64 ? t1 + 1 : 64;
+    const uint32_t w = tl >= 1 ? bp[tl] : 0u;   // step 0 has no word
+    int mine = 0;
+    for (int d = 0; d < n; ++d) {              // wave-uniform trip count and source lane
+      if (lane == d) mine = st;
+      const uint32_t wd = fbits(__shfl(bitsf(w), d, 64));
+      st = (int)((wd >> (4 * st)) & 15u);       // s_{t-1} = bp_t[s_t]
+    }
+    if (tl >= 0) emit(tl, mine);
+  }
+}
+
 // bp: the sequence's T backpointer words (NULL unless path is requested)
 __device__ __forceinline__ void decode_grid(const float *__restrict__ logits, const float *__restrict__ init_logits,
                                             const float *__restrict__ Pm, float *__restrict__ marginals, int32_t *__restrict__ path,
@@ -144,19 +163,9 @@ __device__ __forceinline__ void decode_grid(const float *__restrict__ logits, co
   const float best = rgrid::oct_max(dA);
   if (path_logq && lane == 0) path_logq[b] = best;
   if (!path) return;
-  int st = (int)rgrid::oct_min((vk && dA == best) ? (float)k : 99.0f);
+  const int st = (int)rgrid::oct_min((vk && dA == best) ? (float)k : 99.0f);
   KV_DECODE_FENCE();   // the words lane 0 stored, visible to the loads of every lane below
-  for (int t1 = T - 1; t1 >= 0; t1 -= 64) {   // lane l <-> step t1 - l
-    const int tl = t1 - lane, n = t1 + 1 < 64 ? t1 + 1 : 64;
-    const uint32_t w = tl >= 1 ? bp[tl] : 0u;   // step 0 has no word
-    int mine = 0;
-    for (int d = 0; d < n; ++d) {              // wave-uniform trip count and source lane
-      if (lane == d) mine = st;
-      const uint32_t wd = fbits(__shfl(bitsf(w), d, 64));
-      st = (int)((wd >> (4 * st)) & 15u);       // s_{t-1} = bp_t[s_t]
-    }
-    if (tl >= 0) path[q0 + tl] = mine;
-  }
+  walk_back(bp, T, st, lane, [&](int tl, int mine) { path[q0 + tl] = mine; });
 }
 
 // ---- 8 < K <= 16: phases over LDS --------------------------------------------------------------------------------------------

@@ -17,7 +17,7 @@ LIB_PATH = _HERE / "lib" / "libkvae_lgssm.so"
 KVAE_MAX_DIM = 16
 KVAE_MAX_K = 16
 LSTM_MAX_H, LSTM_MAX_I = 52, 16
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 _STATUS = {1: "KVAE_ERR_DIMS (n, m, p must be in [1,16]; B, T >= 1)", 2: "KVAE_ERR_NULL", 3: "KVAE_ERR_LAUNCH",
            4: "KVAE_ERR_ARG"}
@@ -109,6 +109,13 @@ class SwhProblem(C.Structure):  # kvae_swh_problem
                 + [(k, C.c_void_p) for k in ("u_all", "regime_fore", "a_fore", "S_fore", "mus_fore", "Sigmas_fore", "ll_fore", "levels_fore")])
 
 
+class SwvProblem(C.Structure):  # kvae_swv_problem
+    _fields_ = ([(k, C.c_int32) for k in ("B", "T", "K", "n", "m", "p")]
+                + [(k, C.c_void_p) for k in ("A", "Bm", "Q", "C", "R", "P", "mu0", "Sigma0", "y", "u", "mask", "state_score", "state_mu",
+                                             "state_Sigma", "path", "path_log_joint", "scores", "backptr", "mus_filt", "Sigmas_filt",
+                                             "levels", "out_score", "out_mu", "out_Sigma", "ws_bp", "ws_mu", "ws_Sigma")])
+
+
 class InputGrads(C.Structure):  # kvae_lgssm_input_grads
     _fields_ = [("gA", Stack), ("gB", Stack), ("gC", Stack), ("gQ", Stack),
                 ("gY", C.c_void_p), ("gU", C.c_void_p), ("g_mu0", C.c_void_p), ("g_Sigma0", C.c_void_p)]
@@ -131,7 +138,7 @@ SYMBOLS = (
     "kvae_lgssm_posterior_sample_ws_floats", "kvae_lgssm_predictive", "kvae_lgssm_predictive_bwd",
     "kvae_lgssm_switching_filter", "kvae_lgssm_switching_smoother", "kvae_lgssm_switching_marginal",
     "kvae_lgssm_switching_marginal_bwd", "kvae_lgssm_switching_marginal_ws_floats", "kvae_lgssm_switching_em",
-    "kvae_lgssm_switching_em_ws_floats", "kvae_lgssm_switching_pf", "kvae_lgssm_switching_forecast", "kvae_rnn_wgrad", "kvae_rnn_wgrad_ws_floats", "kvae_linear_fwd",
+    "kvae_lgssm_switching_em_ws_floats", "kvae_lgssm_switching_pf", "kvae_lgssm_switching_forecast", "kvae_lgssm_switching_viterbi", "kvae_rnn_wgrad", "kvae_rnn_wgrad_ws_floats", "kvae_linear_fwd",
     "kvae_linear_bwd_input", "kvae_abi_version", "kvae_last_error", "kvae_build_info",
 )
 
@@ -182,6 +189,8 @@ class LgssmLib:
         d.kvae_lgssm_switching_pf.restype = C.c_int
         d.kvae_lgssm_switching_forecast.argtypes = [C.POINTER(SwhProblem), vp]
         d.kvae_lgssm_switching_forecast.restype = C.c_int
+        d.kvae_lgssm_switching_viterbi.argtypes = [C.POINTER(SwvProblem), vp]
+        d.kvae_lgssm_switching_viterbi.restype = C.c_int
         d.kvae_lgssm_smooth_bwd.argtypes = [P, S, S, G, vp, C.c_int, vp]
         d.kvae_lgssm_smooth_bwd.restype = C.c_int
         d.kvae_lgssm_elbo.argtypes = [P, vp, vp, vp, vp, vp, vp, vp, vp, G, vp]

@@ -8,7 +8,7 @@ argument order, tuple layouts and tensor shapes:
     elbo(mu,Sigma,y,u,A_list,B_list,C_list,Q_list=None,mask=None) -> 0-d tensor
 Additions over the reference: condition, sample_posterior, predictive (exact log p(a_t | a_{0:t-1}, u), no tape),
 log_marginal / marginal (the same density, differentiable: the exact LGSSM training objective) and filter_regimes (the causal
-switching Kalman filter over the generative switching model).
+switching Kalman filter over the generative switching model) with its siblings, among them viterbi_regimes / path_log_joint.
 What differs is the execution: one launch (sixteen sequences per wavefront at (4,4,2), one wavefront
 per sequence at the other shapes; the whole T loop and the RTS sweep inside the kernel) replaces ~580 aten calls per time step, and the backward is a
 hand-derived adjoint kernel instead of an autograd tape.  Inputs must live on a HIP device.
@@ -17,6 +17,8 @@ slot_view); the read-outs' torch restatements it falls back to are lgssm_torch's
 step record or plain stacks - is StepOperands' business (operands.py): every pass leaves its bundle in self._last, and the
 read-outs and the ELBO ask that bundle for their operands.
 """
+import math
+
 import torch
 import torch.nn as nn
 
@@ -308,6 +310,37 @@ class KalmanFilter(nn.Module):
         is hidden or past the end), levels_fore [B,T_o,H]; entries not named in `want` are None."""
         ops = self._switching_operands("forecast_regimes", Y, _NO_CHAIN + "forecast")
         return lgssm_ops.switching_forecast(*ops, Y, U, horizon, self._mask(mask, Y), origins=origins, want=want, state=state)
+
+    @torch.no_grad()
+    def viterbi_regimes(self, Y, U, mask=None, state=None, want=lgssm_ops._SWV_OUTPUTS):
+        """The most likely regime path of the generative switching model on its own (switching dynamics only): the approximate
+        Viterbi decoder of Pavlovic, Rehg & MacCormick over the model of filter_regimes - one survivor path per regime, each with
+        its score and exact Kalman belief - lgssm_ops.switching_viterbi; include/kvae_lgssm.h kvae_lgssm_switching_viterbi.  The
+        regime posterior network plays no part.  state: the "state" entry of an earlier call continues that stream.  Returns
+        switching_viterbi's dict: path [B,T] (int32), path_log_joint [B] = the exact log p(a, s = path | u) (path_log_joint()
+        recomputes it for any path), scores [B,T,K], backptr [B,T,K], mus_filt, Sigmas_filt (the Kalman-filtered belief given
+        path_{0:t}), levels, state; entries not named in `want` are None."""
+        ops = self._switching_operands("viterbi_regimes", Y, _NO_CHAIN + "decode")
+        return lgssm_ops.switching_viterbi(*ops, Y, U, self._mask(mask, Y), want=want, state=state)
+
+    @torch.no_grad()
+    def path_log_joint(self, Y, U, path, mask=None):
+        """log p(a, s = path | u) [B] of ANY regime path [B,T] (integers below K) under the generative switching model, exactly
+        (switching dynamics only): the chain term -log K + sum_t log P[path_{t-1}, path_t] with the prior's unclamped P, plus the
+        prediction-error decomposition of the filter pinned to that path (predictive).  It is the yardstick of a segmentation:
+        viterbi_regimes' path_log_joint is this number for its own path."""
+        self._switching_operands("path_log_joint", Y, _NO_CHAIN + "score a path of")
+        dyn = self.dyn_params
+        Bsz, T = Y.shape[0], Y.shape[1]
+        path = path.to(device=Y.device, dtype=torch.long)
+        if tuple(path.shape) != (Bsz, T):
+            raise ValueError(f"path_log_joint: path must be [B, T] = [{Bsz}, {T}], got {list(path.shape)}")
+        dyn.reset_state()
+        with dyn.pinned(torch.nn.functional.one_hot(path, dyn.K).to(Y.dtype)):
+            seq_ll = self.predictive(Y, U, mask, want=("seq_ll",))["seq_ll"]
+        logP = dyn._prior_matrix(Y.device, Y.dtype).log()
+        chain = logP[path[:, :-1], path[:, 1:]].sum(1) - math.log(dyn.K)   # (a Python constant: nothing is copied to the device)
+        return seq_ll.to(Y.dtype) + chain
 
     def regime_log_marginal(self, Y, U, mask=None):
         """log p(a | u) of the generative switching model with the regimes summed out under GPB2 collapse, DIFFERENTIABLY (switching

@@ -11,7 +11,7 @@ a whole step record, a single tensor carries its gradient) or a plain tensor tha
 ([r,c]) or per-step ([B,T,r,c]).
 
 This module is the bridge only.  The read-outs (regime_decode, rollout, posterior_paths, predictive, log_marginal,
-switching_filter, switching_smoother, switching_log_marginal, switching_em_statistics, switching_pf, switching_forecast) dispatch between their kernel and its restatement in torch ops;
+switching_filter, switching_smoother, switching_log_marginal, switching_em_statistics, switching_pf, switching_forecast, switching_viterbi) dispatch between their kernel and its restatement in torch ops;
 the restatements - also the float64 references of the tests - and safe_cholesky / safe_cholesky_items live in lgssm_torch (no
 native library behind it) and are re-exported here.
 """
@@ -22,10 +22,10 @@ from typing import NamedTuple, Optional
 import torch
 
 from .. import _native as N
-from .lgssm_torch import (_DECODE_OUTPUTS, _EM_OUTPUTS, _EM_PARAMS, _EM_STATS, _LOG_2PI, _PRED_OUTPUTS, _SPF_OUTPUTS, _SWF_OUTPUTS, _SWH_FORE, _SWH_OUTPUTS, _SWS_OUTPUTS, _SWS_SMOOTH, _bt,  # noqa: F401 (re-exported)
-                          SPF_PARTICLES, _spf_draws, _spf_state, _swf_state, _swh_args, _want, lineages, switching_pf_torch, log_marginal_torch, posterior_paths_torch, predictive_torch, regime_decode_torch,
+from .lgssm_torch import (_DECODE_OUTPUTS, _EM_OUTPUTS, _EM_PARAMS, _EM_STATS, _LOG_2PI, _PRED_OUTPUTS, _SPF_OUTPUTS, _SWF_OUTPUTS, _SWH_FORE, _SWH_OUTPUTS, _SWS_OUTPUTS, _SWS_SMOOTH, _SWV_OUTPUTS, _bt,  # noqa: F401 (re-exported)
+                          SPF_PARTICLES, _spf_draws, _spf_state, _swf_state, _swh_args, _swv_state, _want, lineages, switching_pf_torch, log_marginal_torch, posterior_paths_torch, predictive_torch, regime_decode_torch,
                           rollout_torch, safe_cholesky, safe_cholesky_items, switching_em_mstep, switching_em_statistics_torch,
-                          switching_filter_torch, switching_forecast_torch, switching_log_marginal_torch, switching_smoother_torch)
+                          switching_filter_torch, switching_forecast_torch, switching_log_marginal_torch, switching_smoother_torch, switching_viterbi_torch)
 
 
 class Slots(NamedTuple):
@@ -50,7 +50,7 @@ def _empty(dev, *shape, dt=torch.float32):
     return torch.empty(*shape, device=dev, dtype=dt)
 
 
-_INT32_OUTPUTS = ("levels", "levels_fore", "resampled", "regimes", "ancestors", "paths")
+_INT32_OUTPUTS = ("levels", "levels_fore", "resampled", "regimes", "ancestors", "paths", "path", "backptr", "ws_bp")
 
 
 def _wanted(dev, outputs, want, shapes):
@@ -1235,6 +1235,56 @@ def switching_forecast(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U_all, horizon, mask=
     lib.check(N.timed("switching_forecast", Y, lambda: lib.dll.kvae_lgssm_switching_forecast(C.byref(fp), N.stream_for(Y))),
               "kvae_lgssm_switching_forecast")
     del keep, hist
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# approximate Viterbi decoder of the switching model (kvae_lgssm_switching_viterbi, csrc/lgssm_swv.h)
+# ------------------------------------------------------------------------------------------------
+def switching_viterbi_supported(K, n, m, p, ref=None):
+    """Shapes / tensors kvae_lgssm_switching_viterbi is built for: the filter's (switching_filter_supported); the rest takes
+    switching_viterbi_torch."""
+    return switching_filter_supported(K, n, m, p, ref)
+
+
+@torch.no_grad()
+def switching_viterbi(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, want=_SWV_OUTPUTS, state=None, impl=None):
+    """The most likely regime path of the generative switching model by the approximate Viterbi decoder of Pavlovic, Rehg &
+    MacCormick (semantics: include/kvae_lgssm.h, kvae_lgssm_switching_viterbi): the model and operands of
+    switching_filter; one survivor path per regime with its score and exact Kalman belief, a selection where the filter collapses.
+    want: which of "path" [B,T] (int32), "path_log_joint" [B] = the exact log p(a, s = path | u), "scores" [B,T,K] = J_t(j),
+    "backptr" [B,T,K] (int32), "mus_filt" [B,T,n], "Sigmas_filt" [B,T,n,n] (the Kalman-filtered belief given path_{0:t}), "levels"
+    [B,T] (int32), "state" (dict score [B,K], mu [B,K,n], Sigma [B,K,n,n] after the last step) to compute; entries not asked for
+    are None.  state: None or the "state" entry of an earlier call, which continues that stream: scores, backptr and state are then
+    the bits of the whole-sequence call; a chunk's path is conditional on the chunk's own end, and the path of the whole stream
+    follows the concatenated backptr from the lowest arg max of the last scores (backptr[:, 0] of a later chunk points into the
+    chunk before it).  One launch, no host synchronisation, no gradients.
+    impl: None = the HIP kernel where it is built (switching_viterbi_supported), else switching_viterbi_torch; "hip" / "torch"
+    force one."""
+    want = _want("switching_viterbi", _SWV_OUTPUTS, want)
+    if not _sw_route("switching_viterbi", impl, switching_viterbi_supported, A, Bm, Y):
+        return switching_viterbi_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, state, want)
+    (K, n), (Bsz, T, _), dev = A.shape[:2], Y.shape, Y.device
+    pr = N.SwvProblem()
+    pr.B, pr.T, pr.K, pr.n, pr.m, pr.p = Bsz, T, K, n, Bm.shape[2], Y.shape[2]
+    keep = _sw_operands(pr, A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask)
+    st = _swv_state(state, Bsz, K, n)
+    if st is not None:
+        st = _bind(pr, {"state_" + k: _f32c(t.detach().to(dev)) for k, t in zip(("score", "mu", "Sigma"), st)})
+    out = _wanted(dev, _SWV_OUTPUTS, want, dict(path=(Bsz, T), path_log_joint=(Bsz,), scores=(Bsz, T, K), backptr=(Bsz, T, K),
+                                                mus_filt=(Bsz, T, n), Sigmas_filt=(Bsz, T, n, n), levels=(Bsz, T)))
+    if "state" in want:
+        out["state"] = {"score": _empty(dev, Bsz, K), "mu": _empty(dev, Bsz, K, n), "Sigma": _empty(dev, Bsz, K, n, n)}
+        _bind(pr, {"out_" + k: t for k, t in out["state"].items()})
+    walked = {"path": (), "mus_filt": ("ws_mu",), "Sigmas_filt": ("ws_Sigma",)}   # what the backtrace writes: the workspace each reads besides the words
+    ws = _wanted(dev, ("ws_bp", "ws_mu", "ws_Sigma"), {w for k, v in walked.items() if k in want for w in ("ws_bp",) + v},
+                 dict(ws_bp=(Bsz, T), ws_mu=(Bsz, T, K, n), ws_Sigma=(Bsz, T, K, n, n)))
+    _bind(pr, {k: out[k] for k in _SWV_OUTPUTS if k != "state"})
+    _bind(pr, ws)
+    lib = N.lib_for(Y)
+    lib.check(N.timed("switching_viterbi", Y, lambda: lib.dll.kvae_lgssm_switching_viterbi(C.byref(pr), N.stream_for(Y))),
+              "kvae_lgssm_switching_viterbi")
+    del keep, st, ws
     return out
 
 

@@ -12,6 +12,7 @@ _SWS_SMOOTH = ("regime_smooth", "regime_pairs", "mus_smooth", "Sigmas_smooth")
 _SWS_OUTPUTS = _SWF_OUTPUTS + _SWS_SMOOTH
 _SWH_FORE = ("regime_fore", "a_fore", "S_fore", "mus_fore", "Sigmas_fore", "log_lik_fore", "levels_fore")
 _SWH_OUTPUTS = _SWF_OUTPUTS + _SWH_FORE
+_SWV_OUTPUTS = ("path", "path_log_joint", "scores", "backptr", "mus_filt", "Sigmas_filt", "levels", "state")
 
 
 def _want(op, outputs, want):
@@ -291,20 +292,12 @@ def _swf_forward(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, state, history=Fal
     return full, ({k: torch.stack(v, 1) for k, v in hist.items()} if history else None), (A, Bm, Q, Cm, U)
 
 
-def _swf_step(A, Bm, Q, Cm, R, Pt, lw, mu, Sig, y, u, mk, score=False):
-    """One step of the sweep over a batch [N, ...] (the sequences of the filter; the (sequence, origin) items of the forecast): from
-    the carried (lw [N,K], mu [N,K,n], Sig [N,K,n,n]) under the transition matrix Pt, the frame y [N,p], the input u [N,m] and the
-    mask mk [N].  Returns the step's outputs under the names of _SWF_OUTPUTS, the collapsed beliefs it hands on (lw, mu, Sigma) and
-    the pair weights W [N,i,j].  score: also "scored" [N] = logsumexp_ij(lw_i + log Pt[i,j] + l_ij) with the pair densities of y
-    whatever mk says - the density of a frame that the step itself does not condition on."""
-    dev, dt = A.device, A.dtype
-    K, n = A.shape[0], A.shape[1]
-    N = lw.shape[0]
-    eye = torch.eye(n, device=dev, dtype=dt)
-    eyeK = torch.eye(K, device=dev, dtype=dt)
-    ninf = torch.full((), -float("inf"), device=dev, dtype=dt)
+def _sw_pairs(A, Bm, Q, Cm, R, mu, Sig, y, u, mk):
+    """The K^2 Kalman steps of one step of the switching read-outs over a batch [N, ...], indexed [N, i, j, ...] (regime i's belief
+    (mu [N,K,n], Sig [N,K,n,n]) under regime j's dynamics): the filtered pair (muf, Sf), the pair forecast (ap, S), the pair density
+    of y whatever the mask says (lraw), the same with zeros on hidden steps (lij), and the ladder level of S (lv)."""
+    eye = torch.eye(A.shape[1], device=A.device, dtype=A.dtype)
     observed = mk != 0
-    # ---- the K^2 filter steps: [N, i, j, ...] ----
     mp = torch.einsum("jrc,bic->bijr", A, mu) + torch.einsum("jrc,bc->bjr", Bm, u).unsqueeze(1)
     Sp = torch.einsum("jre,biec,jdc->bijrd", A, Sig, A) + Q
     ap = mp @ Cm.mT
@@ -319,6 +312,22 @@ def _swf_step(A, Bm, Q, Cm, R, Pt, lw, mu, Sig, y, u, mk, score=False):
     IKC = eye - Kg @ Cm
     Sf = IKC @ Sp @ IKC.mT + Kg @ R @ Kg.mT
     Sf = 0.5 * (Sf + Sf.mT)
+    return muf, Sf, ap, S, lraw, lij, lv
+
+
+def _swf_step(A, Bm, Q, Cm, R, Pt, lw, mu, Sig, y, u, mk, score=False):
+    """One step of the sweep over a batch [N, ...] (the sequences of the filter; the (sequence, origin) items of the forecast): from
+    the carried (lw [N,K], mu [N,K,n], Sig [N,K,n,n]) under the transition matrix Pt, the frame y [N,p], the input u [N,m] and the
+    mask mk [N].  Returns the step's outputs under the names of _SWF_OUTPUTS, the collapsed beliefs it hands on (lw, mu, Sigma) and
+    the pair weights W [N,i,j].  score: also "scored" [N] = logsumexp_ij(lw_i + log Pt[i,j] + l_ij) with the pair densities of y
+    whatever mk says - the density of a frame that the step itself does not condition on."""
+    dev, dt = A.device, A.dtype
+    K = A.shape[0]
+    N = lw.shape[0]
+    eyeK = torch.eye(K, device=dev, dtype=dt)
+    ninf = torch.full((), -float("inf"), device=dev, dtype=dt)
+    observed = mk != 0
+    muf, Sf, ap, S, lraw, lij, lv = _sw_pairs(A, Bm, Q, Cm, R, mu, Sig, y, u, mk)
 
     def weights(logc):   # (the column softmax W_{i|j}, logsumexp_ij, log w'(j)); a dead column is one-hot at i = j
         cmx = logc.amax(1)                                                       # [N, j]
@@ -359,6 +368,92 @@ def switching_filter_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, sta
     want = _want("switching_filter", _SWF_OUTPUTS, want)
     full, _, _ = _swf_forward(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, state)
     return {k: (full[k] if k in want else None) for k in _SWF_OUTPUTS}
+
+
+def _swv_state(state, Bsz, K, n):
+    if state is None:
+        return None
+    J, mu, Sig = state["score"], state["mu"], state["Sigma"]
+    if J.shape != (Bsz, K) or mu.shape != (Bsz, K, n) or Sig.shape != (Bsz, K, n, n):
+        raise ValueError(f"switching_viterbi: state must hold score [{Bsz},{K}], mu [{Bsz},{K},{n}], Sigma [{Bsz},{K},{n},{n}], got "
+                         f"{tuple(J.shape)}, {tuple(mu.shape)}, {tuple(Sig.shape)}")
+    return J, mu, Sig
+
+
+def _first_max(v, dim):
+    """The lowest index along `dim` among the maxima of v (an argmax over (value == max), whose first hit torch returns)."""
+    return (v == v.amax(dim, keepdim=True)).to(torch.int8).argmax(dim)
+
+
+def _swv_forward(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, state, margins=False):
+    """The sweep and backtrace of switching_viterbi_torch: every output of _SWV_OUTPUTS, and - margins, for the tests - "margin" [B], the smallest decision
+    margin of the sequence: best minus runner-up of c_ij over i at every (t, j) with a finite maximum (the first step of a stream
+    without carried state is left out: its K candidates are one and the same number) and of the final maximum over j; +inf where
+    there is no runner-up."""
+    dt, dev = A.dtype, Y.device
+    K, n = A.shape[0], A.shape[1]
+    Bsz, T, p = Y.shape
+    A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U = (t.detach().to(device=dev, dtype=dt) for t in (A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U))
+    mask = None if mask is None else mask.detach().to(device=dev, dtype=dt).reshape(Bsz, T)
+    st = _swv_state(state, Bsz, K, n)
+    if st is None:
+        J = torch.zeros(Bsz, K, device=dev, dtype=dt)
+        mu, Sig = mu0.expand(Bsz, K, n), Sigma0.expand(Bsz, K, n, n)
+    else:
+        J, mu, Sig = (t.detach().to(device=dev, dtype=dt) for t in st)
+    ninf = torch.full((), -float("inf"), device=dev, dtype=dt)
+    log_uniform, logP = torch.full((K, K), 1.0 / K, device=dev, dtype=dt).log(), P.log()
+    own = torch.arange(K, device=dev).expand(Bsz, K)
+    margin = torch.full((Bsz,), float("inf"), device=dev, dtype=dt)
+
+    def gap(v, dim):   # best minus runner-up along dim; +inf without a finite best or without a runner-up
+        if v.shape[dim] < 2:
+            return torch.full_like(v.amax(dim), float("inf"))
+        top = v.topk(2, dim=dim).values
+        best, second = top.select(dim, 0), top.select(dim, 1)
+        return torch.where(best == ninf, torch.full_like(best, float("inf")), best - second)
+
+    outs = {k: [] for k in ("scores", "backptr", "levels", "mu", "Sigma")}
+    for t in range(T):
+        first = t == 0 and st is None
+        mk = torch.ones(Bsz, device=dev, dtype=dt) if mask is None else mask[:, t]
+        muf, Sf, _, _, _, lij, lv = _sw_pairs(A, Bm, Q, Cm, R, mu, Sig, Y[:, t], U[:, t], mk)
+        prior = J.unsqueeze(-1) + (log_uniform if first else logP)                # [B, i, j]
+        c = prior + lij
+        J = c.amax(1)                                                            # [B, j]
+        bp = torch.where(J == ninf, own, _first_max(c, 1))                       # a column without a finite entry keeps i = j
+        if margins and not first:
+            margin = torch.minimum(margin, gap(c, 1).amin(-1))
+        mu = muf.gather(1, bp[:, None, :, None].expand(Bsz, 1, K, n)).squeeze(1)  # the selected pair's belief: a copy
+        Sig = Sf.gather(1, bp[:, None, :, None, None].expand(Bsz, 1, K, n, n)).squeeze(1)
+        outs["scores"].append(J), outs["backptr"].append(bp.to(torch.int32)), outs["mu"].append(mu), outs["Sigma"].append(Sig)
+        outs["levels"].append(torch.where(prior > ninf, lv, torch.zeros_like(lv)).amax((1, 2)))
+    full = {k: torch.stack(outs[k], 1) for k in ("scores", "backptr", "levels")}
+    full["state"] = {"score": J, "mu": mu, "Sigma": Sig}
+    full["path_log_joint"] = J.amax(-1)
+    if margins:
+        full["margin"] = torch.minimum(margin, gap(J, 1))
+    s = _first_max(J, 1)
+    path = [s]
+    for t in range(T - 1, 0, -1):
+        s = outs["backptr"][t].long().gather(1, s.unsqueeze(1)).squeeze(1)
+        path.append(s)
+    path = torch.stack(path[::-1], 1)                                            # [B, T]
+    full["path"] = path.to(torch.int32)
+    full["mus_filt"] = torch.stack(outs["mu"], 1).gather(2, path[:, :, None, None].expand(Bsz, T, 1, n)).squeeze(2)
+    full["Sigmas_filt"] = torch.stack(outs["Sigma"], 1).gather(2, path[:, :, None, None, None].expand(Bsz, T, 1, n, n)).squeeze(2)
+    return full
+
+
+@torch.no_grad()
+def switching_viterbi_torch(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask=None, state=None, want=_SWV_OUTPUTS):
+    """The equations of kvae_lgssm_switching_viterbi (include/kvae_lgssm.h) in torch ops, vectorised over (B, i, j), in the dtype of
+    A: the pair steps of switching_filter_torch (_sw_pairs), a maximum and a gather in place of the collapse, then the backtrace.
+    The fallback of switching_viterbi and (in float64) the reference its kernel is tested against.  Same arguments and returns as
+    switching_viterbi."""
+    want = _want("switching_viterbi", _SWV_OUTPUTS, want)
+    full = _swv_forward(A, Bm, Q, Cm, R, P, mu0, Sigma0, Y, U, mask, state)
+    return {k: (full[k] if k in want else None) for k in _SWV_OUTPUTS}
 
 
 def _moment_match(w, mu, Sig):

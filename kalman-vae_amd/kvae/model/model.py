@@ -614,6 +614,44 @@ class KVAE(nn.Module):
             out["valid"] = inside if mask is None else inside & (mask[:, target.clamp(max=T - 1)] != 0)
             return self._close_readout(out, a_vae, mask, decode, "x_fore", out["a_fore"][:, -1])
 
+    @torch.no_grad()
+    def viterbi_regimes(self, x, u=None, mask=None, sample_a=False, state=None, smooth=True, decode=False):
+        """Segment each sequence into regimes with the generative switching model itself (switching dynamics only; no counterpart
+        in the reference): ONE coherent regime path and its exact joint score, by the approximate Viterbi decoder of Pavlovic,
+        Rehg & MacCormick (2000) - kvae_lgssm_switching_viterbi.  decode_regimes decodes the amortised q(s | a) of the
+        bidirectional posterior network, which has to be trained (after fit_dynamics_em or kf_objective="regime_marginal" it is
+        not); the per-step argmax of regime_filt / regime_smooth is not a path - it may use transitions P forbids and has no score.
+
+        1. Encode x, as filter_regimes does.  u [B,T,m] or None = zeros; mask [B,T] optional (1 = observed).
+        2. One survivor path per regime, each with its score J_t(j) and the exact Kalman belief along it; every step extends each
+           survivor by the best predecessor (lowest index on ties).  regimes [B,T] (int64) = the path that ends in the best final
+           score; regimes_log_joint [B] = log p(a, s = regimes | u), EXACT for that path (kalman_filter.path_log_joint gives the
+           same number for any path); only the search is approximate.  Also path (int32), path_log_joint, scores [B,T,K],
+           backptr [B,T,K], mus_filt [B,T,n], Sigmas_filt [B,T,n,n] (the Kalman-filtered belief given regimes_{0:t}), levels.
+        3. state: the survivors after the last step; state=prev["state"] continues a stream - scores, backptr and state of the
+           chunks are the bits of the whole-sequence call; a chunk's regimes are conditional on the chunk's own end, the path of
+           the stream follows the concatenated backptr back from the last chunk (backptr[:, 0] of a chunk points into the one
+           before).  A carried state needs smooth=False: the smoother below starts at (mu0, Sigma0).
+        4. smooth=True: the eval-mode smoother pinned to the path, as decode_regimes step 3: mus_smooth, Sigmas_smooth, ABC and
+           a_imputed = C_t mu_{t|T}.  decode=True (needs smooth): x_imputed = decoder(a_imputed).
+        Also returns a_vae and n_obs [B].  No host synchronisation.  Training mode, tau and parameters are left as they were."""
+        dyn = self.kalman_filter.dyn_params
+        prelude = self._switching_readout("viterbi_regimes", x, u, mask, sample_a)   # its shape checks come before these
+        if decode and not smooth:
+            raise ValueError("viterbi_regimes: decode=True needs smooth=True (x_imputed is decoded from the smoothed latents)")
+        if smooth and state is not None:
+            raise ValueError("viterbi_regimes: a carried state needs smooth=False (the pinned smoother starts at (mu0, Sigma0))")
+        with prelude as (a_vae, _, _, u, mask):
+            out = self.kalman_filter.viterbi_regimes(a_vae, u, mask, state=state)
+            out["regimes"], out["regimes_log_joint"] = out["path"].long(), out["path_log_joint"]
+            if smooth:
+                dyn.reset_state()
+                with dyn.pinned(torch.nn.functional.one_hot(out["regimes"], self.K).to(a_vae.dtype)):
+                    ms, Ss, mf, _, _, _, A_list, B_list, C_list = self.kalman_filter.smooth(a_vae, u, mask=mask)
+                a_imputed, _ = self.kalman_filter.emission_means(ms, mf, C_list)
+                out.update(mus_smooth=ms, Sigmas_smooth=Ss, ABC=(A_list, B_list, C_list), a_imputed=a_imputed)
+            return self._close_readout(out, a_vae, mask, decode, "x_imputed", out.get("a_imputed"))
+
     def fit_dynamics_em(self, batches, iters, update=("A", "B", "Q", "C", "P"), sample_a=False, min_count=None):
         """Closed-form EM for the generative switching model on the encoded sequences (switching dynamics only):
         kvae.train.em.fit_dynamics_em.  The encoder, the decoder and the regime posterior network are not touched.  Returns the

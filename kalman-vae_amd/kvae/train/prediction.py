@@ -111,3 +111,28 @@ def forecast_scores(model, batch_or_x, horizon, mask=None, u=None):
     mean = lambda v, w: (torch.where(w, v, torch.zeros_like(v)).sum((0, 1)) / w.sum((0, 1))).tolist()
     return {"mse": mean((r * r).mean(-1), valid), "mse_naive": mean((naive * naive).mean(-1), origin),
             "log_lik": mean(fc["log_lik_fore"].double(), valid), "nis_mean": mean(nis, valid), "count": valid.sum((0, 1)).tolist()}
+
+
+@torch.no_grad()
+def viterbi_scores(model, batch_or_x, mask=None, u=None):
+    """Four segmentations of x [B,T,...] (or a batch, as prediction_scores takes it) under ONE yardstick, the exact joint
+    log p(a, s = path | u) of the generative switching model (KalmanFilter.path_log_joint): the path of KVAE.viterbi_regimes, the
+    path of KVAE.decode_regimes (the amortised posterior network's) and the per-step argmax of filter_regimes' regime_filt and of
+    smooth_regimes' regime_smooth (which need not be paths the prior allows: their joint may be -inf).  Switching dynamics only.
+    Python floats:
+      log_joint_<name>  mean over sequences of the exact joint of that segmentation, <name> in viterbi, decode, filter, smooth
+      agreement_<name>  share of steps on which it equals the Viterbi path (1 for viterbi itself)
+      log_lik           mean over sequences of filter_regimes' log_lik_seq = log p(a | u) with the regimes summed out: the upper
+                        reference of every joint (up to the GPB2 error)"""
+    x = _frames(model, batch_or_x)
+    vit = model.viterbi_regimes(x, u=u, mask=mask, smooth=False)
+    sm = model.smooth_regimes(x, u=u, mask=mask)
+    paths = {"viterbi": vit["regimes"], "decode": model.decode_regimes(x, u=u, mask=mask, smooth=False)["regimes"],
+             "filter": model._argmax_lowest(sm["regime_filt"]), "smooth": sm["regimes"]}
+    kf, a = model.kalman_filter, vit["a_vae"]
+    uu = torch.zeros(a.shape[0], a.shape[1], model.u_dim, device=a.device, dtype=a.dtype) if u is None else u.to(device=a.device, dtype=a.dtype)
+    out = {"log_lik": float(sm["log_lik_seq"].double().mean())}
+    for name, path in paths.items():   # (a pinned path takes no draw: the training flag plays no part)
+        out["log_joint_" + name] = float(kf.path_log_joint(a, uu, path, mask).double().mean())
+        out["agreement_" + name] = float((path == paths["viterbi"]).double().mean())
+    return out
